@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """EPNN inference throughput on MI355X: atoms/sec on a QM9-sized batch (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one forward of the whole hot path (near-pair construction + T GNN steps + T EPN steps) over one
 batch of 1024 synthetic QM9-like molecules padded to N=29, inputs (coordinates, atom features, total charges)
@@ -19,14 +19,24 @@ and `ranks.rccl_ranks` (ncclCommCount) says how many ranks joined.  No torch any
 on a one-GPU box: RCCL refuses two ranks on one device) the ranks share devices, take fewer hardware queues each, and the
 timing exchange runs over the rendezvous store.
 
-Order of a run: one forward and its checks; the COLD measurement (`value_cold`: W warm-up + K timed steps started on a GPU that
+Order of a plain run (only what the headline figure needs): one forward and its sanity check (finite charges, total charge
+conserved); W + K untimed steps (at most PREPASS_MAX) in place of the cold measurement; the launches of the single-launch
+measurement below, unmeasured, as GPU load (`prewarm_ms`); W warm-up steps; barrier; K timed steps; barrier; with
+--dump-outputs DIR the charges of the last timed step go to DIR/charges.npy (float32, the array a caller of
+epnn_forward_xyz_dev receives; ranks > 0 write charges_rank<r>.npy; beyond DUMP_MAX_BYTES a seeded sample of the atoms and
+charges_atom_index.npy); the line.
+
+Order of a --full run: one forward and its checks; the COLD measurement (`value_cold`: W warm-up + K timed steps started on a GPU that
 idled for 0.3 s, what a run without anything in front of its warm-up steps reads); parity against the reference's stored outputs
 and the single-launch measurement (all three skipped by --no-extras); W warm-up steps; barrier; K timed steps; barrier; the same
-steps again with hipEvents for the kernel duration; host-to-host; real-data rate.  The single-launch measurement placed right before the warm-up steps also
-means the timed region starts on a GPU at working clocks: K = 20 steps are 2 ms, and on a GPU that idled before the W = 5
-warm-up steps (--no-extras) they read 182-185 M atoms/s instead of 194-197 M (`order` in the line; profiles/r02_warm_sweep.txt).
+steps again with hipEvents for the kernel duration (roofline); host-to-host; real-data rate; CPU baseline (skipped by
+--no-cpu-baseline).
 
-Prints ONE JSON line on rank 0.  Besides the contract's fields:
+In both, the single-launch batch's launches placed right before the warm-up steps also mean the timed region starts on a GPU at
+working clocks: K = 20 steps are 2 ms, and on a GPU that idled before the W = 5 warm-up steps (--full --no-extras) they read
+182-185 M atoms/s instead of 194-197 M (`order` in the line; profiles/r02_warm_sweep.txt).
+
+Prints ONE JSON line on rank 0.  Besides the contract's fields, a --full run adds:
   roofline.*          dominant kernel k_wave_forward; `frac` is ALGORITHMIC flops of the launches per second of
                       the timed region / `peak`, the bound of the matrix pipe the kernel's products run on (every Dense layer AND the edge
                       products as six bf16 MFMAs per f32-grade product, 2500 / 6 = 416.7 TFLOP/s: `peak_basis`; until the edge products
@@ -66,6 +76,8 @@ if ROOT not in sys.path:
 FP32_MFMA_PEAK_TFLOPS = 157.3
 BF16_MFMA_PEAK_TFLOPS = 2500.0
 KNAME = "k_wave_forward<true,true,true>"
+DUMP_MAX_BYTES = 64 << 20           # --dump-outputs writes at most this much (all ranks together)
+PREPASS_MAX = 2048                  # untimed steps of a plain run in place of the cold measurement (~0.16 s)
 PMC_JSON = os.path.join(ROOT, "profiles", "r05_pmc_bench.json")
 
 
@@ -171,7 +183,7 @@ def collect_pmc(args):
     for name, counters, depth in passes:
         d = os.path.join(base, name)
         cmd = ["rocprofv3", "--pmc"] + counters.split() + ["--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "12", "--warmup", "6", "--no-cpu-baseline", "--no-extras", "--depth", str(depth), "--molecules", str(args.molecules)]
+               "--steps", "12", "--warmup", "6", "--full", "--no-cpu-baseline", "--no-extras", "--depth", str(depth), "--molecules", str(args.molecules)]
         env = dict(os.environ, TMPDIR="/tmp")
         rc = subprocess.run(cmd, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, cwd="/tmp")
         if rc.returncode != 0:
@@ -185,7 +197,7 @@ def collect_pmc(args):
                 vals["launches_" + c] = int(len(g))
     out = {"workload": f"qm9_like_b{args.molecules}_N29", "kernel": KNAME, "kernel_source_sha": kernel_source_sha(),
            "command": "python bench.py --pmc  (child passes: rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --steps 12 "
-                      "--warmup 6 --no-cpu-baseline --no-extras --depth D; FETCH_SIZE / WRITE_SIZE at the bench depth, SQ_* at depth 1)",
+                      "--warmup 6 --full --no-cpu-baseline --no-extras --depth D; FETCH_SIZE / WRITE_SIZE at the bench depth, SQ_* at depth 1)",
            "counters_per_launch": vals}
     if "FETCH_SIZE" in vals and "WRITE_SIZE" in vals:
         # rocprofv3 reports KiB; gfx950's FETCH_SIZE tallies 128-byte requests at 64 bytes (x2), WRITE_SIZE is exact
@@ -273,7 +285,14 @@ def main():
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value (developer switch)")
     ap.add_argument("--real-depth", type=int, default=14, help="batches in flight of the real-data measurement")
     ap.add_argument("--real-only", action="store_true", help="(child of the main run) only the real-data rate, as one JSON object")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: value_cold, parity, single-launch, "
+                    "roofline (the steps again with hipEvents), host-to-host, blocking call, real-data rate, CPU baseline "
+                    "(--no-extras / --no-cpu-baseline trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the charges of the last timed step to DIR/charges.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras_on = args.full and not args.no_extras
 
     if args.real_only:
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
@@ -395,10 +414,11 @@ def main():
     assert np.isfinite(q).all()
     sums = np.add.reduceat(q.astype(np.float64), offsets[:-1])
     assert np.abs(sums - Q).max() < 1e-4, np.abs(sums - Q).max()
-    ns = np.diff(offsets)
-    flops = synth.algorithmic_flops(ns, int(stats[0]))
-    peak, bf_share = synth.mixed_pipe_peak(ns, int(stats[0]), chains_bf16=True)
-    peak_edges_f32 = synth.mixed_pipe_peak(ns, int(stats[0]), chains_bf16=True, edges_bf16=False)[0]     # (the pricing of this line until the edge products moved: 277.2)
+    if args.full:
+        ns = np.diff(offsets)
+        flops = synth.algorithmic_flops(ns, int(stats[0]))
+        peak, bf_share = synth.mixed_pipe_peak(ns, int(stats[0]), chains_bf16=True)
+        peak_edges_f32 = synth.mixed_pipe_peak(ns, int(stats[0]), chains_bf16=True, edges_bf16=False)[0]     # (the pricing of this line until the edge products moved: 277.2)
 
     def timed_steps():
         """W warm-up steps, barrier, K timed steps, barrier -> seconds of the timed region on this rank"""
@@ -416,7 +436,14 @@ def main():
         return dt_
 
     cold_dt = None
-    if not args.no_extras:
+    if not args.full:
+        # a plain run has no cold measurement, but its timed region wants the lanes' history one gives them: without these
+        # untimed steps 200 timed steps read 4-5 % lower (at most PREPASS_MAX of them: beyond it the steps of a run this long
+        # make up the difference themselves)
+        for k in range(min(max(args.warmup, len(lanes)) + args.steps, PREPASS_MAX)):
+            step(k)
+        pipe.sync()
+    if extras_on:
         # the same measurement from an IDLE GPU (nothing but a 0.3 s pause in front of the warm-up steps): the figure a run
         # reads whose timed region is a few milliseconds long and has no load in front of it (clocks: DESIGN.md section 5)
         pipe.sync()
@@ -424,7 +451,7 @@ def main():
         cold_dt = timed_steps()
 
     extras, real, held = {}, None, []
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras_on:
         # (1) the metric's second half, "max |dq| vs reference", and a REAL-data rate: the 871 systems of the reference's
         #     recorded validation split (tests/golden/mixed_val.tar.gz, 3..38 atoms, N = 41) against the TensorFlow
         #     predictions the reference stored for them (models/model_systems/test_pred_charges.npy); its rate is (4)
@@ -456,9 +483,11 @@ def main():
             print(f"[bench] real-data / parity extras skipped: {exc}", file=sys.stderr)
 
     barrier()
-    if not args.no_extras:
+    prewarm_ms = None
+    if extras_on or not args.full:
         # (2) a launch with the GPU to itself: 64 copies of the batch in ONE launch (65536 molecules), one handle, hipEvents
-        #     around each launch: algorithmic flops / duration is that kernel's rate with nothing else on the machine
+        #     around each launch: algorithmic flops / duration is that kernel's rate with nothing else on the machine.  A plain
+        #     run makes the same launches unmeasured: they are its GPU load in front of the warm-up steps (clocks, see above).
         rep = max(1, 65536 // B)
         big_off = np.concatenate([[0]] + [offsets[1:] + r * A for r in range(rep)]).astype(np.int32)
         e0 = pipe.engines[0]
@@ -468,12 +497,17 @@ def main():
             e0.forward_xyz_dev(big_off, big[0], big[1], big[2], big_q, N)
         e0.sync()
         nbig = 10
-        e0.set_option("profile", nbig)
+        if extras_on:
+            e0.set_option("profile", nbig)
+        t1 = time.perf_counter()
         for _ in range(nbig):
             e0.forward_xyz_dev(big_off, big[0], big[1], big[2], big_q, N)
         e0.sync()
-        big_ms = float(np.mean([e0.timing_at(i)[1] for i in range(nbig)]))
-        e0.set_option("profile", 0)
+        if extras_on:
+            big_ms = float(np.mean([e0.timing_at(i)[1] for i in range(nbig)]))
+            e0.set_option("profile", 0)
+        else:
+            big_ms = (time.perf_counter() - t1) / nbig * 1e3       # (wall time: no hipEvents in a plain run)
         # Two further launches of the same batch keep the GPU under load while the warm-up steps are queued, and nothing that
         # idles it (hipFree, the download of the big result) happens before the timed region: see the note on clocks above.
         for _ in range(2):
@@ -499,18 +533,31 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
-    # Kernel durations for the roofline: the same steps again (up to 600), right after the timed region, this time with
-    # hipEvents recorded around every stage on the stream the kernels run on (four event records per forward cost
-    # ~20 us of host time per step, which would otherwise be charged to `value`).
-    prof_steps = min(args.steps, 600)            # enough launches for a stable mean; four hipEvents are kept per forward
-    pipe.set_option("profile", prof_steps)
-    for k in range(prof_steps):
-        step(k)
-    pipe.sync()
-    per_lane = [sum(1 for k in range(prof_steps) if k % len(lanes) == l) for l in range(len(lanes))]
-    # ms per forward: front-end kernels (none: the fused kernel builds its pair lists itself), fused kernel, tiled kernels, total
-    stage = np.array([lanes[l][0].timing_at(i) for l in range(len(lanes)) for i in range(per_lane[l])])
-    pipe.set_option("profile", 0)
+    if args.dump_outputs:
+        # what the last timed step computed: the charges in the output buffer of the lane it ran on
+        q_last = lanes[(args.steps - 1) % n_lanes][4].download((A,))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        suffix = "" if rank == 0 else f"_rank{rank}"
+        budget = DUMP_MAX_BYTES // world
+        if A * 4 > budget:
+            # a larger batch (--molecules): a fixed, seeded sample of the atoms, with their indices
+            idx = np.sort(np.random.default_rng(0).choice(A, budget // 12, replace=False))
+            np.save(os.path.join(args.dump_outputs, f"charges_atom_index{suffix}.npy"), idx.astype(np.float64))
+            q_last = q_last[idx]
+        np.save(os.path.join(args.dump_outputs, f"charges{suffix}.npy"), np.ascontiguousarray(q_last, dtype=np.float32))
+    if args.full:
+        # Kernel durations for the roofline: the same steps again (up to 600), right after the timed region, this time with
+        # hipEvents recorded around every stage on the stream the kernels run on (four event records per forward cost
+        # ~20 us of host time per step, which would otherwise be charged to `value`).
+        prof_steps = min(args.steps, 600)            # enough launches for a stable mean; four hipEvents are kept per forward
+        pipe.set_option("profile", prof_steps)
+        for k in range(prof_steps):
+            step(k)
+        pipe.sync()
+        per_lane = [sum(1 for k in range(prof_steps) if k % len(lanes) == l) for l in range(len(lanes))]
+        # ms per forward: front-end kernels (none: the fused kernel builds its pair lists itself), fused kernel, tiled kernels, total
+        stage = np.array([lanes[l][0].timing_at(i) for l in range(len(lanes)) for i in range(per_lane[l])])
+        pipe.set_option("profile", 0)
 
     if world > 1:
         # MAX over ranks of the timed interval and the total of the atoms: over RCCL when every rank has its own device
@@ -526,20 +573,20 @@ def main():
         per_rank = [(dt, float(A))]
         dt_max, atoms_total, cold_max = dt, float(A), (cold_dt or 0.0)
 
-    if held:
+    if held and extras_on:
         qb = held[3].download((A * rep,))
         assert np.array_equal(qb[:A], q) and np.array_equal(qb[-A:], q)          # batch composition does not change the bits
-        for d in held:
-            d.free()
         extras["single_launch"] = {"molecules": B * rep, "launches": nbig, "kernel_ms_avg": big_ms,
                                    "algorithmic_gflop_per_launch": flops * rep / 1e9,
                                    "achieved": flops * rep / (big_ms * 1e-3) / 1e12,
                                    "frac": flops * rep / (big_ms * 1e-3) / 1e12 / peak,
                                    "atoms_per_s": A * rep / (big_ms * 1e-3)}
+    for d in held:
+        d.free()
     q_after = d_q.download((A,))
     assert np.array_equal(q_after, q)                       # the timed steps produced the charges that were checked
 
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras_on:
         # (3) host to host: Pipeline.map on host arrays, a different batch every call (new plan, PCIe both ways)
         # the number of distinct batches shares no factor with the depth, so every lane really sees a different batch (and
         # builds a new plan) on every call; with 8 batches on 8 lanes each lane would keep meeting the same one
@@ -557,7 +604,7 @@ def main():
                                   "what": "Pipeline.map (epnn_forward_xyz_begin/_end): host xyz/x/Q -> host q, a different "
                                           f"batch of {B} molecules (a new plan) every call on every lane, {len(lanes)} in flight; PCIe inclusive, not `value`"}
 
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras_on:
         # (3b) ONE blocking call at a time (what a caller without a pipeline sees): device-resident, the default mode of a
         #      lone handle (molecules of 17+ atoms split over two wavefronts) and one wavefront per molecule
         from epnn_amd.engine import Engine
@@ -615,45 +662,46 @@ def main():
             print(f"[bench] real-data child failed: {child.stderr[-400:]}", file=sys.stderr)
 
     if rank == 0:
-        k_ms = float(stage[:, 1].mean())                   # duration of one launch (hipEvents on its stream)
-        step_ms = dt_max / args.steps * 1e3
-        # `depth` launches of the SAME kernel share the GPU (one batch is ~1024 wavefronts, the machine holds 2048), so
-        # the duration of one launch measures the share of the machine it got, not the kernel's rate.  achieved =
-        # algorithmic flops of a launch / the time the machine spends per launch (= duration / launches in flight).
-        in_flight = max(1.0, k_ms / step_ms)
-        achieved = flops / (k_ms / in_flight * 1e-3) / 1e12
         workload = f"qm9_like_b{B}_N{N}"
-        pmc = committed_pmc(workload)
-        traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
-        executed = pmc.get("executed_gflop_per_launch") if pmc else None
-        executed_bf = pmc.get("executed_bf16_gflop_per_launch") if pmc else None
-        # time the two matrix pipes need for what the kernel executes on them (PMC), per launch
-        pipe_s = (executed * 1e9 / (FP32_MFMA_PEAK_TFLOPS * 1e12) + executed_bf * 1e9 / (BF16_MFMA_PEAK_TFLOPS * 1e12)) if executed is not None and executed_bf is not None else None
-        roof = {"bound": "mfma", "kernel": KNAME, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                "frac": achieved / peak,
-                "peak_basis": f"the bf16 matrix pipe for {bf_share:.3f} of the algorithmic flops -- every Dense layer and the edge products as six bf16 MFMAs "
-                              f"per f32-grade product, {BF16_MFMA_PEAK_TFLOPS:.0f} / 6 = {BF16_MFMA_PEAK_TFLOPS / 6:.1f} TFLOP/s --, f32 MFMA {FP32_MFMA_PEAK_TFLOPS} for the rest "
-                              "(the EPN read-out); peak = total / (f32 part / 157.3 + bf16-pipe part / 416.7)",
-                "frac_vs_f32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS,
-                "frac_with_edge_products_at_f32_peak": achieved / peak_edges_f32,
-                "frac_basis": "algorithmic flops (SURVEY section 8d); the matrix pipes' own utilisation (executed MFMA flops of either kind, PMC) is pipe_frac",
-                "traffic": traffic, "traffic_unit": "bytes/launch (PMC)",
-                "traffic_source": (pmc["command"] + f"; kernel source {pmc['kernel_source_sha']}; profiles/r05_pmc_bench.json") if pmc else None,
-                "algorithmic_gflop_per_launch": flops / 1e9,
-                "executed_gflop_per_launch": executed,
-                "executed_bf16_gflop_per_launch": executed_bf,
-                "pipe_frac": (pipe_s / (k_ms / in_flight * 1e-3)) if pipe_s else None,
-                "kernel_ms_avg": k_ms, "launches_in_flight": in_flight,
-                "frac_of_one_launch_sharing_the_gpu": flops / (k_ms * 1e-3) / 1e12 / peak,
-                "note": "frac = algorithmic flops per launch / (kernel_ms_avg / launches_in_flight) / peak = flops x launches / "
-                        "wall time of the timed region: `launches_in_flight` launches of this kernel share the GPU, so flops / "
-                        "kernel_ms_avg alone (frac_of_one_launch_sharing_the_gpu, what a rocprofv3 --stats average of THIS command "
-                        "gives) is one launch's share of the machine; single_launch is the same kernel with the GPU to itself; "
-                        "pipe_frac = the time the two matrix pipes need for the MFMA flops the kernel executes (PMC: f32 / 157.3 + "
-                        "bf16 / 2500) over the time it takes",
-                "device_ms_per_forward_avg": float(stage[:, 3].mean())}
-        if "single_launch" in extras:
-            roof["single_launch"] = extras["single_launch"]
+        if args.full:
+            k_ms = float(stage[:, 1].mean())                   # duration of one launch (hipEvents on its stream)
+            step_ms = dt_max / args.steps * 1e3
+            # `depth` launches of the SAME kernel share the GPU (one batch is ~1024 wavefronts, the machine holds 2048), so
+            # the duration of one launch measures the share of the machine it got, not the kernel's rate.  achieved =
+            # algorithmic flops of a launch / the time the machine spends per launch (= duration / launches in flight).
+            in_flight = max(1.0, k_ms / step_ms)
+            achieved = flops / (k_ms / in_flight * 1e-3) / 1e12
+            pmc = committed_pmc(workload)
+            traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
+            executed = pmc.get("executed_gflop_per_launch") if pmc else None
+            executed_bf = pmc.get("executed_bf16_gflop_per_launch") if pmc else None
+            # time the two matrix pipes need for what the kernel executes on them (PMC), per launch
+            pipe_s = (executed * 1e9 / (FP32_MFMA_PEAK_TFLOPS * 1e12) + executed_bf * 1e9 / (BF16_MFMA_PEAK_TFLOPS * 1e12)) if executed is not None and executed_bf is not None else None
+            roof = {"bound": "mfma", "kernel": KNAME, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                    "frac": achieved / peak,
+                    "peak_basis": f"the bf16 matrix pipe for {bf_share:.3f} of the algorithmic flops -- every Dense layer and the edge products as six bf16 MFMAs "
+                                  f"per f32-grade product, {BF16_MFMA_PEAK_TFLOPS:.0f} / 6 = {BF16_MFMA_PEAK_TFLOPS / 6:.1f} TFLOP/s --, f32 MFMA {FP32_MFMA_PEAK_TFLOPS} for the rest "
+                                  "(the EPN read-out); peak = total / (f32 part / 157.3 + bf16-pipe part / 416.7)",
+                    "frac_vs_f32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS,
+                    "frac_with_edge_products_at_f32_peak": achieved / peak_edges_f32,
+                    "frac_basis": "algorithmic flops (SURVEY section 8d); the matrix pipes' own utilisation (executed MFMA flops of either kind, PMC) is pipe_frac",
+                    "traffic": traffic, "traffic_unit": "bytes/launch (PMC)",
+                    "traffic_source": (pmc["command"] + f"; kernel source {pmc['kernel_source_sha']}; profiles/r05_pmc_bench.json") if pmc else None,
+                    "algorithmic_gflop_per_launch": flops / 1e9,
+                    "executed_gflop_per_launch": executed,
+                    "executed_bf16_gflop_per_launch": executed_bf,
+                    "pipe_frac": (pipe_s / (k_ms / in_flight * 1e-3)) if pipe_s else None,
+                    "kernel_ms_avg": k_ms, "launches_in_flight": in_flight,
+                    "frac_of_one_launch_sharing_the_gpu": flops / (k_ms * 1e-3) / 1e12 / peak,
+                    "note": "frac = algorithmic flops per launch / (kernel_ms_avg / launches_in_flight) / peak = flops x launches / "
+                            "wall time of the timed region: `launches_in_flight` launches of this kernel share the GPU, so flops / "
+                            "kernel_ms_avg alone (frac_of_one_launch_sharing_the_gpu, what a rocprofv3 --stats average of THIS command "
+                            "gives) is one launch's share of the machine; single_launch is the same kernel with the GPU to itself; "
+                            "pipe_frac = the time the two matrix pipes need for the MFMA flops the kernel executes (PMC: f32 / 157.3 + "
+                            "bf16 / 2500) over the time it takes",
+                    "device_ms_per_forward_avg": float(stage[:, 3].mean())}
+            if "single_launch" in extras:
+                roof["single_launch"] = extras["single_launch"]
         out = {
             "metric": "atoms/sec (inference), QM9-sized batch",
             "value": atoms_total * args.steps / dt_max,
@@ -662,8 +710,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt_max / args.steps * 1e3,
-            "value_cold": (atoms_total * args.steps / cold_max) if cold_max else None,
-            "prewarm_ms": None if args.no_extras else prewarm_ms,
+            "prewarm_ms": prewarm_ms,
             "enqueue_ms": t_enq * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -678,11 +725,17 @@ def main():
                        "pairs_under_cutoff_per_gpu": int(stats[0]), "entry": "epnn_forward_xyz_dev (coordinates in HBM)",
                        "weights": "decay_model_weights", "parallelism": f"molecule-sharded x{world}",
                        "batches_in_flight_per_gpu": n_lanes},
-            "roofline": roof,
-            "order": ("one forward + checks, " + ("" if args.no_extras else "0.3 s idle + warm-up + timed steps (value_cold), parity on the reference's stored outputs, single-launch measurement (+2 launches of it unmeasured, no idle gap: prewarm_ms of GPU load), ")
-                      + f"{max(args.warmup, n_lanes)} warm-up steps, {args.steps} timed steps, the same steps again with hipEvents"
-                      + ("" if args.no_extras else ", host-to-host, real-data rate")),
         }
+        if args.full:
+            out["value_cold"] = (atoms_total * args.steps / cold_max) if cold_max else None
+            out["roofline"] = roof
+            out["order"] = ("one forward + checks, " + ("" if args.no_extras else "0.3 s idle + warm-up + timed steps (value_cold), parity on the reference's stored outputs, single-launch measurement (+2 launches of it unmeasured, no idle gap: prewarm_ms of GPU load), ")
+                            + f"{max(args.warmup, n_lanes)} warm-up steps, {args.steps} timed steps, the same steps again with hipEvents"
+                            + ("" if args.no_extras else ", host-to-host, real-data rate"))
+        else:
+            out["order"] = (f"one forward + checks, {min(max(args.warmup, n_lanes) + args.steps, PREPASS_MAX)} untimed steps, "
+                            "the single-launch batch's launches unmeasured (prewarm_ms of GPU load, no idle gap), "
+                            f"{max(args.warmup, n_lanes)} warm-up steps, {args.steps} timed steps")
         if world > 1:
             out["ranks"] = {"world_size": world, "timing_backend": backend, "rccl_ranks": rccl_ranks,
                             "ranks_per_device": ranks_on_device, "hw_queues_per_rank": int(os.environ["GPU_MAX_HW_QUEUES"]),
@@ -690,7 +743,7 @@ def main():
         for key in ("parity", "real_data", "host_to_host", "blocking_call"):
             if key in extras:
                 out[key] = extras[key]
-        if not args.no_cpu_baseline and world == 1:         # the reported CPU baseline belongs to the N=1 line only
+        if args.full and not args.no_cpu_baseline and world == 1:     # the reported CPU baseline belongs to the N=1 line only
             out["cpu_baseline"] = cpu_baseline(offsets, xyz, x, Q, N, weights)
         real_stdout.write(json.dumps(out) + "\n")
         real_stdout.flush()

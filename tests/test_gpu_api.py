@@ -287,7 +287,7 @@ def test_bench_two_ranks_on_this_box(tmp_path, launcher):
     per-rank rates and their sum; the torch.distributed.run form gives the same kind of line."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "6", "--no-cpu-baseline", "--no-extras"]
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "6", "--full", "--no-cpu-baseline", "--no-extras"]
     if launcher == "self":
         cmd = [sys.executable] + args
     else:
@@ -317,11 +317,14 @@ def test_bench_two_ranks_on_this_box(tmp_path, launcher):
 
 
 def test_bench_line_of_the_drivers_command(tmp_path):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (what the driver runs): ONE JSON line on stdout with every field of
-    the contract, the roofline and CPU-baseline objects, and this project's extras."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full`: ONE JSON line on stdout with every field of the contract,
+    the roofline and CPU-baseline objects, and this project's extras."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    # the hardware queues the bounds below were set with (bench.py's own choice for one rank per device, _lib.load's default);
+    # a smaller count inherited from the environment puts several lanes on one queue and the line reads ~30 % lower
+    env["GPU_MAX_HW_QUEUES"] = "16"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                          cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -349,6 +352,46 @@ def test_bench_line_of_the_drivers_command(tmp_path):
     for key in ("real_data", "host_to_host", "blocking_call", "order"):
         assert key in o, key
     assert o["blocking_call"]["ms"] < o["blocking_call"]["ms_one_wavefront_per_molecule"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path, weights_decay):
+    """A plain `python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (no --full): ONE JSON line with the
+    contract's fields and none of the --full measurements; DIR/charges.npy holds the charges of the last timed step of the
+    bench batch, the same whichever lane ran that step (K = 20 and K = 7), and equal to a forward of that batch here."""
+    import json
+    from epnn_amd import synth
+    from epnn_amd.engine import Engine
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for steps in (20, 7):
+        d = tmp_path / f"out{steps}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "5",
+                              "--dump-outputs", str(d)], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]
+        o = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+            assert key in o, key
+        assert o["steps"] == steps and o["warmup"] == 5 and o["n_gpus"] == 1 and o["higher_is_better"] is True
+        assert o["unit"] == "atoms/s" and o["dtype"] == "f32" and o["config"]["workload"] == "qm9_like_b1024_N29"
+        assert abs(o["value"] - o["config"]["atoms_per_gpu"] / (o["ms_per_step"] * 1e-3)) <= 1e-6 * o["value"]
+        for key in ("roofline", "cpu_baseline", "value_cold", "parity", "real_data", "host_to_host", "blocking_call"):
+            assert key not in o, key
+        assert sorted(os.listdir(d)) == ["charges.npy"]
+        q = np.load(d / "charges.npy")
+        assert q.dtype == np.float32 and q.shape == (o["config"]["atoms_per_gpu"],)
+        dumps.append(q)
+    assert np.array_equal(dumps[0], dumps[1])
+    offsets, xyz, x, Q, N = synth.qm9_like_batch(B=1024, seed=0, N=29)
+    assert np.isfinite(dumps[0]).all()
+    assert np.abs(np.add.reduceat(dumps[0].astype(np.float64), offsets[:-1]) - Q).max() < 1e-4
+    eng = Engine(nx=9, T=5)
+    eng.set_weights(weights_decay)
+    eng.set_option("wave2", 0)                              # the bench's kernel
+    ref = eng.forward_xyz(offsets, xyz, x, Q, N)
+    eng.close()
+    assert np.abs(dumps[0] - ref).max() <= 1e-6
 
 
 def test_smoke_entry():

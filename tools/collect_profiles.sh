@@ -17,20 +17,20 @@ if [ "$PART" = 0 ] || [ "$PART" = 1 ]; then
 # 1. ONE large launch with the GPU to itself: flops / average duration / peak IS the fraction.  The JSON line and the CSV
 #    describe the SAME command (65536 molecules per launch, depth 1): roofline.algorithmic_gflop_per_launch of the line
 #    / AverageNs of k_wave_forward in the CSV / 157.3 = the single-launch fraction
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/big -- python3 $R/bench.py --molecules 65536 --depth 1 --steps 20 --warmup 2 --no-cpu-baseline --no-extras > $OUT/r05_big_launch_line.json 2> $OUT/big.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/big -- python3 $R/bench.py --molecules 65536 --depth 1 --steps 20 --warmup 2 --full --no-cpu-baseline --no-extras > $OUT/r05_big_launch_line.json 2> $OUT/big.err
 stats $OUT/big $OUT/r05_big_launch_kernel_stats.csv
 echo "big launch done"
 # 2. the default bench command (eight batches in flight)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $R/bench.py --no-cpu-baseline --no-extras > $OUT/r05_bench_line_under_rocprof.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $OUT/r05_bench_line_under_rocprof.json 2> $OUT/bench.err
 stats $OUT/bench $OUT/r05_bench_kernel_stats.csv
 echo "bench done"
 # 3. the driver's command
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench20 -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $OUT/r05_bench20_line_under_rocprof.json 2> $OUT/bench20.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench20 -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras > $OUT/r05_bench20_line_under_rocprof.json 2> $OUT/bench20.err
 stats $OUT/bench20 $OUT/r05_bench20_kernel_stats.csv
 # 4. PMC passes (bench.py --pmc runs them as children before touching the GPU) + the un-profiled lines
 cd $R
-python3 bench.py --pmc > $OUT/r05_bench_line.json 2> $OUT/pmc.err       # (first: it rewrites profiles/r05_pmc_bench.json, which the next line quotes)
-python3 bench.py --steps 20 --warmup 5 > $OUT/r05_bench20_line.json 2>> $OUT/pmc.err
+python3 bench.py --pmc --full > $OUT/r05_bench_line.json 2> $OUT/pmc.err       # (first: it rewrites profiles/r05_pmc_bench.json, which the next line quotes)
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/r05_bench20_line.json 2>> $OUT/pmc.err
 cp profiles/r05_pmc_bench.json $OUT/ 2>/dev/null
 echo "pmc done"
 fi
