@@ -61,6 +61,7 @@ SIGNATURES = {
     "epnn_get_gradients": (C.c_int, [_vp, _fp, C.c_int64]),
     "epnn_set_gradients": (C.c_int, [_vp, _fp, C.c_int64]),
     "epnn_train_apply": (C.c_int, [_vp]),
+    "epnn_charges_vjp_xyz": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, _fp, _fp]),
     "epnn_comm_unique_id": (C.c_int, [C.c_char_p]),
     "epnn_comm_init": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
     "epnn_comm_count": (C.c_int, [_vp, C.POINTER(C.c_int32)]),

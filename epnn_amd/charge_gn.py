@@ -367,6 +367,22 @@ class EPNNModel(_Stack):
         """Compact entry: flat atom arrays instead of dense tensors; N defaults to the model's natom."""
         return self._eng().forward_xyz(offsets, xyz, x, Q, self.natom if N is None else N)
 
+    def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N=None):
+        """Charges and sum_i g[i] dq_i/dxyz of a flat batch: (q (A,), gxyz (A, 3)).  With g = dE/dq of a potential E(q), the
+        charges' part of the forces is -gxyz.  N defaults to the model's natom."""
+        return self._eng().charges_vjp_xyz(offsets, xyz, x, Q, g, self.natom if N is None else N)
+
+    def charge_jacobian_xyz(self, xyz, x, Q, N=None):
+        """One molecule: (q (n,), J (n, n, 3)) with J[i, k] = dq_i / dxyz_k, from ONE call on n copies of the molecule with
+        one-hot cotangents."""
+        xyz = np.asarray(xyz, dtype=np.float32)
+        x = np.asarray(x, dtype=np.float32)
+        n = xyz.shape[0]
+        offsets = (np.arange(n + 1) * n).astype(np.int32)
+        q, gxyz = self.charges_vjp_xyz(offsets, np.tile(xyz, (n, 1)), np.tile(x, (n, 1)), np.full(n, Q, dtype=np.float32),
+                                       np.eye(n, dtype=np.float32).ravel(), N)
+        return q[:n], gxyz.reshape(n, n, 3)
+
     def predict_xyz_stream(self, batches, N=None, depth=8):
         """Charges of every (offsets, xyz, x, Q) batch of `batches`, in order, with `depth` batches in flight on the GPU
         (engine.Pipeline.map: the loop of infer.py:62-76 at the throughput of the compact entry)."""

@@ -50,6 +50,7 @@ static void shape_layers(epnn_handle *h) {
 static double edge_basis(const epnn_config &cfg, const std::vector<double> &mu, std::vector<double> &Bout, std::vector<float> &tab);
 static int create_resources(epnn_handle *h);
 extern "C" int epnn_destroy(epnn_handle *h);
+static void xyz_grad_release(epnn_handle *h);   // epnn_api_grad.hip.h
 
 // The HIP runtime maps a process's streams round-robin onto its hardware queues (GPU_MAX_HW_QUEUES of them) in the order the
 // streams are created, and which queues a pipeline's lanes sit on matters: eight lanes on every other queue run the bench batch at
@@ -242,6 +243,7 @@ extern "C" int epnn_destroy(epnn_handle *h) {
         delete ts;
         h->train = nullptr;
     }
+    xyz_grad_release(h);
     if (h->infer_fused) {
         InferFused *is = reinterpret_cast<InferFused *>(h->infer_fused);
         is->theta.release();
@@ -393,3 +395,4 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
 
 #include "epnn_api_dense.hip.h"
 #include "epnn_api_train.hip.h"
+#include "epnn_api_grad.hip.h"

@@ -1,0 +1,100 @@
+// epnn_charges_vjp_xyz: charges and g^T dq/dxyz of a flat coordinate batch (kernels: epnn_grad_xyz.hip.h).
+// Part of the one translation unit epnn_api.hip.
+#pragma once
+
+// The call's own TrainState: the handle's current weights as a flat vector (refreshed when weights_gen moves on) and the
+// scratch of one forward + backward.  The training state (masters, gradients, Adam moments, step) is never read or written.
+static TrainState *xyz_grad_state(epnn_handle *h) {
+    if (!h->xyz_grad) h->xyz_grad = new TrainState();
+    return reinterpret_cast<TrainState *>(h->xyz_grad);
+}
+static void xyz_grad_release(epnn_handle *h) {
+    if (!h->xyz_grad) return;
+    TrainState *xs = reinterpret_cast<TrainState *>(h->xyz_grad);
+    for (DevBuf *b : {&xs->theta, &xs->grad, &xs->m, &xs->v, &xs->part, &xs->arena, &xs->loss, &xs->d_step}) b->release();
+    delete xs;
+    h->xyz_grad = nullptr;
+}
+
+extern "C" int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                    const float *Q, const float *g, float *q_out, float *gxyz_out) {
+    if (!h || !offsets || !xyz || !x || !Q || !g || !q_out || !gxyz_out) EPNN_FAIL("epnn_charges_vjp_xyz: null argument");
+    if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz: B and N must be positive and offsets[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        if (offsets[b + 1] - offsets[b] > N || offsets[b + 1] - offsets[b] < 1) EPNN_FAIL("epnn_charges_vjp_xyz: molecule %d does not fit N=%d", b, N);
+    HIPCHK(hipSetDevice(h->device));
+    if (h->pending.active && finish_forward(h)) return 1;
+    // the weights epnn_forward_xyz would use: a training step still in flight is waited for, device masters it has updated are
+    // pulled into the host copies (pack_weights; what any inference call does first)
+    if (train_quiesce(h) || pack_weights(h)) return 1;
+    TrainState *xs = xyz_grad_state(h);
+    if (!xs->ready || xs->step != h->weights_gen) {
+        train_layout(h, xs);
+        if (xs->theta.ensure((size_t)xs->P * 4)) return 1;
+        std::vector<float> flat;
+        train_gather_host(h, xs, flat);
+        HIPCHK(hipMemcpyAsync(xs->theta.p, flat.data(), (size_t)xs->P * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));               // (`flat` is pageable and goes out of scope)
+        xs->step = h->weights_gen;                              // (this state takes no optimizer steps: `step` keeps the generation)
+        xs->ready = true;
+    }
+    const int nx = h->cfg.nx, A = offsets[B];
+    const size_t pairs = (size_t)B * N * N, slots = (size_t)B * N;
+    // the train path's inputs, staged and padded as epnn_train_step_xyz does; the label slot carries -g / 2 (see XyzGrad)
+    auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t o_xyz = up256((size_t)(B + 1) * 4), o_x = o_xyz + up256((size_t)A * 3 * 4), o_Q = o_x + up256((size_t)A * nx * 4),
+                 o_y = o_Q + up256((size_t)B * 4), in_bytes = o_y + (size_t)A * 4;
+    if (h->pin_train.ensure(in_bytes) || h->s_train.ensure(in_bytes) || h->sd_e.ensure(pairs * EPNN_EDIM * 4) ||
+        h->sd_mask.ensure(pairs * 4) || h->dn_xs.ensure(slots * nx * 4) || h->dn_hs.ensure(slots * EPNN_EDIM * 4) ||
+        h->dn_qs.ensure(slots * 4) || h->sd_out.ensure(slots * 4) || h->tr_realbuf.ensure(slots * 4))
+        return 1;
+    // [BN] loss terms | [BN] predictions | [BN] zeros | [A][3] gxyz | the coincident-atoms flag;  gE [R][48]
+    const size_t o_zero = 2 * slots, o_gx = 3 * slots, o_bad = o_gx + (size_t)A * 3, nout = o_bad + 1;
+    if (xs->loss.ensure(nout * 4) || xs->grad.ensure(pairs * 48 * 4)) return 1;
+    char *stage = h->pin_train.as<char>();
+    memcpy(stage, offsets, (size_t)(B + 1) * 4);
+    memcpy(stage + o_xyz, xyz, (size_t)A * 3 * 4);
+    memcpy(stage + o_x, x, (size_t)A * nx * 4);
+    memcpy(stage + o_Q, Q, (size_t)B * 4);
+    float *ystage = reinterpret_cast<float *>(stage + o_y);
+    for (int a = 0; a < A; ++a) ystage[a] = -0.5f * g[a];
+    HIPCHK(hipMemcpyAsync(h->s_train.p, stage, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const float *dev = h->s_train.as<float>();
+    const int *d_moff = h->s_train.as<int>();
+    hipLaunchKernelGGL(k_t_pad_inputs, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
+                       (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta,
+                       h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
+                       h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+    HIPCHK(hipGetLastError());
+    float *out = xs->loss.as<float>();
+    HIPCHK(hipMemsetAsync(out + o_zero, 0, (slots + (size_t)A * 3 + 1) * 4, h->stream));
+    HIPCHK(hipMemsetAsync(xs->grad.p, 0, pairs * 48 * 4, h->stream));
+    XyzGrad xg{xs, h->sd_out.as<float>(), out + o_zero, xs->grad.as<float>(), h->tr_realbuf.as<int>()};
+    // the padded slots are exact zeros in every input, as in a coordinate train step: the matrix-pipe kernels skip them
+    if (h->opt_train_skip_padded) { h->tr_moff = d_moff; h->tr_real = h->tr_realbuf.as<int>(); }
+    int rc;
+    if (train_is_fused(h, N))
+        rc = train_fwd_bwd_fused(h, B, N, h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
+                                 h->dn_qs.as<float>(), h->sd_out.as<float>(), out + slots, out, false, false, nullptr, false, &xg);
+    else
+        rc = train_fwd_bwd(h, B, N, h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
+                           h->dn_qs.as<float>(), h->sd_out.as<float>(), out + slots, out, false, &xg);
+    h->tr_moff = nullptr;
+    h->tr_real = nullptr;
+    if (rc) return 1;
+    hipLaunchKernelGGL(k_g_xyz, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B, N,
+                       xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
+                       reinterpret_cast<int *>(out + o_bad));
+    HIPCHK(hipGetLastError());
+    // predictions | zeros | gxyz | flag: one download
+    if (h->pin_tout.ensure((nout - slots) * 4)) return 1;
+    float *back = h->pin_tout.as<float>();
+    HIPCHK(hipMemcpyAsync(back, out + slots, (nout - slots) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (reinterpret_cast<const int *>(back)[nout - slots - 1] != 0)
+        EPNN_FAIL("epnn_charges_vjp_xyz: two atoms of a molecule coincide (distance 0: the edge features have no derivative there)");
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < offsets[b + 1] - offsets[b]; ++i) q_out[offsets[b] + i] = back[(size_t)b * N + i];
+    memcpy(gxyz_out, back + (o_gx - slots), (size_t)A * 3 * 4);
+    return 0;
+}

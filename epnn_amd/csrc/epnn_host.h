@@ -253,6 +253,7 @@ struct epnn_handle {
     DevBuf sd_h, sd_e, sd_x, sd_q, sd_mask, sd_out;
     std::vector<int> dn_neff_host;
     void *train = nullptr;            // TrainState (epnn_train.hip.h)
+    void *xyz_grad = nullptr;         // TrainState of epnn_charges_vjp_xyz (epnn_api_grad.hip.h): its own weights and scratch
 };
 
 // ---- fail-closed collectives.  RCCL has no timeout: a rank that leaves an entry point with an error BEFORE a collective its peers

@@ -12,6 +12,7 @@
 #pragma once
 #include "epnn_host.h"
 #include "epnn_train_fused.hip.h"
+#include "epnn_grad_xyz.hip.h"
 
 struct TDense {            // one Dense inside the flat parameter vector
     int offW, offB, n_in, n_out;
@@ -456,11 +457,12 @@ static inline unsigned t_grid(size_t n) { return (unsigned)std::min<size_t>((n +
 
 // Forward + backward of the literal dense algorithm for B molecules padded to N.  Device pointers:
 // e [B][N][N][48], mask [B][N][N], x [B][N][nx], h0 [B][N][48], q0 [B][N], y [B][N] -> pred [B][N], loss [B];
-// gradients are ADDED into ts->grad (caller zeroes it).
+// gradients are ADDED into ts->grad (caller zeroes it).  xg (epnn_charges_vjp_xyz): the state of xg, the seed of xg, no weight
+// gradients, the edge columns of every first Dense's dX added into xg->gE.
 static int train_fwd_bwd(epnn_handle *h, int B, int N, const float *d_e, const float *d_mask, const float *d_x,
                          const float *d_h0, const float *d_q0, const float *d_y, float *d_pred, float *d_loss,
-                         bool size_only = false) {
-    TrainState *ts = train_state(h);
+                         bool size_only = false, const XyzGrad *xg = nullptr) {
+    TrainState *ts = xg ? xg->ts : train_state(h);
     if (!ts->ready) EPNN_FAIL("training: call epnn_train_init first");
     const int T = h->cfg.T, nx = h->cfg.nx, H = EPNN_EDIM, E = EPNN_EDIM, F = nx + H + 1, D = 2 * F + E;
     const int BN = B * N;
@@ -475,7 +477,7 @@ static int train_fwd_bwd(epnn_handle *h, int B, int N, const float *d_e, const f
     const TDense *UL = genu ? ts->updv.data() : ts->upd;
     size_t part_elems = (size_t)(D + 1) * 48;
     for (int l = 0; l < NU; ++l) part_elems = std::max(part_elems, (size_t)(UL[l].n_in + 1) * UL[l].n_out);
-    if (ts->part.ensure((size_t)NSL * part_elems * 4)) return 1;
+    if (!xg && ts->part.ensure((size_t)NSL * part_elems * 4)) return 1;
     // ---- arena
     size_t need = 0;
     auto sz = [&](size_t n) { size_t o = need; need += (n + 63) & ~size_t(63); return o; };
@@ -521,6 +523,7 @@ static int train_fwd_bwd(epnn_handle *h, int B, int N, const float *d_e, const f
             hipLaunchKernelGGL(k_t_mm_dx, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, dY, Ypost, theta + d.offW, dX,
                                (int)rows, d.n_in, d.n_out, ntk);
         }
+        if (xg) return;                                 // (charge gradients: the weights' are not formed)
         // ~64 rows per slice: the pair-row GEMMs (B*N*N rows) spread over the whole GPU, the per-atom ones stay small
         const int nsl = (int)std::min<size_t>(NSL, std::max<size_t>(1, rows / 64));
         const int tot = (d.n_in + 1) * d.n_out;
@@ -571,7 +574,10 @@ static int train_fwd_bwd(epnn_handle *h, int B, int N, const float *d_e, const f
     HIPCHK(hipMemcpyAsync(d_pred, qcur, (size_t)BN * 4, hipMemcpyDeviceToDevice, st));
     // ================================================================ loss (charge_gn.py:397-398)
     float *gq = P(o_gq), *gfeat = P(o_gfeat), *gh = P(o_gh), *da = P(o_da);
-    hipLaunchKernelGGL(k_t_loss, dim3(B), dim3(64), 0, st, d_y, qcur, gq, d_loss, N);
+    hipLaunchKernelGGL(k_t_loss, dim3(B), dim3(64), 0, st, xg ? xg->yseed : d_y, xg ? xg->zero : qcur, gq, d_loss, N);
+    auto edge_cols = [&](const float *dX) {
+        if (xg) hipLaunchKernelGGL(k_g_edge_dx, dim3(t_grid(R * 48)), dim3(256), 0, st, dX, xg->gE, (int)R, D, 2 * F, N, xg->real);
+    };
     HIPCHK(hipMemsetAsync(gfeat, 0, (size_t)BN * H * 4, st));
     // ================================================================ backward: EPN
     for (int t = T - 1; t >= 0; --t) {
@@ -584,6 +590,7 @@ static int train_fwd_bwd(epnn_handle *h, int B, int N, const float *d_e, const f
             dense_bwd(H2, df, nullptr, ts->pas[t][2], P(o_dA), R);          // dH2 (post-activation gradient)
             dense_bwd(H1, P(o_dA), H2, ts->pas[t][1], P(o_dB), R);          // masks dH2 by H2 > 0
             dense_bwd(X, P(o_dB), H1, ts->pas[t][0], P(o_dX), R);
+            edge_cols(P(o_dX));
             hipLaunchKernelGGL(k_t_rows_bwd, dim3(t_grid((size_t)BN * F)), dim3(256), 0, st, P(o_dX), da, B, N, F, E, dir);
         }
         hipLaunchKernelGGL(k_t_epn_fold, dim3(t_grid((size_t)BN * (H + 1))), dim3(256), 0, st, da, gfeat, gq, BN, nx, H);
@@ -601,6 +608,7 @@ static int train_fwd_bwd(epnn_handle *h, int B, int N, const float *d_e, const f
         dense_bwd(P(g.H2), P(o_dC), nullptr, ts->msg[t][2], P(o_dA), R);
         dense_bwd(P(g.H1), P(o_dA), P(g.H2), ts->msg[t][1], P(o_dB), R);
         dense_bwd(P(g.X), P(o_dB), P(g.H1), ts->msg[t][0], P(o_dX), R);
+        edge_cols(P(o_dX));
         HIPCHK(hipMemsetAsync(da, 0, (size_t)BN * F * 4, st));
         hipLaunchKernelGGL(k_t_rows_bwd, dim3(t_grid((size_t)BN * F)), dim3(256), 0, st, P(o_dX), da, B, N, F, E, 0);
         hipLaunchKernelGGL(k_t_gh_prev, dim3(t_grid((size_t)BN * H)), dim3(256), 0, st, P(o_dU0), nm, da, gh, BN, nx, H, 32);
@@ -615,8 +623,9 @@ static int train_fwd_bwd(epnn_handle *h, int B, int N, const float *d_e, const f
 // they were 18 launches of their own).  d_loss receives one loss term per atom slot [B][N].
 static int train_fwd_bwd_fused(epnn_handle *h, int B, int N, const float *d_e, const float *d_mask, const float *d_x,
                                const float *d_h0, const float *d_q0, const float *d_y, float *d_pred, float *d_loss,
-                               bool size_only = false, bool adam_now = false, float *out_host = nullptr, bool step_on_device = false) {
-    TrainState *ts = train_state(h);
+                               bool size_only = false, bool adam_now = false, float *out_host = nullptr, bool step_on_device = false,
+                               const XyzGrad *xg = nullptr) {
+    TrainState *ts = xg ? xg->ts : train_state(h);
     if (!ts->ready) EPNN_FAIL("training: call epnn_train_init first");
     ts->host_out = out_host != nullptr;
     if (step_on_device && ts->d_step.ensure(8)) return 1;
@@ -726,6 +735,14 @@ static int train_fwd_bwd_fused(epnn_handle *h, int B, int N, const float *d_e, c
     // sweeps alternate between two dz1 buffers, so a launch may still read the previous one's while it writes its own.
     int nb = 0;
     int pmode = -1, poW1 = 0, pfirst = 0;
+    // charge gradients (xg): behind every sweep, the edge columns of its dz1 W1^T into gE (the sweeps alternate between two dz1
+    // buffers: the next-but-one overwrites this one)
+    auto edge_rows = [&](const float *dz1, const TDense &W1, int nd) {
+        if (!xg) return;
+        const unsigned grid = (unsigned)std::min<size_t>((((R + 15) / 16) + 3) / 4, 4096);
+        hipLaunchKernelGGL(k_g_edge_dz1, dim3(grid), dim3(256), 0, st, dz1, theta + W1.offW + 2 * F * 32, xg->gE, (int)R, nd, R * 32,
+                           N, xg->real);
+    };
     auto chain = [&](TfPair &A) {
         A.dz1 = P((nb & 1) ? o_dz1b : o_dz1a);
         A.pdz1 = P((nb & 1) ? o_dz1a : o_dz1b);
@@ -741,9 +758,10 @@ static int train_fwd_bwd_fused(epnn_handle *h, int B, int N, const float *d_e, c
     for (int t = T - 1; t >= 0; --t) {
         TfPair A = pair_args(ts->pas[t], feats, t ? P(es[t - 1].qn) : d_q0);
         A.H1 = P(es[t].H1); A.H2 = P(es[t].H2); A.part = P(o_pp[t]);
-        A.first = t == T - 1; A.y = d_y; A.pred = d_pred;
+        A.first = t == T - 1; A.y = xg ? xg->yseed : d_y; A.pred = xg ? xg->zero : d_pred;
         chain(A);
         hipLaunchKernelGGL(k_tb_pair_bwd_mm<1>, dim3(bwd_grid), dim3(EPNN_TF_NT), lds_bwd_mm(2), st, A, TfUpd{});
+        edge_rows(A.dz1, ts->pas[t][0], 2);
         pmode = 1; poW1 = ts->pas[t][0].offW; pfirst = t == T - 1;
     }
     for (int t = T - 1; t >= 0; --t) {
@@ -754,7 +772,12 @@ static int train_fwd_bwd_fused(epnn_handle *h, int B, int N, const float *d_e, c
         TfUpd Ub = upd_args(t, hin);                                   // (the update MLP's backward first)
         Ub.dU0 = P(((nb - 1) & 1) ? o_dU0b : o_dU0);                   // chain() has counted this launch
         hipLaunchKernelGGL(k_tb_pair_bwd_mm<0>, dim3(bwd_grid), dim3(EPNN_TF_NT), lds_bwd_mm(1), st, A, Ub);
+        edge_rows(A.dz1, ts->msg[t][0], 1);
         pmode = 0; poW1 = ts->msg[t][0].offW; pfirst = 0;
+    }
+    if (xg) {                                       // (charge gradients: the weights' partials are not summed)
+        HIPCHK(hipGetLastError());
+        return 0;
     }
     // ================================================================ gradient = sum of the workgroups' partials (+ Adam)
     TfReduce Rd{};

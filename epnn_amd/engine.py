@@ -270,6 +270,20 @@ class Engine:
                                            C.byref(loss), int(bool(apply))), self.lib)
         return q, loss.value
 
+    def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N):
+        """Flat batch and a cotangent g (A,) of the charges -> (q (A,), gxyz (A, 3) = sum_i g[i] dq_i/dxyz).  Touches no
+        training state; works without train_init."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        xyz, x, Q, g = _f32(xyz), _f32(x), _f32(Q), _f32(g)
+        B, A = len(offsets) - 1, int(offsets[-1])
+        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,) or g.shape != (A,):
+            raise EpnnError("charges_vjp_xyz: array shapes do not match offsets")
+        q = np.empty((A,), dtype=np.float32)
+        gxyz = np.empty((A, 3), dtype=np.float32)
+        check(self.lib.epnn_charges_vjp_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(g), fptr(q),
+                                            fptr(gxyz)), self.lib)
+        return q, gxyz
+
     def get_gradients(self):
         g = np.empty((self.param_count(),), dtype=np.float32)
         check(self.lib.epnn_get_gradients(self.h, fptr(g), g.size), self.lib)

@@ -178,6 +178,21 @@ int epnn_train_step_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, co
 int epnn_get_gradients(epnn_handle *h, float *out, int64_t count);
 int epnn_set_gradients(epnn_handle *h, const float *in, int64_t count);
 int epnn_train_apply(epnn_handle *h);
+/* Charge gradients with respect to the coordinates (forces of a potential whose energy depends on the charges): for the flat
+ * batch epnn_forward_xyz takes and a cotangent g[A] (one value per real atom), q_out[A] = the charges and
+ * gxyz_out[A][3] = sum_i g[i] dq_i/dxyz, molecule by molecule.  N enters as in the forward (padded partners contribute to the
+ * message sums); the pair and node masks are constants (they come from comparisons); the cutoff factor is smooth at the cutoff.
+ * The handle's cutoff, eta and Gaussian centres are used, as in the forward.  Contract:
+ *   - works on a handle that never called epnn_train_init;
+ *   - uses the handle's current weights, the ones epnn_forward_xyz would use (including weights a training loop has just updated);
+ *   - leaves weights, gradients (epnn_get_gradients), Adam moments and the step count untouched;
+ *   - waits first for a "train_async" step still in flight;
+ *   - every shape and update `layers` epnn_train_step_xyz takes: the row-fused kernels up to N = 96 ("train_fused"), the
+ *     layer-by-layer ones above that and for update layers other than [32, 32];
+ *   - fails (epnn_last_error) on a bad offsets array, a molecule that does not fit N, a null pointer, or two coincident atoms.
+ * Bit-reproducible; a molecule's rows do not depend on the rest of the batch (at the same N). */
+int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                         const float *g, float *q_out, float *gxyz_out);
 /* RCCL communicator (one rank per GPU): the gradient is summed with ONE ncclAllReduce of the flat vector; the same
  * communicator carries the row exchange of a partitioned large system (epnn_set_partition with exchange == NULL). */
 int epnn_comm_unique_id(char *out128);
