@@ -227,7 +227,7 @@ extern "C" int epnn_destroy(epnn_handle *h) {
                       &h->d_status, &h->d_guard, &h->d_bsum, &h->d_pi, &h->d_pj, &h->d_psym, &h->d_pe, &h->d_pwi, &h->d_pwj, &h->s_xyz,
                       &h->s_train, &h->s_misc, &h->s_gx, &h->s_pt, &h->f_pw, &h->d_etab, &h->l_a, &h->l_P, &h->l_R, &h->l_zp, &h->l_S0,
                       &h->l_corr, &h->l_dl, &h->l_tiles, &h->l_csr_off, &h->l_csr_ent, &h->l_cnt, &h->l_nm,
-                      &h->d_deg, &h->d_incoff, &h->d_nbr, &h->d_nearbits, &h->d_desti, &h->d_destj, &h->d_prec, &h->l_Nn, &h->l_Yb, &h->l_qbuf,
+                      &h->d_deg, &h->d_incoff, &h->d_nbr, &h->d_nearbits, &h->d_box, &h->d_desti, &h->d_destj, &h->d_prec, &h->l_Nn, &h->l_Yb, &h->l_qbuf,
                       &h->l_Pst, &h->l_Rst, &h->l_lmol, &h->l_typrow, &h->l_typtab, &h->l_stype, &h->l_typhash,
                       &h->l_stasks, &h->l_schunk, &h->l_sfin, &h->l_sfrac, &h->l_stasks2, &h->l_sfrac2, &h->dn_xs, &h->dn_hs, &h->dn_qs, &h->dn_nms,
                       &h->dn_flag, &h->dn_neff, &h->dn_den, &h->tr_realbuf, &h->dn_xf, &h->dn_hf, &h->dn_qf, &h->dn_nmf, &h->dn_out, &h->sd_h,
@@ -261,6 +261,7 @@ extern "C" int epnn_destroy(epnn_handle *h) {
     h->pin_tout.release();
     h->pin_out.release();
     h->pin_neff.release();
+    h->pin_box.release();
     if (h->ev_t1) (void)hipEventDestroy(h->ev_t1);
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);

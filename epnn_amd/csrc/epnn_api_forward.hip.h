@@ -374,29 +374,36 @@ static int make_front_args(epnn_handle *h, const float *d_xyz, FrontArgs &F) {
     }
     return 0;
 }
-static int run_frontend_xyz(epnn_handle *h, const FrontArgs &F) {
+// d_box: the box rows [B][3] of a periodic forward (minimum-image distances), null for open molecules
+static int run_frontend_xyz(epnn_handle *h, const FrontArgs &F, const float *d_box = nullptr) {
     const unsigned rows = (unsigned)((F.A + 3) / 4);
-    hipLaunchKernelGGL(k_front_count, dim3(rows), dim3(256), 0, h->stream, F);
+    if (d_box) hipLaunchKernelGGL(k_front_count_pbc, dim3(rows), dim3(256), 0, h->stream, F, d_box);
+    else hipLaunchKernelGGL(k_front_count, dim3(rows), dim3(256), 0, h->stream, F);
     hipLaunchKernelGGL(k_front_scan_both, dim3(1), dim3(1024), 0, h->stream, F);
-    hipLaunchKernelGGL(k_front_fill, dim3(rows), dim3(256), 0, h->stream, F);
+    if (d_box) hipLaunchKernelGGL(k_front_fill_pbc, dim3(rows), dim3(256), 0, h->stream, F, d_box);
+    else hipLaunchKernelGGL(k_front_fill, dim3(rows), dim3(256), 0, h->stream, F);
     hipLaunchKernelGGL(k_front_link, dim3((unsigned)std::min<size_t>(((size_t)h->pcap + 255) / 256, 1024)), dim3(256), 0, h->stream, F);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 static bool wave_front_ok(const epnn_handle *h) { return h->opt_wave_front && h->cfg.e_dim == EPNN_EDIM && h->edge_res < 1e-8; }
-static int enqueue_forward_planned(epnn_handle *h, const float *d_xyz, const float *d_x, const float *d_Q, float *d_q, bool front_ok);
+static int enqueue_forward_planned(epnn_handle *h, const float *d_xyz, const float *d_x, const float *d_Q, float *d_q, bool front_ok,
+                                   const float *d_box);
+// d_box: box rows [B][3] on the device (periodic forward) or null.  A periodic forward always takes the separate front-end: the
+// fused kernels read its pair list (molecules of up to 32 atoms), everything larger is tiled, as with "wave_front" 0.
 static int enqueue_forward_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz,
-                               const float *d_x, const float *d_Q, float *d_q) {
+                               const float *d_x, const float *d_Q, float *d_q, const float *d_box = nullptr) {
     HIPCHK(hipSetDevice(h->device));
     if (pack_weights(h)) return 1;
-    const bool front_ok = wave_front_ok(h);
+    const bool front_ok = !d_box && wave_front_ok(h);
     if (build_plan(h, B, N, offsets, front_ok)) return 1;
     // from here to the first row exchange of a partitioned system a failure is reported to the other processes (comm_guard)
     if (large_exchanges_over_rccl(h, 1)) h->guard_pending = true;
-    return comm_guard_exit(h, enqueue_forward_planned(h, d_xyz, d_x, d_Q, d_q, front_ok), "partitioned forward (row exchange)");
+    return comm_guard_exit(h, enqueue_forward_planned(h, d_xyz, d_x, d_Q, d_q, front_ok, d_box), "partitioned forward (row exchange)");
 }
-static int enqueue_forward_planned(epnn_handle *h, const float *d_xyz, const float *d_x, const float *d_Q, float *d_q, bool front_ok) {
+static int enqueue_forward_planned(epnn_handle *h, const float *d_xyz, const float *d_x, const float *d_Q, float *d_q, bool front_ok,
+                                   const float *d_box) {
     const Plan &P = h->plan;
     // Small molecules (fused kernel): the wavefront builds its molecule's pair list itself (slots for every i<j pair, so
     // nothing can overflow; G products in the 16-dimensional edge basis, used only when it represents the features to
@@ -431,9 +438,9 @@ static int enqueue_forward_planned(epnn_handle *h, const float *d_xyz, const flo
     const FrontArgs *front_later = nullptr;
     if (!pure) {
         if (make_front_args(h, d_xyz, F)) return 1;
-        if (h->opt_large_merge && !P.large_list.empty() && (front_small || P.fused_count() == 0)) front_later = &F;
+        if (!d_box && h->opt_large_merge && !P.large_list.empty() && (front_small || P.fused_count() == 0)) front_later = &F;
         else {
-            if (run_frontend_xyz(h, F)) return 1;
+            if (run_frontend_xyz(h, F, d_box)) return 1;
             if (ev) { HIPCHK(hipEventRecord(ev[1], h->stream)); *ev_has |= 1; }
         }
     }
@@ -503,25 +510,62 @@ static int finish_forward(epnn_handle *h) {
     EPNN_FAIL("forward: capacity regrow did not converge");
 }
 
-extern "C" int epnn_forward_xyz_dev(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz,
-                                    const float *d_x, const float *d_Q, float *d_q_out) {
-    if (!h || !offsets || !d_xyz || !d_x || !d_Q || !d_q_out) EPNN_FAIL("epnn_forward_xyz_dev: null argument");
+// Box rows of a periodic forward (include/epnn.h): finite, >= 0, and a periodic length of at least twice the cutoff
+static int check_box(int B, const float *box, double cutoff, const char *what) {
+    if (!box) EPNN_FAIL("%s: null box", what);
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < 3; ++k) {
+            const float L = box[3 * b + k];
+            uint32_t bits;                        // (the library is built with -ffinite-math-only: std::isfinite would fold to true)
+            memcpy(&bits, &L, 4);
+            if ((bits & 0x7f800000u) == 0x7f800000u || L < 0.f)
+                EPNN_FAIL("%s: box[%d][%d] = %g: a length must be finite and >= 0 (0: open axis)", what, b, k, (double)L);
+            if (L > 0.f && (double)L < 2.0 * cutoff)
+                EPNN_FAIL("%s: box[%d][%d] = %g is shorter than twice the cutoff (%g)", what, b, k, (double)L, 2.0 * cutoff);
+        }
+    return 0;
+}
+
+// the box rows of a forward of the device-resident entry, in the status slot it uses (the forward two calls back, which used the
+// same slot, has been waited for): page-locked copy, one upload on the stream
+static const float *upload_box(epnn_handle *h, int slot, const std::vector<float> &box) {
+    const size_t stride = (box.size() * 4 + 255) & ~size_t(255);
+    if (h->pin_box.cap < 2 * stride || h->d_box.cap < 2 * stride) {
+        if (hipStreamSynchronize(h->stream) != hipSuccess || h->pin_box.ensure(2 * stride) || h->d_box.ensure(2 * stride)) return nullptr;
+    }
+    char *hp = h->pin_box.as<char>() + slot * stride;
+    char *dp = h->d_box.as<char>() + slot * stride;
+    memcpy(hp, box.data(), box.size() * 4);
+    if (hipMemcpyAsync(dp, hp, box.size() * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return nullptr;
+    return reinterpret_cast<const float *>(dp);
+}
+
+// h_box: host box rows of a periodic forward, uploaded by every enqueue of it (a redo too); d_box: box rows already on the device
+// (staged with the host entry's inputs).  Both null: open molecules.
+static int forward_xyz_dev_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz, const float *d_x,
+                                const float *d_Q, float *d_q_out, const float *h_box, const float *d_box) {
     auto &pd = h->pending;
     const void *key[4] = {d_xyz, d_x, d_Q, d_q_out};
+    std::vector<float> boxv;
+    if (h_box) boxv.assign(h_box, h_box + (size_t)B * 3);
     // The SAME forward again (same batch, same device buffers: a trajectory, a benchmark loop) while the previous one may still need
     // a look at its status: enqueue first, check after -- nothing is (re)allocated for a plan that is reused, the two forwards
     // report through two status slots, and a forward that did overflow is redone with its successor behind it.  (Waiting for the
     // previous forward before enqueueing left the GPU idle for the host's 15 us between any two forwards of the tiled path.)
     const Plan &P0 = h->plan;
+    // (a periodic forward is the same forward only in the same cells: a changed box, as in an NPT run, waits for the one before)
     const bool ahead = h->opt_forward_ahead && pd.active && memcmp(pd.key, key, sizeof(key)) == 0 && P0.valid && P0.B == B && P0.N == N &&
-                       (int)P0.offsets.size() == B + 1 && memcmp(P0.offsets.data(), offsets, (B + 1) * sizeof(int)) == 0 && h->part_world == 1;
+                       (int)P0.offsets.size() == B + 1 && memcmp(P0.offsets.data(), offsets, (B + 1) * sizeof(int)) == 0 && h->part_world == 1 &&
+                       !d_box && pd.box == boxv;
     if (!ahead && pd.active && finish_forward(h)) return 1;     // previous call may still need a regrow
     const int old_slot = pd.slot;
     std::function<int()> old_redo;
     if (ahead) old_redo = pd.redo;
     h->st_slot = ahead ? (old_slot ^ 1) : h->st_slot;
     h->h_status = h->h_status_base + 4 * h->st_slot;
-    if (enqueue_forward_xyz(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out)) return 1;
+    const float *db = d_box;
+    if (!boxv.empty() && !(db = upload_box(h, h->st_slot, boxv))) EPNN_FAIL("epnn_forward_xyz_pbc_dev: box upload failed");
+    if (enqueue_forward_xyz(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, db)) return 1;
     if (h->last_front && !ahead) {            // nothing can overflow with the in-kernel front-end: no need to look at this forward
         pd.active = false;                    // again, the caller may queue the next one right away (the headline loop: nothing else
         return 0;                             // is done per call)
@@ -529,8 +573,10 @@ extern "C" int epnn_forward_xyz_dev(epnn_handle *h, int B, int N, const int32_t 
     HIPCHK(hipEventRecord(h->ev_done[h->st_slot], h->stream));
     const bool new_active = !h->last_front;
     std::vector<int> offs(offsets, offsets + B + 1);
-    auto redo = [h, B, N, offs, d_xyz, d_x, d_Q, d_q_out]() {
-        const int rc = enqueue_forward_xyz(h, B, N, offs.data(), d_xyz, d_x, d_Q, d_q_out);
+    auto redo = [h, B, N, offs, d_xyz, d_x, d_Q, d_q_out, boxv, d_box]() {
+        const float *db = d_box;
+        if (!boxv.empty() && !(db = upload_box(h, h->st_slot, boxv))) EPNN_FAIL("epnn_forward_xyz_pbc_dev: box upload failed");
+        const int rc = enqueue_forward_xyz(h, B, N, offs.data(), d_xyz, d_x, d_Q, d_q_out, db);
         if (!rc) (void)hipEventRecord(h->ev_done[h->st_slot], h->stream);
         return rc;
     };
@@ -564,7 +610,22 @@ extern "C" int epnn_forward_xyz_dev(epnn_handle *h, int B, int N, const int32_t 
     pd.redo = redo;
     pd.slot = h->st_slot;
     memcpy(pd.key, key, sizeof(key));
+    pd.box.swap(boxv);
     return 0;
+}
+
+extern "C" int epnn_forward_xyz_dev(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz,
+                                    const float *d_x, const float *d_Q, float *d_q_out) {
+    if (!h || !offsets || !d_xyz || !d_x || !d_Q || !d_q_out) EPNN_FAIL("epnn_forward_xyz_dev: null argument");
+    return forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, nullptr, nullptr);
+}
+
+extern "C" int epnn_forward_xyz_pbc_dev(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz, const float *d_x,
+                                        const float *d_Q, const float *box, float *d_q_out) {
+    if (!h || !offsets || !d_xyz || !d_x || !d_Q || !d_q_out) EPNN_FAIL("epnn_forward_xyz_pbc_dev: null argument");
+    if (B < 1) EPNN_FAIL("epnn_forward_xyz_pbc_dev: empty batch");
+    if (check_box(B, box, (double)h->cfg.cutoff, "epnn_forward_xyz_pbc_dev")) return 1;
+    return forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, box, nullptr);
 }
 
 // Row-block partition of a SINGLE large system over `world` processes: the all-pairs sweep -- all of
@@ -595,9 +656,9 @@ extern "C" int epnn_sync(epnn_handle *h) {
 // its arrays at once), uploads + kernel + download of the charges are queued, and the call returns without waiting for
 // the GPU.  end: waits and hands the charges over.  One forward per handle between begin and end; several handles
 // (engine.Pipeline) keep several batches in flight.
-extern "C" int epnn_forward_xyz_begin(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz,
-                                      const float *x, const float *Q) {
-    if (!h || !offsets || !xyz || !x || !Q) EPNN_FAIL("epnn_forward_xyz_begin: null argument");
+// box: host box rows [B][3] of a periodic forward (staged with the other inputs), or null
+static int forward_xyz_begin_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                  const float *box) {
     HIPCHK(hipSetDevice(h->device));
     if (h->hostcall.active) EPNN_FAIL("epnn_forward_xyz_begin: collect the previous forward with epnn_forward_xyz_end first");
     if (B < 1) EPNN_FAIL("epnn_forward_xyz: empty batch");
@@ -607,7 +668,8 @@ extern "C" int epnn_forward_xyz_begin(epnn_handle *h, int B, int N, const int32_
     if (h->pending.active && finish_forward(h)) return 1;
     auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
     const size_t n_xyz = (size_t)A * 3, n_x = (size_t)A * nx;
-    const size_t o_x = up256(n_xyz * 4), o_Q = o_x + up256(n_x * 4), in_bytes = o_Q + (size_t)B * 4;
+    const size_t o_x = up256(n_xyz * 4), o_Q = o_x + up256(n_x * 4), o_box = o_Q + up256((size_t)B * 4),
+                 in_bytes = box ? o_box + (size_t)B * 12 : o_Q + (size_t)B * 4;
     // ONE host-to-device copy per forward: the inputs are staged behind the plan's index arrays in the same page-locked
     // buffer, whose device mirror has the same layout.  (Separate copies for xyz, x, Q and the index arrays kept the copy
     // engine busy 73 us per batch of 1024 molecules -- of the 86 us the GPU needs for it -- and the kernels of different
@@ -624,6 +686,7 @@ extern "C" int epnn_forward_xyz_begin(epnn_handle *h, int B, int N, const int32_
     memcpy(stage, xyz, n_xyz * 4);
     memcpy(stage + o_x, x, n_x * 4);
     memcpy(stage + o_Q, Q, (size_t)B * 4);
+    if (box) memcpy(stage + o_box, box, (size_t)B * 12);
     const size_t from = fresh ? 0 : off;
     HIPCHK(hipMemcpyAsync(h->d_ctl.as<char>() + from, h->pin_ctl.as<char>() + from, off + in_bytes - from, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipEventRecord(h->ev_ctl, h->stream));
@@ -635,10 +698,16 @@ extern "C" int epnn_forward_xyz_begin(epnn_handle *h, int B, int N, const int32_
     // no device-to-host copy is queued.  With one, the copy engine's queue holds "results of batch k" (which waits for
     // kernel k) in front of "inputs of batch k+1", and the kernels of different handles run one after the other instead
     // of side by side (kernel trace: 0.75 instead of 4.2 kernels in flight).
-    if (epnn_forward_xyz_dev(h, B, N, offsets, d_xyz, d_x, d_Q, h->pin_out.as<float>())) return 1;
+    const float *d_box = box ? reinterpret_cast<const float *>(dev + o_box) : nullptr;
+    if (forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, h->pin_out.as<float>(), nullptr, d_box)) return 1;
     h->hostcall.active = true;
     h->hostcall.A = A;
     return 0;
+}
+extern "C" int epnn_forward_xyz_begin(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz,
+                                      const float *x, const float *Q) {
+    if (!h || !offsets || !xyz || !x || !Q) EPNN_FAIL("epnn_forward_xyz_begin: null argument");
+    return forward_xyz_begin_impl(h, B, N, offsets, xyz, x, Q, nullptr);
 }
 
 extern "C" int epnn_forward_xyz_end(epnn_handle *h, float *q_out) {
@@ -658,16 +727,32 @@ extern "C" int epnn_forward_xyz(epnn_handle *h, int B, int N, const int32_t *off
     return epnn_forward_xyz_end(h, q_out);
 }
 
+extern "C" int epnn_forward_xyz_pbc(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                    const float *Q, const float *box, float *q_out) {
+    if (!h || !offsets || !xyz || !x || !Q || !q_out) EPNN_FAIL("epnn_forward_xyz_pbc: null argument");
+    if (B < 1) EPNN_FAIL("epnn_forward_xyz_pbc: empty batch");
+    if (check_box(B, box, (double)h->cfg.cutoff, "epnn_forward_xyz_pbc")) return 1;
+    if (h->hostcall.active) EPNN_FAIL("epnn_forward_xyz_pbc: collect the forward begun with epnn_forward_xyz_begin first");
+    if (forward_xyz_begin_impl(h, B, N, offsets, xyz, x, Q, box)) return 1;
+    return epnn_forward_xyz_end(h, q_out);
+}
+
 // ------------------------------------------------------------------------------------------------ edges
+// box: the cell [3] of a periodic call (staged behind the coordinates, minimum-image distances), or null
 static int edges_impl(epnn_handle *h, int n, const float *xyz, int num, double cutoff, double eta, const double *d_mu,
-                      float *e_out, double *c_out) {
+                      float *e_out, double *c_out, const float *box = nullptr) {
     const size_t total = (size_t)n * n * num, nn = (size_t)n * n;
-    if (h->s_xyz.ensure((size_t)n * 3 * 4) || h->s_misc.ensure(total * 4 + (c_out ? nn * 8 + 8 : 0))) return 1;
+    if (h->s_xyz.ensure((size_t)n * 3 * 4 + (box ? 12 : 0)) || h->s_misc.ensure(total * 4 + (c_out ? nn * 8 + 8 : 0))) return 1;
     double *d_c = c_out ? reinterpret_cast<double *>(h->s_misc.as<char>() + ((total * 4 + 7) & ~size_t(7))) : nullptr;
     HIPCHK(hipMemcpyAsync(h->s_xyz.p, xyz, (size_t)n * 3 * 4, hipMemcpyHostToDevice, h->stream));
+    if (box) HIPCHK(hipMemcpyAsync(h->s_xyz.as<float>() + (size_t)n * 3, box, 12, hipMemcpyHostToDevice, h->stream));
     const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(k_edges_dense, dim3(grid), dim3(256), 0, h->stream, h->s_xyz.as<float>(), n, num, cutoff, eta, d_mu,
-                       h->s_misc.as<float>(), d_c);
+    if (box)
+        hipLaunchKernelGGL(k_edges_dense_pbc, dim3(grid), dim3(256), 0, h->stream, h->s_xyz.as<float>(), h->s_xyz.as<float>() + (size_t)n * 3,
+                           n, num, cutoff, eta, d_mu, h->s_misc.as<float>(), d_c);
+    else
+        hipLaunchKernelGGL(k_edges_dense, dim3(grid), dim3(256), 0, h->stream, h->s_xyz.as<float>(), n, num, cutoff, eta, d_mu,
+                           h->s_misc.as<float>(), d_c);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(e_out, h->s_misc.p, total * 4, hipMemcpyDeviceToHost, h->stream));
     if (c_out) HIPCHK(hipMemcpyAsync(c_out, d_c, nn * 8, hipMemcpyDeviceToHost, h->stream));
@@ -684,9 +769,8 @@ extern "C" int epnn_edges(epnn_handle *h, int n, const float *xyz, float *e_out)
 
 // get_init_edges with the reference's own parameters (charge_gn.py:122: num, and the constants 3.0 / 2.0 of :148-161 as
 // arguments): any number of channels, plus the cutoff weights C[n][n] (float64) the reference returns tiled.
-extern "C" int epnn_edges_ex(epnn_handle *h, int n, const float *xyz, int num, double cutoff, double eta, float *e_out,
-                             double *c_out) {
-    if (!h || !xyz || !e_out || n < 1 || num < 2 || !(cutoff > 0.1)) EPNN_FAIL("epnn_edges_ex: bad argument");
+static int edges_ex_impl(epnn_handle *h, int n, const float *xyz, int num, double cutoff, double eta, float *e_out, double *c_out,
+                         const float *box) {
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
     // mu = np.linspace(0.1, cutoff, num): arange(num)*step + start, last element forced to stop
@@ -697,5 +781,17 @@ extern "C" int epnn_edges_ex(epnn_handle *h, int n, const float *xyz, int num, d
     if (h->d_mu_ex.ensure((size_t)num * sizeof(double))) return 1;
     HIPCHK(hipMemcpyAsync(h->d_mu_ex.p, mu.data(), (size_t)num * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));      // mu is a local
-    return edges_impl(h, n, xyz, num, cutoff, eta, h->d_mu_ex.as<double>(), e_out, c_out);
+    return edges_impl(h, n, xyz, num, cutoff, eta, h->d_mu_ex.as<double>(), e_out, c_out, box);
+}
+extern "C" int epnn_edges_ex(epnn_handle *h, int n, const float *xyz, int num, double cutoff, double eta, float *e_out,
+                             double *c_out) {
+    if (!h || !xyz || !e_out || n < 1 || num < 2 || !(cutoff > 0.1)) EPNN_FAIL("epnn_edges_ex: bad argument");
+    return edges_ex_impl(h, n, xyz, num, cutoff, eta, e_out, c_out, nullptr);
+}
+// epnn_edges_ex in the periodic cell box[3]
+extern "C" int epnn_edges_pbc(epnn_handle *h, int n, const float *xyz, const float *box, int num, double cutoff, double eta,
+                              float *e_out, double *c_out) {
+    if (!h || !xyz || !e_out || n < 1 || num < 2 || !(cutoff > 0.1)) EPNN_FAIL("epnn_edges_pbc: bad argument");
+    if (check_box(1, box, cutoff, "epnn_edges_pbc")) return 1;
+    return edges_ex_impl(h, n, xyz, num, cutoff, eta, e_out, c_out, box);
 }

@@ -16,10 +16,9 @@ static void xyz_grad_release(epnn_handle *h) {
     h->xyz_grad = nullptr;
 }
 
-extern "C" int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                                    const float *Q, const float *g, float *q_out, float *gxyz_out) {
-    if (!h || !offsets || !xyz || !x || !Q || !g || !q_out || !gxyz_out) EPNN_FAIL("epnn_charges_vjp_xyz: null argument");
-    if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz: B and N must be positive and offsets[0] must be 0");
+// box: host box rows [B][3] of periodic cells (minimum-image distances; staged with the other inputs), or null
+static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                const float *g, float *q_out, float *gxyz_out, const float *box) {
     for (int b = 0; b < B; ++b)
         if (offsets[b + 1] - offsets[b] > N || offsets[b + 1] - offsets[b] < 1) EPNN_FAIL("epnn_charges_vjp_xyz: molecule %d does not fit N=%d", b, N);
     HIPCHK(hipSetDevice(h->device));
@@ -43,7 +42,7 @@ extern "C" int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t 
     // the train path's inputs, staged and padded as epnn_train_step_xyz does; the label slot carries -g / 2 (see XyzGrad)
     auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
     const size_t o_xyz = up256((size_t)(B + 1) * 4), o_x = o_xyz + up256((size_t)A * 3 * 4), o_Q = o_x + up256((size_t)A * nx * 4),
-                 o_y = o_Q + up256((size_t)B * 4), in_bytes = o_y + (size_t)A * 4;
+                 o_y = o_Q + up256((size_t)B * 4), o_box = o_y + up256((size_t)A * 4), in_bytes = box ? o_box + (size_t)B * 12 : o_y + (size_t)A * 4;
     if (h->pin_train.ensure(in_bytes) || h->s_train.ensure(in_bytes) || h->sd_e.ensure(pairs * EPNN_EDIM * 4) ||
         h->sd_mask.ensure(pairs * 4) || h->dn_xs.ensure(slots * nx * 4) || h->dn_hs.ensure(slots * EPNN_EDIM * 4) ||
         h->dn_qs.ensure(slots * 4) || h->sd_out.ensure(slots * 4) || h->tr_realbuf.ensure(slots * 4))
@@ -58,13 +57,20 @@ extern "C" int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t 
     memcpy(stage + o_Q, Q, (size_t)B * 4);
     float *ystage = reinterpret_cast<float *>(stage + o_y);
     for (int a = 0; a < A; ++a) ystage[a] = -0.5f * g[a];
+    if (box) memcpy(stage + o_box, box, (size_t)B * 12);
     HIPCHK(hipMemcpyAsync(h->s_train.p, stage, in_bytes, hipMemcpyHostToDevice, h->stream));
     const float *dev = h->s_train.as<float>();
     const int *d_moff = h->s_train.as<int>();
-    hipLaunchKernelGGL(k_t_pad_inputs, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
-                       (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta,
-                       h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
-                       h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+    if (box)
+        hipLaunchKernelGGL(k_t_pad_inputs_pbc, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
+                           (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), (int)(o_box / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff,
+                           (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(),
+                           h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+    else
+        hipLaunchKernelGGL(k_t_pad_inputs, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
+                           (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta,
+                           h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
+                           h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
     HIPCHK(hipGetLastError());
     float *out = xs->loss.as<float>();
     HIPCHK(hipMemsetAsync(out + o_zero, 0, (slots + (size_t)A * 3 + 1) * 4, h->stream));
@@ -82,9 +88,14 @@ extern "C" int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t 
     h->tr_moff = nullptr;
     h->tr_real = nullptr;
     if (rc) return 1;
-    hipLaunchKernelGGL(k_g_xyz, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B, N,
-                       xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
-                       reinterpret_cast<int *>(out + o_bad));
+    if (box)
+        hipLaunchKernelGGL(k_g_xyz_pbc, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B,
+                           N, xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
+                           reinterpret_cast<int *>(out + o_bad), reinterpret_cast<const float *>(dev + o_box / 4));
+    else
+        hipLaunchKernelGGL(k_g_xyz, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B, N,
+                           xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
+                           reinterpret_cast<int *>(out + o_bad));
     HIPCHK(hipGetLastError());
     // predictions | zeros | gxyz | flag: one download
     if (h->pin_tout.ensure((nout - slots) * 4)) return 1;
@@ -92,9 +103,25 @@ extern "C" int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t 
     HIPCHK(hipMemcpyAsync(back, out + slots, (nout - slots) * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (reinterpret_cast<const int *>(back)[nout - slots - 1] != 0)
-        EPNN_FAIL("epnn_charges_vjp_xyz: two atoms of a molecule coincide (distance 0: the edge features have no derivative there)");
+        EPNN_FAIL(box ? "epnn_charges_vjp_xyz_pbc: two atoms of a molecule or their periodic images coincide (distance 0: the edge features have no derivative there)"
+                      : "epnn_charges_vjp_xyz: two atoms of a molecule coincide (distance 0: the edge features have no derivative there)");
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < offsets[b + 1] - offsets[b]; ++i) q_out[offsets[b] + i] = back[(size_t)b * N + i];
     memcpy(gxyz_out, back + (o_gx - slots), (size_t)A * 3 * 4);
     return 0;
+}
+
+extern "C" int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                    const float *Q, const float *g, float *q_out, float *gxyz_out) {
+    if (!h || !offsets || !xyz || !x || !Q || !g || !q_out || !gxyz_out) EPNN_FAIL("epnn_charges_vjp_xyz: null argument");
+    if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz: B and N must be positive and offsets[0] must be 0");
+    return charges_vjp_xyz_impl(h, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, nullptr);
+}
+
+extern "C" int epnn_charges_vjp_xyz_pbc(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                        const float *Q, const float *box, const float *g, float *q_out, float *gxyz_out) {
+    if (!h || !offsets || !xyz || !x || !Q || !g || !q_out || !gxyz_out) EPNN_FAIL("epnn_charges_vjp_xyz_pbc: null argument");
+    if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz_pbc: B and N must be positive and offsets[0] must be 0");
+    if (check_box(B, box, (double)h->cfg.cutoff, "epnn_charges_vjp_xyz_pbc")) return 1;
+    return charges_vjp_xyz_impl(h, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, box);
 }

@@ -5,10 +5,11 @@
 // ------------------------------------------------------------------------------------------------ training
 // dense (B,N,N,.) make_model inputs from a flat coordinate batch: what gen_padded_init_state builds on the host
 // the body: `in(k)` reads word k of the staged block  offsets | xyz | x | Q | y  (word offsets o_*), wherever that block is
-template <typename IN>
+// PBC: minimum-image distances in the cells box [B][3] at word o_box of the block (epnn_charges_vjp_xyz_pbc)
+template <bool PBC = false, typename IN>
 __device__ __forceinline__ void t_pad_inputs_body(IN &&in, int o_xyz, int o_x, int o_Q, int o_y, int B, int N, int nx, int E, double cutoff,
                                                   double eta, const double *mu, float *e, float *mask, float *xs, float *hs, float *qs,
-                                                  float *ys, int *real_out, int *moff_out) {
+                                                  float *ys, int *real_out, int *moff_out, int o_box = 0) {
     // a thread per (pair, four channels): one thread per pair was 48 double-precision exp in a row on 7 workgroups (13 us of a
     // 0.27 ms one-molecule step); the distance and the cutoff are recomputed by the 12 threads of a pair
     const size_t pairs = (size_t)B * N * N;
@@ -26,8 +27,13 @@ __device__ __forceinline__ void t_pad_inputs_body(IN &&in, int o_xyz, int o_x, i
         if (real) {
             // distance exactly as scipy.spatial.distance_matrix on float32 coordinates promoted to float64 (epnn_dist)
             const int pi_ = o_xyz + 3 * (a0 + i), pj_ = o_xyz + 3 * (a0 + j);
-            const double dx = (double)in(pj_) - (double)in(pi_), dy = (double)in(pj_ + 1) - (double)in(pi_ + 1),
-                         dz = (double)in(pj_ + 2) - (double)in(pi_ + 2);
+            double dx = (double)in(pj_) - (double)in(pi_), dy = (double)in(pj_ + 1) - (double)in(pi_ + 1),
+                   dz = (double)in(pj_ + 2) - (double)in(pi_ + 2);
+            if (PBC) {
+                dx = epnn_mic(dx, (double)in(o_box + 3 * b));
+                dy = epnn_mic(dy, (double)in(o_box + 3 * b + 1));
+                dz = epnn_mic(dz, (double)in(o_box + 3 * b + 2));
+            }
             D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
             Cc = (cos(pi_d * (D - 0.0) / cutoff) + 1.0) / 2.0;
             if (D >= cutoff) Cc = 0.0;
@@ -53,6 +59,12 @@ __global__ __launch_bounds__(256) void k_t_pad_inputs(const float *blk, int o_xy
                                                       double cutoff, double eta, const double *mu, float *e, float *mask, float *xs,
                                                       float *hs, float *qs, float *ys, int *real_out) {
     t_pad_inputs_body([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys, real_out, nullptr);
+}
+__global__ __launch_bounds__(256) void k_t_pad_inputs_pbc(const float *blk, int o_xyz, int o_x, int o_Q, int o_y, int o_box, int B, int N,
+                                                          int nx, int E, double cutoff, double eta, const double *mu, float *e, float *mask,
+                                                          float *xs, float *hs, float *qs, float *ys, int *real_out) {
+    t_pad_inputs_body<true>([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys,
+                            real_out, nullptr, o_box);
 }
 // ... or riding in the kernel's own argument block (up to 3.6 KB: one molecule of up to ~69 atoms): no upload, i.e. no copy kernel
 // and no launch boundary in front of the step (5 us of a 0.22 ms one-molecule step); the offsets are left in device memory for the

@@ -63,15 +63,33 @@ __device__ __forceinline__ double epnn_dist2p(double xi, double yi, double zi, c
     const double dx = (double)p[0] - xi, dy = (double)p[1] - yi, dz = (double)p[2] - zi;
     return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
 }
+
+// Periodic cells (orthorhombic; include/epnn.h): box[b][k] > 0 is the length of periodic axis k of molecule b, 0 an open axis.
+// Minimum image of a float64 displacement d: d - k L with k = rint(d / L) (|d - k L| <= L / 2).  k L is exact (k is small, L a
+// float32), and so is the difference for any d within a few box lengths; the host reference computes the same expression.
+__device__ __forceinline__ double epnn_mic(double d, double L) {
+    return L > 0.0 ? __dadd_rn(d, -__dmul_rn(L, rint(d / L))) : d;
+}
+// epnn_dist2p with minimum-image components (L* the box row as float64)
+__device__ __forceinline__ double epnn_dist2p_pbc(double xi, double yi, double zi, const float *p, double Lx, double Ly, double Lz) {
+    const double dx = epnn_mic((double)p[0] - xi, Lx), dy = epnn_mic((double)p[1] - yi, Ly), dz = epnn_mic((double)p[2] - zi, Lz);
+    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+// a coordinate moved into [0, L] on a periodic axis (for the float32 pre-test only: the float64 test measures unwrapped coordinates)
+__device__ __forceinline__ float epnn_wrap_coord(float x, float L) {
+    if (!(L > 0.f)) return x;
+    const double Ld = (double)L;
+    return (float)((double)x - Ld * floor((double)x / Ld));
+}
 // A workgroup = four consecutive rows, one wave each.  The candidates' coordinates go through LDS in blocks of
 // EPNN_FRONT_JB atoms, staged once for the four rows with every load of a thread in flight (a wave that fetched its 64
 // candidates per trip straight from memory paid one L2 round trip per trip: 35 of them for a 2220-atom system).  Rows of a
 // workgroup that belong to another molecule than its first row (molecule boundaries) read memory directly.
 #define EPNN_FRONT_JB 2048
 // calls body(j, near, d2, trip) for every candidate j of the row's molecule, 64 per trip (trip t = candidates 64 t .. of the
-// molecule), lane = candidate; wave-uniform trips
-template <typename Body>
-__device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, int row, bool live, Body &&body) {
+// molecule), lane = candidate; wave-uniform trips.  PBC: minimum-image distances in the cells of `box` [B][3].
+template <bool PBC = false, typename Body>
+__device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, int row, bool live, Body &&body, const float *box = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int row0 = row - (tid >> 6);                        // the workgroup's first row
     const int b0 = F.mol_of[row0], beg0 = F.moff[b0], end0 = F.moff[b0 + 1];
@@ -85,11 +103,38 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
     }
     // float32 first: only a candidate whose float32 squared distance comes within 1e-4 (relative) of the cutoff's gets the
     // float64 evaluation that decides (float32 differences, squares and sums are good to a few 1e-7)
-    const float cut2f = (float)(F.cut2 * 1.0001);
+    float cut2f = (float)(F.cut2 * 1.0001);
+    float Lxf = 0.f, Lyf = 0.f, Lzf = 0.f, ixf = 0.f, iyf = 0.f, izf = 0.f;
+    double Lx = 0.0, Ly = 0.0, Lz = 0.0;                      // the row's cell
+    if (PBC) {
+        // Periodic pre-test: the staged candidates and the row atom are first moved into the cell (epnn_wrap_coord: float64, then
+        // rounded, error <= u L with u = 2^-24), their float32 difference (|.| <= L, error <= u L) is wrapped again by
+        // rint(f / L).  A component then differs from the float64 minimum image by at most 3 u L -- the same image -- or, where the
+        // two roundings pick different images (|d| within a few u L of L / 2), its magnitude exceeds the float64 one's by at most
+        // ~6 u L; 8 u L bounds both.  With D < c the float32 sum of squares is then at most
+        //     (c^2 + 2 sqrt(3) 8 u L c + 3 (8 u L)^2) (1 + 4 u)  =  c^2 (1 + 27.7 r + 192 r^2 + 4 u),   r = u L / c,
+        // so the margin 1e-4 + 64 r + 256 r^2 (L the longest periodic axis) never rejects a pair the float64 test accepts, for any
+        // box length and for coordinates any number of box lengths outside the cell (the wrap is done in float64).
+        const float *bx = box + 3 * b0;
+        Lxf = bx[0]; Lyf = bx[1]; Lzf = bx[2];
+        ixf = Lxf > 0.f ? 1.f / Lxf : 0.f; iyf = Lyf > 0.f ? 1.f / Lyf : 0.f; izf = Lzf > 0.f ? 1.f / Lzf : 0.f;
+        const double r = 0x1p-24 * (double)fmaxf(Lxf, fmaxf(Lyf, Lzf)) / F.cutoff;
+        cut2f = (float)(F.cut2 * (1.0001 + r * (64.0 + 256.0 * r)));
+        const float *br = box + 3 * b;
+        Lx = (double)br[0]; Ly = (double)br[1]; Lz = (double)br[2];
+        xf = epnn_wrap_coord(xf, Lxf); yf = epnn_wrap_coord(yf, Lyf); zf = epnn_wrap_coord(zf, Lzf);
+    }
     for (int jb = beg0; jb < end0; jb += EPNN_FRONT_JB) {
         const int nb = min(EPNN_FRONT_JB, end0 - jb);
         __syncthreads();
-        for (int i = tid; i < nb * 3; i += 256) sx[i] = F.xyz[(size_t)jb * 3 + i];
+        if (PBC) {
+            for (int i = tid; i < nb * 3; i += 256) {
+                const int k = i % 3;
+                sx[i] = epnn_wrap_coord(F.xyz[(size_t)jb * 3 + i], k == 0 ? Lxf : (k == 1 ? Lyf : Lzf));
+            }
+        } else {
+            for (int i = tid; i < nb * 3; i += 256) sx[i] = F.xyz[(size_t)jb * 3 + i];
+        }
         __syncthreads();
         if (shared)
             for (int j0 = 0; j0 < nb; j0 += 64) {
@@ -97,9 +142,14 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
                 double d2 = 0.0;
                 bool near = false;
                 if (j < nb && jb + j != row) {
-                    const float fx = sx[3 * j] - xf, fy = sx[3 * j + 1] - yf, fz = sx[3 * j + 2] - zf;
+                    float fx = sx[3 * j] - xf, fy = sx[3 * j + 1] - yf, fz = sx[3 * j + 2] - zf;
+                    if (PBC) {
+                        fx = fmaf(-Lxf, rintf(fx * ixf), fx);
+                        fy = fmaf(-Lyf, rintf(fy * iyf), fy);
+                        fz = fmaf(-Lzf, rintf(fz * izf), fz);
+                    }
                     if (fx * fx + fy * fy + fz * fz < cut2f) {
-                        d2 = epnn_dist2p(xi, yi, zi, sx + 3 * j);
+                        d2 = PBC ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * ((size_t)jb + j), Lx, Ly, Lz) : epnn_dist2p(xi, yi, zi, sx + 3 * j);
                         near = d2 < F.cut2;
                     }
                 }
@@ -113,7 +163,7 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
             double d2 = 0.0;
             bool near = false;
             if (j < end && j != row) {
-                d2 = epnn_dist2p(xi, yi, zi, F.xyz + 3 * j);
+                d2 = PBC ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * j, Lx, Ly, Lz) : epnn_dist2p(xi, yi, zi, F.xyz + 3 * j);
                 near = d2 < F.cut2;
             }
             body(j, near, d2, (j0 - beg) >> 6);
@@ -122,18 +172,19 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
 }
 
 // one wave per row i: partners j != i of the same molecule with D < cutoff -- how many in all, how many with j > i
-__device__ __forceinline__ void front_count_body(const FrontArgs &F, float *sx, int blk) {
+template <bool PBC = false>
+__device__ __forceinline__ void front_count_body(const FrontArgs &F, float *sx, int blk, const float *box = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blk * 4 + wave;
     const bool live = row < F.A;
     int up = 0, all = 0;
     unsigned long long mine = 0ull;                           // lane t keeps the decisions of trip t
-    front_scan_row(F, sx, row, live, [&](int j, bool near, double, int trip) {
+    front_scan_row<PBC>(F, sx, row, live, [&](int j, bool near, double, int trip) {
         const unsigned long long bal = __ballot(near);
         all += __popcll(bal);
         up += __popcll(__ballot(near && j > row));
         if (trip == lane) mine = bal;
-    });
+    }, box);
     if (live && lane == 0) {
         F.row_cnt[row] = up;
         F.deg[row] = all;
@@ -143,6 +194,11 @@ __device__ __forceinline__ void front_count_body(const FrontArgs &F, float *sx, 
 __global__ __launch_bounds__(256) void k_front_count(FrontArgs F) {
     __shared__ float sx[EPNN_FRONT_JB * 3];
     front_count_body(F, sx, (int)blockIdx.x);
+}
+// ... in the periodic cells box [B][3] (epnn_forward_xyz_pbc)
+__global__ __launch_bounds__(256) void k_front_count_pbc(FrontArgs F, const float *box) {
+    __shared__ float sx[EPNN_FRONT_JB * 3];
+    front_count_body<true>(F, sx, (int)blockIdx.x, box);
 }
 
 // both prefix sums in ONE single-workgroup launch (1024 threads x 8 elements per round, a carry between rounds): a
@@ -267,8 +323,8 @@ struct FrontFillShared {
 // rows (systems of up to EPNN_FRONT_INLINE_A atoms: 2 x 2220 words per workgroup for the protein, against a launch of a single
 // workgroup, 6.9 us, between the count and the fill), writes them for the later launches, and the last workgroup the totals
 #define EPNN_FRONT_INLINE_A 8192
-template <bool INLINE = false>
-__device__ __forceinline__ void front_fill_body(const FrontArgs &F, FrontFillShared &Sh, int blk) {
+template <bool INLINE = false, bool PBC = false>
+__device__ __forceinline__ void front_fill_body(const FrontArgs &F, FrontFillShared &Sh, int blk, const float *box = nullptr) {
     float *sx = Sh.sx;
     auto &s_j = Sh.s_j;
     auto &s_D = Sh.s_D;
@@ -379,24 +435,29 @@ __device__ __forceinline__ void front_fill_body(const FrontArgs &F, FrontFillSha
         const int b = live ? F.mol_of[row] : 0, beg = live ? F.moff[b] : 0;
         const unsigned long long word = live && lane < F.bits_w ? F.bits[(size_t)row * F.bits_w + lane] : 0ull;
         unsigned long long trips = __ballot(word != 0ull);
-        double xi = 0.0, yi = 0.0, zi = 0.0;
+        double xi = 0.0, yi = 0.0, zi = 0.0, Lx = 0.0, Ly = 0.0, Lz = 0.0;
         if (live) { xi = (double)F.xyz[3 * row]; yi = (double)F.xyz[3 * row + 1]; zi = (double)F.xyz[3 * row + 2]; }
+        if (PBC && live) { Lx = (double)box[3 * b]; Ly = (double)box[3 * b + 1]; Lz = (double)box[3 * b + 2]; }
         while (trips) {
             const int t = __ffsll((long long)trips) - 1;
             trips &= trips - 1ull;
             const unsigned long long bal = __shfl(word, t, 64);
             const int j = beg + 64 * t + lane;
             const bool near = (bal >> lane) & 1ull;
-            const double d2 = near ? epnn_dist2p(xi, yi, zi, F.xyz + 3 * j) : 0.0;
+            const double d2 = near ? (PBC ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * j, Lx, Ly, Lz) : epnn_dist2p(xi, yi, zi, F.xyz + 3 * j)) : 0.0;
             body(j, near, d2, t);
         }
         return;
     }
-    front_scan_row(F, sx, row, live, body);
+    front_scan_row<PBC>(F, sx, row, live, body, box);
 }
 __global__ __launch_bounds__(256) void k_front_fill(FrontArgs F) {
     __shared__ FrontFillShared Sh;
     front_fill_body<false>(F, Sh, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_front_fill_pbc(FrontArgs F, const float *box) {
+    __shared__ FrontFillShared Sh;
+    front_fill_body<false, true>(F, Sh, (int)blockIdx.x, box);
 }
 
 // one thread per pair (i, j): where does i sit in j's incidence row?  (rows are ascending and short: a few loads in flight)
@@ -424,16 +485,20 @@ __device__ __forceinline__ void front_link_body(const FrontArgs &F, int blk, int
 }
 __global__ __launch_bounds__(256) void k_front_link(FrontArgs F) { front_link_body(F, (int)blockIdx.x, (int)gridDim.x); }
 
-// epnn_edges: dense (n,n,e_dim) tensor exactly like get_init_edges, one thread per (i,j,ch)
-__global__ __launch_bounds__(256) void k_edges_dense(const float *xyz, int n, int e_dim, double cutoff, double eta,
-                                                     const double *mu, float *e_out, double *c_out) {
+// epnn_edges: dense (n,n,e_dim) tensor exactly like get_init_edges, one thread per (i,j,ch).  PBC: minimum-image distances in the
+// cell box[3] (epnn_edges_pbc)
+template <bool PBC>
+__device__ __forceinline__ void edges_dense_body(const float *xyz, const float *box, int n, int e_dim, double cutoff, double eta,
+                                                 const double *mu, float *e_out, double *c_out) {
     const size_t total = (size_t)n * n * e_dim;
     const double pi_d = 3.141592653589793;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
         const int ch = (int)(idx % e_dim);
         const size_t pr = idx / e_dim;
         const int j = (int)(pr % n), i = (int)(pr / n);
-        const double D = epnn_dist(xyz, i, j);
+        const double D = PBC ? sqrt(epnn_dist2p_pbc((double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], xyz + 3 * j,
+                                                    (double)box[0], (double)box[1], (double)box[2]))
+                             : epnn_dist(xyz, i, j);
         double C = (cos(pi_d * (D - 0.0) / cutoff) + 1.0) / 2.0;
         if (D >= cutoff) C = 0.0;
         if (D <= 0.0) C = 1.0;
@@ -442,4 +507,12 @@ __global__ __launch_bounds__(256) void k_edges_dense(const float *xyz, int n, in
         e_out[idx] = (float)(C * exp(-eta * (d * d)));
         if (c_out && ch == 0) c_out[pr] = C;                  // the cutoff weights the reference returns tiled (charge_gn.py:163)
     }
+}
+__global__ __launch_bounds__(256) void k_edges_dense(const float *xyz, int n, int e_dim, double cutoff, double eta,
+                                                     const double *mu, float *e_out, double *c_out) {
+    edges_dense_body<false>(xyz, nullptr, n, e_dim, cutoff, eta, mu, e_out, c_out);
+}
+__global__ __launch_bounds__(256) void k_edges_dense_pbc(const float *xyz, const float *box, int n, int e_dim, double cutoff, double eta,
+                                                         const double *mu, float *e_out, double *c_out) {
+    edges_dense_body<true>(xyz, box, n, e_dim, cutoff, eta, mu, e_out, c_out);
 }

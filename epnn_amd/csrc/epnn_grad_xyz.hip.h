@@ -13,6 +13,7 @@
 // depend on the other molecules of a batch.
 #pragma once
 #include "epnn_host.h"
+#include "epnn_frontend.hip.h"
 #include "epnn_train_fused.hip.h"
 
 struct TrainState;
@@ -83,9 +84,11 @@ __global__ __launch_bounds__(256) void k_g_edge_dz1(const float *dz1, const floa
 // Edge-featurisation backward: one wavefront per real atom (a = moff[b] + i).  Lane j (and j + 64, ...) forms the pair (i, j):
 // D from the float32 coordinates in double exactly as k_t_pad_inputs does, gD_ij + gD_ji over the 48 channels, and its
 // contribution (gD_ij + gD_ji) (r_i - r_j) / D; the lanes' sums are combined by a fixed butterfly.  bad: set when two atoms of a
-// molecule coincide (D = 0: the distance has no derivative there).
-__global__ __launch_bounds__(64) void k_g_xyz(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
-                                              double eta, const double *mu, float *gxyz, int *bad) {
+// molecule coincide (D = 0: the distance has no derivative there).  PBC: minimum-image displacements in the cells box [B][3]
+// (their derivative is that of the unwrapped displacement: the image shift is a constant).
+template <bool PBC>
+__device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff, double eta,
+                                           const double *mu, float *gxyz, int *bad, const float *box) {
     const int a = blockIdx.x, lane = threadIdx.x;
     int lo = 0, hi = B;                               // molecule b: moff[b] <= a < moff[b + 1]
     while (hi - lo > 1) {
@@ -95,11 +98,14 @@ __global__ __launch_bounds__(64) void k_g_xyz(const float *xyz, const int *moff,
     const int b = lo, a0 = moff[b], n = moff[b + 1] - a0, i = a - a0;
     const double pi_d = 3.141592653589793;
     const double xi = xyz[3 * a], yi = xyz[3 * a + 1], zi = xyz[3 * a + 2];
+    double Lx = 0.0, Ly = 0.0, Lz = 0.0;
+    if (PBC) { Lx = (double)box[3 * b]; Ly = (double)box[3 * b + 1]; Lz = (double)box[3 * b + 2]; }
     double s[3] = {0.0, 0.0, 0.0};
     for (int j = lane; j < n; j += 64) {
         if (j == i) continue;
         const int aj = a0 + j;
-        const double dx = (double)xyz[3 * aj] - xi, dy = (double)xyz[3 * aj + 1] - yi, dz = (double)xyz[3 * aj + 2] - zi;
+        double dx = (double)xyz[3 * aj] - xi, dy = (double)xyz[3 * aj + 1] - yi, dz = (double)xyz[3 * aj + 2] - zi;
+        if (PBC) { dx = epnn_mic(dx, Lx); dy = epnn_mic(dy, Ly); dz = epnn_mic(dz, Lz); }
         const double D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
         if (!(D > 0.0)) { *bad = 1; continue; }
         if (D >= cutoff) continue;                    // C = 0 and C' = 0 beyond the cutoff
@@ -122,4 +128,12 @@ __global__ __launch_bounds__(64) void k_g_xyz(const float *xyz, const int *moff,
         s[c] = v;
     }
     if (lane < 3) gxyz[3 * a + lane] = (float)(lane == 0 ? s[0] : (lane == 1 ? s[1] : s[2]));
+}
+__global__ __launch_bounds__(64) void k_g_xyz(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
+                                              double eta, const double *mu, float *gxyz, int *bad) {
+    g_xyz_body<false>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, nullptr);
+}
+__global__ __launch_bounds__(64) void k_g_xyz_pbc(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
+                                                  double eta, const double *mu, float *gxyz, int *bad, const float *box) {
+    g_xyz_body<true>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, box);
 }

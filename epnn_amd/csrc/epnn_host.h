@@ -145,6 +145,8 @@ struct epnn_handle {
     DevBuf d_pi, d_pj, d_psym, d_pe, d_pwi, d_pwj;
     DevBuf d_deg, d_incoff, d_nbr, d_desti, d_destj, d_prec;   // incidence rows of the pair list (epnn_frontend.hip.h)
     DevBuf d_nearbits;                // the count pass's D < cutoff decisions, a bit per candidate (FrontArgs::bits)
+    DevBuf d_box;                     // box rows of epnn_forward_xyz_pbc_dev, two slots (the status slot of the forward: st_slot)
+    PinBuf pin_box;                   // ... and their page-locked staging
     int opt_front_inline = 1;         // developer switch: 0 = the prefix sums of the pair list always in a launch of their own
     int opt_front_bits = 1;           // developer switch: 0 = the fill pass measures every distance again
     int pcap = 0;
@@ -246,6 +248,7 @@ struct epnn_handle {
         std::function<int()> redo;    // re-enqueues the same forward after a capacity regrow
         int slot = 0;                 // its status slot / completion event
         const void *key[4] = {nullptr, nullptr, nullptr, nullptr};      // the device buffers of a device-resident compact forward
+        std::vector<float> box;       // its box rows (periodic forward; empty: open molecules)
     } pending;
     // dense front-end workspace (epnn_dense.hip.h)
     DevBuf dn_den;

@@ -12,6 +12,17 @@ from ._lib import W_MSG, W_PAS, W_UPD, EpnnConfig, EpnnError, check, fptr, iptr
 _WHICH = {"msg": W_MSG, "upd": W_UPD, "pas": W_PAS}
 
 
+def _box_rows(box, B):
+    """A periodic cell argument -> (B, 3) float32 rows: shape (3,) applies to every molecule, (B, 3) gives one row each.  Lengths
+    > 0 are periodic axes, 0 open ones (include/epnn.h); the library checks the values."""
+    box = np.asarray(box, dtype=np.float32)
+    if box.shape == (3,):
+        return np.ascontiguousarray(np.tile(box, (B, 1)))
+    if box.shape != (B, 3):
+        raise ValueError(f"box must have shape (3,) or ({B}, 3), got {box.shape}")
+    return np.ascontiguousarray(box)
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -121,18 +132,28 @@ class Engine:
         check(self.lib.epnn_edges(self.h, n, fptr(xyz), fptr(out)), self.lib)
         return out
 
-    def edges_ex(self, xyz, num, cutoff=3.0, eta=2.0):
-        """get_init_edges with its own parameters: (e float32 (n,n,num), C float64 (n,n)) from the device kernel."""
+    def edges_ex(self, xyz, num, cutoff=3.0, eta=2.0, box=None):
+        """get_init_edges with its own parameters: (e float32 (n,n,num), C float64 (n,n)) from the device kernel.  box (3,):
+        minimum-image distances in that periodic cell (include/epnn.h)."""
         xyz = _f32(xyz)
         n = xyz.shape[0]
         e = np.empty((n, n, int(num)), dtype=np.float32)
         c = np.empty((n, n), dtype=np.float64)
-        check(self.lib.epnn_edges_ex(self.h, n, fptr(xyz), int(num), float(cutoff), float(eta), fptr(e),
-                                     c.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
+        if box is None:
+            check(self.lib.epnn_edges_ex(self.h, n, fptr(xyz), int(num), float(cutoff), float(eta), fptr(e),
+                                         c.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
+        else:
+            box = np.asarray(box, dtype=np.float32)
+            if box.shape != (3,):
+                raise ValueError(f"edges_ex: box must have shape (3,), got {box.shape}")
+            box = np.ascontiguousarray(box)
+            check(self.lib.epnn_edges_pbc(self.h, n, fptr(xyz), fptr(box), int(num), float(cutoff), float(eta), fptr(e),
+                                          c.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
         return e, c
 
-    def forward_xyz(self, offsets, xyz, x, Q, N):
-        """Flat batch: offsets (B+1,), xyz (A,3), x (A,nx), Q (B,) -> q (A,) float32."""
+    def forward_xyz(self, offsets, xyz, x, Q, N, box=None):
+        """Flat batch: offsets (B+1,), xyz (A,3), x (A,nx), Q (B,) -> q (A,) float32.  box (3,) or (B, 3): periodic cells
+        (include/epnn.h: > 0 periodic length, 0 open axis)."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
         B = len(offsets) - 1
@@ -140,7 +161,12 @@ class Engine:
         if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
             raise EpnnError(f"forward_xyz: shapes xyz {xyz.shape} x {x.shape} Q {Q.shape} do not match offsets (A={A}, B={B}, nx={self.nx})")
         out = np.empty((A,), dtype=np.float32)
-        check(self.lib.epnn_forward_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(out)), self.lib)
+        if box is None:
+            check(self.lib.epnn_forward_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(out)), self.lib)
+        else:
+            box = _box_rows(box, B)
+            check(self.lib.epnn_forward_xyz_pbc(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(box), fptr(out)),
+                  self.lib)
         return out
 
     def forward_xyz_begin(self, offsets, xyz, x, Q, N):
@@ -270,9 +296,9 @@ class Engine:
                                            C.byref(loss), int(bool(apply))), self.lib)
         return q, loss.value
 
-    def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N):
+    def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N, box=None):
         """Flat batch and a cotangent g (A,) of the charges -> (q (A,), gxyz (A, 3) = sum_i g[i] dq_i/dxyz).  Touches no
-        training state; works without train_init."""
+        training state; works without train_init.  box (3,) or (B, 3): periodic cells, as in forward_xyz."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         xyz, x, Q, g = _f32(xyz), _f32(x), _f32(Q), _f32(g)
         B, A = len(offsets) - 1, int(offsets[-1])
@@ -280,8 +306,13 @@ class Engine:
             raise EpnnError("charges_vjp_xyz: array shapes do not match offsets")
         q = np.empty((A,), dtype=np.float32)
         gxyz = np.empty((A, 3), dtype=np.float32)
-        check(self.lib.epnn_charges_vjp_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(g), fptr(q),
-                                            fptr(gxyz)), self.lib)
+        if box is None:
+            check(self.lib.epnn_charges_vjp_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(g), fptr(q),
+                                                fptr(gxyz)), self.lib)
+        else:
+            box = _box_rows(box, B)
+            check(self.lib.epnn_charges_vjp_xyz_pbc(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(box), fptr(g),
+                                                    fptr(q), fptr(gxyz)), self.lib)
         return q, gxyz
 
     def get_gradients(self):
@@ -373,10 +404,15 @@ class Engine:
             check(self.lib.epnn_memcpy_h2d(self.h, C.c_void_p(d_ptr + 4 * row_len * row_lo), rows.ctypes.data_as(C.c_void_p),
                                            rows.nbytes), self.lib)
 
-    def forward_xyz_dev(self, offsets, d_xyz, d_x, d_Q, d_q, N):
+    def forward_xyz_dev(self, offsets, d_xyz, d_x, d_Q, d_q, N, box=None):
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        check(self.lib.epnn_forward_xyz_dev(self.h, len(offsets) - 1, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr,
-                                            d_Q.ptr, d_q.ptr), self.lib)
+        if box is None:
+            check(self.lib.epnn_forward_xyz_dev(self.h, len(offsets) - 1, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr,
+                                                d_Q.ptr, d_q.ptr), self.lib)
+        else:
+            box = _box_rows(box, len(offsets) - 1)
+            check(self.lib.epnn_forward_xyz_pbc_dev(self.h, len(offsets) - 1, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr,
+                                                    d_Q.ptr, fptr(box), d_q.ptr), self.lib)
 
     def sync(self):
         check(self.lib.epnn_sync(self.h), self.lib)

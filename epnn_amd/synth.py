@@ -4,7 +4,9 @@ There is no network for datasets, so bench.py runs on molecules generated here:
   * QM9-like: atom counts from the empirical histogram of the 1338 QM9 files of the reference's `mixed` set,
     element mix H/C/O/N/F, coordinates by random sequential addition (min separation 0.95 A, each new atom
     within 1.0-1.6 A of an existing one) which gives ~8 partners within the 3 A cutoff per atom like the real set.
-  * periodic-like box: uniform atoms at density 0.1 / A^3 with min separation 0.9 A and the protein's element mix.
+  * periodic-like box: uniform atoms at density 0.1 / A^3 with min separation 0.9 A and the protein's element mix (an open
+    cluster: atoms near a face lose partners);
+  * periodic box: the same in a periodic cubic cell, the separation enforced across the faces (periodic_box_system).
 """
 from __future__ import annotations
 
@@ -108,6 +110,44 @@ def box_system(n_atoms=100_000, seed=0, density=0.1, min_sep=0.9):
     symbols = rng.choice(names, size=n_atoms, p=ep)
     offsets = np.array([0, n_atoms], dtype=np.int32)
     return offsets, pts.astype(np.float32), features(symbols), np.zeros(1, dtype=np.float32), n_atoms
+
+
+def periodic_box_system(n_atoms=10_000, seed=0, density=0.1, min_sep=0.9):
+    """One periodic cubic cell: uniform atoms at `density` with the minimum separation enforced across the faces (minimum
+    image), the element mix of box_system.  Returns (offsets, xyz, x, Q, N, box) with box (1, 3) float32."""
+    rng = np.random.default_rng(seed)
+    side = float(np.float32((n_atoms / density) ** (1.0 / 3.0)))
+    ncell = max(1, int(side // min_sep))                 # cells at least min_sep wide: neighbours within the 27 around a cell
+    width = side / ncell
+    around = [(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)]
+    grid = {}
+    pts = []
+    m2 = min_sep * min_sep
+    while len(pts) < n_atoms:
+        for p in rng.uniform(0, side, size=(4096, 3)).tolist():
+            c = [int(v // width) % ncell for v in p]
+            ok = True
+            for da, db, dc in around:
+                for q in grid.get(((c[0] + da) % ncell, (c[1] + db) % ncell, (c[2] + dc) % ncell), ()):
+                    v = [p[k] - q[k] for k in range(3)]
+                    v = [u - side * round(u / side) for u in v]
+                    if v[0] * v[0] + v[1] * v[1] + v[2] * v[2] < m2:
+                        ok = False
+                        break
+                if not ok:
+                    break
+            if ok:
+                pts.append(p)
+                grid.setdefault(tuple(c), []).append(p)
+                if len(pts) == n_atoms:
+                    break
+    names = [e for e, _ in PROTEIN_ELEMS]
+    ep = np.array([p for _, p in PROTEIN_ELEMS])
+    ep /= ep.sum()
+    symbols = rng.choice(names, size=n_atoms, p=ep)
+    offsets = np.array([0, n_atoms], dtype=np.int32)
+    box = np.full((1, 3), side, dtype=np.float32)
+    return offsets, np.array(pts, dtype=np.float32), features(symbols), np.zeros(1, dtype=np.float32), n_atoms, box
 
 
 def algorithmic_flops(ns, near_unordered_pairs, nx=9, T=5, E=48, H=32, parts=False, chains_bf16=False, edges_bf16=True):

@@ -193,6 +193,35 @@ int epnn_train_apply(epnn_handle *h);
  * Bit-reproducible; a molecule's rows do not depend on the rest of the batch (at the same N). */
 int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                          const float *g, float *q_out, float *gxyz_out);
+
+/* ---- periodic systems (orthorhombic cells).  The model sees the geometry only through the pair distances D_ij of
+ * get_init_edges (charge_gn.py:122-163); a periodic call replaces them by minimum-image distances and changes nothing else.
+ *   box[b][0..2] (float32, Angstrom, host memory) is the cell of molecule b of the batch:
+ *     box[b][k] > 0   axis k is periodic with that length, which must be at least 2 * cutoff (6 A at the default cutoff);
+ *     box[b][k] == 0  axis k is open (slabs, wires; open molecules can share a batch with periodic cells);
+ *     negative, NaN and infinite lengths are refused, and so is a periodic length below 2 * cutoff.
+ *   Distance: per axis d = (double)x_j - (double)x_i; on a periodic axis d - k L with k = rint(d / L) (|d - k L| <= L / 2) and L
+ *     the float32 length as double; D = sqrt((dx*dx + dy*dy) + dz*dz) in the order of the open case.  With L >= 2 cutoff at most
+ *     one image of a pair is within the cutoff, so one e_ij per pair stays exact; where k is ambiguous (|d| near L / 2) every image
+ *     is at least a cutoff away.  Coordinates need not lie in the cell.
+ *   Unchanged: N and the padded partners, Q (the charge of the cell), C[D <= 0] = 1, the is_near tolerance, charge conservation.
+ *   Derivative: that of a minimum-image displacement with respect to x_i / x_j is that of the unwrapped one (the image shift is
+ *     constant); box derivatives (dq/dL, virial, stress) are not provided.  Triclinic cells are not supported.
+ *   Routing: a periodic forward always builds its pair list with the separate front-end launches; molecules of up to 32 atoms run
+ *     the fused kernel on that list, larger ones the tiled kernels (the path wave_front = 0 (include/epnn_dev.h) takes).  With every box row 0 the
+ *     result is bit-identical to epnn_forward_xyz with wave_front = 0 (include/epnn_dev.h), and epnn_charges_vjp_xyz_pbc to epnn_charges_vjp_xyz.
+ *   A partitioned handle (epnn_set_partition) runs periodic systems too. */
+int epnn_forward_xyz_pbc(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                         const float *box, float *q_out);
+/* Device-resident xyz/x/Q/q_out, box rows on the host (uploaded with the call; they may change on every call, as in an NPT run). */
+int epnn_forward_xyz_pbc_dev(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz, const float *d_x,
+                             const float *d_Q, const float *box, float *d_q_out);
+/* epnn_charges_vjp_xyz in periodic cells, with its contract; coincident periodic images of two atoms are refused. */
+int epnn_charges_vjp_xyz_pbc(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                             const float *Q, const float *box, const float *g, float *q_out, float *gxyz_out);
+/* epnn_edges_ex in the periodic cell box[3]: minimum-image edge features and cutoff weights of one system. */
+int epnn_edges_pbc(epnn_handle *h, int n, const float *xyz, const float *box, int num, double cutoff, double eta, float *e_out,
+                   double *c_out);
 /* RCCL communicator (one rank per GPU): the gradient is summed with ONE ncclAllReduce of the flat vector; the same
  * communicator carries the row exchange of a partitioned large system (epnn_set_partition with exchange == NULL). */
 int epnn_comm_unique_id(char *out128);
