@@ -35,6 +35,7 @@ SIGNATURES = {
     "epnn_version": (C.c_int, []),
     "epnn_device_count": (C.c_int, []),
     "epnn_create": (C.c_int, [C.POINTER(EpnnConfig), C.c_int, C.POINTER(_vp)]),
+    "epnn_create_fused": (C.c_int, [C.POINTER(EpnnConfig), C.c_int, C.POINTER(_vp)]),
     "epnn_destroy": (C.c_int, [_vp]),
     "epnn_skip_hw_queues": (C.c_int, [C.c_int, C.c_int]),
     "epnn_set_weights": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _fp, _fp]),

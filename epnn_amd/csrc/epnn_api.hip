@@ -81,14 +81,21 @@ extern "C" int epnn_skip_hw_queues(int device, int n) {
     return 0;
 }
 
+static int create_impl(const epnn_config *cfg, int device, epnn_handle **out, int nx_max);
 extern "C" int epnn_create(const epnn_config *cfg, int device, epnn_handle **out) {
+    return create_impl(cfg, device, out, EPNN_F1 - EPNN_EDIM - 1);      // what the tiled kernels' feature image holds
+}
+extern "C" int epnn_create_fused(const epnn_config *cfg, int device, epnn_handle **out) {
+    return create_impl(cfg, device, out, 4 * EPNN_XS - 3);              // what the fused kernels' xq operand holds
+}
+static int create_impl(const epnn_config *cfg, int device, epnn_handle **out, int nx_max) {
     if (!cfg || !out) EPNN_FAIL("epnn_create: null argument");
     if (cfg->h_dim != cfg->e_dim) EPNN_FAIL("epnn_create: e_dim (%d) must equal h_dim (%d): make_model gives e_inp h_dim channels (charge_gn.py:377)", cfg->e_dim, cfg->h_dim);
     if (cfg->h_dim < 1 || cfg->h_dim > EPNN_EDIM)
         EPNN_FAIL("epnn_create: h_dim = e_dim must be in 1..%d (the kernels hold %d channels; a smaller model runs zero-padded, a larger one is not built)", EPNN_EDIM, EPNN_EDIM);
     if (cfg->hidden != EPNN_HID) EPNN_FAIL("epnn_create: hidden must be %d", EPNN_HID);
     if (cfg->T < 1 || cfg->T > EPNN_MAXT) EPNN_FAIL("epnn_create: T must be in 1..%d", EPNN_MAXT);
-    if (cfg->nx < 1 || cfg->nx + EPNN_EDIM + 1 > EPNN_F1) EPNN_FAIL("epnn_create: nx must be in 1..%d", EPNN_F1 - EPNN_EDIM - 1);
+    if (cfg->nx < 1 || cfg->nx > nx_max) EPNN_FAIL("epnn_create: nx must be in 1..%d", nx_max);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         EPNN_FAIL("epnn_create: no HIP device visible; the EPNN hot path has no CPU fallback");

@@ -37,6 +37,7 @@ static int enqueue_dense(epnn_handle *h, int B, int N, int mode, const float *d_
                          const float *d_q, const float *d_mask, float *d_out) {
     HIPCHK(hipSetDevice(h->device));
     if (B < 1 || N < 1) EPNN_FAIL("dense forward: B and N must be positive");
+    EPNN_NOT_FUSED_ONLY(h, "dense forward");
     if (pack_weights(h)) return 1;
     const int nx = h->cfg.nx;
     const size_t slots = (size_t)B * N;

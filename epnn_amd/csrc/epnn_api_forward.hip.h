@@ -85,6 +85,7 @@ static int build_plan(epnn_handle *h, int B, int N, const int32_t *offsets, bool
         pbase[b] = (int)run;
         run += small || mid ? (long long)n * (n - 1) / 2 : 0;
     }
+    if (!P.large_list.empty()) EPNN_NOT_FUSED_ONLY(h, "forward (a molecule that takes the tiled kernels)");
     if (run > 0x7fffffffLL / 64) EPNN_FAIL("forward: batch too large (%lld pair slots)", run);
     P.pair_slots = (int)run;
     memcpy(c_moff, offsets, (size_t)(B + 1) * sizeof(int));

@@ -21,6 +21,7 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
                                 const float *g, float *q_out, float *gxyz_out, const float *box) {
     for (int b = 0; b < B; ++b)
         if (offsets[b + 1] - offsets[b] > N || offsets[b + 1] - offsets[b] < 1) EPNN_FAIL("epnn_charges_vjp_xyz: molecule %d does not fit N=%d", b, N);
+    EPNN_NOT_FUSED_ONLY(h, "epnn_charges_vjp_xyz");
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
     // the weights epnn_forward_xyz would use: a training step still in flight is waited for, device masters it has updated are

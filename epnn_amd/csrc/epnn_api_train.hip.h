@@ -88,6 +88,7 @@ static int train_quiesce(epnn_handle *h) {
 }
 extern "C" int epnn_train_init(epnn_handle *h, float lr, float beta1, float beta2, float eps) {
     if (!h) EPNN_FAIL("epnn_train_init: null handle");
+    EPNN_NOT_FUSED_ONLY(h, "epnn_train_init");
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
     if (train_quiesce(h)) return 1;
@@ -329,6 +330,7 @@ static int train_step_dense_impl(epnn_handle *h, int B, int N, const float *h_in
                                  float *loss_out, int apply) {
     if (!h || !h_inp || !e_inp || !x_inp || !q_inp || !mask_inp || !y) EPNN_FAIL("epnn_train_step_dense: null argument");
     if (B < 1 || N < 1) EPNN_FAIL("epnn_train_step_dense: B and N must be positive");
+    EPNN_NOT_FUSED_ONLY(h, "epnn_train_step_dense");
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
     if (train_quiesce(h)) return 1;               // (this entry re-uploads the tensors the previous step's kernels read)
@@ -401,6 +403,7 @@ extern "C" int epnn_train_step_xyz(epnn_handle *h, int B, int N, const int32_t *
 static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                                const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply) {
     if (!h || !offsets || !xyz || !x || !Q || !y_flat) EPNN_FAIL("epnn_train_step_xyz: null argument");
+    EPNN_NOT_FUSED_ONLY(h, "epnn_train_step_xyz");
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
     if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_train_step_xyz: B and N must be positive and offsets[0] must be 0");

@@ -436,12 +436,46 @@ static int pack_weights(epnn_handle *h) {
             return off;
         };
         auto frag_bf3 = [&](auto &&fn) { return frag_bf3s([&](int q, int s, int out) { return fn(accf(s, q), out); }); };
+        // a K = 16 kernel as three bf16 pieces per weight for v_mfma_f32_16x16x16_bf16, [2][3][64 lanes][2 dwords]: lane (q, m) of row
+        // block rb: K slots s = 0..3 = fn(q, s, 16 rb + m); dword j = slots 2j | 2j+1 << 16
+        auto frag_bf3k16 = [&](auto &&fn) {
+            const int off = alloc((size_t)2 * 3 * 64 * 2);
+            for (int rb = 0; rb < 2; ++rb)
+                for (int l = 0; l < 64; ++l) {
+                    uint32_t pc[3][4];
+                    for (int s = 0; s < 4; ++s) {
+                        float v = (float)fn(l >> 4, s, 16 * rb + (l & 15));
+                        for (int k = 0; k < 3; ++k) {
+                            uint32_t bits;
+                            memcpy(&bits, &v, 4);
+                            bits &= 0xffff0000u;
+                            float top;
+                            memcpy(&top, &bits, 4);
+                            pc[k][s] = bits >> 16;
+                            v = v - top;
+                        }
+                    }
+                    for (int k = 0; k < 3; ++k)
+                        for (int j = 0; j < 2; ++j) {
+                            const uint32_t word = pc[k][2 * j] | pc[k][2 * j + 1] << 16;
+                            memcpy(&buf[off + ((rb * 3 + k) * 64 + l) * 2 + j], &word, 4);
+                        }
+                }
+            return off;
+        };
         auto xq_row = [&](const float *W1, const float *b1, int r0, int phi, int m, double nmrow) -> double {
             if (phi == 0) return nmrow;
             if (phi <= nx) return W1[(size_t)(r0 + phi - 1) * 32 + m];
             if (phi == nx + 1) return W1[(size_t)(r0 + nx + EPNN_EDIM) * 32 + m];
             if (phi == nx + 2) return b1 ? b1[m] : 0.0;
             return 0.0;
+        };
+        // the xq block of a first Dense as a K = 16 kernel in the slot order of wave_xq_slot (nmrow: the node mask's row, or none)
+        auto xq_bf3k16 = [&](const float *W1, const float *b1, int r0, const double *nmrow) {
+            return frag_bf3k16([&](int q, int s, int out) -> double {
+                const int phi = wave_xq_slot(q, s, nx);
+                return phi < 0 ? 0.0 : xq_row(W1, b1, r0, phi, out, nmrow ? nmrow[out] : 0.0);
+            });
         };
         auto unfolded = [&](const float *W1, const float *b1, int r0) {      // xq steps, then the 12 h steps
             return frag(2, EPNN_XS + 12, [&](int s, int q, int m) -> double {
@@ -470,41 +504,11 @@ static int pack_weights(epnn_handle *h) {
             });
             if (HU == 32) {      // the same two blocks as bf16 pieces (the per-atom chains on the bf16 pipe; 32-unit update MLPs)
                 o.hb = frag_bf3([&](int in, int out) { return prod[(size_t)in * 32 + out]; });
-                o.xb = frag_bf3s([&](int q, int s, int out) -> double {
-                    const int phi = wave_xq_slot(q, s, nx);
-                    return phi < 0 ? 0.0 : xq_row(W1, b1, r0, phi, out, cb[out]);
-                });
+                o.xb = xq_bf3k16(W1, b1, r0, cb.data());
             }
             return o;
         };
         const bool have_basis = (int)h->edge_B.size() == EPNN_EDIM * EPNN_ER;
-        // a K = 16 kernel as three bf16 pieces per weight for v_mfma_f32_16x16x16_bf16, [2][3][64 lanes][2 dwords]: lane (q, m) of row
-        // block rb: K slots s = 0..3 = fn(q, s, 16 rb + m); dword j = slots 2j | 2j+1 << 16
-        auto frag_bf3k16 = [&](auto &&fn) {
-            const int off = alloc((size_t)2 * 3 * 64 * 2);
-            for (int rb = 0; rb < 2; ++rb)
-                for (int l = 0; l < 64; ++l) {
-                    uint32_t pc[3][4];
-                    for (int s = 0; s < 4; ++s) {
-                        float v = (float)fn(l >> 4, s, 16 * rb + (l & 15));
-                        for (int k = 0; k < 3; ++k) {
-                            uint32_t bits;
-                            memcpy(&bits, &v, 4);
-                            bits &= 0xffff0000u;
-                            float top;
-                            memcpy(&top, &bits, 4);
-                            pc[k][s] = bits >> 16;
-                            v = v - top;
-                        }
-                    }
-                    for (int k = 0; k < 3; ++k)
-                        for (int j = 0; j < 2; ++j) {
-                            const uint32_t word = pc[k][2 * j] | pc[k][2 * j + 1] << 16;
-                            memcpy(&buf[off + ((rb * 3 + k) * 64 + l) * 2 + j], &word, 4);
-                        }
-                }
-            return off;
-        };
         auto pair_common = [&](HostDense (&mm)[3], int &we, int &we16, int &we16b, int &w2, int &b2) {
             const float *W1 = mm[0].W.data(), *W2 = mm[1].W.data(), *bb2 = mm[1].b.data();
             we = frag(2, 12, [&](int s, int q, int m) { return (double)W1[(size_t)(2 * F + 12 * q + s) * 32 + m]; });
@@ -586,6 +590,11 @@ static int pack_weights(epnn_handle *h) {
         }
         X.wi0 = unfolded(h->msg[0][0].W.data(), h->msg[0][0].b.data(), 0);
         X.wj0 = unfolded(h->msg[0][0].W.data(), nullptr, F);
+        X.wi0xb = X.wj0xb = 0;
+        if (HU == 32) {
+            X.wi0xb = xq_bf3k16(h->msg[0][0].W.data(), h->msg[0][0].b.data(), 0, nullptr);
+            X.wj0xb = xq_bf3k16(h->msg[0][0].W.data(), nullptr, F, nullptr);
+        }
         X.u1h0 = frag(NRU, 12, [&](int s, int q, int m) { return (double)Wu1[(size_t)accf(s, q) * HU + m]; });
         X.u3 = frag(3, KU, [&](int s, int q, int m) { return (double)Wu3[(size_t)accf(s, q) * EPNN_EDIM + m]; });
         X.bu3 = vec(48, [&](int k) { return (double)bu3[k]; });

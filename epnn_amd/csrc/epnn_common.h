@@ -85,18 +85,19 @@ struct WaveGnnPack {           // GNN step t
     int pwi, pwj;         // [2][8+XS][64]  acc rows: Wu3 M_h;  xq rows: [M_h^T bu3, M_x, M_q, b1]   (M = Wi / Wj of step t+1)
     int pu1;              // [2][8][64]   acc order     Wu3 Wu1_H
     int cu3;              // [32]         Wu1_H^T bu3
-    // the same kernels as three bf16 pieces per weight, [2][3][64][4] dwords each (w2b's layout; 32-unit update MLPs only): the
-    // per-atom chains on the bf16 matrix pipe.  `..hb` = the K = 32 block that multiplies nm u2 (acc order), `..xb` = the xq block in
-    // the slot order of wave_xq_slot
+    // the same kernels as three bf16 pieces per weight (32-unit update MLPs only): the per-atom chains on the bf16 matrix pipe.
+    // `..hb` = the K = 32 block that multiplies nm u2 (acc order), [2][3][64][4] dwords each (w2b's layout); `..xb` = the xq block,
+    // a K = 16 operand in the slot order of wave_xq_slot, [2][3][64][2] dwords each (we16b's layout, v_mfma_f32_16x16x16_bf16)
     int u1sb, u2b, pu1b, pwihb, pwixb, pwjhb, pwjxb;
 };
-// K slot (lane group q, slot s of the lane) of the xq block's operand -> index into xq (0 node mask, 1..nx x, nx + 1 q, nx + 2 one),
-// -1 = empty.  Lane group 0: mask, one, charge, x[0..4]; lane group 1: x[5..9].  (Every value is a float32 -- x is whatever the
+// K slot (lane group q, slot s of the lane: K index 4q + s of v_mfma_f32_16x16x16_bf16) of the xq block's operand -> index into xq
+// (0 node mask, 1..nx x, nx + 1 q, nx + 2 one), -1 = empty.  Lane group 0: mask, one, charge, x[0]; lane group q >= 1:
+// x[4q - 3 .. 4q]: nx + 3 <= 16 values fill the 16 slots exactly at nx = 13.  (Every value is a float32 -- x is whatever the
 // caller's feature columns hold -- and is split into three pieces like any other operand.)
 __host__ __device__ static inline int wave_xq_slot(int q, int s, int nx) {
-    if (q == 0) return s == 0 ? 0 : (s == 1 ? nx + 2 : (s == 2 ? nx + 1 : (s - 3 < nx ? s - 2 : -1)));
-    if (q == 1) return 5 + s < nx ? 6 + s : -1;
-    return -1;
+    const int k = 4 * q + s;
+    if (k < 3) return k == 0 ? 0 : (k == 1 ? nx + 2 : nx + 1);
+    return k - 3 < nx ? k - 2 : -1;
 }
 struct WaveEpnPack {           // EPN step t
     int we, w2, b2, w3;   // w3: [32]
@@ -105,12 +106,13 @@ struct WaveEpnPack {           // EPN step t
     int we16b;            // [2][3][64][2] dwords: B^T We_t as three bf16 pieces per weight (see WaveGnnPack)
     int wi, wj;           // [2][XS+12][64]  xq rows, then h rows (acc order over 48 features): h given by the caller
     int wif, wjf;         // [2][8+XS][64]   acc rows: Wu3 M_h;  xq rows: [M_h^T bu3, M_x, M_q, b1]: h = nm (Wu3^T u2 + bu3) of the GNN stack
-    int wifhb, wifxb, wjfhb, wjfxb;      // wif / wjf as bf16 pieces (see WaveGnnPack)
+    int wifhb, wifxb, wjfhb, wjfxb;      // wif / wjf as bf16 pieces (see WaveGnnPack: ..hb K = 32, ..xb K = 16)
 };
 struct WaveIndex {
     WaveGnnPack g[EPNN_MAXT];
     WaveEpnPack e[EPNN_MAXT];
     int wi0, wj0;         // [2][XS+12][64]  first GNN step (h given by the caller, usually zeros)
+    int wi0xb, wj0xb;     // [2][3][64][2] dwords: the xq rows of wi0 / wj0 as bf16 pieces (see WaveGnnPack's ..xb; 32-unit update MLPs only)
     int u1h0;             // [2][12][64]     acc order over 48 features  Wu1_H
     int u3;               // [3][8][64]      acc order  Wu3 (48 outputs = 3 row blocks)
     int bu3;              // [48]

@@ -270,6 +270,15 @@ struct epnn_handle {
 // an update MLP that is neither [32, 32] nor embedded in it: the tiled path runs its generic update stage, the block-per-wavefront
 // kernels are not built for it; the one-wavefront-per-molecule kernel has a 64-unit variant (upd_wide), without it everything is tiled
 static inline bool upd_generic_stage(const epnn_handle *h) { return h->upd_generic && !h->upd_embed; }
+// A handle of epnn_create_fused with more atom-feature columns than the tiled kernels' feature image holds (EPNN_F1): only the fused
+// kernels of the coordinate entries run it (their xq operand holds nx + 3 <= 16 values); every other entry refuses it by name.
+static inline bool fused_only(const epnn_handle *h) { return h->cfg.nx + EPNN_EDIM + 1 > EPNN_F1; }
+#define EPNN_NOT_FUSED_ONLY(h, what)                                                                                              \
+    do {                                                                                                                          \
+        if (fused_only(h))                                                                                                        \
+            EPNN_FAIL("%s: nx = %d (epnn_create_fused) runs on the fused kernels only: epnn_forward_xyz and its variants, molecules of at most %d atoms", \
+                      what, (h)->cfg.nx, EPNN_W2_NMAX4);                                                                          \
+    } while (0)
 static inline bool upd_tiled_only(const epnn_handle *h) { return h->upd_generic && !h->upd_embed && !h->upd_wide; }
 static inline bool comm_collectives(const epnn_handle *h) { return h->comm && (h->comm_world > 1 || h->opt_part_collective); }
 static inline int comm_guard(epnn_handle *h, int local_fail, const char *what) {

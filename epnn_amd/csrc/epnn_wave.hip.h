@@ -240,6 +240,34 @@ __device__ __forceinline__ void w16_mm_bf(const u32x4 (&w)[2][3], u32x4 z1, u32x
     _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_)                                                         \
         _Pragma("unroll") for (int pc_ = 0; pc_ < 3; ++pc_)                                                     \
             (dst)[rb_][pc_] = reinterpret_cast<const u32x4 *>(wp + (size_t)(unsigned)(off))[(rb_ * 3 + pc_) * 64 + lane];
+// ---- the same at K = 16 (v_mfma_f32_16x16x16_bf16, half the pipe time): operands of up to 16 values -- the pair coordinates of a G
+// product and the xq block (node mask, one, charge, x: wave_xq_slot).  Lane 16 q + m holds row / column m and the K slots
+// 4 q .. 4 q + 3 as two dwords of bf16 pairs; the split of a lane's four values is one remainder MFMA per level.
+__device__ __forceinline__ void w16_split3k16(f32x4 x, w16_u32x2 &p1, w16_u32x2 &p2, w16_u32x2 &p3) {
+    const w16_u32x2 I = w16_ident();
+    p1 = w16_pack_hi2(x);
+    x = w16_rem(I, p1[0], p1[1], x);
+    p2 = w16_pack_hi2(x);
+    x = w16_rem(I, p2[0], p2[1], x);
+    p3 = w16_pack_hi2(x);
+}
+// D[rb] += W[rb] z, the partial products in w16_mm_bf's order (smallest terms first)
+__device__ __forceinline__ void w16_mm_bfk16(const w16_u32x2 (&w)[2][3], const w16_u32x2 (&z)[3], f32x4 (&d)[2]) {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        d[rb] = w16_rem(w[rb][0], z[2][0], z[2][1], d[rb]);
+        d[rb] = w16_rem(w[rb][1], z[1][0], z[1][1], d[rb]);
+        d[rb] = w16_rem(w[rb][2], z[0][0], z[0][1], d[rb]);
+        d[rb] = w16_rem(w[rb][0], z[1][0], z[1][1], d[rb]);
+        d[rb] = w16_rem(w[rb][1], z[0][0], z[0][1], d[rb]);
+        d[rb] = w16_rem(w[rb][0], z[0][0], z[0][1], d[rb]);
+    }
+}
+// a K = 16 three-piece kernel: [2 row blocks][3 pieces][64 lanes][2 dwords], one 8-byte load each
+#define W16_LDB16(dst, off)                                                                                     \
+    _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_)                                                         \
+        _Pragma("unroll") for (int pc_ = 0; pc_ < 3; ++pc_)                                                     \
+            (dst)[rb_][pc_] = reinterpret_cast<const w16_u32x2 *>(wp + (size_t)(unsigned)(off))[(rb_ * 3 + pc_) * 64 + lane];
 __device__ __forceinline__ f32x4 w16_relu(f32x4 v) {
     return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
 }
@@ -331,22 +359,9 @@ __device__ __forceinline__ void w16_feed(const f32x4 (&a)[NRB], float (&in)[4 * 
     w16_u32x2 gwb[2][3];                                                                                                  \
     auto g_mm = [&](const float (&e)[KE], f32x4 (&d)[2]) {      /* d[rb] += We[rb] e for 16 pairs (columns) */            \
         if constexpr (GB) {                                                                                               \
-            const w16_u32x2 I = w16_ident();                                                                              \
-            f32x4 x = {e[0], e[1], e[2], e[3]};                                                                           \
-            w16_u32x2 z1, z2, z3;                                                                                         \
-            z1 = w16_pack_hi2(x);                                                                                         \
-            x = w16_rem(I, z1[0], z1[1], x);                                                                              \
-            z2 = w16_pack_hi2(x);                                                                                         \
-            x = w16_rem(I, z2[0], z2[1], x);                                                                              \
-            z3 = w16_pack_hi2(x);                                                                                         \
-            _Pragma("unroll") for (int rb = 0; rb < 2; ++rb) {                                                            \
-                d[rb] = w16_rem(gwb[rb][0], z3[0], z3[1], d[rb]);                                                         \
-                d[rb] = w16_rem(gwb[rb][1], z2[0], z2[1], d[rb]);                                                         \
-                d[rb] = w16_rem(gwb[rb][2], z1[0], z1[1], d[rb]);                                                         \
-                d[rb] = w16_rem(gwb[rb][0], z2[0], z2[1], d[rb]);                                                         \
-                d[rb] = w16_rem(gwb[rb][1], z1[0], z1[1], d[rb]);                                                         \
-                d[rb] = w16_rem(gwb[rb][0], z1[0], z1[1], d[rb]);                                                         \
-            }                                                                                                             \
+            w16_u32x2 z[3];                                                                                               \
+            w16_split3k16(f32x4{e[0], e[1], e[2], e[3]}, z[0], z[1], z[2]);                                               \
+            w16_mm_bfk16(gwb, z, d);                                                                                      \
         } else {                                                                                                          \
             w16_mm<2, KE>(gw, e, d);                                                                                      \
         }                                                                                                                 \
@@ -355,9 +370,7 @@ __device__ __forceinline__ void w16_feed(const f32x4 (&a)[NRB], float (&in)[4 * 
 #define GW_LD(off, offb)                                                                                                  \
     do {                                                                                                                  \
         if constexpr (GB) {                                                                                               \
-            _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_)                                                           \
-                _Pragma("unroll") for (int pc_ = 0; pc_ < 3; ++pc_)                                                       \
-                    gwb[rb_][pc_] = reinterpret_cast<const w16_u32x2 *>(wp + (size_t)(unsigned)(offb))[(rb_ * 3 + pc_) * 64 + lane]; \
+            W16_LDB16(gwb, offb);                                                                                         \
         } else { W16_LD(gw, off, 2, KE); }                                                                                \
     } while (0)
 template <bool GNN, bool EPN, bool FRONT, int NRU = 2>
@@ -631,16 +644,16 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
 
     // The per-atom chains (update MLP, the next step's P / R / u1pre, the EPN stack's P / R) on the bf16 matrix pipe as well (32-unit
     // update MLPs; -DEPNN_CHAIN_F32: f32 MFMAs as before): the K = 32 inputs S, u1 and nm u2 are split like the sweep's activations,
-    // the xq block (mask, one, charge, x) is one more operand of up to 13 values in the slot order of wave_xq_slot.
+    // the xq block (mask, one, charge, x) is one more operand of up to 16 values -- a K = 16 one, in the slot order of wave_xq_slot.
 #ifdef EPNN_CHAIN_F32
     constexpr bool CHB = false;
 #else
     constexpr bool CHB = NRU == 2 && GNN;
 #endif
     u32x4 Bp0[3], Bp1[3];                                  // nm u2 of the last step as pieces (CHB)
-    u32x4 xqb0[3], xqb1[3];                                // the xq operand's pieces (CHB)
-    // (slots: wave_xq_slot -- lane group 0: mask, one, charge, x[0..4]; 1: x[5..9].  Only the charge changes, between EPN steps:
-    //  its three pieces go into the low half of dword 1 of the three operand pieces of lane group 0; nothing else is kept)
+    w16_u32x2 xqb0[3], xqb1[3];                            // the xq operand's pieces (CHB)
+    // (slots: wave_xq_slot -- lane group 0: mask, one, charge, x[0]; q >= 1: x[4q - 3 .. 4q].  Only the charge changes, between EPN
+    //  steps: its three pieces go into the low half of dword 1 of the three operand pieces of lane group 0; nothing else is kept)
     float qc0 = 0.f, qc1 = 0.f;                            // the columns' charges, the same bits in every lane
     auto xq_charge = [&]() {
         if (q != 0) return;
@@ -655,25 +668,30 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             xqb1[k][1] = (xqb1[k][1] & 0xffff0000u) | (__float_as_uint(pc1[k]) >> 16);
         }
     };
+    // d += W xq for the two column blocks (wx: a K = 16 pack in the slot order of wave_xq_slot)
+    auto xq_mm = [&](const w16_u32x2 (&wx)[2][3], f32x4 (&d0)[2], f32x4 (&d1)[2]) {
+        w16_mm_bfk16(wx, xqb0, d0);
+        if (two) w16_mm_bfk16(wx, xqb1, d1);
+    };
     if constexpr (CHB) {
-        float xs0[8], xs1[8];
+        f32x4 xs0, xs1;
         qc0 = cat0 ? qa0 : 0.f;
         qc1 = cat1 ? qa1 : 0.f;
 #pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
+        for (int s_ = 0; s_ < 4; ++s_) {
             // (unconditional loads of clamped columns, selects afterwards)
-            const int k = q == 0 ? s_ - 3 : 5 + s_, kc = min(max(k, 0), nx - 1);
+            const int k = 4 * q + s_ - 3, kc = min(max(k, 0), nx - 1);
             const float u0 = A.xin[(size_t)ia0 * A.nx + kc], u1 = A.xin[(size_t)ia1 * A.nx + kc];
-            const bool isx = q < 2 && k >= 0 && k < nx;
+            const bool isx = k >= 0 && k < nx;
             float v0 = isx && cat0 ? u0 : 0.f, v1 = isx && cat1 ? u1 : 0.f;
             if (q == 0 && s_ == 0) { v0 = nm0; v1 = nm1; }
             if (q == 0 && s_ == 1) { v0 = cat0 ? 1.f : 0.f; v1 = cat1 ? 1.f : 0.f; }
-            if (q == 0 && s_ == 2) { v0 = cat0 ? qa0 : 0.f; v1 = cat1 ? qa1 : 0.f; }
+            if (q == 0 && s_ == 2) { v0 = qc0; v1 = qc1; }
             xs0[s_] = v0;
             xs1[s_] = v1;
         }
-        w16_split3(xs0, xqb0[0], xqb0[1], xqb0[2]);
-        w16_split3(xs1, xqb1[0], xqb1[1], xqb1[2]);
+        w16_split3k16(xs0, xqb0[0], xqb0[1], xqb0[2]);
+        w16_split3k16(xs1, xqb1[0], xqb1[1], xqb1[2]);
     }
     WAVE_STAMP();   // init done
     const float Nf = (float)A.N, padw = (float)(A.N - n);
@@ -747,9 +765,16 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
         f32x4 b2v[2];
         // ---- step 0: G rows, then P / R / u1pre from (xq | h)
         {
+            // the xq block of Wi / Wj: its K = 16 bf16 pieces (CHB), or the f32 xq steps; the h steps only when h is given
             float wa[2][EPNN_XS], wc[2][EPNN_XS];
-            W16_LDX(wa, X.wi0, 2, EPNN_XS, EPNN_XS + 12, 0);      // the xq steps; the h steps only when h is given
-            W16_LDX(wc, X.wj0, 2, EPNN_XS, EPNN_XS + 12, 0);
+            w16_u32x2 wax[2][3], wcx[2][3];
+            if constexpr (CHB) {
+                W16_LDB16(wax, X.wi0xb);
+                W16_LDB16(wcx, X.wj0xb);
+            } else {
+                W16_LDX(wa, X.wi0, 2, EPNN_XS, EPNN_XS + 12, 0);
+                W16_LDX(wc, X.wj0, 2, EPNN_XS, EPNN_XS + 12, 0);
+            }
             WAVE_FENCE();
             gtiles();
 #ifdef EPNN_SWEEP_F32
@@ -764,9 +789,14 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             for (int rb = 0; rb < 2; ++rb) { P0[rb] = w16_splat(0.f); P1[rb] = w16_splat(0.f); }
 #pragma unroll
             for (int rb = 0; rb < NRU; ++rb) { U0[rb] = w16_splat(0.f); U1[rb] = w16_splat(0.f); }
-            w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wa, xq0, P0, xs3);
-            w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wc, xq0, r0, xs3);
-            if (two) { w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wa, xq1, P1, xs3); w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wc, xq1, r1, xs3); }
+            if constexpr (CHB) {
+                xq_mm(wax, P0, P1);
+                xq_mm(wcx, r0, r1);
+            } else {
+                w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wa, xq0, P0, xs3);
+                w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wc, xq0, r0, xs3);
+                if (two) { w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wa, xq1, P1, xs3); w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wc, xq1, r1, xs3); }
+            }
             if (have_h) {                                   // layer-level entry: h given by the caller
                 float wh[2][12], hin0[12], hin1[12];
 #pragma unroll
@@ -1052,25 +1082,26 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             if constexpr (CHB) {
               if (!lastg) {
                 // next step: G rows, then P / R / u1pre from (nm u2 pieces | xq operand) through the folded matrices' pieces
-                u32x4 wh[2][3], wx[2][3];
+                u32x4 wh[2][3];
+                w16_u32x2 wx[2][3];
                 W16_LDB(wh, M.pwihb);
-                W16_LDB(wx, M.pwixb);
+                W16_LDB16(wx, M.pwixb);
                 WAVE_FENCE();
                 gtiles();
                 if (t < 2) WAVE_STAMP();   // G tiles
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb) { P0[rb] = w16_splat(0.f); P1[rb] = w16_splat(0.f); }
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], P0);
-                w16_mm_bf(wx, xqb0[0], xqb0[1], xqb0[2], P0);
-                if (two) { w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], P1); w16_mm_bf(wx, xqb1[0], xqb1[1], xqb1[2], P1); }
+                if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], P1);
+                xq_mm(wx, P0, P1);
                 W16_LDB(wh, M.pwjhb);
-                W16_LDB(wx, M.pwjxb);
+                W16_LDB16(wx, M.pwjxb);
                 f32x4 cu[2];
                 vecu(M.cu3, cu);
                 f32x4 r0[2] = {w16_splat(0.f), w16_splat(0.f)}, r1[2] = {w16_splat(0.f), w16_splat(0.f)};
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], r0);
-                w16_mm_bf(wx, xqb0[0], xqb0[1], xqb0[2], r0);
-                if (two) { w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], r1); w16_mm_bf(wx, xqb1[0], xqb1[1], xqb1[2], r1); }
+                if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], r1);
+                xq_mm(wx, r0, r1);
                 if (cat0) { w16_st(Rl + n16 * EPNN_PST + fo, r0[0]); w16_st(Rl + n16 * EPNN_PST + 16 + fo, r0[1]); }
                 if (own1) { w16_st(Rl + col1 * EPNN_PST + fo, r1[0]); w16_st(Rl + col1 * EPNN_PST + 16 + fo, r1[1]); }
                 W16_LDB(wh, M.pu1b);
@@ -1180,22 +1211,23 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             const WaveEpnPack &M = X.e[t];
             if constexpr (CHB && FOLD) {
                 // P / R of this step from (nm u2 pieces | xq operand): the bf16 pipe (see CHB)
-                u32x4 wh[2][3], wx[2][3];
+                u32x4 wh[2][3];
+                w16_u32x2 wx[2][3];
                 W16_LDB(wh, M.wifhb);
-                W16_LDB(wx, M.wifxb);
+                W16_LDB16(wx, M.wifxb);
                 WAVE_FENCE();
                 f32x4 d0[2] = {w16_splat(0.f), w16_splat(0.f)}, d1[2] = {w16_splat(0.f), w16_splat(0.f)};
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], d0);
-                w16_mm_bf(wx, xqb0[0], xqb0[1], xqb0[2], d0);
-                if (two) { w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], d1); w16_mm_bf(wx, xqb1[0], xqb1[1], xqb1[2], d1); }
+                if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], d1);
+                xq_mm(wx, d0, d1);
                 W16_LDB(wh, M.wjfhb);
-                W16_LDB(wx, M.wjfxb);
+                W16_LDB16(wx, M.wjfxb);
                 if (cat0) { w16_st(Pl + n16 * EPNN_PST + fo, d0[0]); w16_st(Pl + n16 * EPNN_PST + 16 + fo, d0[1]); }
                 if (own1) { w16_st(Pl + col1 * EPNN_PST + fo, d1[0]); w16_st(Pl + col1 * EPNN_PST + 16 + fo, d1[1]); }
                 d0[0] = w16_splat(0.f); d0[1] = w16_splat(0.f); d1[0] = w16_splat(0.f); d1[1] = w16_splat(0.f);
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], d0);
-                w16_mm_bf(wx, xqb0[0], xqb0[1], xqb0[2], d0);
-                if (two) { w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], d1); w16_mm_bf(wx, xqb1[0], xqb1[1], xqb1[2], d1); }
+                if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], d1);
+                xq_mm(wx, d0, d1);
                 if (cat0) { w16_st(Rl + n16 * EPNN_PST + fo, d0[0]); w16_st(Rl + n16 * EPNN_PST + 16 + fo, d0[1]); }
                 if (own1) { w16_st(Rl + col1 * EPNN_PST + fo, d1[0]); w16_st(Rl + col1 * EPNN_PST + 16 + fo, d1[1]); }
             } else {
@@ -1349,24 +1381,32 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 }
                 dq0 = w16_sumq(dq0);
                 dq1 = w16_sumq(dq1);
-#pragma unroll
-                for (int s = 0; s < EPNN_XS; ++s)
-                    if (s == qs && q == ql) { xq0[s] += cat0 ? dq0 : 0.f; xq1[s] += cat1 ? dq1 : 0.f; }
                 if constexpr (CHB && FOLD) {               // (the same sums in every lane: lane group 0 holds the charge's slot)
                     qc0 += cat0 ? dq0 : 0.f;
                     qc1 += cat1 ? dq1 : 0.f;
                     xq_charge();
+                } else {
+#pragma unroll
+                    for (int s = 0; s < EPNN_XS; ++s)
+                        if (s == qs && q == ql) { xq0[s] += cat0 ? dq0 : 0.f; xq1[s] += cat1 ? dq1 : 0.f; }
                 }
             }
             wave_sync_lds();
             if (t < 2) WAVE_STAMP();   // charge update
         }
-#pragma unroll
-        for (int s = 0; s < EPNN_XS; ++s)
-            if (s == qs && q == ql) {
-                if (cat0) A.q_out[a0 + n16] = xq0[s];
-                if (own1) A.q_out[a0 + col1] = xq1[s];
+        if constexpr (CHB && FOLD) {                       // (the float32 xq steps are not kept: the charge is qc0 / qc1)
+            if (q == 0) {
+                if (cat0) A.q_out[a0 + n16] = qc0;
+                if (own1) A.q_out[a0 + col1] = qc1;
             }
+        } else {
+#pragma unroll
+            for (int s = 0; s < EPNN_XS; ++s)
+                if (s == qs && q == ql) {
+                    if (cat0) A.q_out[a0 + n16] = xq0[s];
+                    if (own1) A.q_out[a0 + col1] = xq1[s];
+                }
+        }
     }
     if (FRONT && A.handoff && lane == 0) wave_handoff(A, np);
     WAVE_STAMP();

@@ -137,7 +137,8 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
 #else
     constexpr bool CHB = true;
 #endif
-    u32x4 Bp[3], xqb[3];
+    u32x4 Bp[3];
+    w16_u32x2 xqb[3];                                       // (a K = 16 operand: wave_xq_slot)
     float qc = cat ? qa : 0.f;                              // the column's charge, the same bits in every lane
     auto xq_charge = [&]() {                                // (k_wave_forward: the charge's pieces into the low half of dword 1)
         if (q != 0) return;
@@ -148,18 +149,18 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
         for (int k = 0; k < 3; ++k) xqb[k][1] = (xqb[k][1] & 0xffff0000u) | (__float_as_uint(pc[k]) >> 16);
     };
     if constexpr (CHB) {
-        float xs_[8];
+        f32x4 xs_;
 #pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) {
-            const int k = q == 0 ? s_ - 3 : 5 + s_, kc = min(max(k, 0), nx - 1);
+        for (int s_ = 0; s_ < 4; ++s_) {
+            const int k = 4 * q + s_ - 3, kc = min(max(k, 0), nx - 1);
             const float u = A.xin[(size_t)ia * nx + kc];
-            float v = q < 2 && k >= 0 && k < nx && cat ? u : 0.f;
+            float v = k >= 0 && k < nx && cat ? u : 0.f;
             if (q == 0 && s_ == 0) v = nm;
             if (q == 0 && s_ == 1) v = cat ? 1.f : 0.f;
-            if (q == 0 && s_ == 2) v = cat ? qa : 0.f;
+            if (q == 0 && s_ == 2) v = qc;
             xs_[s_] = v;
         }
-        w16_split3(xs_, xqb[0], xqb[1], xqb[2]);
+        w16_split3k16(xs_, xqb[0], xqb[1], xqb[2]);
     }
     const bool have_h = !FRONT && A.h_in != nullptr;        // h given by the caller (make_model's h_inp); zeros with the compact entry
     f32x4 hk[3] = {w16_splat(0.f), w16_splat(0.f), w16_splat(0.f)};
@@ -328,8 +329,14 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
         f32x4 b2v[2];
         {
             float wa[2][EPNN_XS], wc[2][EPNN_XS];
-            W16_LDX(wa, X.wi0, 2, EPNN_XS, EPNN_XS + 12, 0);
-            W16_LDX(wc, X.wj0, 2, EPNN_XS, EPNN_XS + 12, 0);
+            w16_u32x2 wax[2][3], wcx[2][3];
+            if constexpr (CHB) {
+                W16_LDB16(wax, X.wi0xb);
+                W16_LDB16(wcx, X.wj0xb);
+            } else {
+                W16_LDX(wa, X.wi0, 2, EPNN_XS, EPNN_XS + 12, 0);
+                W16_LDX(wc, X.wj0, 2, EPNN_XS, EPNN_XS + 12, 0);
+            }
             WAVE_FENCE();
             gtiles();
 #ifdef EPNN_SWEEP_F32
@@ -342,8 +349,13 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
             f32x4 r[2] = {w16_splat(0.f), w16_splat(0.f)};
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) { P[rb] = w16_splat(0.f); U[rb] = w16_splat(0.f); }
-            w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wa, xq, P, xs3);
-            w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wc, xq, r, xs3);
+            if constexpr (CHB) {
+                w16_mm_bfk16(wax, xqb, P);
+                w16_mm_bfk16(wcx, xqb, r);
+            } else {
+                w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wa, xq, P, xs3);
+                w16_mm_skip<2, EPNN_XS, EPNN_XS - 1>(wc, xq, r, xs3);
+            }
             if (have_h) {                                   // the h steps of Wi / Wj and the h block of the update MLP's first layer
                 float wh[2][12], hin[12];
 #pragma unroll
@@ -529,22 +541,23 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
             }
             if constexpr (CHB) {
               if (!lastg) {
-                u32x4 wh[2][3], wx[2][3];
+                u32x4 wh[2][3];
+                w16_u32x2 wx[2][3];
                 W16_LDB(wh, M.pwihb);
-                W16_LDB(wx, M.pwixb);
+                W16_LDB16(wx, M.pwixb);
                 WAVE_FENCE();
                 gtiles();
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb) P[rb] = w16_splat(0.f);
                 w16_mm_bf(wh, Bp[0], Bp[1], Bp[2], P);
-                w16_mm_bf(wx, xqb[0], xqb[1], xqb[2], P);
+                w16_mm_bfk16(wx, xqb, P);
                 W16_LDB(wh, M.pwjhb);
-                W16_LDB(wx, M.pwjxb);
+                W16_LDB16(wx, M.pwjxb);
                 f32x4 cu[2];
                 vec2(M.cu3, cu);
                 f32x4 r[2] = {w16_splat(0.f), w16_splat(0.f)};
                 w16_mm_bf(wh, Bp[0], Bp[1], Bp[2], r);
-                w16_mm_bf(wx, xqb[0], xqb[1], xqb[2], r);
+                w16_mm_bfk16(wx, xqb, r);
                 if (own) { w16_st(Rl + col * EPNN_PST + fo, r[0]); w16_st(Rl + col * EPNN_PST + 16 + fo, r[1]); }
                 if (nxt > 0 && !blk1) { w16_st(P0t + col * EPNN_PST + fo, P[0]); w16_st(P0t + col * EPNN_PST + 16 + fo, P[1]); }
                 W16_LDB(wh, M.pu1b);
@@ -608,19 +621,20 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
         for (int t = 0; t < Te; ++t) {
             const WaveEpnPack &M = X.e[t];
             if constexpr (CHB) {
-                u32x4 wh[2][3], wx[2][3];
+                u32x4 wh[2][3];
+                w16_u32x2 wx[2][3];
                 W16_LDB(wh, M.wifhb);
-                W16_LDB(wx, M.wifxb);
+                W16_LDB16(wx, M.wifxb);
                 WAVE_FENCE();
                 f32x4 d[2] = {w16_splat(0.f), w16_splat(0.f)};
                 w16_mm_bf(wh, Bp[0], Bp[1], Bp[2], d);
-                w16_mm_bf(wx, xqb[0], xqb[1], xqb[2], d);
+                w16_mm_bfk16(wx, xqb, d);
                 W16_LDB(wh, M.wjfhb);
-                W16_LDB(wx, M.wjfxb);
+                W16_LDB16(wx, M.wjfxb);
                 if (own) { w16_st(Pl + col * EPNN_PST + fo, d[0]); w16_st(Pl + col * EPNN_PST + 16 + fo, d[1]); }
                 d[0] = w16_splat(0.f); d[1] = w16_splat(0.f);
                 w16_mm_bf(wh, Bp[0], Bp[1], Bp[2], d);
-                w16_mm_bf(wx, xqb[0], xqb[1], xqb[2], d);
+                w16_mm_bfk16(wx, xqb, d);
                 if (own) { w16_st(Rl + col * EPNN_PST + fo, d[0]); w16_st(Rl + col * EPNN_PST + 16 + fo, d[1]); }
             } else {
                 constexpr int KS = 8 + EPNN_XS, SK = 7 + EPNN_XS;
@@ -743,18 +757,23 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
                 const float *row = Dm + (cat ? col : 0) * DSTW;
                 for (int j = q; j < n; j += 4) dq += row[j];
                 dq = w16_sumq(dq);
-#pragma unroll
-                for (int s = 0; s < EPNN_XS; ++s)
-                    if (s == qs && q == ql) xq[s] += cat ? dq : 0.f;
                 if constexpr (CHB) {
                     qc += cat ? dq : 0.f;
                     xq_charge();
+                } else {
+#pragma unroll
+                    for (int s = 0; s < EPNN_XS; ++s)
+                        if (s == qs && q == ql) xq[s] += cat ? dq : 0.f;
                 }
             }
         }
+        if constexpr (CHB) {                                // (the float32 xq steps are not kept: the charge is qc)
+            if (q == 0 && own) A.q_out[a0 + col] = qc;
+        } else {
 #pragma unroll
-        for (int s = 0; s < EPNN_XS; ++s)
-            if (s == qs && q == ql && own) A.q_out[a0 + col] = xq[s];
+            for (int s = 0; s < EPNN_XS; ++s)
+                if (s == qs && q == ql && own) A.q_out[a0 + col] = xq[s];
+        }
     }
     if (A.handoff) {
         sync();

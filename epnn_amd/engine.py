@@ -56,13 +56,14 @@ class DeviceArray:
 
 
 class Engine:
-    def __init__(self, nx=9, h_dim=48, e_dim=48, T=5, hidden=32, cutoff=3.0, eta=2.0, near_tol=1e-5, device=0):
+    def __init__(self, nx=9, h_dim=48, e_dim=48, T=5, hidden=32, cutoff=3.0, eta=2.0, near_tol=1e-5, device=0, fused_only=False):
+        """fused_only: epnn_create_fused -- nx up to 13, and with nx > 10 only forward_xyz* on molecules of at most 64 atoms."""
         self.lib = _lib.load()
         self.cfg = EpnnConfig(nx, h_dim, e_dim, T, hidden, cutoff, eta, near_tol)
         self.nx, self.h_dim, self.e_dim, self.T = nx, h_dim, e_dim, T
         self.device = device
         h = C.c_void_p()
-        check(self.lib.epnn_create(C.byref(self.cfg), device, C.byref(h)), self.lib)
+        check((self.lib.epnn_create_fused if fused_only else self.lib.epnn_create)(C.byref(self.cfg), device, C.byref(h)), self.lib)
         self.h = h
         self._upd_layers = [hidden, hidden]              # hidden widths of the update MLP (set_update_layers)
 

@@ -61,7 +61,8 @@ int epnn_device_count(void);
  * MLP only (make_model: MLP_layer(layers, out_dim=h_dim), charge_gn.py:371); the message and pass MLPs are ([32, 32], 32) and
  * ([32, 32], 1) by its own constants (:52, :84), and every width follows h_dim (:369-374).  Every checkpoint it ships and both of
  * its scripts use layers = [32, 32], h_dim = e_dim = 48 (:413-417, infer.py:47-50).
- *   free :  nx in 1..10 (atom feature columns; 9 and 10 are the reference's two tables), T in 1..8, cutoff, eta, near_tol,
+ *   free :  nx in 1..10 (atom feature columns; 9 and 10 are the reference's two tables; up to 13 on the fused kernels alone:
+ *           epnn_create_fused), T in 1..8, cutoff, eta, near_tol,
  *           h_dim = e_dim in 1..48 (below 48 the model runs as a 48-channel one: zero channels of h and e, zero rows / columns of
  *           the kernels that touch them -- exact, the padding feeds nothing, stays zero through every step and has zero gradient;
  *           every weight, tensor and epnn_edges row at this interface has the MODEL's h_dim channels),
@@ -79,6 +80,12 @@ int epnn_device_count(void);
  * that way (28 M atoms/s on the bench batch: tools/bench_layers.py).  The training step of any `layers` but [32, 32] runs one launch per Dense layer ("train_fused" = 0's kernels)
  * on the model's own shapes -- the same results to float32 rounding, several times slower per small molecule. */
 int epnn_create(const epnn_config *cfg, int device, epnn_handle **out);
+/* The same with nx in 1..13: what the fused kernels' operand of (node mask, x, charge, one) holds, nx + 3 <= 16.  A handle with
+ * nx > 10 runs on the fused kernels ONLY: epnn_forward_xyz, its _begin / _end / _dev / _pbc variants, molecules of at most 64
+ * atoms (32 where the in-kernel front-end is not used: periodic cells), update MLPs of at most [64, 64].  A molecule that would
+ * take the tiled kernels, the dense and layer-level entries, the training step and the charge gradients fail with a message that says
+ * so; the weight entries work as ever.  With nx <= 10 the handle is epnn_create's. */
+int epnn_create_fused(const epnn_config *cfg, int device, epnn_handle **out);
 int epnn_destroy(epnn_handle *h);
 /* Leaves out `n` of the process's hardware queues: the HIP runtime deals a process's streams onto its hardware queues in the order
  * they are created (every handle owns one stream), and a pipeline of several handles runs faster with its lanes on every other
