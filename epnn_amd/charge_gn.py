@@ -198,11 +198,12 @@ class EPN_layer(_Stack):
 
 
 # --------------------------------------------------------------------------------------------- featurisation
-def get_init_edges(xyz, molecular_splits, num=32, cutoff=3.0, eta=2.0, box=None):
+def get_init_edges(xyz, molecular_splits, num=32, cutoff=3.0, eta=2.0, box=None, cell=None):
     """charge_gn.py:122-163.  Returns (e float32 (n,n,num), C float64 (n,n,num)).  ``molecular_splits`` is accepted
     and, as in the reference, does not influence the result (adj is computed there and never used); a 1-D non-empty
     array makes the reference print and exit(), which is reported here as an error instead.  ``box`` (3,): minimum-image
-    distances in that orthorhombic cell (lengths > 0 periodic, 0 open; include/epnn.h)."""
+    distances in that orthorhombic cell (lengths > 0 periodic, 0 open; include/epnn.h); ``cell`` (3, 3): in that general cell (rows
+    are the lattice vectors, a zero row an open axis)."""
     molecular_splits = np.asarray(molecular_splits)
     if molecular_splits.ndim == 1 and molecular_splits.shape != (0,):
         raise ValueError("get_init_edges: the reference calls exit() for 1-D non-empty molecular_splits (charge_gn.py:134-145)")
@@ -210,7 +211,7 @@ def get_init_edges(xyz, molecular_splits, num=32, cutoff=3.0, eta=2.0, box=None)
     if xyz.ndim != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
         raise ValueError(f"get_init_edges: xyz must be (n, 3), got {xyz.shape}")
     # distances in float64 from the float32-rounded coordinates, cosine cutoff, Gaussians, float32 cast: k_edges_dense
-    e, C = _scratch_engine().edges_ex(xyz, num, cutoff, eta, box=box)
+    e, C = _scratch_engine().edges_ex(xyz, num, cutoff, eta, box=box, cell=cell)
     return e, np.tile(C[:, :, None], [1, 1, num])
 
 
@@ -364,27 +365,32 @@ class EPNNModel(_Stack):
 
     predict = __call__
 
-    def predict_xyz(self, offsets, xyz, x, Q, N=None, box=None):
+    def predict_xyz(self, offsets, xyz, x, Q, N=None, box=None, cell=None):
         """Compact entry: flat atom arrays instead of dense tensors; N defaults to the model's natom.  box (3,) or (B, 3):
-        periodic cells (include/epnn.h)."""
-        return self._eng().forward_xyz(offsets, xyz, x, Q, self.natom if N is None else N, box=box)
+        periodic cells; cell (3, 3) or (B, 3, 3): general cells (include/epnn.h)."""
+        return self._eng().forward_xyz(offsets, xyz, x, Q, self.natom if N is None else N, box=box, cell=cell)
 
-    def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N=None, box=None):
+    def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N=None, box=None, cell=None, strain=False):
         """Charges and sum_i g[i] dq_i/dxyz of a flat batch: (q (A,), gxyz (A, 3)).  With g = dE/dq of a potential E(q), the
-        charges' part of the forces is -gxyz.  N defaults to the model's natom; box as in predict_xyz."""
-        return self._eng().charges_vjp_xyz(offsets, xyz, x, Q, g, self.natom if N is None else N, box=box)
+        charges' part of the forces is -gxyz.  N defaults to the model's natom; box and cell as in predict_xyz.  strain=True adds
+        gstrain (B, 3, 3), the derivative with respect to a homogeneous strain of coordinates and cell: (q, gxyz, gstrain)."""
+        return self._eng().charges_vjp_xyz(offsets, xyz, x, Q, g, self.natom if N is None else N, box=box, cell=cell, strain=strain)
 
-    def charge_jacobian_xyz(self, xyz, x, Q, N=None, box=None):
+    def charge_jacobian_xyz(self, xyz, x, Q, N=None, box=None, cell=None):
         """One molecule: (q (n,), J (n, n, 3)) with J[i, k] = dq_i / dxyz_k, from ONE call on n copies of the molecule with
-        one-hot cotangents.  box (3,): its periodic cell."""
+        one-hot cotangents.  box (3,): its periodic cell; cell (3, 3): its general cell."""
         xyz = np.asarray(xyz, dtype=np.float32)
         x = np.asarray(x, dtype=np.float32)
         n = xyz.shape[0]
         offsets = (np.arange(n + 1) * n).astype(np.int32)
         if box is not None and np.asarray(box).shape != (3,):
             raise ValueError(f"charge_jacobian_xyz: box must have shape (3,), got {np.asarray(box).shape}")
+        if cell is not None and np.asarray(cell).shape != (3, 3):
+            raise ValueError(f"charge_jacobian_xyz: cell must have shape (3, 3), got {np.asarray(cell).shape}")
+        if box is not None and cell is not None:
+            raise ValueError("charge_jacobian_xyz: give box or cell, not both")
         q, gxyz = self.charges_vjp_xyz(offsets, np.tile(xyz, (n, 1)), np.tile(x, (n, 1)), np.full(n, Q, dtype=np.float32),
-                                       np.eye(n, dtype=np.float32).ravel(), N, box=box)
+                                       np.eye(n, dtype=np.float32).ravel(), N, box=box, cell=cell)
         return q[:n], gxyz.reshape(n, n, 3)
 
     def predict_xyz_stream(self, batches, N=None, depth=8):

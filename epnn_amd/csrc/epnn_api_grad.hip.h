@@ -16,9 +16,12 @@ static void xyz_grad_release(epnn_handle *h) {
     h->xyz_grad = nullptr;
 }
 
-// box: host box rows [B][3] of periodic cells (minimum-image distances; staged with the other inputs), or null
+// box: host box rows [B][3] of periodic cells (minimum-image distances; staged with the other inputs), or null.  cells: the
+// EpnnCell records [B] of general cells (check_cell) instead, staged the same way; gstrain_out [B][3][3]: with cells, the strain
+// derivative (k_g_xyz_cell / k_g_strain_mol), or null.
 static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                const float *g, float *q_out, float *gxyz_out, const float *box) {
+                                const float *g, float *q_out, float *gxyz_out, const float *box, const EpnnCell *cells = nullptr,
+                                float *gstrain_out = nullptr) {
     for (int b = 0; b < B; ++b)
         if (offsets[b + 1] - offsets[b] > N || offsets[b + 1] - offsets[b] < 1) EPNN_FAIL("epnn_charges_vjp_xyz: molecule %d does not fit N=%d", b, N);
     EPNN_NOT_FUSED_ONLY(h, "epnn_charges_vjp_xyz");
@@ -43,14 +46,16 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
     // the train path's inputs, staged and padded as epnn_train_step_xyz does; the label slot carries -g / 2 (see XyzGrad)
     auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
     const size_t o_xyz = up256((size_t)(B + 1) * 4), o_x = o_xyz + up256((size_t)A * 3 * 4), o_Q = o_x + up256((size_t)A * nx * 4),
-                 o_y = o_Q + up256((size_t)B * 4), o_box = o_y + up256((size_t)A * 4), in_bytes = box ? o_box + (size_t)B * 12 : o_y + (size_t)A * 4;
+                 o_y = o_Q + up256((size_t)B * 4), o_box = o_y + up256((size_t)A * 4), in_bytes = cells ? o_box + (size_t)B * sizeof(EpnnCell) : (box ? o_box + (size_t)B * 12 : o_y + (size_t)A * 4);
     if (h->pin_train.ensure(in_bytes) || h->s_train.ensure(in_bytes) || h->sd_e.ensure(pairs * EPNN_EDIM * 4) ||
         h->sd_mask.ensure(pairs * 4) || h->dn_xs.ensure(slots * nx * 4) || h->dn_hs.ensure(slots * EPNN_EDIM * 4) ||
         h->dn_qs.ensure(slots * 4) || h->sd_out.ensure(slots * 4) || h->tr_realbuf.ensure(slots * 4))
         return 1;
     // [BN] loss terms | [BN] predictions | [BN] zeros | [A][3] gxyz | the coincident-atoms flag;  gE [R][48]
-    const size_t o_zero = 2 * slots, o_gx = 3 * slots, o_bad = o_gx + (size_t)A * 3, nout = o_bad + 1;
-    if (xs->loss.ensure(nout * 4) || xs->grad.ensure(pairs * 48 * 4)) return 1;
+    // ... | [B][9] gstrain (when asked for); behind them, not downloaded, the atoms' strain shares [A][6] float64
+    const size_t o_zero = 2 * slots, o_gx = 3 * slots, o_bad = o_gx + (size_t)A * 3, o_gs = o_bad + 1,
+                 nout = o_gs + (gstrain_out ? (size_t)B * 9 : 0), o_share = (nout * 4 + 7) & ~size_t(7);
+    if (xs->loss.ensure(gstrain_out ? o_share + (size_t)A * 48 : nout * 4) || xs->grad.ensure(pairs * 48 * 4)) return 1;
     char *stage = h->pin_train.as<char>();
     memcpy(stage, offsets, (size_t)(B + 1) * 4);
     memcpy(stage + o_xyz, xyz, (size_t)A * 3 * 4);
@@ -58,11 +63,17 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
     memcpy(stage + o_Q, Q, (size_t)B * 4);
     float *ystage = reinterpret_cast<float *>(stage + o_y);
     for (int a = 0; a < A; ++a) ystage[a] = -0.5f * g[a];
-    if (box) memcpy(stage + o_box, box, (size_t)B * 12);
+    if (cells) memcpy(stage + o_box, cells, (size_t)B * sizeof(EpnnCell));
+    else if (box) memcpy(stage + o_box, box, (size_t)B * 12);
     HIPCHK(hipMemcpyAsync(h->s_train.p, stage, in_bytes, hipMemcpyHostToDevice, h->stream));
     const float *dev = h->s_train.as<float>();
     const int *d_moff = h->s_train.as<int>();
-    if (box)
+    if (cells)
+        hipLaunchKernelGGL(k_t_pad_inputs_cell, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
+                           (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), (int)(o_box / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff,
+                           (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(),
+                           h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+    else if (box)
         hipLaunchKernelGGL(k_t_pad_inputs_pbc, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
                            (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), (int)(o_box / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff,
                            (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(),
@@ -89,7 +100,13 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
     h->tr_moff = nullptr;
     h->tr_real = nullptr;
     if (rc) return 1;
-    if (box)
+    if (cells) {
+        double *share = gstrain_out ? reinterpret_cast<double *>(xs->loss.as<char>() + o_share) : nullptr;
+        hipLaunchKernelGGL(k_g_xyz_cell, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B,
+                           N, xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
+                           reinterpret_cast<int *>(out + o_bad), reinterpret_cast<const EpnnCell *>(dev + o_box / 4), share);
+        if (share) hipLaunchKernelGGL(k_g_strain_mol, dim3((unsigned)B), dim3(64), 0, h->stream, share, d_moff, out + o_gs);
+    } else if (box)
         hipLaunchKernelGGL(k_g_xyz_pbc, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B,
                            N, xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
                            reinterpret_cast<int *>(out + o_bad), reinterpret_cast<const float *>(dev + o_box / 4));
@@ -103,12 +120,14 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
     float *back = h->pin_tout.as<float>();
     HIPCHK(hipMemcpyAsync(back, out + slots, (nout - slots) * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (reinterpret_cast<const int *>(back)[nout - slots - 1] != 0)
-        EPNN_FAIL(box ? "epnn_charges_vjp_xyz_pbc: two atoms of a molecule or their periodic images coincide (distance 0: the edge features have no derivative there)"
+    if (reinterpret_cast<const int *>(back)[o_bad - slots] != 0)
+        EPNN_FAIL(cells ? "epnn_charges_vjp_xyz_cell: two atoms of a molecule or their periodic images coincide (distance 0: the edge features have no derivative there)"
+                  : box ? "epnn_charges_vjp_xyz_pbc: two atoms of a molecule or their periodic images coincide (distance 0: the edge features have no derivative there)"
                       : "epnn_charges_vjp_xyz: two atoms of a molecule coincide (distance 0: the edge features have no derivative there)");
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < offsets[b + 1] - offsets[b]; ++i) q_out[offsets[b] + i] = back[(size_t)b * N + i];
     memcpy(gxyz_out, back + (o_gx - slots), (size_t)A * 3 * 4);
+    if (gstrain_out) memcpy(gstrain_out, back + (o_gs - slots), (size_t)B * 9 * 4);
     return 0;
 }
 
@@ -125,4 +144,14 @@ extern "C" int epnn_charges_vjp_xyz_pbc(epnn_handle *h, int B, int N, const int3
     if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz_pbc: B and N must be positive and offsets[0] must be 0");
     if (check_box(B, box, (double)h->cfg.cutoff, "epnn_charges_vjp_xyz_pbc")) return 1;
     return charges_vjp_xyz_impl(h, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, box);
+}
+
+extern "C" int epnn_charges_vjp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                         const float *Q, const float *cell, const float *g, float *q_out, float *gxyz_out,
+                                         float *gstrain_out) {
+    if (!h || !offsets || !xyz || !x || !Q || !g || !q_out || !gxyz_out) EPNN_FAIL("epnn_charges_vjp_xyz_cell: null argument");
+    if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz_cell: B and N must be positive and offsets[0] must be 0");
+    std::vector<EpnnCell> cells;
+    if (check_cell(B, cell, (double)h->cfg.cutoff, "epnn_charges_vjp_xyz_cell", cells)) return 1;
+    return charges_vjp_xyz_impl(h, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, nullptr, cells.data(), gstrain_out);
 }

@@ -5,11 +5,13 @@
 // ------------------------------------------------------------------------------------------------ training
 // dense (B,N,N,.) make_model inputs from a flat coordinate batch: what gen_padded_init_state builds on the host
 // the body: `in(k)` reads word k of the staged block  offsets | xyz | x | Q | y  (word offsets o_*), wherever that block is
-// PBC: minimum-image distances in the cells box [B][3] at word o_box of the block (epnn_charges_vjp_xyz_pbc)
-template <bool PBC = false, typename IN>
+// PBC 1: minimum-image distances in the cells box [B][3] at word o_box of the block (epnn_charges_vjp_xyz_pbc); PBC 2: in the
+// general cells `cells` [B] (epnn_charges_vjp_xyz_cell)
+template <int PBC = 0, typename IN>
 __device__ __forceinline__ void t_pad_inputs_body(IN &&in, int o_xyz, int o_x, int o_Q, int o_y, int B, int N, int nx, int E, double cutoff,
                                                   double eta, const double *mu, float *e, float *mask, float *xs, float *hs, float *qs,
-                                                  float *ys, int *real_out, int *moff_out, int o_box = 0) {
+                                                  float *ys, int *real_out, int *moff_out, int o_box = 0,
+                                                  const EpnnCell *cells = nullptr) {
     // a thread per (pair, four channels): one thread per pair was 48 double-precision exp in a row on 7 workgroups (13 us of a
     // 0.27 ms one-molecule step); the distance and the cutoff are recomputed by the 12 threads of a pair
     const size_t pairs = (size_t)B * N * N;
@@ -29,7 +31,14 @@ __device__ __forceinline__ void t_pad_inputs_body(IN &&in, int o_xyz, int o_x, i
             const int pi_ = o_xyz + 3 * (a0 + i), pj_ = o_xyz + 3 * (a0 + j);
             double dx = (double)in(pj_) - (double)in(pi_), dy = (double)in(pj_ + 1) - (double)in(pi_ + 1),
                    dz = (double)in(pj_ + 2) - (double)in(pi_ + 2);
-            if (PBC) {
+            if (PBC == 2) {
+                const EpnnCell &c = cells[b];
+                double g[9], av[9];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) { g[k] = c.g[k]; av[k] = (double)c.a[k]; }
+                epnn_mic_cell(dx, dy, dz, g, av);
+            }
+            if (PBC == 1) {
                 dx = epnn_mic(dx, (double)in(o_box + 3 * b));
                 dy = epnn_mic(dy, (double)in(o_box + 3 * b + 1));
                 dz = epnn_mic(dz, (double)in(o_box + 3 * b + 2));
@@ -63,8 +72,15 @@ __global__ __launch_bounds__(256) void k_t_pad_inputs(const float *blk, int o_xy
 __global__ __launch_bounds__(256) void k_t_pad_inputs_pbc(const float *blk, int o_xyz, int o_x, int o_Q, int o_y, int o_box, int B, int N,
                                                           int nx, int E, double cutoff, double eta, const double *mu, float *e, float *mask,
                                                           float *xs, float *hs, float *qs, float *ys, int *real_out) {
-    t_pad_inputs_body<true>([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys,
-                            real_out, nullptr, o_box);
+    t_pad_inputs_body<1>([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys,
+                         real_out, nullptr, o_box);
+}
+// o_cell: the word (a multiple of 2) at which the EpnnCell records of the B molecules start
+__global__ __launch_bounds__(256) void k_t_pad_inputs_cell(const float *blk, int o_xyz, int o_x, int o_Q, int o_y, int o_cell, int B, int N,
+                                                           int nx, int E, double cutoff, double eta, const double *mu, float *e, float *mask,
+                                                           float *xs, float *hs, float *qs, float *ys, int *real_out) {
+    t_pad_inputs_body<2>([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys,
+                         real_out, nullptr, 0, reinterpret_cast<const EpnnCell *>(blk + o_cell));
 }
 // ... or riding in the kernel's own argument block (up to 3.6 KB: one molecule of up to ~69 atoms): no upload, i.e. no copy kernel
 // and no launch boundary in front of the step (5 us of a 0.22 ms one-molecule step); the offsets are left in device memory for the

@@ -81,14 +81,68 @@ __device__ __forceinline__ float epnn_wrap_coord(float x, float L) {
     const double Ld = (double)L;
     return (float)((double)x - Ld * floor((double)x / Ld));
 }
+// General (triclinic) cells (include/epnn.h): what the device needs of one molecule's cell, prepared in float64 by the host's
+// check_cell.  Row k of `a` is lattice vector a_k (the caller's float32 entries), row k of `g` its dual vector g_k inside the span
+// of the periodic rows (g_k . a_l = delta_kl); an open axis has a zero row in both, so that it drops out of every sum below
+// without a branch (n_k = rint(0) = 0, d - 0 * 0 = d exactly).
+struct EpnnCell {
+    double g[9];
+    float a[9];
+    float pre_eps;                    // float32 pre-test (front_scan_row): a fractional part this close to 1/2 is not trusted
+    float pre_margin;                 // ... and the factor on cutoff^2 it compares with
+    float pre_ext;                    // ... and the largest component a position may have to take part in it
+};
+static_assert(sizeof(EpnnCell) == 120, "EpnnCell is staged as 30 words");
+// The image of a float64 displacement that the cell contract names: n_k = rint(g_k . d) from the unshifted d (products and sums in
+// this order, nothing contracted), then d' = ((d - n_0 a_0) - n_1 a_1) - n_2 a_2 per component.  n_k a_kc is exact (a small integer
+// times a float32).  A diagonal cell reduces to epnn_mic per axis except at rounding ties, which lie a cutoff away.
+__device__ __forceinline__ void epnn_mic_cell(double &dx, double &dy, double &dz, const double *g, const double *a) {
+    const double n0 = rint(__dadd_rn(__dadd_rn(__dmul_rn(g[0], dx), __dmul_rn(g[1], dy)), __dmul_rn(g[2], dz)));
+    const double n1 = rint(__dadd_rn(__dadd_rn(__dmul_rn(g[3], dx), __dmul_rn(g[4], dy)), __dmul_rn(g[5], dz)));
+    const double n2 = rint(__dadd_rn(__dadd_rn(__dmul_rn(g[6], dx), __dmul_rn(g[7], dy)), __dmul_rn(g[8], dz)));
+    dx = __dadd_rn(__dadd_rn(__dadd_rn(dx, -__dmul_rn(n0, a[0])), -__dmul_rn(n1, a[3])), -__dmul_rn(n2, a[6]));
+    dy = __dadd_rn(__dadd_rn(__dadd_rn(dy, -__dmul_rn(n0, a[1])), -__dmul_rn(n1, a[4])), -__dmul_rn(n2, a[7]));
+    dz = __dadd_rn(__dadd_rn(__dadd_rn(dz, -__dmul_rn(n0, a[2])), -__dmul_rn(n1, a[5])), -__dmul_rn(n2, a[8]));
+}
+// a cell's dual and lattice vectors as float64 registers (cell index wave-uniform: scalar loads)
+struct EpnnCellD {
+    double g[9], a[9];
+    float ext;
+    __device__ __forceinline__ void load(const EpnnCell *cells, int b) {
+        const EpnnCell &c = cells[__builtin_amdgcn_readfirstlane(b)];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { g[k] = c.g[k]; a[k] = (double)c.a[k]; }
+        ext = c.pre_ext;
+    }
+};
+// epnn_dist2p with the displacement of epnn_mic_cell
+__device__ __forceinline__ double epnn_dist2p_cell(double xi, double yi, double zi, const float *p, const EpnnCellD &c) {
+    double dx = (double)p[0] - xi, dy = (double)p[1] - yi, dz = (double)p[2] - zi;
+    epnn_mic_cell(dx, dy, dz, c.g, c.a);
+    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+// a position moved into the cell along its periodic axes, r - sum_k floor(g_k . r) a_k in float64, rounded to float32 (for the
+// float32 pre-test only).  Along open directions nothing is wrapped: a position with a component above pre_ext afterwards is
+// marked (x = EPNN_PRE_SKIP) and its pairs go to the float64 test untested.
+#define EPNN_PRE_SKIP 1e30f
+__device__ __forceinline__ void epnn_wrap_cell(float &x, float &y, float &z, const EpnnCellD &c) {
+    const double rx = x, ry = y, rz = z;
+    const double n0 = floor(c.g[0] * rx + c.g[1] * ry + c.g[2] * rz), n1 = floor(c.g[3] * rx + c.g[4] * ry + c.g[5] * rz),
+                 n2 = floor(c.g[6] * rx + c.g[7] * ry + c.g[8] * rz);
+    x = (float)(rx - n0 * c.a[0] - n1 * c.a[3] - n2 * c.a[6]);
+    y = (float)(ry - n0 * c.a[1] - n1 * c.a[4] - n2 * c.a[7]);
+    z = (float)(rz - n0 * c.a[2] - n1 * c.a[5] - n2 * c.a[8]);
+    if (fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z))) > c.ext) x = EPNN_PRE_SKIP;
+}
 // A workgroup = four consecutive rows, one wave each.  The candidates' coordinates go through LDS in blocks of
 // EPNN_FRONT_JB atoms, staged once for the four rows with every load of a thread in flight (a wave that fetched its 64
 // candidates per trip straight from memory paid one L2 round trip per trip: 35 of them for a 2220-atom system).  Rows of a
 // workgroup that belong to another molecule than its first row (molecule boundaries) read memory directly.
 #define EPNN_FRONT_JB 2048
 // calls body(j, near, d2, trip) for every candidate j of the row's molecule, 64 per trip (trip t = candidates 64 t .. of the
-// molecule), lane = candidate; wave-uniform trips.  PBC: minimum-image distances in the cells of `box` [B][3].
-template <bool PBC = false, typename Body>
+// molecule), lane = candidate; wave-uniform trips.  PBC 1: minimum-image distances in the cells of `box` [B][3]; PBC 2: in the
+// general cells that `box` points to (EpnnCell [B]).
+template <int PBC = 0, typename Body>
 __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, int row, bool live, Body &&body, const float *box = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int row0 = row - (tid >> 6);                        // the workgroup's first row
@@ -106,7 +160,42 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
     float cut2f = (float)(F.cut2 * 1.0001);
     float Lxf = 0.f, Lyf = 0.f, Lzf = 0.f, ixf = 0.f, iyf = 0.f, izf = 0.f;
     double Lx = 0.0, Ly = 0.0, Lz = 0.0;                      // the row's cell
-    if (PBC) {
+    EpnnCellD cr, c0;                                         // PBC 2: the row's cell, and the staged molecule's
+    float gf[9], af[9], peps = 0.f;
+    if (PBC == 2) {
+        // General-cell pre-test.  S = |a_0| + |a_1| + |a_2|, w = the smallest width, u = 2^-24.  The staged candidates and the row
+        // atom are moved into the cell along its periodic axes in float64 (epnn_wrap_cell) and rounded.  Inside the span of the
+        // periodic rows every component is then at most S in magnitude; along open directions (zero rows, which need not be
+        // Cartesian axes: a tilted slab or wire) nothing bounds it, and the rounding error grows with it.  So a position takes part
+        // only if all its components are at most X = S + 1024 A (no open axis: X = S, which always holds); any other position is
+        // marked and every pair with it goes to the float64 test untested.  For the rest: a rounded component is good to u X, the
+        // float32 difference f of two of them (|f_c| <= 2 X) to 4 u X.  With float32 copies of the dual vectors (relative error
+        // u), p_k = g_k . f is computed with an error of at most
+        //     |g_k| (sqrt(3) 4 u X + u |f| + 3 u |f|) <= 21 u X / w_k                                   (|f| <= 2 sqrt(3) X),
+        // so pre_eps = 32 u X / w bounds it on every axis.  The exact p_k differs from g_k . d of the unwrapped float64 displacement
+        // by an integer.  If the float64 test accepts the pair (D < c), its image has |g_k . d'| <= D / w_k < 1/2 on every axis.
+        //   (a) Some |p_k - rintf(p_k)| >= 1/2 - pre_eps: the float32 rounding may pick another image than the float64 one, which
+        //       in a sheared cell can be much longer.  Such a candidate is passed on to the float64 test untested.
+        //   (b) Otherwise the exact fractional parts lie inside (-1/2, 1/2) around the same integers: n_k is the float64 choice,
+        //       and f - sum n_k a_k (three fmaf per component, operands <= 3 X: 9 u X more) differs from d' by at most
+        //       13 u X per component; 16 u X is used.  With D < c the float32 sum of squares is at most
+        //           (c^2 + 2 sqrt(3) 16 u X c + 3 (16 u X)^2) (1 + 4 u)  =  c^2 (1 + 55.4 r + 768 r^2 + 4 u),   r = u X / c,
+        //       and pre_margin = 1.0001 + 96 r + 1024 r^2 covers it.
+        // Either way the pre-test never rejects a pair the float64 test accepts, for any valid cell (pre_eps >= 1/2, an extremely
+        // thin and long cell, just switches the pre-test off), for coordinates any number of cells outside it (the wrap is
+        // done in float64) and any distance out along an open direction.  check_cell computes the constants in float64;
+        // tests/test_cell_pretest.py runs the same arithmetic in NumPy against the float64 rule.
+        const EpnnCell *cells = reinterpret_cast<const EpnnCell *>(box);
+        c0.load(cells, b0);
+        cr.load(cells, b);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { gf[k] = (float)c0.g[k]; af[k] = (float)c0.a[k]; }
+        const EpnnCell &cc = cells[__builtin_amdgcn_readfirstlane(b0)];
+        peps = 0.5f - cc.pre_eps;
+        cut2f = (float)(F.cut2 * (double)cc.pre_margin);
+        epnn_wrap_cell(xf, yf, zf, c0);
+    }
+    if (PBC == 1) {
         // Periodic pre-test: the staged candidates and the row atom are first moved into the cell (epnn_wrap_coord: float64, then
         // rounded, error <= u L with u = 2^-24), their float32 difference (|.| <= L, error <= u L) is wrapped again by
         // rint(f / L).  A component then differs from the float64 minimum image by at most 3 u L -- the same image -- or, where the
@@ -127,7 +216,13 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
     for (int jb = beg0; jb < end0; jb += EPNN_FRONT_JB) {
         const int nb = min(EPNN_FRONT_JB, end0 - jb);
         __syncthreads();
-        if (PBC) {
+        if (PBC == 2) {
+            for (int jj = tid; jj < nb; jj += 256) {
+                float px = F.xyz[((size_t)jb + jj) * 3], py = F.xyz[((size_t)jb + jj) * 3 + 1], pz = F.xyz[((size_t)jb + jj) * 3 + 2];
+                epnn_wrap_cell(px, py, pz, c0);
+                sx[3 * jj] = px; sx[3 * jj + 1] = py; sx[3 * jj + 2] = pz;
+            }
+        } else if (PBC == 1) {
             for (int i = tid; i < nb * 3; i += 256) {
                 const int k = i % 3;
                 sx[i] = epnn_wrap_coord(F.xyz[(size_t)jb * 3 + i], k == 0 ? Lxf : (k == 1 ? Lyf : Lzf));
@@ -143,13 +238,26 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
                 bool near = false;
                 if (j < nb && jb + j != row) {
                     float fx = sx[3 * j] - xf, fy = sx[3 * j + 1] - yf, fz = sx[3 * j + 2] - zf;
-                    if (PBC) {
+                    bool pass = false;
+                    if (PBC == 1) {
                         fx = fmaf(-Lxf, rintf(fx * ixf), fx);
                         fy = fmaf(-Lyf, rintf(fy * iyf), fy);
                         fz = fmaf(-Lzf, rintf(fz * izf), fz);
                     }
-                    if (fx * fx + fy * fy + fz * fz < cut2f) {
-                        d2 = PBC ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * ((size_t)jb + j), Lx, Ly, Lz) : epnn_dist2p(xi, yi, zi, sx + 3 * j);
+                    if (PBC == 2) {
+                        const float p0 = gf[0] * fx + gf[1] * fy + gf[2] * fz, p1 = gf[3] * fx + gf[4] * fy + gf[5] * fz,
+                                    p2 = gf[6] * fx + gf[7] * fy + gf[8] * fz;
+                        const float n0 = rintf(p0), n1 = rintf(p1), n2 = rintf(p2);
+                        pass = !(fmaxf(fabsf(p0 - n0), fmaxf(fabsf(p1 - n1), fabsf(p2 - n2))) < peps) ||
+                               fmaxf(fabsf(sx[3 * j]), fabsf(xf)) > 0.5f * EPNN_PRE_SKIP;
+                        fx = fmaf(-n2, af[6], fmaf(-n1, af[3], fmaf(-n0, af[0], fx)));
+                        fy = fmaf(-n2, af[7], fmaf(-n1, af[4], fmaf(-n0, af[1], fy)));
+                        fz = fmaf(-n2, af[8], fmaf(-n1, af[5], fmaf(-n0, af[2], fz)));
+                    }
+                    if ((PBC == 2 && pass) || fx * fx + fy * fy + fz * fz < cut2f) {
+                        d2 = PBC == 2   ? epnn_dist2p_cell(xi, yi, zi, F.xyz + 3 * ((size_t)jb + j), cr)
+                             : PBC == 1 ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * ((size_t)jb + j), Lx, Ly, Lz)
+                                        : epnn_dist2p(xi, yi, zi, sx + 3 * j);
                         near = d2 < F.cut2;
                     }
                 }
@@ -163,7 +271,9 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
             double d2 = 0.0;
             bool near = false;
             if (j < end && j != row) {
-                d2 = PBC ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * j, Lx, Ly, Lz) : epnn_dist2p(xi, yi, zi, F.xyz + 3 * j);
+                d2 = PBC == 2   ? epnn_dist2p_cell(xi, yi, zi, F.xyz + 3 * j, cr)
+                     : PBC == 1 ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * j, Lx, Ly, Lz)
+                                : epnn_dist2p(xi, yi, zi, F.xyz + 3 * j);
                 near = d2 < F.cut2;
             }
             body(j, near, d2, (j0 - beg) >> 6);
@@ -172,7 +282,7 @@ __device__ __forceinline__ void front_scan_row(const FrontArgs &F, float *sx, in
 }
 
 // one wave per row i: partners j != i of the same molecule with D < cutoff -- how many in all, how many with j > i
-template <bool PBC = false>
+template <int PBC = 0>
 __device__ __forceinline__ void front_count_body(const FrontArgs &F, float *sx, int blk, const float *box = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blk * 4 + wave;
@@ -198,7 +308,12 @@ __global__ __launch_bounds__(256) void k_front_count(FrontArgs F) {
 // ... in the periodic cells box [B][3] (epnn_forward_xyz_pbc)
 __global__ __launch_bounds__(256) void k_front_count_pbc(FrontArgs F, const float *box) {
     __shared__ float sx[EPNN_FRONT_JB * 3];
-    front_count_body<true>(F, sx, (int)blockIdx.x, box);
+    front_count_body<1>(F, sx, (int)blockIdx.x, box);
+}
+// ... in the general cells `cells` [B] (epnn_forward_xyz_cell)
+__global__ __launch_bounds__(256) void k_front_count_cell(FrontArgs F, const EpnnCell *cells) {
+    __shared__ float sx[EPNN_FRONT_JB * 3];
+    front_count_body<2>(F, sx, (int)blockIdx.x, reinterpret_cast<const float *>(cells));
 }
 
 // both prefix sums in ONE single-workgroup launch (1024 threads x 8 elements per round, a carry between rounds): a
@@ -323,7 +438,7 @@ struct FrontFillShared {
 // rows (systems of up to EPNN_FRONT_INLINE_A atoms: 2 x 2220 words per workgroup for the protein, against a launch of a single
 // workgroup, 6.9 us, between the count and the fill), writes them for the later launches, and the last workgroup the totals
 #define EPNN_FRONT_INLINE_A 8192
-template <bool INLINE = false, bool PBC = false>
+template <bool INLINE = false, int PBC = 0>
 __device__ __forceinline__ void front_fill_body(const FrontArgs &F, FrontFillShared &Sh, int blk, const float *box = nullptr) {
     float *sx = Sh.sx;
     auto &s_j = Sh.s_j;
@@ -437,14 +552,19 @@ __device__ __forceinline__ void front_fill_body(const FrontArgs &F, FrontFillSha
         unsigned long long trips = __ballot(word != 0ull);
         double xi = 0.0, yi = 0.0, zi = 0.0, Lx = 0.0, Ly = 0.0, Lz = 0.0;
         if (live) { xi = (double)F.xyz[3 * row]; yi = (double)F.xyz[3 * row + 1]; zi = (double)F.xyz[3 * row + 2]; }
-        if (PBC && live) { Lx = (double)box[3 * b]; Ly = (double)box[3 * b + 1]; Lz = (double)box[3 * b + 2]; }
+        if (PBC == 1 && live) { Lx = (double)box[3 * b]; Ly = (double)box[3 * b + 1]; Lz = (double)box[3 * b + 2]; }
+        EpnnCellD cr;
+        if (PBC == 2) cr.load(reinterpret_cast<const EpnnCell *>(box), b);
         while (trips) {
             const int t = __ffsll((long long)trips) - 1;
             trips &= trips - 1ull;
             const unsigned long long bal = __shfl(word, t, 64);
             const int j = beg + 64 * t + lane;
             const bool near = (bal >> lane) & 1ull;
-            const double d2 = near ? (PBC ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * j, Lx, Ly, Lz) : epnn_dist2p(xi, yi, zi, F.xyz + 3 * j)) : 0.0;
+            const double d2 = !near       ? 0.0
+                              : PBC == 2 ? epnn_dist2p_cell(xi, yi, zi, F.xyz + 3 * j, cr)
+                              : PBC == 1 ? epnn_dist2p_pbc(xi, yi, zi, F.xyz + 3 * j, Lx, Ly, Lz)
+                                         : epnn_dist2p(xi, yi, zi, F.xyz + 3 * j);
             body(j, near, d2, t);
         }
         return;
@@ -457,7 +577,11 @@ __global__ __launch_bounds__(256) void k_front_fill(FrontArgs F) {
 }
 __global__ __launch_bounds__(256) void k_front_fill_pbc(FrontArgs F, const float *box) {
     __shared__ FrontFillShared Sh;
-    front_fill_body<false, true>(F, Sh, (int)blockIdx.x, box);
+    front_fill_body<false, 1>(F, Sh, (int)blockIdx.x, box);
+}
+__global__ __launch_bounds__(256) void k_front_fill_cell(FrontArgs F, const EpnnCell *cells) {
+    __shared__ FrontFillShared Sh;
+    front_fill_body<false, 2>(F, Sh, (int)blockIdx.x, reinterpret_cast<const float *>(cells));
 }
 
 // one thread per pair (i, j): where does i sit in j's incidence row?  (rows are ascending and short: a few loads in flight)
@@ -486,8 +610,8 @@ __device__ __forceinline__ void front_link_body(const FrontArgs &F, int blk, int
 __global__ __launch_bounds__(256) void k_front_link(FrontArgs F) { front_link_body(F, (int)blockIdx.x, (int)gridDim.x); }
 
 // epnn_edges: dense (n,n,e_dim) tensor exactly like get_init_edges, one thread per (i,j,ch).  PBC: minimum-image distances in the
-// cell box[3] (epnn_edges_pbc)
-template <bool PBC>
+// cell box[3] (epnn_edges_pbc); PBC 2: in the general cell that box points to (one EpnnCell, epnn_edges_cell)
+template <int PBC>
 __device__ __forceinline__ void edges_dense_body(const float *xyz, const float *box, int n, int e_dim, double cutoff, double eta,
                                                  const double *mu, float *e_out, double *c_out) {
     const size_t total = (size_t)n * n * e_dim;
@@ -496,9 +620,16 @@ __device__ __forceinline__ void edges_dense_body(const float *xyz, const float *
         const int ch = (int)(idx % e_dim);
         const size_t pr = idx / e_dim;
         const int j = (int)(pr % n), i = (int)(pr / n);
-        const double D = PBC ? sqrt(epnn_dist2p_pbc((double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], xyz + 3 * j,
-                                                    (double)box[0], (double)box[1], (double)box[2]))
-                             : epnn_dist(xyz, i, j);
+        double D;
+        if (PBC == 2) {
+            EpnnCellD c;
+            c.load(reinterpret_cast<const EpnnCell *>(box), 0);
+            D = sqrt(epnn_dist2p_cell((double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], xyz + 3 * j, c));
+        } else if (PBC == 1)
+            D = sqrt(epnn_dist2p_pbc((double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], xyz + 3 * j, (double)box[0],
+                                     (double)box[1], (double)box[2]));
+        else
+            D = epnn_dist(xyz, i, j);
         double C = (cos(pi_d * (D - 0.0) / cutoff) + 1.0) / 2.0;
         if (D >= cutoff) C = 0.0;
         if (D <= 0.0) C = 1.0;
@@ -510,9 +641,13 @@ __device__ __forceinline__ void edges_dense_body(const float *xyz, const float *
 }
 __global__ __launch_bounds__(256) void k_edges_dense(const float *xyz, int n, int e_dim, double cutoff, double eta,
                                                      const double *mu, float *e_out, double *c_out) {
-    edges_dense_body<false>(xyz, nullptr, n, e_dim, cutoff, eta, mu, e_out, c_out);
+    edges_dense_body<0>(xyz, nullptr, n, e_dim, cutoff, eta, mu, e_out, c_out);
 }
 __global__ __launch_bounds__(256) void k_edges_dense_pbc(const float *xyz, const float *box, int n, int e_dim, double cutoff, double eta,
                                                          const double *mu, float *e_out, double *c_out) {
-    edges_dense_body<true>(xyz, box, n, e_dim, cutoff, eta, mu, e_out, c_out);
+    edges_dense_body<1>(xyz, box, n, e_dim, cutoff, eta, mu, e_out, c_out);
+}
+__global__ __launch_bounds__(256) void k_edges_dense_cell(const float *xyz, const EpnnCell *cell, int n, int e_dim, double cutoff,
+                                                          double eta, const double *mu, float *e_out, double *c_out) {
+    edges_dense_body<2>(xyz, reinterpret_cast<const float *>(cell), n, e_dim, cutoff, eta, mu, e_out, c_out);
 }

@@ -85,10 +85,16 @@ __global__ __launch_bounds__(256) void k_g_edge_dz1(const float *dz1, const floa
 // D from the float32 coordinates in double exactly as k_t_pad_inputs does, gD_ij + gD_ji over the 48 channels, and its
 // contribution (gD_ij + gD_ji) (r_i - r_j) / D; the lanes' sums are combined by a fixed butterfly.  bad: set when two atoms of a
 // molecule coincide (D = 0: the distance has no derivative there).  PBC: minimum-image displacements in the cells box [B][3]
-// (their derivative is that of the unwrapped displacement: the image shift is a constant).
-template <bool PBC>
+// (their derivative is that of the unwrapped displacement: the image shift is a constant).  PBC 2: in the general cells that box
+// points to (EpnnCell [B]).
+// Strain derivative (PBC 2, strain != null): under r -> (1 + eps) r, a_k -> (1 + eps) a_k every image displacement d' becomes
+// (1 + eps) d', so dD/d eps_ac = d'_a d'_c / D and, with F = sum_i g_i q_i,
+//     dF/d eps_ac = sum over pairs i < j with D < cutoff of (gD_ij + gD_ji) d'_a d'_c / D.
+// This wavefront sees each of its atom's pairs, the partner's wavefront sees them again: the atom's share is half the sum over its
+// partners, kept in float64 as strain[a][xx, yy, zz, yz, xz, xy]; k_g_strain_mol adds a molecule's atoms up.
+template <int PBC>
 __device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff, double eta,
-                                           const double *mu, float *gxyz, int *bad, const float *box) {
+                                           const double *mu, float *gxyz, int *bad, const float *box, double *strain = nullptr) {
     const int a = blockIdx.x, lane = threadIdx.x;
     int lo = 0, hi = B;                               // molecule b: moff[b] <= a < moff[b + 1]
     while (hi - lo > 1) {
@@ -99,13 +105,17 @@ __device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, in
     const double pi_d = 3.141592653589793;
     const double xi = xyz[3 * a], yi = xyz[3 * a + 1], zi = xyz[3 * a + 2];
     double Lx = 0.0, Ly = 0.0, Lz = 0.0;
-    if (PBC) { Lx = (double)box[3 * b]; Ly = (double)box[3 * b + 1]; Lz = (double)box[3 * b + 2]; }
+    if (PBC == 1) { Lx = (double)box[3 * b]; Ly = (double)box[3 * b + 1]; Lz = (double)box[3 * b + 2]; }
+    EpnnCellD cr;
+    if (PBC == 2) cr.load(reinterpret_cast<const EpnnCell *>(box), b);
     double s[3] = {0.0, 0.0, 0.0};
+    double W[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int j = lane; j < n; j += 64) {
         if (j == i) continue;
         const int aj = a0 + j;
         double dx = (double)xyz[3 * aj] - xi, dy = (double)xyz[3 * aj + 1] - yi, dz = (double)xyz[3 * aj + 2] - zi;
-        if (PBC) { dx = epnn_mic(dx, Lx); dy = epnn_mic(dy, Ly); dz = epnn_mic(dz, Lz); }
+        if (PBC == 1) { dx = epnn_mic(dx, Lx); dy = epnn_mic(dy, Ly); dz = epnn_mic(dz, Lz); }
+        if (PBC == 2) epnn_mic_cell(dx, dy, dz, cr.g, cr.a);
         const double D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
         if (!(D > 0.0)) { *bad = 1; continue; }
         if (D >= cutoff) continue;                    // C = 0 and C' = 0 beyond the cutoff
@@ -120,6 +130,11 @@ __device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, in
         s[0] -= w * dx;
         s[1] -= w * dy;
         s[2] -= w * dz;
+        if (PBC == 2 && strain) {
+            const double hw = 0.5 * w;
+            W[0] += hw * dx * dx; W[1] += hw * dy * dy; W[2] += hw * dz * dz;
+            W[3] += hw * dy * dz; W[4] += hw * dx * dz; W[5] += hw * dx * dy;
+        }
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -128,12 +143,49 @@ __device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, in
         s[c] = v;
     }
     if (lane < 3) gxyz[3 * a + lane] = (float)(lane == 0 ? s[0] : (lane == 1 ? s[1] : s[2]));
+    if (PBC == 2 && strain) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double v = W[c];
+            for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+            if (lane == 0) strain[6 * (size_t)a + c] = v;
+        }
+    }
 }
 __global__ __launch_bounds__(64) void k_g_xyz(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
                                               double eta, const double *mu, float *gxyz, int *bad) {
-    g_xyz_body<false>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, nullptr);
+    g_xyz_body<0>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, nullptr);
 }
 __global__ __launch_bounds__(64) void k_g_xyz_pbc(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
                                                   double eta, const double *mu, float *gxyz, int *bad, const float *box) {
-    g_xyz_body<true>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, box);
+    g_xyz_body<1>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, box);
+}
+__global__ __launch_bounds__(64) void k_g_xyz_cell(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
+                                                   double eta, const double *mu, float *gxyz, int *bad, const EpnnCell *cells,
+                                                   double *strain) {
+    g_xyz_body<2>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, reinterpret_cast<const float *>(cells), strain);
+}
+// The per-atom strain shares of k_g_xyz_cell summed per molecule, one wavefront each: lane l adds atoms l, l + 64, ... of the
+// molecule in ascending order, a fixed butterfly combines the lanes (no atomics: bit-reproducible, and a molecule's result does not
+// depend on the rest of the batch).  out [B][3][3] float32, the full symmetric matrix.
+__global__ __launch_bounds__(64) void k_g_strain_mol(const double *strain, const int *moff, float *out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int a0 = moff[b], a1 = moff[b + 1];
+    double W[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int a = a0 + lane; a < a1; a += 64)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) W[c] += strain[6 * (size_t)a + c];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        double v = W[c];
+        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+        W[c] = v;
+    }
+    if (lane == 0) {
+        float *o = out + 9 * (size_t)b;
+        o[0] = (float)W[0]; o[4] = (float)W[1]; o[8] = (float)W[2];
+        o[5] = o[7] = (float)W[3];
+        o[2] = o[6] = (float)W[4];
+        o[1] = o[3] = (float)W[5];
+    }
 }

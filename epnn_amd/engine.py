@@ -23,6 +23,22 @@ def _box_rows(box, B):
     return np.ascontiguousarray(box)
 
 
+def _cell_rows(cell, B):
+    """A general cell argument -> (B, 3, 3) float32: shape (3, 3) applies to every molecule, (B, 3, 3) gives one cell each.  Row k
+    is lattice vector a_k, a row of zeros an open axis (include/epnn.h); the library checks the values."""
+    cell = np.asarray(cell, dtype=np.float32)
+    if cell.shape == (3, 3):
+        return np.ascontiguousarray(np.tile(cell, (B, 1, 1)))
+    if cell.shape != (B, 3, 3):
+        raise ValueError(f"cell must have shape (3, 3) or ({B}, 3, 3), got {cell.shape}")
+    return np.ascontiguousarray(cell)
+
+
+def _one_periodic_argument(box, cell):
+    if box is not None and cell is not None:
+        raise ValueError("box and cell are two descriptions of the same thing: give one of them")
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -133,14 +149,22 @@ class Engine:
         check(self.lib.epnn_edges(self.h, n, fptr(xyz), fptr(out)), self.lib)
         return out
 
-    def edges_ex(self, xyz, num, cutoff=3.0, eta=2.0, box=None):
+    def edges_ex(self, xyz, num, cutoff=3.0, eta=2.0, box=None, cell=None):
         """get_init_edges with its own parameters: (e float32 (n,n,num), C float64 (n,n)) from the device kernel.  box (3,):
-        minimum-image distances in that periodic cell (include/epnn.h)."""
+        minimum-image distances in that periodic cell; cell (3, 3): in that general cell (include/epnn.h)."""
+        _one_periodic_argument(box, cell)
         xyz = _f32(xyz)
         n = xyz.shape[0]
         e = np.empty((n, n, int(num)), dtype=np.float32)
         c = np.empty((n, n), dtype=np.float64)
-        if box is None:
+        if cell is not None:
+            cell = np.asarray(cell, dtype=np.float32)
+            if cell.shape != (3, 3):
+                raise ValueError(f"edges_ex: cell must have shape (3, 3), got {cell.shape}")
+            cell = np.ascontiguousarray(cell)
+            check(self.lib.epnn_edges_cell(self.h, n, fptr(xyz), fptr(cell), int(num), float(cutoff), float(eta), fptr(e),
+                                           c.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
+        elif box is None:
             check(self.lib.epnn_edges_ex(self.h, n, fptr(xyz), int(num), float(cutoff), float(eta), fptr(e),
                                          c.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
         else:
@@ -152,9 +176,11 @@ class Engine:
                                           c.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
         return e, c
 
-    def forward_xyz(self, offsets, xyz, x, Q, N, box=None):
+    def forward_xyz(self, offsets, xyz, x, Q, N, box=None, cell=None):
         """Flat batch: offsets (B+1,), xyz (A,3), x (A,nx), Q (B,) -> q (A,) float32.  box (3,) or (B, 3): periodic cells
-        (include/epnn.h: > 0 periodic length, 0 open axis)."""
+        (include/epnn.h: > 0 periodic length, 0 open axis).  cell (3, 3) or (B, 3, 3): general (triclinic) cells, row k the
+        lattice vector a_k, a zero row an open axis."""
+        _one_periodic_argument(box, cell)
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
         B = len(offsets) - 1
@@ -162,7 +188,11 @@ class Engine:
         if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
             raise EpnnError(f"forward_xyz: shapes xyz {xyz.shape} x {x.shape} Q {Q.shape} do not match offsets (A={A}, B={B}, nx={self.nx})")
         out = np.empty((A,), dtype=np.float32)
-        if box is None:
+        if cell is not None:
+            cell = _cell_rows(cell, B)
+            check(self.lib.epnn_forward_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), fptr(out)),
+                  self.lib)
+        elif box is None:
             check(self.lib.epnn_forward_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(out)), self.lib)
         else:
             box = _box_rows(box, B)
@@ -297,9 +327,15 @@ class Engine:
                                            C.byref(loss), int(bool(apply))), self.lib)
         return q, loss.value
 
-    def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N, box=None):
+    def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N, box=None, cell=None, strain=False):
         """Flat batch and a cotangent g (A,) of the charges -> (q (A,), gxyz (A, 3) = sum_i g[i] dq_i/dxyz).  Touches no
-        training state; works without train_init.  box (3,) or (B, 3): periodic cells, as in forward_xyz."""
+        training state; works without train_init.  box (3,) or (B, 3): periodic cells, as in forward_xyz; cell (3, 3) or
+        (B, 3, 3): general cells.  strain=True (with cell, or with neither: open molecules) returns (q, gxyz, gstrain) with
+        gstrain (B, 3, 3) the derivative of sum_i g[i] q_i with respect to a homogeneous strain of coordinates and cell
+        (include/epnn.h: dF/dH = inv(H).T @ gstrain for the cell matrix H at fixed fractional coordinates)."""
+        _one_periodic_argument(box, cell)
+        if strain and box is not None:
+            raise ValueError("charges_vjp_xyz: strain=True takes the cell as cell= (np.diag(box) for an orthorhombic one)")
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         xyz, x, Q, g = _f32(xyz), _f32(x), _f32(Q), _f32(g)
         B, A = len(offsets) - 1, int(offsets[-1])
@@ -307,6 +343,12 @@ class Engine:
             raise EpnnError("charges_vjp_xyz: array shapes do not match offsets")
         q = np.empty((A,), dtype=np.float32)
         gxyz = np.empty((A, 3), dtype=np.float32)
+        if cell is not None or strain:
+            cell = _cell_rows(np.zeros((3, 3), np.float32) if cell is None else cell, B)
+            gs = np.empty((B, 3, 3), dtype=np.float32) if strain else None
+            check(self.lib.epnn_charges_vjp_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), fptr(g),
+                                                     fptr(q), fptr(gxyz), fptr(gs) if strain else None), self.lib)
+            return (q, gxyz, gs) if strain else (q, gxyz)
         if box is None:
             check(self.lib.epnn_charges_vjp_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(g), fptr(q),
                                                 fptr(gxyz)), self.lib)
@@ -405,9 +447,14 @@ class Engine:
             check(self.lib.epnn_memcpy_h2d(self.h, C.c_void_p(d_ptr + 4 * row_len * row_lo), rows.ctypes.data_as(C.c_void_p),
                                            rows.nbytes), self.lib)
 
-    def forward_xyz_dev(self, offsets, d_xyz, d_x, d_Q, d_q, N, box=None):
+    def forward_xyz_dev(self, offsets, d_xyz, d_x, d_Q, d_q, N, box=None, cell=None):
+        _one_periodic_argument(box, cell)
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        if box is None:
+        if cell is not None:
+            cell = _cell_rows(cell, len(offsets) - 1)
+            check(self.lib.epnn_forward_xyz_cell_dev(self.h, len(offsets) - 1, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr,
+                                                     d_Q.ptr, fptr(cell), d_q.ptr), self.lib)
+        elif box is None:
             check(self.lib.epnn_forward_xyz_dev(self.h, len(offsets) - 1, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr,
                                                 d_Q.ptr, d_q.ptr), self.lib)
         else:

@@ -6,7 +6,8 @@ There is no network for datasets, so bench.py runs on molecules generated here:
     within 1.0-1.6 A of an existing one) which gives ~8 partners within the 3 A cutoff per atom like the real set.
   * periodic-like box: uniform atoms at density 0.1 / A^3 with min separation 0.9 A and the protein's element mix (an open
     cluster: atoms near a face lose partners);
-  * periodic box: the same in a periodic cubic cell, the separation enforced across the faces (periodic_box_system).
+  * periodic box: the same in a periodic cubic cell, the separation enforced across the faces (periodic_box_system);
+  * sheared cell: the same in a triclinic cell of that volume (triclinic_cell_system).
 """
 from __future__ import annotations
 
@@ -148,6 +149,52 @@ def periodic_box_system(n_atoms=10_000, seed=0, density=0.1, min_sep=0.9):
     offsets = np.array([0, n_atoms], dtype=np.int32)
     box = np.full((1, 3), side, dtype=np.float32)
     return offsets, np.array(pts, dtype=np.float32), features(symbols), np.zeros(1, dtype=np.float32), n_atoms, box
+
+
+def triclinic_cell_system(n_atoms=10_000, seed=0, density=0.1, min_sep=0.9, shear=((0.3, 0.0, 0.0), (-0.2, 0.25, 0.0))):
+    """One periodic sheared cell: the analogue of periodic_box_system with lattice vectors a = (s, 0, 0),
+    b = (shear[0][0] s, s, 0), c = (shear[1][0] s, shear[1][1] s, s) -- the volume s^3 and so the density of the cubic cell of
+    side s -- uniform atoms with the minimum separation enforced between all images, the element mix of box_system.
+    Returns (offsets, xyz, x, Q, N, cell) with cell (1, 3, 3) float32 (rows are the lattice vectors)."""
+    rng = np.random.default_rng(seed)
+    side = float(np.float32((n_atoms / density) ** (1.0 / 3.0)))
+    cell = np.array([[side, 0.0, 0.0], [shear[0][0] * side, side, 0.0], [shear[1][0] * side, shear[1][1] * side, side]],
+                    dtype=np.float32)
+    H = cell.astype(np.float64)
+    G = np.linalg.inv(H)                                   # fractional coordinates f = r @ G, r = f @ H
+    width = 1.0 / np.sqrt((G * G).sum(0))                  # perpendicular widths of the three axes
+    ncell = max(1, int(width.min() // min_sep))            # fractional bins at least min_sep wide: neighbours within the 27 around
+    around = [(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)]
+    Hl = H.tolist()
+    grid = {}
+    pts = []
+    m2 = min_sep * min_sep
+    while len(pts) < n_atoms:
+        for f in rng.uniform(0, 1, size=(4096, 3)).tolist():
+            c = [int(v * ncell) % ncell for v in f]
+            ok = True
+            for da, db, dc in around:
+                for q in grid.get(((c[0] + da) % ncell, (c[1] + db) % ncell, (c[2] + dc) % ncell), ()):
+                    u = [f[k] - q[k] for k in range(3)]
+                    u = [t - round(t) for t in u]
+                    v = [u[0] * Hl[0][k] + u[1] * Hl[1][k] + u[2] * Hl[2][k] for k in range(3)]
+                    if v[0] * v[0] + v[1] * v[1] + v[2] * v[2] < m2:
+                        ok = False
+                        break
+                if not ok:
+                    break
+            if ok:
+                pts.append(f)
+                grid.setdefault(tuple(c), []).append(f)
+                if len(pts) == n_atoms:
+                    break
+    names = [e for e, _ in PROTEIN_ELEMS]
+    ep = np.array([p for _, p in PROTEIN_ELEMS])
+    ep /= ep.sum()
+    symbols = rng.choice(names, size=n_atoms, p=ep)
+    offsets = np.array([0, n_atoms], dtype=np.int32)
+    xyz = (np.array(pts) @ H).astype(np.float32)
+    return offsets, xyz, features(symbols), np.zeros(1, dtype=np.float32), n_atoms, cell[None]
 
 
 def algorithmic_flops(ns, near_unordered_pairs, nx=9, T=5, E=48, H=32, parts=False, chains_bf16=False, edges_bf16=True):

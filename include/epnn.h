@@ -213,7 +213,7 @@ int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, c
  *     is at least a cutoff away.  Coordinates need not lie in the cell.
  *   Unchanged: N and the padded partners, Q (the charge of the cell), C[D <= 0] = 1, the is_near tolerance, charge conservation.
  *   Derivative: that of a minimum-image displacement with respect to x_i / x_j is that of the unwrapped one (the image shift is
- *     constant); box derivatives (dq/dL, virial, stress) are not provided.  Triclinic cells are not supported.
+ *     constant).  Triclinic cells, and the derivative with respect to the cell (dq/dL, virial, stress), are the _cell entries below.
  *   Routing: a periodic forward always builds its pair list with the separate front-end launches; molecules of up to 32 atoms run
  *     the fused kernel on that list, larger ones the tiled kernels (the path wave_front = 0 (include/epnn_dev.h) takes).  With every box row 0 the
  *     result is bit-identical to epnn_forward_xyz with wave_front = 0 (include/epnn_dev.h), and epnn_charges_vjp_xyz_pbc to epnn_charges_vjp_xyz.
@@ -229,6 +229,55 @@ int epnn_charges_vjp_xyz_pbc(epnn_handle *h, int B, int N, const int32_t *offset
 /* epnn_edges_ex in the periodic cell box[3]: minimum-image edge features and cutoff weights of one system. */
 int epnn_edges_pbc(epnn_handle *h, int n, const float *xyz, const float *box, int num, double cutoff, double eta, float *e_out,
                    double *c_out);
+/* ---- periodic systems, general (triclinic) cells, and the strain derivative of the charges.
+ *   cell[b][k][0..2] (float32, Angstrom, host memory): row k of molecule b is the lattice vector a_k.
+ *     A row of three zeros is an open axis (slabs, wires; with all three rows zero an open molecule in the same batch).
+ *     Refused, epnn_last_error naming molecule and axis: a NaN or infinite entry; non-zero rows that are linearly dependent; a
+ *     periodic axis whose PERPENDICULAR WIDTH is below 2 * cutoff.  The width of periodic axis k is w_k = 1 / |g_k| with g_k the
+ *     dual vector of a_k inside the span of the periodic rows (g_k . a_l = delta_kl for periodic l).  Three periodic rows: g_k are
+ *     the columns of the inverse cell matrix, w_k = |det| / |a_l x a_m|; two: w_a = |a x b| / |b|; one: |a|.  Edge lengths do not
+ *     decide it: the cell (6.5,0,0), (5,6.5,0), (0,0,7) has every edge above 6 A and a width of 5.15 A, and is refused at the
+ *     default cutoff.  For a hexagonal cell with a 120 (or 60) degree angle the width is a sqrt(3) / 2: a >= 6.93 A.
+ *   Distance, all in float64 from the float32 inputs: d = r_j - r_i; n_k = rint(g_k . d) for every periodic k, the dot product
+ *     summed as (g_k0 dx + g_k1 dy) + g_k2 dz; d' = ((d - n_0 a_0) - n_1 a_1) - n_2 a_2 per component (each n_k a_kc is exact);
+ *     D = sqrt((dx'^2 + dy'^2) + dz'^2) in the order of the open and orthorhombic code.  g_k is computed by the library on the host
+ *     in float64 (cross products divided by the determinant; two rows: (b x n) / |n|^2 and (n x a) / |n|^2 with n = a x b; one
+ *     row: a / |a|^2).
+ *   Why that is enough: a displacement shorter than the cutoff has |g_k . d'| <= |d'| / w_k < 1/2 on every periodic axis, so with
+ *     w_k >= 2 * cutoff it is the image the rounding returns, and the only image within the cutoff.  Beyond the cutoff the image
+ *     returned need not be the shortest one (in a sheared cell it often is not): that does not matter, because e, C and the
+ *     is_near weight are zero there -- epnn_edges_cell's C output included.  Coordinates need not lie in the cell; the cell may
+ *     change on every call.
+ *   Unchanged, as for box: N and the padded partners, Q (the charge of the cell), C[D <= 0] = 1, the is_near tolerance, charge
+ *     conservation.  A diagonal cell diag(Lx, Ly, Lz) (zeros allowed) gives the bits of the box = (Lx, Ly, Lz) entries, an
+ *     all-zero cell those of the open entries on the same route (the rule reduces to d - L rint(d / L) except at rounding ties,
+ *     which lie at least a cutoff away); these entries run their own kernels for every cell, diagonal or not.
+ *   Routing and the other terms of the contract are those of the _pbc twin of each entry: the separate front-end, the fused kernel
+ *     on its list up to 32 atoms, the tiled kernels above; a partitioned handle works; the _dev form uploads the cell with the call
+ *     and treats a changed cell as a different forward; the gradient entry leaves the training state alone and refuses
+ *     coincident atoms or images.
+ *   Strain derivative (gstrain_out [B][3][3], or NULL): with F = sum_i g_i q_i of one molecule and the homogeneous deformation
+ *     r -> (1 + eps) r, a_k -> (1 + eps) a_k,
+ *         gstrain[b][a][c] = dF/d eps_ac at eps = 0 = sum over pairs i < j with D < cutoff of (dF/dD_ij) d'_a d'_c / D_ij,
+ *     accumulated in float64 per atom and summed per molecule in a fixed order (no atomics: bit-reproducible, independent of the
+ *     rest of the batch), stored as the full symmetric matrix in float32.  For an open molecule pass an all-zero cell.
+ *     What a caller gets from it, W = gstrain[b], H the cell matrix (rows a_k), G = inverse of H:
+ *       - derivative with respect to the lattice vectors at fixed fractional coordinates:  dF/dH = G^T W   (dF/dH[k][c] = dF/da_kc);
+ *       - orthorhombic cell:  dF/dL_k = W_kk / L_k;
+ *       - with g = dE/dq of a potential E(q, r), W is the charges' part of the virial of E (the stress is W / volume, with the
+ *         sign convention of dE/d eps); the part of E at fixed q is the caller's.
+ *     gstrain_out = NULL gives the same q_out and gxyz_out bits. */
+int epnn_forward_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                          const float *cell, float *q_out);
+/* Device-resident xyz/x/Q/q_out, cells [B][3][3] on the host (validated and uploaded with the call; they may change on every call). */
+int epnn_forward_xyz_cell_dev(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz, const float *d_x,
+                              const float *d_Q, const float *cell, float *d_q_out);
+/* epnn_edges_ex in the general cell cell[3][3]. */
+int epnn_edges_cell(epnn_handle *h, int n, const float *xyz, const float *cell, int num, double cutoff, double eta, float *e_out,
+                    double *c_out);
+/* epnn_charges_vjp_xyz in general cells, with its contract, and the strain derivative described above. */
+int epnn_charges_vjp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                              const float *Q, const float *cell, const float *g, float *q_out, float *gxyz_out, float *gstrain_out);
 /* RCCL communicator (one rank per GPU): the gradient is summed with ONE ncclAllReduce of the flat vector; the same
  * communicator carries the row exchange of a partitioned large system (epnn_set_partition with exchange == NULL). */
 int epnn_comm_unique_id(char *out128);
