@@ -373,12 +373,16 @@ class EPNNModel(_Stack):
     def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N=None, box=None, cell=None, strain=False):
         """Charges and sum_i g[i] dq_i/dxyz of a flat batch: (q (A,), gxyz (A, 3)).  With g = dE/dq of a potential E(q), the
         charges' part of the forces is -gxyz.  N defaults to the model's natom; box and cell as in predict_xyz.  strain=True adds
-        gstrain (B, 3, 3), the derivative with respect to a homogeneous strain of coordinates and cell: (q, gxyz, gstrain)."""
+        gstrain (B, 3, 3), the derivative with respect to a homogeneous strain of coordinates and cell: (q, gxyz, gstrain).
+        Large systems (B N^2 above 2^22) run from the pair list without (N, N, .) tensors (engine option "grad_path")."""
         return self._eng().charges_vjp_xyz(offsets, xyz, x, Q, g, self.natom if N is None else N, box=box, cell=cell, strain=strain)
 
     def charge_jacobian_xyz(self, xyz, x, Q, N=None, box=None, cell=None):
         """One molecule: (q (n,), J (n, n, 3)) with J[i, k] = dq_i / dxyz_k, from ONE call on n copies of the molecule with
-        one-hot cotangents.  box (3,): its periodic cell; cell (3, 3): its general cell."""
+        one-hot cotangents.  box (3,): its periodic cell; cell (3, 3): its general cell.  The call is a batch of B = n molecules
+        at N >= n, so under the automatic "grad_path" (engine option) B N^2 = n^3 passes 2^22 at n = 162 and the call moves from the
+        dense path to the pair-list path there (the faster one at that size: profiles/r09_grad_large.txt); set the option to 1 or 2
+        on the engine to keep one path across sizes."""
         xyz = np.asarray(xyz, dtype=np.float32)
         x = np.asarray(x, dtype=np.float32)
         n = xyz.shape[0]

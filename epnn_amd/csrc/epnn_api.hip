@@ -51,6 +51,7 @@ static double edge_basis(const epnn_config &cfg, const std::vector<double> &mu, 
 static int create_resources(epnn_handle *h);
 extern "C" int epnn_destroy(epnn_handle *h);
 static void xyz_grad_release(epnn_handle *h);   // epnn_api_grad.hip.h
+static void grad_large_release(epnn_handle *h);
 
 // The HIP runtime maps a process's streams round-robin onto its hardware queues (GPU_MAX_HW_QUEUES of them) in the order the
 // streams are created, and which queues a pipeline's lanes sit on matters: eight lanes on every other queue run the bench batch at
@@ -251,6 +252,7 @@ extern "C" int epnn_destroy(epnn_handle *h) {
         h->train = nullptr;
     }
     xyz_grad_release(h);
+    grad_large_release(h);
     if (h->infer_fused) {
         InferFused *is = reinterpret_cast<InferFused *>(h->infer_fused);
         is->theta.release();
@@ -374,6 +376,7 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
     else if (!strcmp(name, "sync_spin_us")) { h->opt_sync_spin_us = std::max(0, value); }
     else if (!strcmp(name, "large_dedupe")) { h->opt_large_dedupe = value != 0; h->types_overflowed = false; }
     else if (!strcmp(name, "train_fused")) { if (value != 0 && value != 1) EPNN_FAIL("epnn_set_option: train_fused must be 0 (one launch per Dense layer) or 1 (row-fused kernels)"); h->opt_train_fused = value; }
+    else if (!strcmp(name, "grad_path")) { if (value < 0 || value > 2) EPNN_FAIL("epnn_set_option: grad_path must be 0 (by size), 1 (dense path) or 2 (pair-list path)"); h->opt_grad_path = value; }
     else if (!strcmp(name, "train_async")) { h->opt_train_async = value != 0; }
     else if (!strcmp(name, "train_graph")) { h->opt_train_graph = value != 0; }
     // ---- developer switches (include/epnn_dev.h)

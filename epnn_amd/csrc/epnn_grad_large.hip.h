@@ -1,0 +1,462 @@
+// Charge gradients with respect to the coordinates from the pair list (option "grad_path" = 2): the kernels.
+// Part of the one translation unit epnn_api.hip.
+//
+// The dense path (epnn_grad_xyz.hip.h) pads every molecule to [B][N][N] rows.  This path runs the factorised form of DESIGN.md
+// section 2 backwards on per-atom rows [A][32] / [A][48], the list of pairs under the cutoff (pi, pj, pe [P][48], near weights)
+// and its incidence slots (epnn_frontend.hip.h): nothing of size N^2 exists.  tests/grad_large_ref.py is the same algebra in
+// float64.
+//
+//   forward with checkpoints     h_t [T+1][A][48], S_t [T][A][32], q_t [T+1][A]; everything else is recomputed
+//   EPN stack, t = T-1 .. 0      listed pairs only, both orders of the pass MLP, seed +-0.5 w (gq_i - gq_j); the first layer's
+//                                gradients go to the two atoms' incidence slots, every atom sums its own row in slot order
+//   GNN step t >= 1              update MLP backward -> dS_i; all-pairs backward sweep (k_gl_sweep, f32 MFMA) as a row pass
+//                                (dP_i = sum_j dz1_ij) and a column pass (dR_j = sum_i dz1_ij); near pairs as correction rows in the
+//                                incidence slots; the (N - n) padded partners in closed form per atom
+//   GNN step 0                   a_i = [x_i | 0 | Q/n] does not depend on the coordinates: only the listed pairs' dG
+//   edges -> coordinates         gE [P][48] -> gD (float64) -> +-gD d / D into the pair's two slots, summed per atom in float64
+//
+// Plain float32 throughout (the Dense layers of the two sweeps on v_mfma_f32_16x16x4_f32).  Every sum has a fixed order, there
+// are no float atomics: results are bit-reproducible and a molecule's rows do not depend on the rest of the batch (the number of
+// pieces its partner range is cut into depends on its own size alone).
+//
+// Why the checkpointed forward is this file's own (k_gl_proj, k_gl_sweep<0>, k_gl_gnn_pair<0>, k_gl_gnn_tail, k_gl_epn_*) and not the
+// tiled forward of epnn_large.hip.h: the backward needs S_t and h_t of every step as rows in memory (the tiled forward folds W3 and
+// Wu3 into the next step's matrices and never forms h between steps, and its first step runs by atom types), and it takes its ReLU
+// decisions from recomputed f32 pre-activations, which must be the ones the forward took -- the tiled sweep's bf16 three-piece
+// products round differently from the f32 MFMAs of the two backward passes.  The charges of this forward therefore agree with
+// epnn_forward_xyz to float32 accumulation (2e-4 in the tests), not bit for bit, like the dense path's.
+#pragma once
+#include "epnn_host.h"
+#include "epnn_frontend.hip.h"
+
+#define GL_H 32                   // hidden width of every MLP, and of the summed messages
+#define GL_E 48                   // channels of h and e
+
+struct GlPair {                   // a message / pass MLP: first Dense split by input block (rows of W1: a_i | a_j | e_ij)
+    const float *Wi, *Wj, *We, *b1, *W2, *b2, *W3, *b3;      // W3 [32][32], b3 [32] (message) or [32], [1] (pass)
+};
+struct GlUpd {                    // update MLP [h | M] (80) -> 32 -> 32 -> 48
+    const float *U1, *c1, *U2, *c2, *U3, *c3;
+};
+struct GlGeom {                   // the batch
+    const int *moff, *mol_of;     // [B + 1], [A]
+    int A, N, nx;
+};
+
+// sum_k v[k] W[k][col] over the 32 rows of a [32][stride] block (v in LDS, the 32 lanes of a half read one row: coalesced)
+__device__ __forceinline__ float gl_dotT(const float *W, int stride, int col, const float *v) {
+    float acc = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < GL_H; ++k) acc = fmaf(v[k], W[k * stride + col], acc);
+    return acc;
+}
+// sum_k W[row][k] v[k]: the transposed product of a backward
+__device__ __forceinline__ float gl_dotN(const float *W, int stride, int row, const float *v, int n) {
+    float acc = 0.f;
+    for (int k = 0; k < n; ++k) acc = fmaf(W[row * stride + k], v[k], acc);
+    return acc;
+}
+
+// ---------------------------------------------------------------------------------------------------------- per atom: projections
+// One wavefront per atom: a = [x | h | q], P = Wi^T a + b1 (lanes 0..31), R = Wj^T a (lanes 32..63), then the sweeps' second
+// operands Yc = b2 + W2^T P (column pass) and Yb = b2 + W2^T R (row pass).  h: rows [A][48] or null (zeros); q: [A] or null (Q/n).
+__global__ __launch_bounds__(64) void k_gl_proj(GlPair M, GlGeom G, const float *x, const float *h, const float *q, const float *Q,
+                                                float *P, float *R, float *Yb, float *Yc) {
+    __shared__ float av[64], pr[2][GL_H];
+    const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
+    const int F = G.nx + GL_E + 1;
+    if (lane < G.nx) av[lane] = x[(size_t)a * G.nx + lane];
+    if (lane < GL_E) av[G.nx + lane] = h ? h[(size_t)a * GL_E + lane] : 0.f;
+    if (lane == 63) {
+        const int b = G.mol_of[a];
+        av[G.nx + GL_E] = q ? q[a] : Q[b] / (float)(G.moff[b + 1] - G.moff[b]);
+    }
+    __syncthreads();
+    const float *W = half ? M.Wj : M.Wi;
+    float acc = half ? 0.f : M.b1[f];
+    for (int k = 0; k < F; ++k) acc = fmaf(av[k], W[k * GL_H + f], acc);
+    pr[half][f] = acc;
+    (half ? R : P)[(size_t)a * GL_H + f] = acc;
+    __syncthreads();
+    if (Yb) (half ? Yb : Yc)[(size_t)a * GL_H + f] = M.b2[f] + gl_dotT(M.W2, GL_H, f, pr[half]);
+}
+
+// ---------------------------------------------------------------------------------------------------------- the all-pairs sweeps
+// One wavefront per task = (16 resident atoms as the columns of an MFMA tile, one piece of their molecule's partner range).
+// Lane 16 qd + c owns column c and of it the features 16 rb + 4 qd + r (rb = 0, 1; r = 0..3) -- the accumulator layout of
+// v_mfma_f32_16x16x4_f32; with the K steps ordered s = 4 rb' + r' such a set of eight values is the next product's B operand as
+// it stands.  Per partner (its rows are wave-uniform loads: 16 lanes read one address):
+//     z1   = max(X_res, -X_str)                 relu(P + R) less the streamed row, which Y carries: Y = b2 + W2^T X_str
+//     z2pre = W2^T z1 + Y                       16 MFMAs
+//   MODE 0 (forward, row pass: resident P_i, streamed R_j, Yb_j):    S_i  += relu(z2pre)
+//   MODE 1 (backward, row pass: resident P_i, dS_i):                  dP_i += [X_res > -X_str] W2 (dS_i [z2pre > 0])     16 more
+//   MODE 2 (backward, column pass: resident R_j; streamed P_i, Yc_i, dS_i):  dR_j += the same with the streamed dS_i
+// The sums stay in the lane that owns them; out [piece][A][32] gets one row per (piece, resident atom), written by exactly one
+// wavefront (an empty piece writes zeros), and the per-atom kernels add the pieces in order.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_gl_sweep(const int4 *tasks, const int *moff, int A, const float *W2, const float *Xres,
+                                                 const float *Xstr, const float *Y, const float *dS, float *out) {
+    const int lane = threadIdx.x, c = lane & 15, qd = lane >> 4;
+    const int4 tk = tasks[blockIdx.x];                          // (first resident atom, molecule, piece, pieces)
+    const int a0 = moff[tk.y], a1 = moff[tk.y + 1];
+    const int len = (a1 - a0 + tk.w - 1) / tk.w;
+    const int j0 = min(a0 + tk.z * len, a1), j1 = min(j0 + len, a1);
+    const int col = tk.x + c;
+    const bool valid = col < a1;
+    const int colc = valid ? col : a1 - 1;
+    float wf[2][8], wb[2][8];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int kf = 16 * (s >> 2) + 4 * qd + (s & 3), m = 16 * rb + c;
+            wf[rb][s] = W2[kf * GL_H + m];                      // out[m] = sum_k W2[k][m] z1[k]
+            wb[rb][s] = W2[m * GL_H + kf];                      // out[m] = sum_k W2[m][k] d2[k]
+        }
+    float xr[8], ds[8], acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int f = 16 * (e >> 2) + 4 * qd + (e & 3);
+        xr[e] = Xres[(size_t)colc * GL_H + f];
+        ds[e] = (MODE == 1 && valid) ? dS[(size_t)colc * GL_H + f] : 0.f;
+        acc[e] = 0.f;
+    }
+    for (int j = j0; j < j1; ++j) {
+        const float *xs = Xstr + (size_t)j * GL_H + 4 * qd, *ys = Y + (size_t)j * GL_H + 4 * qd;
+        const f32x4 n0 = *reinterpret_cast<const f32x4 *>(xs), n1 = *reinterpret_cast<const f32x4 *>(xs + 16);
+        f32x4 o0 = *reinterpret_cast<const f32x4 *>(ys), o1 = *reinterpret_cast<const f32x4 *>(ys + 16);
+        float nn[8], z1[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { nn[e] = -n0[e]; nn[4 + e] = -n1[e]; }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) z1[e] = fmaxf(xr[e], nn[e]);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[0][s], z1[s], o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[1][s], z1[s], o1, 0, 0, 0);
+        }
+        if (MODE == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { acc[e] += fmaxf(o0[e], 0.f); acc[4 + e] += fmaxf(o1[e], 0.f); }
+        } else {
+            float d2[8];
+            if (MODE == 2) {
+                const float *dp = dS + (size_t)j * GL_H + 4 * qd;
+                const f32x4 d0 = *reinterpret_cast<const f32x4 *>(dp), d1 = *reinterpret_cast<const f32x4 *>(dp + 16);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? d0[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? d1[e] : 0.f; }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? ds[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? ds[4 + e] : 0.f; }
+            }
+            f32x4 g0 = {0.f, 0.f, 0.f, 0.f}, g1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                g0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[0][s], d2[s], g0, 0, 0, 0);
+                g1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[1][s], d2[s], g1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[e] += xr[e] > nn[e] ? g0[e] : 0.f;
+                acc[4 + e] += xr[4 + e] > nn[4 + e] ? g1[e] : 0.f;
+            }
+        }
+    }
+    if (valid) {
+        float *o = out + ((size_t)tk.z * A + col) * GL_H + 4 * qd;
+        *reinterpret_cast<f32x4 *>(o) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+        *reinterpret_cast<f32x4 *>(o + 16) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- per listed pair
+// One wavefront per listed pair {i < j}: lanes 0..31 take the order (i, j), lanes 32..63 the order (j, i), a lane one hidden
+// unit.  G = We^T e_ij is the same for both (e_ij == e_ji).
+struct GlPairs {
+    const int *pi, *pj, *dest_i, *dest_j;
+    const float *pe, *pw;
+};
+
+// GNN step: the pair's correction rows.  BWD 0: relu(W2^T relu(P + R + G) + b2) minus the same without G, into the first atom's
+// slot (corr [slots][32]).  BWD 1: dz1 with G minus dz1 without it into slotP of the first and slotR of the second atom (null for
+// step 0, which needs no dP / dR), and gE_ij += We (dz1_ij + dz1_ji) with G.
+template <int BWD>
+__global__ __launch_bounds__(64) void k_gl_gnn_pair(GlPair M, GlPairs L, const float *P, const float *R, const float *dS, float *slotP,
+                                                    float *slotR, float *gE) {
+    __shared__ float ev[GL_E], z[2][2][GL_H], d2[2][2][GL_H], dg[2][GL_H];
+    const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
+    const int i = L.pi[p], j = L.pj[p];
+    const int a = half ? j : i, b = half ? i : j;                 // this half's row is [a_a | a_b | e]
+    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) return;               // (a pair without both slots would be a front-end fault: write nothing)
+    if (lane < GL_E) ev[lane] = L.pe[(size_t)p * GL_E + lane];
+    __syncthreads();
+    float g = 0.f;
+    for (int k = 0; k < GL_E; ++k) g = fmaf(ev[k], M.We[k * GL_H + f], g);
+    const float base = P[(size_t)a * GL_H + f] + R[(size_t)b * GL_H + f];
+    const float z1g = base + g;
+    z[half][0][f] = fmaxf(z1g, 0.f);
+    z[half][1][f] = fmaxf(base, 0.f);
+    __syncthreads();
+    const float z2g = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half][0]), z2n = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half][1]);
+    const int sa = half ? L.dest_j[p] : L.dest_i[p], sb = half ? L.dest_i[p] : L.dest_j[p];
+    if (!BWD) {
+        slotP[(size_t)sa * GL_H + f] = fmaxf(z2g, 0.f) - fmaxf(z2n, 0.f);
+        return;
+    }
+    const float dsv = dS[(size_t)a * GL_H + f];
+    d2[half][0][f] = z2g > 0.f ? dsv : 0.f;
+    d2[half][1][f] = z2n > 0.f ? dsv : 0.f;
+    __syncthreads();
+    const float dg1 = z1g > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half][0], GL_H) : 0.f;
+    const float dn1 = base > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half][1], GL_H) : 0.f;
+    if (slotP) {
+        slotP[(size_t)sa * GL_H + f] = dg1 - dn1;
+        slotR[(size_t)sb * GL_H + f] = dg1 - dn1;
+    }
+    dg[half][f] = dg1;
+    __syncthreads();
+    if (lane < GL_E) {
+        float acc = 0.f;
+        for (int k = 0; k < GL_H; ++k) acc = fmaf(M.We[lane * GL_H + k], dg[0][k] + dg[1][k], acc);
+        gE[(size_t)p * GL_E + lane] += acc;
+    }
+}
+
+// EPN step.  BWD 0: delta = (f(a_i, a_j, e) - f(a_j, a_i, e)) / 2, slotq[dest_i] = w delta, slotq[dest_j] = -w delta.
+// BWD 1: the row [a_i | a_j | e] is seeded with s = w (gq_i - gq_j) / 2, the row [a_j | a_i | e] with -s; a row's dz1 goes to slotP
+// of its first atom and slotR of its second, and gE_ij += We (dz1_ij + dz1_ji).
+template <int BWD>
+__global__ __launch_bounds__(64) void k_gl_epn_pair(GlPair M, GlPairs L, const float *P, const float *R, const float *gq, float *slotq,
+                                                    float *slotP, float *slotR, float *gE) {
+    __shared__ float ev[GL_E], z[2][GL_H], d2[2][GL_H], dg[2][GL_H], red[2][GL_H];
+    const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
+    const int i = L.pi[p], j = L.pj[p];
+    const int a = half ? j : i, b = half ? i : j;
+    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) return;
+    if (lane < GL_E) ev[lane] = L.pe[(size_t)p * GL_E + lane];
+    __syncthreads();
+    float g = 0.f;
+    for (int k = 0; k < GL_E; ++k) g = fmaf(ev[k], M.We[k * GL_H + f], g);
+    const float z1 = P[(size_t)a * GL_H + f] + R[(size_t)b * GL_H + f] + g;
+    z[half][f] = fmaxf(z1, 0.f);
+    __syncthreads();
+    const float z2 = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half]);
+    const float w = L.pw[p];
+    const int sa = half ? L.dest_j[p] : L.dest_i[p], sb = half ? L.dest_i[p] : L.dest_j[p];
+    if (!BWD) {
+        red[half][f] = fmaxf(z2, 0.f) * M.W3[f];
+        __syncthreads();
+        if (f == 0) {
+            float fi = 0.f, fj = 0.f;                               // (b3 cancels in the difference)
+            for (int k = 0; k < GL_H; ++k) { fi += red[0][k]; fj += red[1][k]; }
+            const float delta = 0.5f * (fi - fj);
+            slotq[sa] = half ? -(w * delta) : w * delta;
+        }
+        return;
+    }
+    const float seed = 0.5f * w * (gq[i] - gq[j]);
+    d2[half][f] = z2 > 0.f ? (half ? -seed : seed) * M.W3[f] : 0.f;
+    __syncthreads();
+    const float dz1 = z1 > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half], GL_H) : 0.f;
+    slotP[(size_t)sa * GL_H + f] = dz1;
+    slotR[(size_t)sb * GL_H + f] = dz1;
+    dg[half][f] = dz1;
+    __syncthreads();
+    if (lane < GL_E) {
+        float acc = 0.f;
+        for (int k = 0; k < GL_H; ++k) acc = fmaf(M.We[lane * GL_H + k], dg[0][k] + dg[1][k], acc);
+        gE[(size_t)p * GL_E + lane] += acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- per atom
+// the pieces a molecule's partner range is cut into: by its own size alone (16 atoms per task; about 2048 tasks fill the GPU)
+__host__ __device__ __forceinline__ int gl_pieces(int n) {
+    const int tiles = (n + 15) / 16, want = (2048 + tiles - 1) / tiles;
+    return want < 1 ? 1 : (want > 16 ? 16 : want);
+}
+
+// End of a forward GNN step, one wavefront per atom: S = pieces in order + (N - n) relu(W2^T relu(P) + b2) + the atom's correction
+// slots in order; M = W3^T S + N b3; h' = update MLP([h | M]).  S and h' are the step's checkpoints.
+__global__ __launch_bounds__(64) void k_gl_gnn_tail(GlPair M, GlUpd U, GlGeom G, const int *inc_off, const float *part, const float *corr,
+                                                    const float *P, const float *h, float *S_out, float *h_out) {
+    __shared__ float v[GL_H], u0[GL_E + GL_H], u1[GL_H], u2[GL_H];
+    const int a = blockIdx.x, lane = threadIdx.x;
+    const int b = G.mol_of[a], n = G.moff[b + 1] - G.moff[b];
+    if (lane < GL_H) v[lane] = fmaxf(P[(size_t)a * GL_H + lane], 0.f);
+    if (lane < GL_E) u0[lane] = h ? h[(size_t)a * GL_E + lane] : 0.f;
+    __syncthreads();
+    if (lane < GL_H) {
+        float s = 0.f;
+        const int np = gl_pieces(n);
+        for (int k = 0; k < np; ++k) s += part[((size_t)k * G.A + a) * GL_H + lane];
+        s += (float)(G.N - n) * fmaxf(M.b2[lane] + gl_dotT(M.W2, GL_H, lane, v), 0.f);
+        for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += corr[(size_t)k * GL_H + lane];
+        S_out[(size_t)a * GL_H + lane] = s;
+        u1[lane] = s;
+    }
+    __syncthreads();
+    if (lane < GL_H) u0[GL_E + lane] = (float)G.N * M.b3[lane] + gl_dotT(M.W3, GL_H, lane, u1);
+    __syncthreads();
+    float t = 0.f;
+    if (lane < GL_H) {
+        t = U.c1[lane];
+        for (int k = 0; k < GL_E + GL_H; ++k) t = fmaf(u0[k], U.U1[k * GL_H + lane], t);
+    }
+    __syncthreads();
+    if (lane < GL_H) u1[lane] = fmaxf(t, 0.f);
+    __syncthreads();
+    if (lane < GL_H) u2[lane] = fmaxf(U.c2[lane] + gl_dotT(U.U2, GL_H, lane, u1), 0.f);
+    __syncthreads();
+    if (lane < GL_E) h_out[(size_t)a * GL_E + lane] = U.c3[lane] + gl_dotT(U.U3, GL_E, lane, u2);
+}
+
+// Backward of the update MLP, one wavefront per atom: recomputes u1pre, u2pre from the checkpoints (h, S), carries gh [48] back:
+// gh_prev [A][48] = the h columns of the first layer's input gradient, dS [A][32] = W3 (its M columns).
+__global__ __launch_bounds__(64) void k_gl_upd_bwd(GlPair M, GlUpd U, GlGeom G, const float *h, const float *S, const float *gh,
+                                                   float *gh_prev, float *dS) {
+    __shared__ float u0[GL_E + GL_H], sv[GL_H], u1[GL_H], gv[GL_E], d2[GL_H], d1[GL_H], gm[GL_H];
+    const int a = blockIdx.x, lane = threadIdx.x;
+    if (lane < GL_E) { u0[lane] = h ? h[(size_t)a * GL_E + lane] : 0.f; gv[lane] = gh[(size_t)a * GL_E + lane]; }
+    if (lane < GL_H) sv[lane] = S[(size_t)a * GL_H + lane];
+    __syncthreads();
+    if (lane < GL_H) u0[GL_E + lane] = (float)G.N * M.b3[lane] + gl_dotT(M.W3, GL_H, lane, sv);
+    __syncthreads();
+    float t = 0.f;
+    if (lane < GL_H) {
+        t = U.c1[lane];
+        for (int k = 0; k < GL_E + GL_H; ++k) t = fmaf(u0[k], U.U1[k * GL_H + lane], t);
+        u1[lane] = fmaxf(t, 0.f);
+    }
+    __syncthreads();
+    if (lane < GL_H) {
+        const float u2pre = U.c2[lane] + gl_dotT(U.U2, GL_H, lane, u1);
+        d2[lane] = u2pre > 0.f ? gl_dotN(U.U3, GL_E, lane, gv, GL_E) : 0.f;
+    }
+    __syncthreads();
+    if (lane < GL_H) d1[lane] = t > 0.f ? gl_dotN(U.U2, GL_H, lane, d2, GL_H) : 0.f;
+    __syncthreads();
+    if (lane < GL_E) gh_prev[(size_t)a * GL_E + lane] = gl_dotN(U.U1, GL_H, lane, d1, GL_H);
+    if (lane < GL_H) gm[lane] = gl_dotN(U.U1, GL_H, GL_E + lane, d1, GL_H);
+    __syncthreads();
+    if (lane < GL_H) dS[(size_t)a * GL_H + lane] = gl_dotN(M.W3, GL_H, lane, gm, GL_H);
+}
+
+// End of a backward GNN step t >= 1, one wavefront per atom (lanes 0..31: dP, lanes 32..63: dR): pieces in order, dP's padded
+// partners in closed form, the atom's slots in order; then gh = gh_prev + the h columns of Wi dP + Wj dR (in place).
+__global__ __launch_bounds__(64) void k_gl_gnn_atom_bwd(GlPair M, GlGeom G, const int *inc_off, const float *partP, const float *partR,
+                                                        const float *slotP, const float *slotR, const float *P, const float *dS,
+                                                        float *gh) {
+    __shared__ float v[GL_H], d2[GL_H], dv[2][GL_H];
+    const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
+    const int b = G.mol_of[a], n = G.moff[b + 1] - G.moff[b];
+    const float pa = P[(size_t)a * GL_H + f];
+    if (!half) v[f] = fmaxf(pa, 0.f);
+    __syncthreads();
+    if (!half) d2[f] = M.b2[f] + gl_dotT(M.W2, GL_H, f, v) > 0.f ? dS[(size_t)a * GL_H + f] : 0.f;
+    __syncthreads();
+    const float *part = half ? partR : partP, *slot = half ? slotR : slotP;
+    float s = 0.f;
+    const int np = gl_pieces(n);
+    for (int k = 0; k < np; ++k) s += part[((size_t)k * G.A + a) * GL_H + f];
+    if (!half) s += (float)(G.N - n) * (pa > 0.f ? gl_dotN(M.W2, GL_H, f, d2, GL_H) : 0.f);
+    for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slot[(size_t)k * GL_H + f];
+    dv[half][f] = s;
+    __syncthreads();
+    if (lane < GL_E) {
+        const int row = G.nx + lane;
+        gh[(size_t)a * GL_E + lane] += gl_dotN(M.Wi, GL_H, row, dv[0], GL_H) + gl_dotN(M.Wj, GL_H, row, dv[1], GL_H);
+    }
+}
+
+// EPN forward: every atom adds its transfer slots in order.
+__global__ __launch_bounds__(256) void k_gl_epn_atom(int A, const int *inc_off, const float *slotq, const float *q, float *q_out) {
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= A) return;
+    float s = q[a];
+    for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slotq[k];
+    q_out[a] = s;
+}
+// the charges before the first EPN step: Q / n
+__global__ __launch_bounds__(256) void k_gl_q0(GlGeom G, const float *Q, float *q) {
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= G.A) return;
+    const int b = G.mol_of[a];
+    q[a] = Q[b] / (float)(G.moff[b + 1] - G.moff[b]);
+}
+
+// EPN backward, one wavefront per atom: dP / dR from the slots in order, then gfeat += the h columns and gq += the q column of
+// Wi dP + Wj dR.
+__global__ __launch_bounds__(64) void k_gl_epn_atom_bwd(GlPair M, GlGeom G, const int *inc_off, const float *slotP, const float *slotR,
+                                                        float *gfeat, float *gq) {
+    __shared__ float dv[2][GL_H];
+    const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
+    const float *slot = half ? slotR : slotP;
+    float s = 0.f;
+    for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slot[(size_t)k * GL_H + f];
+    dv[half][f] = s;
+    __syncthreads();
+    if (lane <= GL_E) {
+        const int row = G.nx + lane;                               // lane 48: the charge's column
+        const float add = gl_dotN(M.Wi, GL_H, row, dv[0], GL_H) + gl_dotN(M.Wj, GL_H, row, dv[1], GL_H);
+        if (lane < GL_E) gfeat[(size_t)a * GL_E + lane] += add;
+        else gq[a] += add;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- edges -> coordinates
+// One thread per listed pair: the displacement d = image of r_j - r_i and D in float64 exactly as the front-end measures them (GEO 0
+// open, 1 box rows [B][3], 2 EpnnCell records [B]), gD = sum_k gE_k de_k/dD, w = gD / D; the first atom's slot gets -w d, the
+// second's +w d (d D / d r_i = (r_i - r_j) / D), and with strain each gets half of w d_a d_c (xx, yy, zz, yz, xz, xy).
+// slotx [slots][9] float64.  bad: bit 0 = two atoms or images coincide, bit 1 = a pair without both slots (atomicOr: the word does
+// not depend on which thread comes last).
+template <int GEO>
+__global__ __launch_bounds__(256) void k_gl_pair_xyz(GlPairs L, int npairs, const int *mol_of, const float *xyz, const float *geo,
+                                                     const float *gE, double cutoff, double eta, const double *mu, double *slotx, int *bad) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npairs) return;
+    const int i = L.pi[p], j = L.pj[p], b = mol_of[i];
+    double dx = (double)xyz[3 * j] - (double)xyz[3 * i], dy = (double)xyz[3 * j + 1] - (double)xyz[3 * i + 1],
+           dz = (double)xyz[3 * j + 2] - (double)xyz[3 * i + 2];
+    if (GEO == 1) {
+        dx = epnn_mic(dx, (double)geo[3 * b]); dy = epnn_mic(dy, (double)geo[3 * b + 1]); dz = epnn_mic(dz, (double)geo[3 * b + 2]);
+    }
+    if (GEO == 2) {
+        const EpnnCell &c = reinterpret_cast<const EpnnCell *>(geo)[b];
+        double a[9];
+        for (int k = 0; k < 9; ++k) a[k] = (double)c.a[k];
+        epnn_mic_cell(dx, dy, dz, c.g, a);
+    }
+    const double D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
+    double w = 0.0;
+    if (!(D > 0.0)) atomicOr(bad, 1);
+    else if (D < cutoff) {
+        const double pi_d = 3.141592653589793;
+        const double C = (cos(pi_d * D / cutoff) + 1.0) / 2.0, dC = -0.5 * (pi_d / cutoff) * sin(pi_d * D / cutoff);
+        double gD = 0.0;
+        for (int k = 0; k < GL_E; ++k) {
+            const double u = D - mu[k], ex = exp(-eta * (u * u));
+            gD += (double)gE[(size_t)p * GL_E + k] * (dC - 2.0 * eta * u * C) * ex;
+        }
+        w = gD / D;
+    }
+    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) { atomicOr(bad, 2); return; }
+    double *si = slotx + 9 * (size_t)L.dest_i[p], *sj = slotx + 9 * (size_t)L.dest_j[p];
+    si[0] = -w * dx; si[1] = -w * dy; si[2] = -w * dz;
+    sj[0] = w * dx; sj[1] = w * dy; sj[2] = w * dz;
+    const double hw = 0.5 * w;
+    const double s6[6] = {hw * dx * dx, hw * dy * dy, hw * dz * dz, hw * dy * dz, hw * dx * dz, hw * dx * dy};
+    for (int k = 0; k < 6; ++k) { si[3 + k] = s6[k]; sj[3 + k] = s6[k]; }
+}
+// every atom adds its slots in order, in float64: gxyz [A][3] float32, and its strain share [A][6] float64 (k_g_strain_mol adds
+// a molecule's atoms up) when asked for
+__global__ __launch_bounds__(256) void k_gl_atom_xyz(int A, const int *inc_off, const double *slotx, float *gxyz, double *share) {
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= A) return;
+    double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = inc_off[a]; k < inc_off[a + 1]; ++k)
+        for (int c = 0; c < 9; ++c) s[c] += slotx[9 * (size_t)k + c];
+    for (int c = 0; c < 3; ++c) gxyz[3 * (size_t)a + c] = (float)s[c];
+    if (share)
+        for (int c = 0; c < 6; ++c) share[6 * (size_t)a + c] = s[3 + c];
+}

@@ -257,6 +257,8 @@ struct epnn_handle {
     std::vector<int> dn_neff_host;
     void *train = nullptr;            // TrainState (epnn_train.hip.h)
     void *xyz_grad = nullptr;         // TrainState of epnn_charges_vjp_xyz (epnn_api_grad.hip.h): its own weights and scratch
+    void *grad_large = nullptr;       // GradLarge: weights, inputs and scratch of its pair-list path ("grad_path")
+    int opt_grad_path = 0;            // epnn_charges_vjp_xyz*: 0 = the dense path up to B N^2 = 2^22 and the pair-list path above, 1 = dense, 2 = pair list
 };
 
 // ---- fail-closed collectives.  RCCL has no timeout: a rank that leaves an entry point with an error BEFORE a collective its peers

@@ -332,7 +332,9 @@ class Engine:
         training state; works without train_init.  box (3,) or (B, 3): periodic cells, as in forward_xyz; cell (3, 3) or
         (B, 3, 3): general cells.  strain=True (with cell, or with neither: open molecules) returns (q, gxyz, gstrain) with
         gstrain (B, 3, 3) the derivative of sum_i g[i] q_i with respect to a homogeneous strain of coordinates and cell
-        (include/epnn.h: dF/dH = inv(H).T @ gstrain for the cell matrix H at fixed fractional coordinates)."""
+        (include/epnn.h: dF/dH = inv(H).T @ gstrain for the cell matrix H at fixed fractional coordinates).
+        set_option("grad_path", v) chooses the implementation: 0 (default) the dense path while B N^2 <= 2^22 and the pair-list
+        path (per-atom rows and the pairs under the cutoff only: large systems) above that, 1 / 2 force one of them."""
         _one_periodic_argument(box, cell)
         if strain and box is not None:
             raise ValueError("charges_vjp_xyz: strain=True takes the cell as cell= (np.diag(box) for an orthorhombic one)")

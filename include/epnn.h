@@ -197,7 +197,15 @@ int epnn_train_apply(epnn_handle *h);
  *   - every shape and update `layers` epnn_train_step_xyz takes: the row-fused kernels up to N = 96 ("train_fused"), the
  *     layer-by-layer ones above that and for update layers other than [32, 32];
  *   - fails (epnn_last_error) on a bad offsets array, a molecule that does not fit N, a null pointer, or two coincident atoms.
- * Bit-reproducible; a molecule's rows do not depend on the rest of the batch (at the same N). */
+ * Bit-reproducible; a molecule's rows do not depend on the rest of the batch (at the same N).
+ * Two implementations stand behind this entry and its _pbc / _cell forms (option "grad_path"): the dense path -- the training
+ * step's forward + backward on rows padded to [B][N][N], whose scratch grows with B N^2 (gE alone is B N^2 48 floats) -- and the
+ * pair-list path, which keeps per-atom rows and the list of pairs under the cutoff only (about 3 KB per atom and 1.1 KB per
+ * listed pair; a 100 000-atom cell: 0.94 GB and 4.2 s, ten forwards: profiles/r09_grad_large.txt).  Both compute the same function (float32 rounding and
+ * ReLU decisions within it apart) under the same contract; the pair-list path is built for update layers [32, 32] on a handle
+ * without epnn_set_partition.  The handle keeps the scratch of its largest call on either path until epnn_destroy.  After a
+ * call on the pair-list path epnn_last_stats gives out[0] = listed pairs, out[1] = 0,
+ * out[2] = bytes of device scratch the call used. */
 int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                          const float *g, float *q_out, float *gxyz_out);
 
@@ -328,6 +336,10 @@ int epnn_timing_at(epnn_handle *h, int idx, float *out4);
  *   "train_fused"       1 (default) = train step with one workgroup per atom and pair MLP, Dense layers and weight gradients as f32
  *                       MFMA tiles, 2T + 2T + 1 launches; 0 = one launch per Dense layer on materialised rows (also taken above 96
  *                       atoms and for update layers other than [32, 32])
+ *   "grad_path"         which implementation epnn_charges_vjp_xyz and its _pbc / _cell forms run: 0 (default) = the dense path while
+ *                       B N^2 <= 2^22 (every call that fitted a GPU before takes the path it took, bit for bit), the pair-list path
+ *                       above that; 1 = always the dense path; 2 = always the pair-list path (refused by name for update layers other
+ *                       than [32, 32] and on a partitioned handle, which stay on the dense path under 0)
  *   "train_async"       1 (default) = a training step returns as soon as its forward pass is done (loss and predictions are on the host
  *                       then; backward and optimizer keep running, every call that reads weights or gradients waits for them); 0 = a
  *                       step returns when all of it is done
