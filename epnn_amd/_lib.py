@@ -59,6 +59,7 @@ SIGNATURES = {
     "epnn_param_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "epnn_train_step_dense": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int]),
     "epnn_train_step_xyz": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int]),
+    "epnn_train_step_xyz_cell": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int]),
     "epnn_get_gradients": (C.c_int, [_vp, _fp, C.c_int64]),
     "epnn_set_gradients": (C.c_int, [_vp, _fp, C.c_int64]),
     "epnn_train_apply": (C.c_int, [_vp]),

@@ -377,6 +377,14 @@ class EPNNModel(_Stack):
         Large systems (B N^2 above 2^22) run from the pair list without (N, N, .) tensors (engine option "grad_path")."""
         return self._eng().charges_vjp_xyz(offsets, xyz, x, Q, g, self.natom if N is None else N, box=box, cell=cell, strain=strain)
 
+    def train_step_xyz(self, optimizer, offsets, xyz, x, Q, y, N=None, apply=True, box=None, cell=None):
+        """One training step (loss = sum (y - q)^2 over the atoms, its gradient, one Adam step of `optimizer` unless apply=False) on a
+        flat batch with reference charges y (A,): (q (A,), loss).  N defaults to the model's natom; box and cell as in predict_xyz:
+        crystals, slabs and solvated boxes train like open molecules.  With box or cell, large systems (B N^2 above 2^22) run from
+        the pair list without (N, N, .) tensors (engine option "train_path")."""
+        eng = optimizer.bind(self)
+        return eng.train_step_xyz(offsets, xyz, x, Q, y, self.natom if N is None else N, apply=apply, box=box, cell=cell)
+
     def charge_jacobian_xyz(self, xyz, x, Q, N=None, box=None, cell=None):
         """One molecule: (q (n,), J (n, n, 3)) with J[i, k] = dq_i / dxyz_k, from ONE call on n copies of the molecule with
         one-hot cotangents.  box (3,): its periodic cell; cell (3, 3): its general cell.  The call is a batch of B = n molecules

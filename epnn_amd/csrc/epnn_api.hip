@@ -377,6 +377,7 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
     else if (!strcmp(name, "large_dedupe")) { h->opt_large_dedupe = value != 0; h->types_overflowed = false; }
     else if (!strcmp(name, "train_fused")) { if (value != 0 && value != 1) EPNN_FAIL("epnn_set_option: train_fused must be 0 (one launch per Dense layer) or 1 (row-fused kernels)"); h->opt_train_fused = value; }
     else if (!strcmp(name, "grad_path")) { if (value < 0 || value > 2) EPNN_FAIL("epnn_set_option: grad_path must be 0 (by size), 1 (dense path) or 2 (pair-list path)"); h->opt_grad_path = value; }
+    else if (!strcmp(name, "train_path")) { if (value < 0 || value > 2) EPNN_FAIL("epnn_set_option: train_path must be 0 (by size), 1 (dense path) or 2 (pair-list path)"); h->opt_train_path = value; }
     else if (!strcmp(name, "train_async")) { h->opt_train_async = value != 0; }
     else if (!strcmp(name, "train_graph")) { h->opt_train_graph = value != 0; }
     // ---- developer switches (include/epnn_dev.h)
@@ -407,3 +408,4 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
 #include "epnn_api_dense.hip.h"
 #include "epnn_api_train.hip.h"
 #include "epnn_api_grad.hip.h"
+#include "epnn_api_train_large.hip.h"

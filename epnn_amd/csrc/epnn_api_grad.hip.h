@@ -195,10 +195,10 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
         const float *ht = t ? hck + t * nE : nullptr;
         hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, gl->msg[t], G, d_x, ht, (const float *)nullptr, d_Q, dP, dR, Yb, Yc);
         hipLaunchKernelGGL(k_gl_sweep<0>, dim3(nt), w64, 0, h->stream, d_tasks, d_moff, A, gl->msg[t].W2, (const float *)dP, (const float *)dR,
-                           (const float *)Yb, (const float *)nullptr, partP);
+                           (const float *)Yb, (const float *)nullptr, partP, (int)nt, 1, (float *)nullptr);
         if (np > 0)
             hipLaunchKernelGGL(k_gl_gnn_pair<0>, dim3(gP), w64, 0, h->stream, gl->msg[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)nullptr, slotP, (float *)nullptr, (float *)nullptr);
+                               (const float *)nullptr, slotP, (float *)nullptr, (float *)nullptr, GlTape{});
         hipLaunchKernelGGL(k_gl_gnn_tail, dim3(A), w64, 0, h->stream, gl->msg[t], gl->upd, G, inc, (const float *)partP, (const float *)slotP,
                            (const float *)dP, ht, Sck + t * nH, hck + (t + 1) * nE);
     }
@@ -210,7 +210,7 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
                            (float *)nullptr, (float *)nullptr);
         if (np > 0)
             hipLaunchKernelGGL(k_gl_epn_pair<0>, dim3(gP), w64, 0, h->stream, gl->pas[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)nullptr, slotq, (float *)nullptr, (float *)nullptr, (float *)nullptr);
+                               (const float *)nullptr, slotq, (float *)nullptr, (float *)nullptr, (float *)nullptr, GlTape{});
         hipLaunchKernelGGL(k_gl_epn_atom, dim3(gA), dim3(256), 0, h->stream, A, inc, (const float *)slotq, (const float *)(qck + (size_t)t * A),
                            qck + (size_t)(t + 1) * A);
     }
@@ -229,31 +229,31 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
                            (float *)nullptr, (float *)nullptr);
         if (np > 0)
             hipLaunchKernelGGL(k_gl_epn_pair<1>, dim3(gP), w64, 0, h->stream, gl->pas[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)gq, (float *)nullptr, slotP, slotR, gE);
-        hipLaunchKernelGGL(k_gl_epn_atom_bwd, dim3(A), w64, 0, h->stream, gl->pas[t], G, inc, (const float *)slotP, (const float *)slotR, gh, gq);
+                               (const float *)gq, (float *)nullptr, slotP, slotR, gE, GlTape{});
+        hipLaunchKernelGGL(k_gl_epn_atom_bwd, dim3(A), w64, 0, h->stream, gl->pas[t], G, inc, (const float *)slotP, (const float *)slotR, gh, gq, GlTape{});
     }
     HIPCHK(hipGetLastError());
     // ---- backward: GNN steps
     for (int t = T - 1; t >= 0; --t) {
         const float *ht = t ? hck + t * nE : nullptr;
         hipLaunchKernelGGL(k_gl_upd_bwd, dim3(A), w64, 0, h->stream, gl->msg[t], gl->upd, G, ht, (const float *)(Sck + t * nH), (const float *)gh,
-                           ghp, dS);
+                           ghp, dS, GlTape{});
         hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, gl->msg[t], G, d_x, ht, (const float *)nullptr, d_Q, dP, dR, Yb, Yc);
         if (t == 0) {                                            // a_i of step 0 is constant: only dG of the listed pairs
             if (np > 0)
                 hipLaunchKernelGGL(k_gl_gnn_pair<1>, dim3(gP), w64, 0, h->stream, gl->msg[t], L, (const float *)dP, (const float *)dR,
-                                   (const float *)dS, (float *)nullptr, (float *)nullptr, gE);
+                                   (const float *)dS, (float *)nullptr, (float *)nullptr, gE, GlTape{});
             break;
         }
         hipLaunchKernelGGL(k_gl_sweep<1>, dim3(nt), w64, 0, h->stream, d_tasks, d_moff, A, gl->msg[t].W2, (const float *)dP, (const float *)dR,
-                           (const float *)Yb, (const float *)dS, partP);
+                           (const float *)Yb, (const float *)dS, partP, (int)nt, 1, (float *)nullptr);
         hipLaunchKernelGGL(k_gl_sweep<2>, dim3(nt), w64, 0, h->stream, d_tasks, d_moff, A, gl->msg[t].W2, (const float *)dR, (const float *)dP,
-                           (const float *)Yc, (const float *)dS, partR);
+                           (const float *)Yc, (const float *)dS, partR, (int)nt, 1, (float *)nullptr);
         if (np > 0)
             hipLaunchKernelGGL(k_gl_gnn_pair<1>, dim3(gP), w64, 0, h->stream, gl->msg[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)dS, slotP, slotR, gE);
+                               (const float *)dS, slotP, slotR, gE, GlTape{});
         hipLaunchKernelGGL(k_gl_gnn_atom_bwd, dim3(A), w64, 0, h->stream, gl->msg[t], G, inc, (const float *)partP, (const float *)partR,
-                           (const float *)slotP, (const float *)slotR, (const float *)dP, (const float *)dS, ghp);
+                           (const float *)slotP, (const float *)slotR, (const float *)dP, (const float *)dS, ghp, GlTape{});
         std::swap(gh, ghp);
     }
     HIPCHK(hipGetLastError());

@@ -408,8 +408,10 @@ static int train_step_dense_impl(epnn_handle *h, int B, int N, const float *h_in
 }
 
 // train_step from a flat coordinate batch: y_flat / q_out_flat are per real atom [A]
+// cells: the EpnnCell records [B] of general cells (epnn_train_step_xyz_cell: minimum-image distances, k_t_pad_inputs_cell), or null
 static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                               const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply);
+                               const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply,
+                               const EpnnCell *cells = nullptr);
 extern "C" int epnn_train_step_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                                    const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply) {
     if (!train_step_guarded(h, apply)) return train_step_xyz_impl(h, B, N, offsets, xyz, x, Q, y_flat, q_out_flat, loss_out, apply);
@@ -417,7 +419,8 @@ extern "C" int epnn_train_step_xyz(epnn_handle *h, int B, int N, const int32_t *
     return comm_guard_exit(h, train_step_xyz_impl(h, B, N, offsets, xyz, x, Q, y_flat, q_out_flat, loss_out, apply), "train step (gradient all-reduce)");
 }
 static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                               const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply) {
+                               const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply,
+                               const EpnnCell *cells) {
     if (!h || !offsets || !xyz || !x || !Q || !y_flat) EPNN_FAIL("epnn_train_step_xyz: null argument");
     EPNN_NOT_FUSED_ONLY(h, "epnn_train_step_xyz");
     HIPCHK(hipSetDevice(h->device));
@@ -431,7 +434,8 @@ static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offs
     // copies from pageable memory were ~50 us of a 0.5 ms step before its first kernel could start)
     auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
     const size_t o_xyz = up256((size_t)(B + 1) * 4), o_x = o_xyz + up256((size_t)A * 3 * 4), o_Q = o_x + up256((size_t)A * nx * 4),
-                 o_y = o_Q + up256((size_t)B * 4), in_bytes = o_y + (size_t)A * 4;
+                 o_y = o_Q + up256((size_t)B * 4), o_cell = o_y + up256((size_t)A * 4),
+                 in_bytes = cells ? o_cell + (size_t)B * sizeof(EpnnCell) : o_y + (size_t)A * 4;
     if (h->train) {
         // the previous step's backward pass may still be running ("train_async"): it reads the buffers below
         TrainState *ts0 = train_state(h);
@@ -448,7 +452,7 @@ static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offs
     // one molecule (or two small ones): the inputs are few enough to ride in the padding kernel's argument block, packed (no 256-byte
     // sections) -- no upload; otherwise ONE upload of the staged block
     const size_t packed_words = (size_t)(B + 1) + (size_t)A * (3 + nx + 1) + B;
-    if (h->opt_train_inline && packed_words <= EPNN_PAD_INLINE_WORDS) {
+    if (h->opt_train_inline && packed_words <= EPNN_PAD_INLINE_WORDS && !cells) {
         PadInline P;
         int k = 0;
         memcpy(P.w + k, offsets, (size_t)(B + 1) * 4); k += B + 1;
@@ -466,10 +470,17 @@ static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offs
         memcpy(stage + o_x, x, (size_t)A * nx * 4);
         memcpy(stage + o_Q, Q, (size_t)B * 4);
         memcpy(stage + o_y, y_flat, (size_t)A * 4);
+        if (cells) memcpy(stage + o_cell, cells, (size_t)B * sizeof(EpnnCell));
         HIPCHK(hipMemcpyAsync(h->s_train.p, stage, in_bytes, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_t_pad_inputs, dim3(pgrid), dim3(256), 0, h->stream, reinterpret_cast<const float *>(dev), w_xyz, w_x, w_Q, w_y, B, N, nx,
-                           h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(),
-                           h->dn_xs.as<float>(), h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+        if (cells)
+            hipLaunchKernelGGL(k_t_pad_inputs_cell, dim3(pgrid), dim3(256), 0, h->stream, reinterpret_cast<const float *>(dev), w_xyz, w_x, w_Q, w_y,
+                               (int)(o_cell / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(),
+                               h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(), h->dn_qs.as<float>(),
+                               h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+        else
+            hipLaunchKernelGGL(k_t_pad_inputs, dim3(pgrid), dim3(256), 0, h->stream, reinterpret_cast<const float *>(dev), w_xyz, w_x, w_Q, w_y, B, N, nx,
+                               h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(),
+                               h->dn_xs.as<float>(), h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
     }
     HIPCHK(hipGetLastError());
     std::vector<float> pred(q_out_flat ? slots : 0);

@@ -15,6 +15,9 @@
 //   GNN step 0                   a_i = [x_i | 0 | Q/n] does not depend on the coordinates: only the listed pairs' dG
 //   edges -> coordinates         gE [P][48] -> gD (float64) -> +-gD d / D into the pair's two slots, summed per atom in float64
 //
+// A training step (option "train_path", epnn_train_large.hip.h) runs the same kernels with step 0 in full and a GlTape: they then also
+// store the rows its weight gradients are outer products of, and the row pass adds up dW2 / db2 of all pairs (k_gl_sweep<1, 1>).
+//
 // Plain float32 throughout (the Dense layers of the two sweeps on v_mfma_f32_16x16x4_f32).  Every sum has a fixed order, there
 // are no float atomics: results are bit-reproducible and a molecule's rows do not depend on the rest of the batch (the number of
 // pieces its partner range is cut into depends on its own size alone).
@@ -41,6 +44,18 @@ struct GlUpd {                    // update MLP [h | M] (80) -> 32 -> 32 -> 48
 struct GlGeom {                   // the batch
     const int *moff, *mol_of;     // [B + 1], [A]
     int A, N, nx;
+};
+// What a training step (epnn_train_large.hip.h) keeps of the backward kernels' intermediates for its weight gradients; all null
+// (GlTape{}) in a gradient call, which stores nothing.  Rows of 32 unless noted.
+//   z1, d2   a Dense-2 input and its output gradient: EPN pair p, order o at row 2 p + o; GNN pair p, order o at rows 4 p + 2 o
+//            (with G) and 4 p + 2 o + 1 (without G, d2 negated: the correction rows' sign); GNN atom a at row pad0 + a: relu(P_a)
+//            and (N - n) d2 of its padded partners
+//   dz       [pairs] dz1_ij + dz1_ji with G (the We block);  r3 [2 pairs] relu(z2) times the row's seed (W3 of a pass MLP)
+//   u0 [A][80], u1, u2, ud2, ud1, gm [A]   the update MLP's activations and pre-activation gradients, gm = dM
+//   dv [A][64]   dP_a | dR_a, complete
+struct GlTape {
+    float *z1, *d2, *dz, *r3, *u0, *u1, *u2, *ud2, *ud1, *gm, *dv;
+    size_t pad0;
 };
 
 // sum_k v[k] W[k][col] over the 32 rows of a [32][stride] block (v in LDS, the 32 lanes of a half read one row: coalesced)
@@ -93,17 +108,19 @@ __global__ __launch_bounds__(64) void k_gl_proj(GlPair M, GlGeom G, const float 
 //   MODE 2 (backward, column pass: resident R_j; streamed P_i, Yc_i, dS_i):  dR_j += the same with the streamed dS_i
 // The sums stay in the lane that owns them; out [piece][A][32] gets one row per (piece, resident atom), written by exactly one
 // wavefront (an empty piece writes zeros), and the per-atom kernels add the pieces in order.
-template <int MODE>
+// WG 1 (a training step's row pass, MODE 1): the wavefront also adds up the weight gradient of the second Dense over every pair
+// it sees, dW2[k][m] += sum_c z1_c[k] d2_c[m] and db2[m] += sum_c d2_c[m] with z1 = relu(P + R) itself.  That product reduces over
+// the tile's columns, which the accumulator layout keeps in the lane index: the two 16 x 32 tiles go through LDS (rows of GL_TS
+// floats) and come back as MFMA operands with the column on the K index, 16 more v_mfma_f32_16x16x4_f32 per partner; the 32 x 32 + 32
+// sums stay in registers across the partners of all `run` tasks of the wavefront (tasks blockIdx.x * run ...) and leave as one row
+// of wpart [wavefronts][1056], which k_tl_reduce_sweep adds up in order.  A gradient call has run = 1 and one task per wavefront.
+#define GL_TS 36
+template <int MODE, int WG = 0>
 __global__ __launch_bounds__(64) void k_gl_sweep(const int4 *tasks, const int *moff, int A, const float *W2, const float *Xres,
-                                                 const float *Xstr, const float *Y, const float *dS, float *out) {
+                                                 const float *Xstr, const float *Y, const float *dS, float *out, int ntask, int run,
+                                                 float *wpart) {
+    __shared__ float tz[WG ? 16 * GL_TS : 1], td[WG ? 16 * GL_TS : 1];
     const int lane = threadIdx.x, c = lane & 15, qd = lane >> 4;
-    const int4 tk = tasks[blockIdx.x];                          // (first resident atom, molecule, piece, pieces)
-    const int a0 = moff[tk.y], a1 = moff[tk.y + 1];
-    const int len = (a1 - a0 + tk.w - 1) / tk.w;
-    const int j0 = min(a0 + tk.z * len, a1), j1 = min(j0 + len, a1);
-    const int col = tk.x + c;
-    const bool valid = col < a1;
-    const int colc = valid ? col : a1 - 1;
     float wf[2][8], wb[2][8];
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
@@ -113,59 +130,109 @@ __global__ __launch_bounds__(64) void k_gl_sweep(const int4 *tasks, const int *m
             wf[rb][s] = W2[kf * GL_H + m];                      // out[m] = sum_k W2[k][m] z1[k]
             wb[rb][s] = W2[m * GL_H + kf];                      // out[m] = sum_k W2[m][k] d2[k]
         }
-    float xr[8], ds[8], acc[8];
+    f32x4 aw[2][2] = {{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}};
+    float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int t_end = min(ntask, ((int)blockIdx.x + 1) * run);
+    for (int task = (int)blockIdx.x * run; task < t_end; ++task) {
+        const int4 tk = tasks[task];                                // (first resident atom, molecule, piece, pieces)
+        const int a0 = moff[tk.y], a1 = moff[tk.y + 1];
+        const int len = (a1 - a0 + tk.w - 1) / tk.w;
+        const int j0 = min(a0 + tk.z * len, a1), j1 = min(j0 + len, a1);
+        const int col = tk.x + c;
+        const bool valid = col < a1;
+        const int colc = valid ? col : a1 - 1;
+        float xr[8], ds[8], acc[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int f = 16 * (e >> 2) + 4 * qd + (e & 3);
-        xr[e] = Xres[(size_t)colc * GL_H + f];
-        ds[e] = (MODE == 1 && valid) ? dS[(size_t)colc * GL_H + f] : 0.f;
-        acc[e] = 0.f;
-    }
-    for (int j = j0; j < j1; ++j) {
-        const float *xs = Xstr + (size_t)j * GL_H + 4 * qd, *ys = Y + (size_t)j * GL_H + 4 * qd;
-        const f32x4 n0 = *reinterpret_cast<const f32x4 *>(xs), n1 = *reinterpret_cast<const f32x4 *>(xs + 16);
-        f32x4 o0 = *reinterpret_cast<const f32x4 *>(ys), o1 = *reinterpret_cast<const f32x4 *>(ys + 16);
-        float nn[8], z1[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { nn[e] = -n0[e]; nn[4 + e] = -n1[e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) z1[e] = fmaxf(xr[e], nn[e]);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[0][s], z1[s], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[1][s], z1[s], o1, 0, 0, 0);
+        for (int e = 0; e < 8; ++e) {
+            const int f = 16 * (e >> 2) + 4 * qd + (e & 3);
+            xr[e] = Xres[(size_t)colc * GL_H + f];
+            ds[e] = (MODE == 1 && valid) ? dS[(size_t)colc * GL_H + f] : 0.f;
+            acc[e] = 0.f;
         }
-        if (MODE == 0) {
+        for (int j = j0; j < j1; ++j) {
+            const float *xs = Xstr + (size_t)j * GL_H + 4 * qd, *ys = Y + (size_t)j * GL_H + 4 * qd;
+            const f32x4 n0 = *reinterpret_cast<const f32x4 *>(xs), n1 = *reinterpret_cast<const f32x4 *>(xs + 16);
+            f32x4 o0 = *reinterpret_cast<const f32x4 *>(ys), o1 = *reinterpret_cast<const f32x4 *>(ys + 16);
+            float nn[8], z1[8];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { acc[e] += fmaxf(o0[e], 0.f); acc[4 + e] += fmaxf(o1[e], 0.f); }
-        } else {
-            float d2[8];
-            if (MODE == 2) {
-                const float *dp = dS + (size_t)j * GL_H + 4 * qd;
-                const f32x4 d0 = *reinterpret_cast<const f32x4 *>(dp), d1 = *reinterpret_cast<const f32x4 *>(dp + 16);
+            for (int e = 0; e < 4; ++e) { nn[e] = -n0[e]; nn[4 + e] = -n1[e]; }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? d0[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? d1[e] : 0.f; }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? ds[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? ds[4 + e] : 0.f; }
-            }
-            f32x4 g0 = {0.f, 0.f, 0.f, 0.f}, g1 = {0.f, 0.f, 0.f, 0.f};
+            for (int e = 0; e < 8; ++e) z1[e] = fmaxf(xr[e], nn[e]);
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                g0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[0][s], d2[s], g0, 0, 0, 0);
-                g1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[1][s], d2[s], g1, 0, 0, 0);
+                o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[0][s], z1[s], o0, 0, 0, 0);
+                o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[1][s], z1[s], o1, 0, 0, 0);
             }
+            if (MODE == 0) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[e] += xr[e] > nn[e] ? g0[e] : 0.f;
-                acc[4 + e] += xr[4 + e] > nn[4 + e] ? g1[e] : 0.f;
+                for (int e = 0; e < 4; ++e) { acc[e] += fmaxf(o0[e], 0.f); acc[4 + e] += fmaxf(o1[e], 0.f); }
+            } else {
+                float d2[8];
+                if (MODE == 2) {
+                    const float *dp = dS + (size_t)j * GL_H + 4 * qd;
+                    const f32x4 d0 = *reinterpret_cast<const f32x4 *>(dp), d1 = *reinterpret_cast<const f32x4 *>(dp + 16);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? d0[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? d1[e] : 0.f; }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? ds[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? ds[4 + e] : 0.f; }
+                }
+                if (WG) {
+                    // (an invalid column has dS = 0, so d2 = 0: its z1 row, the last real atom's, adds nothing)
+                    *reinterpret_cast<f32x4 *>(&tz[c * GL_TS + 4 * qd]) = f32x4{fmaxf(xr[0] - nn[0], 0.f), fmaxf(xr[1] - nn[1], 0.f), fmaxf(xr[2] - nn[2], 0.f), fmaxf(xr[3] - nn[3], 0.f)};
+                    *reinterpret_cast<f32x4 *>(&tz[c * GL_TS + 16 + 4 * qd]) = f32x4{fmaxf(xr[4] - nn[4], 0.f), fmaxf(xr[5] - nn[5], 0.f), fmaxf(xr[6] - nn[6], 0.f), fmaxf(xr[7] - nn[7], 0.f)};
+                    *reinterpret_cast<f32x4 *>(&td[c * GL_TS + 4 * qd]) = f32x4{d2[0], d2[1], d2[2], d2[3]};
+                    *reinterpret_cast<f32x4 *>(&td[c * GL_TS + 16 + 4 * qd]) = f32x4{d2[4], d2[5], d2[6], d2[7]};
+                    __syncthreads();
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {                       // K = the columns 4 q .. 4 q + 3; this lane's is 4 q + qd
+                        const float *zr = &tz[(4 * q + qd) * GL_TS + c], *dr = &td[(4 * q + qd) * GL_TS + c];
+                        const float za = zr[0], zb = zr[16], da = dr[0], db = dr[16];
+                        aw[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(za, da, aw[0][0], 0, 0, 0);
+                        aw[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(za, db, aw[0][1], 0, 0, 0);
+                        aw[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(zb, da, aw[1][0], 0, 0, 0);
+                        aw[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(zb, db, aw[1][1], 0, 0, 0);
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) bsum[e] += d2[e];
+                }
+                f32x4 g0 = {0.f, 0.f, 0.f, 0.f}, g1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    g0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[0][s], d2[s], g0, 0, 0, 0);
+                    g1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[1][s], d2[s], g1, 0, 0, 0);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    acc[e] += xr[e] > nn[e] ? g0[e] : 0.f;
+                    acc[4 + e] += xr[4 + e] > nn[4 + e] ? g1[e] : 0.f;
+                }
             }
         }
+        if (valid) {
+            float *o = out + ((size_t)tk.z * A + col) * GL_H + 4 * qd;
+            *reinterpret_cast<f32x4 *>(o) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+            *reinterpret_cast<f32x4 *>(o + 16) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+        }
     }
-    if (valid) {
-        float *o = out + ((size_t)tk.z * A + col) * GL_H + 4 * qd;
-        *reinterpret_cast<f32x4 *>(o) = f32x4{acc[0], acc[1], acc[2], acc[3]};
-        *reinterpret_cast<f32x4 *>(o + 16) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    if (WG) {
+        // lane (qd, c) holds dW2[16 fa + 4 qd + r][16 fb + c]; db2: the 16 lanes of a feature are added in lane order
+        float *o = wpart + (size_t)blockIdx.x * (GL_H * GL_H + GL_H);
+#pragma unroll
+        for (int fa = 0; fa < 2; ++fa)
+#pragma unroll
+            for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[(16 * fa + 4 * qd + r) * GL_H + 16 * fb + c] = aw[fa][fb][r];
+        *reinterpret_cast<f32x4 *>(&tz[c * GL_TS + 4 * qd]) = f32x4{bsum[0], bsum[1], bsum[2], bsum[3]};
+        *reinterpret_cast<f32x4 *>(&tz[c * GL_TS + 16 + 4 * qd]) = f32x4{bsum[4], bsum[5], bsum[6], bsum[7]};
+        __syncthreads();
+        if (lane < GL_H) {
+            float sum = 0.f;
+            for (int k = 0; k < 16; ++k) sum += tz[k * GL_TS + lane];
+            o[GL_H * GL_H + lane] = sum;
+        }
     }
 }
 
@@ -182,7 +249,7 @@ struct GlPairs {
 // step 0, which needs no dP / dR), and gE_ij += We (dz1_ij + dz1_ji) with G.
 template <int BWD>
 __global__ __launch_bounds__(64) void k_gl_gnn_pair(GlPair M, GlPairs L, const float *P, const float *R, const float *dS, float *slotP,
-                                                    float *slotR, float *gE) {
+                                                    float *slotR, float *gE, GlTape K) {
     __shared__ float ev[GL_E], z[2][2][GL_H], d2[2][2][GL_H], dg[2][GL_H];
     const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     const int i = L.pi[p], j = L.pj[p];
@@ -206,6 +273,11 @@ __global__ __launch_bounds__(64) void k_gl_gnn_pair(GlPair M, GlPairs L, const f
     const float dsv = dS[(size_t)a * GL_H + f];
     d2[half][0][f] = z2g > 0.f ? dsv : 0.f;
     d2[half][1][f] = z2n > 0.f ? dsv : 0.f;
+    if (K.z1) {
+        const size_t r = (4 * (size_t)p + 2 * half) * GL_H + f;
+        K.z1[r] = z[half][0][f]; K.z1[r + GL_H] = z[half][1][f];
+        K.d2[r] = d2[half][0][f]; K.d2[r + GL_H] = -d2[half][1][f];
+    }
     __syncthreads();
     const float dg1 = z1g > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half][0], GL_H) : 0.f;
     const float dn1 = base > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half][1], GL_H) : 0.f;
@@ -215,6 +287,10 @@ __global__ __launch_bounds__(64) void k_gl_gnn_pair(GlPair M, GlPairs L, const f
     }
     dg[half][f] = dg1;
     __syncthreads();
+    if (K.dz) {                                                   // (a training step: the We block's rows, no gE)
+        if (lane < GL_H) K.dz[(size_t)p * GL_H + lane] = dg[0][lane] + dg[1][lane];
+        return;
+    }
     if (lane < GL_E) {
         float acc = 0.f;
         for (int k = 0; k < GL_H; ++k) acc = fmaf(M.We[lane * GL_H + k], dg[0][k] + dg[1][k], acc);
@@ -227,7 +303,7 @@ __global__ __launch_bounds__(64) void k_gl_gnn_pair(GlPair M, GlPairs L, const f
 // of its first atom and slotR of its second, and gE_ij += We (dz1_ij + dz1_ji).
 template <int BWD>
 __global__ __launch_bounds__(64) void k_gl_epn_pair(GlPair M, GlPairs L, const float *P, const float *R, const float *gq, float *slotq,
-                                                    float *slotP, float *slotR, float *gE) {
+                                                    float *slotP, float *slotR, float *gE, GlTape K) {
     __shared__ float ev[GL_E], z[2][GL_H], d2[2][GL_H], dg[2][GL_H], red[2][GL_H];
     const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     const int i = L.pi[p], j = L.pj[p];
@@ -256,12 +332,22 @@ __global__ __launch_bounds__(64) void k_gl_epn_pair(GlPair M, GlPairs L, const f
     }
     const float seed = 0.5f * w * (gq[i] - gq[j]);
     d2[half][f] = z2 > 0.f ? (half ? -seed : seed) * M.W3[f] : 0.f;
+    if (K.z1) {
+        const size_t r = (2 * (size_t)p + half) * GL_H + f;
+        K.z1[r] = z[half][f];
+        K.d2[r] = d2[half][f];
+        K.r3[r] = fmaxf(z2, 0.f) * (half ? -seed : seed);
+    }
     __syncthreads();
     const float dz1 = z1 > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half], GL_H) : 0.f;
     slotP[(size_t)sa * GL_H + f] = dz1;
     slotR[(size_t)sb * GL_H + f] = dz1;
     dg[half][f] = dz1;
     __syncthreads();
+    if (K.dz) {
+        if (lane < GL_H) K.dz[(size_t)p * GL_H + lane] = dg[0][lane] + dg[1][lane];
+        return;
+    }
     if (lane < GL_E) {
         float acc = 0.f;
         for (int k = 0; k < GL_H; ++k) acc = fmaf(M.We[lane * GL_H + k], dg[0][k] + dg[1][k], acc);
@@ -314,7 +400,7 @@ __global__ __launch_bounds__(64) void k_gl_gnn_tail(GlPair M, GlUpd U, GlGeom G,
 // Backward of the update MLP, one wavefront per atom: recomputes u1pre, u2pre from the checkpoints (h, S), carries gh [48] back:
 // gh_prev [A][48] = the h columns of the first layer's input gradient, dS [A][32] = W3 (its M columns).
 __global__ __launch_bounds__(64) void k_gl_upd_bwd(GlPair M, GlUpd U, GlGeom G, const float *h, const float *S, const float *gh,
-                                                   float *gh_prev, float *dS) {
+                                                   float *gh_prev, float *dS, GlTape K) {
     __shared__ float u0[GL_E + GL_H], sv[GL_H], u1[GL_H], gv[GL_E], d2[GL_H], d1[GL_H], gm[GL_H];
     const int a = blockIdx.x, lane = threadIdx.x;
     if (lane < GL_E) { u0[lane] = h ? h[(size_t)a * GL_E + lane] : 0.f; gv[lane] = gh[(size_t)a * GL_E + lane]; }
@@ -332,6 +418,7 @@ __global__ __launch_bounds__(64) void k_gl_upd_bwd(GlPair M, GlUpd U, GlGeom G, 
     if (lane < GL_H) {
         const float u2pre = U.c2[lane] + gl_dotT(U.U2, GL_H, lane, u1);
         d2[lane] = u2pre > 0.f ? gl_dotN(U.U3, GL_E, lane, gv, GL_E) : 0.f;
+        if (K.u2) K.u2[(size_t)a * GL_H + lane] = fmaxf(u2pre, 0.f);
     }
     __syncthreads();
     if (lane < GL_H) d1[lane] = t > 0.f ? gl_dotN(U.U2, GL_H, lane, d2, GL_H) : 0.f;
@@ -339,6 +426,14 @@ __global__ __launch_bounds__(64) void k_gl_upd_bwd(GlPair M, GlUpd U, GlGeom G, 
     if (lane < GL_E) gh_prev[(size_t)a * GL_E + lane] = gl_dotN(U.U1, GL_H, lane, d1, GL_H);
     if (lane < GL_H) gm[lane] = gl_dotN(U.U1, GL_H, GL_E + lane, d1, GL_H);
     __syncthreads();
+    if (K.u0) {
+        K.u0[(size_t)a * (GL_E + GL_H) + lane] = u0[lane];
+        if (lane < GL_E + GL_H - 64) K.u0[(size_t)a * (GL_E + GL_H) + 64 + lane] = u0[64 + lane];
+        if (lane < GL_H) {
+            const size_t r = (size_t)a * GL_H + lane;
+            K.u1[r] = u1[lane]; K.ud2[r] = d2[lane]; K.ud1[r] = d1[lane]; K.gm[r] = gm[lane];
+        }
+    }
     if (lane < GL_H) dS[(size_t)a * GL_H + lane] = gl_dotN(M.W3, GL_H, lane, gm, GL_H);
 }
 
@@ -346,7 +441,7 @@ __global__ __launch_bounds__(64) void k_gl_upd_bwd(GlPair M, GlUpd U, GlGeom G, 
 // partners in closed form, the atom's slots in order; then gh = gh_prev + the h columns of Wi dP + Wj dR (in place).
 __global__ __launch_bounds__(64) void k_gl_gnn_atom_bwd(GlPair M, GlGeom G, const int *inc_off, const float *partP, const float *partR,
                                                         const float *slotP, const float *slotR, const float *P, const float *dS,
-                                                        float *gh) {
+                                                        float *gh, GlTape K) {
     __shared__ float v[GL_H], d2[GL_H], dv[2][GL_H];
     const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     const int b = G.mol_of[a], n = G.moff[b + 1] - G.moff[b];
@@ -362,6 +457,13 @@ __global__ __launch_bounds__(64) void k_gl_gnn_atom_bwd(GlPair M, GlGeom G, cons
     if (!half) s += (float)(G.N - n) * (pa > 0.f ? gl_dotN(M.W2, GL_H, f, d2, GL_H) : 0.f);
     for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slot[(size_t)k * GL_H + f];
     dv[half][f] = s;
+    if (K.dv) {
+        K.dv[(size_t)a * 64 + lane] = s;
+        if (!half) {
+            K.z1[(K.pad0 + a) * GL_H + f] = v[f];
+            K.d2[(K.pad0 + a) * GL_H + f] = (float)(G.N - n) * d2[f];
+        }
+    }
     __syncthreads();
     if (lane < GL_E) {
         const int row = G.nx + lane;
@@ -388,13 +490,14 @@ __global__ __launch_bounds__(256) void k_gl_q0(GlGeom G, const float *Q, float *
 // EPN backward, one wavefront per atom: dP / dR from the slots in order, then gfeat += the h columns and gq += the q column of
 // Wi dP + Wj dR.
 __global__ __launch_bounds__(64) void k_gl_epn_atom_bwd(GlPair M, GlGeom G, const int *inc_off, const float *slotP, const float *slotR,
-                                                        float *gfeat, float *gq) {
+                                                        float *gfeat, float *gq, GlTape K) {
     __shared__ float dv[2][GL_H];
     const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     const float *slot = half ? slotR : slotP;
     float s = 0.f;
     for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slot[(size_t)k * GL_H + f];
     dv[half][f] = s;
+    if (K.dv) K.dv[(size_t)a * 64 + lane] = s;
     __syncthreads();
     if (lane <= GL_E) {
         const int row = G.nx + lane;                               // lane 48: the charge's column

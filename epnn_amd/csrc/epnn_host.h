@@ -259,6 +259,7 @@ struct epnn_handle {
     void *xyz_grad = nullptr;         // TrainState of epnn_charges_vjp_xyz (epnn_api_grad.hip.h): its own weights and scratch
     void *grad_large = nullptr;       // GradLarge: weights, inputs and scratch of its pair-list path ("grad_path")
     int opt_grad_path = 0;            // epnn_charges_vjp_xyz*: 0 = the dense path up to B N^2 = 2^22 and the pair-list path above, 1 = dense, 2 = pair list
+    int opt_train_path = 0;           // epnn_train_step_xyz_cell: the same choice for a training step
 };
 
 // ---- fail-closed collectives.  RCCL has no timeout: a rank that leaves an entry point with an error BEFORE a collective its peers

@@ -314,8 +314,13 @@ class Engine:
                                              fptr(y), fptr(pred), C.byref(loss), int(bool(apply))), self.lib)
         return pred, loss.value
 
-    def train_step_xyz(self, offsets, xyz, x, Q, y, N, apply=True):
-        """Flat batch; y per real atom (A,). Returns (q (A,), summed loss)."""
+    def train_step_xyz(self, offsets, xyz, x, Q, y, N, apply=True, box=None, cell=None):
+        """Flat batch; y per real atom (A,). Returns (q (A,), summed loss).  box (3,) or (B, 3): periodic cells, cell (3, 3) or
+        (B, 3, 3): general cells, as in forward_xyz; with one of them the step runs epnn_train_step_xyz_cell, whose implementation
+        set_option("train_path", v) chooses: 0 (default) the dense path while B N^2 <= 2^22 and the pair-list path (per-atom rows and
+        the pairs under the cutoff only: large systems) above that, 1 / 2 force one of them.  Without box and cell it is the dense
+        step of epnn_train_step_xyz at any size."""
+        _one_periodic_argument(box, cell)
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         xyz, x, Q, y = _f32(xyz), _f32(x), _f32(Q), _f32(y)
         B, A = len(offsets) - 1, int(offsets[-1])
@@ -323,6 +328,15 @@ class Engine:
             raise EpnnError("train_step_xyz: array shapes do not match offsets")
         q = np.empty((A,), dtype=np.float32)
         loss = C.c_float()
+        if box is not None or cell is not None:
+            if cell is None:
+                box = _box_rows(box, B)
+                cell = np.zeros((B, 3, 3), dtype=np.float32)
+                cell[:, [0, 1, 2], [0, 1, 2]] = box
+            cell = _cell_rows(cell, B)
+            check(self.lib.epnn_train_step_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), fptr(y),
+                                                    fptr(q), C.byref(loss), int(bool(apply))), self.lib)
+            return q, loss.value
         check(self.lib.epnn_train_step_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(y), fptr(q),
                                            C.byref(loss), int(bool(apply))), self.lib)
         return q, loss.value

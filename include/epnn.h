@@ -286,6 +286,22 @@ int epnn_edges_cell(epnn_handle *h, int n, const float *xyz, const float *cell, 
 /* epnn_charges_vjp_xyz in general cells, with its contract, and the strain derivative described above. */
 int epnn_charges_vjp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                               const float *Q, const float *cell, const float *g, float *q_out, float *gxyz_out, float *gstrain_out);
+/* ---- training on periodic and large systems.  epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
+ * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
+ * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's
+ * flat vector (epnn_get_gradients); apply != 0 adds the guarded all-reduce and the Adam step, as in epnn_train_step_xyz.  Two
+ * implementations stand behind it (option "train_path"): the dense path -- epnn_train_step_xyz's kernels on rows padded to
+ * [B][N][N] whose distances are minimum-image ones, with "train_fused", "train_async" and "train_graph" as there -- and the
+ * pair-list path: the checkpointed forward and the backward of epnn_charges_vjp_xyz's pair-list path seeded with 2 (q - y), with
+ * the weight gradients summed per atom, per listed pair and, for the second Dense of a message MLP, over all pairs inside the
+ * backward sweep (f32 MFMA).  The pair-list path reads the device masters directly, keeps per-atom rows and the listed pairs only
+ * (scratch O(atoms + listed pairs) plus constant-size partial sums; profiles/r10_train_large.txt), is bit-reproducible (no atomics,
+ * every sum in a fixed order), waits for a dense "train_async" step still in flight, and returns when all of it is done: it has
+ * to wait for the pair count once anyway, so "train_async" and "train_graph" do not apply to it.  It is built for update layers
+ * [32, 32] on a handle without epnn_set_partition.  After a call on it epnn_last_stats gives out[0] = listed pairs, out[1] = 0,
+ * out[2] = bytes of device scratch the call used.  epnn_train_step_xyz itself never takes the pair-list path. */
+int epnn_train_step_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                             const float *cell, const float *y_flat, float *q_out_flat, float *loss_out, int apply);
 /* RCCL communicator (one rank per GPU): the gradient is summed with ONE ncclAllReduce of the flat vector; the same
  * communicator carries the row exchange of a partitioned large system (epnn_set_partition with exchange == NULL). */
 int epnn_comm_unique_id(char *out128);
@@ -340,6 +356,10 @@ int epnn_timing_at(epnn_handle *h, int idx, float *out4);
  *                       B N^2 <= 2^22 (every call that fitted a GPU before takes the path it took, bit for bit), the pair-list path
  *                       above that; 1 = always the dense path; 2 = always the pair-list path (refused by name for update layers other
  *                       than [32, 32] and on a partitioned handle, which stay on the dense path under 0)
+ *   "train_path"        which implementation epnn_train_step_xyz_cell runs (epnn_train_step_xyz always runs the dense one): 0 (default) =
+ *                       the dense path while B N^2 <= 2^22, the pair-list path above that; 1 = always the dense path; 2 = always the
+ *                       pair-list path (refused by name for update layers other than [32, 32] and on a partitioned handle, which
+ *                       stay on the dense path under 0)
  *   "train_async"       1 (default) = a training step returns as soon as its forward pass is done (loss and predictions are on the host
  *                       then; backward and optimizer keep running, every call that reads weights or gradients waits for them); 0 = a
  *                       step returns when all of it is done
