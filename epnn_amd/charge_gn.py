@@ -377,6 +377,15 @@ class EPNNModel(_Stack):
         Large systems (B N^2 above 2^22) run from the pair list without (N, N, .) tensors (engine option "grad_path")."""
         return self._eng().charges_vjp_xyz(offsets, xyz, x, Q, g, self.natom if N is None else N, box=box, cell=cell, strain=strain)
 
+    def charges_jvp_xyz(self, offsets, xyz, x, Q, N=None, v=None, strain=None, dQ=None, box=None, cell=None):
+        """Charges and their derivative along a direction, forward mode: (q (A,), tq (A,)) with tq = J v + (dq/d eps) : strain +
+        (dq/dQ) dQ for a coordinate tangent v (A, 3), a strain (3, 3) or (B, 3, 3) and a total-charge tangent dQ (scalar or (B,)),
+        each optional.  With v an MD velocity tq is the charge flux dq/dt (dipole rate: sum_i q_i v_i + sum_i r_i tq_i); dQ = 1
+        alone gives dq/dQ.  One call costs about one forward of the pair-list gradient path.  N defaults to the model's natom; box
+        and cell as in predict_xyz."""
+        return self._eng().charges_jvp_xyz(offsets, xyz, x, Q, self.natom if N is None else N, v=v, strain=strain, dQ=dQ, box=box,
+                                           cell=cell)
+
     def train_step_xyz(self, optimizer, offsets, xyz, x, Q, y, N=None, apply=True, box=None, cell=None):
         """One training step (loss = sum (y - q)^2 over the atoms, its gradient, one Adam step of `optimizer` unless apply=False) on a
         flat batch with reference charges y (A,): (q (A,), loss).  N defaults to the model's natom; box and cell as in predict_xyz:

@@ -374,6 +374,51 @@ class Engine:
                                                     fptr(q), fptr(gxyz)), self.lib)
         return q, gxyz
 
+    def charges_jvp_xyz(self, offsets, xyz, x, Q, N, v=None, strain=None, dQ=None, box=None, cell=None):
+        """Forward mode: flat batch and a direction -> (q (A,), tq (A,)), tq the derivative of the charges along it
+        (epnn_charges_jvp_xyz_cell): v (A, 3) a tangent of the coordinates (an MD velocity: tq = dq/dt), strain (3, 3) or
+        (B, 3, 3) a homogeneous strain E of coordinates and cell (the one gstrain of charges_vjp_xyz is the derivative for),
+        dQ a scalar or (B,) a tangent of the total charges (dQ = 1 alone: dq/dQ, the condensed Fukui function).  Each may be
+        None (= 0); the three add up.  box (3,) or (B, 3), cell (3, 3) or (B, 3, 3) as in forward_xyz; neither: open molecules.
+        One call costs about one forward of the pair-list gradient path, whose charges q has bit for bit; it touches no training
+        state and works without train_init."""
+        _one_periodic_argument(box, cell)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
+        B, A = len(offsets) - 1, int(offsets[-1])
+        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
+            raise EpnnError("charges_jvp_xyz: array shapes do not match offsets")
+        if v is not None:
+            v = _f32(v)
+            if v.shape != (A, 3):
+                raise ValueError(f"charges_jvp_xyz: v must have shape ({A}, 3), got {v.shape}")
+        if strain is not None:
+            strain = np.asarray(strain, dtype=np.float32)
+            if strain.shape == (3, 3):
+                strain = np.tile(strain, (B, 1, 1))
+            if strain.shape != (B, 3, 3):
+                raise ValueError(f"charges_jvp_xyz: strain must have shape (3, 3) or ({B}, 3, 3), got {strain.shape}")
+            strain = np.ascontiguousarray(strain)
+        if dQ is not None:
+            dQ = np.asarray(dQ, dtype=np.float32)
+            if dQ.shape == ():
+                dQ = np.full((B,), dQ, dtype=np.float32)
+            if dQ.shape != (B,):
+                raise ValueError(f"charges_jvp_xyz: dQ must be a scalar or have shape ({B},), got {dQ.shape}")
+            dQ = np.ascontiguousarray(dQ)
+        if box is not None:
+            box = _box_rows(box, B)
+            cell = np.zeros((B, 3, 3), dtype=np.float32)
+            cell[:, [0, 1, 2], [0, 1, 2]] = box
+        if cell is not None:
+            cell = _cell_rows(cell, B)
+        opt = lambda a: None if a is None else fptr(a)
+        q = np.empty((A,), dtype=np.float32)
+        tq = np.empty((A,), dtype=np.float32)
+        check(self.lib.epnn_charges_jvp_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), opt(cell), opt(v),
+                                                 opt(strain), opt(dQ), fptr(q), fptr(tq)), self.lib)
+        return q, tq
+
     def get_gradients(self):
         g = np.empty((self.param_count(),), dtype=np.float32)
         check(self.lib.epnn_get_gradients(self.h, fptr(g), g.size), self.lib)

@@ -286,6 +286,41 @@ int epnn_edges_cell(epnn_handle *h, int n, const float *xyz, const float *cell, 
 /* epnn_charges_vjp_xyz in general cells, with its contract, and the strain derivative described above. */
 int epnn_charges_vjp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                               const float *Q, const float *cell, const float *g, float *q_out, float *gxyz_out, float *gstrain_out);
+/* ---- forward mode: the charges and their directional derivative (the other half of epnn_charges_vjp_xyz_cell, which gives
+ * g^T dq/dxyz and gstrain).  For the flat batch of epnn_forward_xyz_cell, a tangent vxyz[A][3] of the coordinates, a strain tangent
+ * vstrain[B][3][3] = E and a tangent vQ[B] of the total charges (each may be NULL = 0; all three NULL gives tq = 0),
+ *     q_out[i]  = the charges,
+ *     tq_out[i] = sum_k (dq_i/dr_k) . v_k + sum_ac (dq_i/d eps_ac) E_ac + (dq_i/dQ) vQ,     molecule by molecule:
+ * the charge flux dq/dt = J v along an MD velocity (the sum_i r_i dq_i/dt part of a dipole derivative), the response of the charges
+ * to a cell deformation, and with vQ = 1 alone the condensed Fukui function dq/dQ (sum_i tq_i = vQ per molecule by construction).
+ * The strain is the one gstrain is defined for: r -> (1 + eps) r, a_k -> (1 + eps) a_k; image shifts, pair and node masks and the
+ * is_near weights (charge_gn.py:90-94) are constants, as in the VJP.  cell [B][3][3] has the meaning and the checks of
+ * epnn_forward_xyz_cell (a diagonal cell is a box, a zero row an open axis); NULL: open molecules.
+ *   Edges (get_init_edges, charge_gn.py:122-163): for a listed pair with the front-end's image d' and distance D, in float64,
+ *     tD = d' . (v_j - v_i) / D + d'^T E d' / D,     te_k = (C'(D) - 2 eta (D - mu_k) C(D)) exp(-eta (D - mu_k)^2) tD,
+ *   stored as a float32 row te[P][48].
+ *   GNN_layer.call (charge_gn.py:57-75), per step in the factorised form: ta_i = [0 | th_i | vQ / n], tP = Wi^T ta, tR = Wj^T ta;
+ *     z1 = relu(P_i + R_j + We^T e_ij), tz1 = [z1 > 0] (tP_i + tR_j + We^T te_ij); z2 = relu(W2^T z1 + b2), tz2 = [z2 > 0] W2^T tz1;
+ *     tS_i = sum over all N partners of tz2 (an all-pairs sweep on f32 MFMA tiles for the pairs without e, the listed pairs as
+ *     corrections, the (N - n) padded partners in closed form); tM = W3^T tS; th' = the update MLP's tangent on [th | tM].
+ *   EPN_layer.call (charge_gn.py:88-119), per step: tq_i += sum over listed j of w_ij (tf_ij - tf_ji) / 2 with tf the tangent of the
+ *     pass MLP on [a_i | a_j | e_ij], a = [x | h_T | q_t], ta = [0 | th_T | tq_t].
+ * Contract: that of the pair-list path of epnn_charges_vjp_xyz ("grad_path" = 2), whatever that option is set to: works on a handle
+ * that never trained, uses the current weights, leaves weights, gradients, Adam state and step count untouched, waits first for a
+ * "train_async" step in flight; refuses by name update layers other than [32, 32], a partitioned handle, bad offsets, a molecule
+ * that does not fit N, null xyz / x / Q / outputs, coincident atoms or images (the handle stays usable); h_dim below 48 runs
+ * zero-padded; bit-reproducible (no float atomics, every sum in a fixed order); a molecule's rows do not depend on the rest of the
+ * batch at the same N.  q_out has the bits of that path's q_out: the primal is its checkpointed forward, operation by operation,
+ * and every ReLU decision of a tangent is taken from the float32 pre-activation its backward takes it from, so that
+ * sum_i g_i tq_i = gxyz . v + gstrain : E holds between the two entries to float32 rounding of the sums.
+ * One call costs about one extra forward of that path, keeps no checkpoints and nothing of size N^2.  Device scratch, with
+ * pieces = max over the molecules of min(16, ceil(2048 / ceil(n / 16))):
+ *     bytes = A (1592 + 4 nx + 257 pieces) + 980 listed pairs + 13 KB      (12 A more with vxyz; +- 256 per buffer of rounding)
+ * shared with the gradient path: the handle keeps the scratch of its largest call of either until epnn_destroy.  After a call
+ * epnn_last_stats gives out[0] = listed pairs, out[1] = 0, out[2] = bytes of device scratch the call used. */
+int epnn_charges_jvp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                              const float *cell, const float *vxyz, const float *vstrain, const float *vQ, float *q_out,
+                              float *tq_out);
 /* ---- training on periodic and large systems.  epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
  * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
  * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's
