@@ -407,6 +407,7 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
 
 #include "epnn_api_dense.hip.h"
 #include "epnn_api_train.hip.h"
+#include "epnn_api_pairlist.hip.h"
 #include "epnn_api_grad.hip.h"
 #include "epnn_api_train_large.hip.h"
 #include "epnn_api_jvp.hip.h"

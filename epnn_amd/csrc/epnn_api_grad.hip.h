@@ -1,7 +1,7 @@
 // epnn_charges_vjp_xyz: charges and g^T dq/dxyz of a flat coordinate batch (kernels: epnn_grad_xyz.hip.h).
 // Part of the one translation unit epnn_api.hip.
 #pragma once
-#include "epnn_grad_large.hip.h"
+#include "epnn_api_pairlist.hip.h"
 
 // The call's own TrainState: the handle's current weights as a flat vector (refreshed when weights_gen moves on) and the
 // scratch of one forward + backward.  The training state (masters, gradients, Adam moments, step) is never read or written.
@@ -18,203 +18,39 @@ static void xyz_grad_release(epnn_handle *h) {
 }
 
 // ------------------------------------------------------------------------------------------------ pair-list path ("grad_path")
-// The same result from the pair list (kernels and arithmetic: epnn_grad_large.hip.h): per-atom rows, the near pairs of the
-// separate front-end and their incidence slots, nothing of size N^2.  Its own weights (plain Keras layout, refreshed when
-// weights_gen moves on), inputs and scratch: neither the training state nor the forward's plan and pair list are touched.
-struct GradLarge {
-    long wgen = -1;
-    DevBuf w, in, work;
-    PinBuf pin_in, pin_out;
-    GlPair msg[EPNN_MAXT], pas[EPNN_MAXT];
-    GlUpd upd;
-};
-static GradLarge *grad_large_state(epnn_handle *h) {
-    if (!h->grad_large) h->grad_large = new GradLarge();
-    return reinterpret_cast<GradLarge *>(h->grad_large);
-}
-static void grad_large_release(epnn_handle *h) {
-    if (!h->grad_large) return;
-    GradLarge *gl = reinterpret_cast<GradLarge *>(h->grad_large);
-    gl->w.release(); gl->in.release(); gl->work.release(); gl->pin_in.release(); gl->pin_out.release();
-    delete gl;
-    h->grad_large = nullptr;
-}
-static bool grad_large_possible(const epnn_handle *h) { return !h->upd_generic && h->part_world == 1; }
-// automatic routing: the dense path while its [B][N][N] tensors stay small (no caller of this repository's tests, bench or tools
-// is above it, so every call that ran before takes the path it took)
-static bool grad_large_auto(int B, int N) { return (size_t)B * (size_t)N * (size_t)N > ((size_t)1 << 22); }
-
-static int grad_large_weights(epnn_handle *h, GradLarge *gl) {
-    if (gl->wgen == h->weights_gen) return 0;
-    const int F = h->cfg.nx + GL_E + 1, T = h->cfg.T;
-    std::vector<float> flat;
-    auto put = [&](const std::vector<float> &v) { const size_t o = flat.size(); flat.insert(flat.end(), v.begin(), v.end()); return o; };
-    size_t om[EPNN_MAXT][6], op[EPNN_MAXT][6], ou[6];
-    for (int t = 0; t < T; ++t)
-        for (int pass = 0; pass < 2; ++pass) {
-            const HostDense *L = pass ? h->pas[t] : h->msg[t];
-            size_t *o = pass ? op[t] : om[t];
-            if (L[0].n_in != 2 * F + GL_E || L[0].n_out != GL_H || L[1].n_in != GL_H || L[1].n_out != GL_H || L[2].n_in != GL_H ||
-                L[2].n_out != (pass ? 1 : GL_H))
-                EPNN_FAIL("epnn_charges_vjp_xyz (pair-list path): unexpected shape of a %s MLP", pass ? "pass" : "message");
-            for (int l = 0; l < 3; ++l) { o[2 * l] = put(L[l].W); o[2 * l + 1] = put(L[l].b); }
-        }
-    if (h->upd[0].n_in != GL_E + GL_H || h->upd[0].n_out != GL_H || h->upd[1].n_out != GL_H || h->upd[2].n_out != GL_E)
-        EPNN_FAIL("epnn_charges_vjp_xyz (pair-list path): unexpected shape of the update MLP");
-    for (int l = 0; l < 3; ++l) { ou[2 * l] = put(h->upd[l].W); ou[2 * l + 1] = put(h->upd[l].b); }
-    HIPCHK(hipStreamSynchronize(h->stream));                      // (no call of this path is in flight: they all end with a wait)
-    if (gl->w.ensure(flat.size() * 4)) return 1;
-    HIPCHK(hipMemcpy(gl->w.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
-    const float *base = gl->w.as<float>();
-    for (int t = 0; t < T; ++t)
-        for (int pass = 0; pass < 2; ++pass) {
-            const size_t *o = pass ? op[t] : om[t];
-            GlPair &M = pass ? gl->pas[t] : gl->msg[t];
-            M.Wi = base + o[0]; M.Wj = M.Wi + (size_t)F * GL_H; M.We = M.Wj + (size_t)F * GL_H;
-            M.b1 = base + o[1]; M.W2 = base + o[2]; M.b2 = base + o[3]; M.W3 = base + o[4]; M.b3 = base + o[5];
-        }
-    gl->upd = GlUpd{base + ou[0], base + ou[1], base + ou[2], base + ou[3], base + ou[4], base + ou[5]};
-    gl->wgen = h->weights_gen;
-    return 0;
-}
-
+// State, weights, the call's set-up and the checkpointed forward: epnn_api_pairlist.hip.h.  Here: this entry's scratch and its backward.
 static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                   const float *g, float *q_out, float *gxyz_out, const float *box, const EpnnCell *cells,
                                   float *gstrain_out) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
-    const int nx = h->cfg.nx, T = h->cfg.T, A = offsets[B];
+    const int T = h->cfg.T, A = offsets[B];
     const char *name = cells ? "epnn_charges_vjp_xyz_cell" : box ? "epnn_charges_vjp_xyz_pbc" : "epnn_charges_vjp_xyz";
-    // sweep tasks: 16 resident atoms x one piece of their molecule's partner range
-    std::vector<int4> tasks;
-    int maxp = 1;
-    for (int b = 0; b < B; ++b) {
-        const int n = offsets[b + 1] - offsets[b], np = gl_pieces(n);
-        maxp = std::max(maxp, np);
-        for (int a0 = offsets[b]; a0 < offsets[b + 1]; a0 += 16)
-            for (int k = 0; k < np; ++k) tasks.push_back(make_int4(a0, b, k, np));
-    }
-    auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    // ---- inputs and the front-end's per-atom counts: one upload
-    size_t at = 0;
-    auto place = [&](size_t bytes) { const size_t o = at; at += up256(bytes); return o; };
-    const size_t o_off = place((size_t)(B + 1) * 4), o_molof = place((size_t)A * 4), o_mflag = place((size_t)B * 4),
-                 o_task = place(tasks.size() * sizeof(int4)), o_xyz = place((size_t)A * 12), o_x = place((size_t)A * nx * 4),
-                 o_Q = place((size_t)B * 4), o_g = place((size_t)A * 4),
-                 o_geo = place(cells ? (size_t)B * sizeof(EpnnCell) : box ? (size_t)B * 12 : 0), in_bytes = at;
-    const size_t o_rowcnt = place((size_t)(A + 1) * 4), o_rowoff = place((size_t)(A + 1) * 4), o_deg = place((size_t)(A + 1) * 4),
-                 o_incoff = place((size_t)(A + 1) * 4), o_status = place(16);
-    if (gl->pin_in.ensure(in_bytes) || gl->in.ensure(at) || gl->pin_out.ensure(64)) return 1;
-    char *st = gl->pin_in.as<char>();
-    memcpy(st + o_off, offsets, (size_t)(B + 1) * 4);
-    int *molof = reinterpret_cast<int *>(st + o_molof), *mflag = reinterpret_cast<int *>(st + o_mflag);
-    for (int b = 0; b < B; ++b) {
-        mflag[b] = 1;
-        for (int a = offsets[b]; a < offsets[b + 1]; ++a) molof[a] = b;
-    }
-    memcpy(st + o_task, tasks.data(), tasks.size() * sizeof(int4));
-    memcpy(st + o_xyz, xyz, (size_t)A * 12);
-    memcpy(st + o_x, x, (size_t)A * nx * 4);
-    memcpy(st + o_Q, Q, (size_t)B * 4);
-    memcpy(st + o_g, g, (size_t)A * 4);
-    if (cells) memcpy(st + o_geo, cells, (size_t)B * sizeof(EpnnCell));
-    else if (box) memcpy(st + o_geo, box, (size_t)B * 12);
-    char *din = gl->in.as<char>();
-    HIPCHK(hipMemcpyAsync(din, st, in_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(din + o_status, 0, 16, h->stream));
-    const int *d_moff = reinterpret_cast<const int *>(din + o_off), *d_molof = reinterpret_cast<const int *>(din + o_molof);
-    const int4 *d_tasks = reinterpret_cast<const int4 *>(din + o_task);
-    const float *d_xyz = reinterpret_cast<const float *>(din + o_xyz), *d_x = reinterpret_cast<const float *>(din + o_x),
-                *d_Q = reinterpret_cast<const float *>(din + o_Q), *d_g = reinterpret_cast<const float *>(din + o_g),
-                *d_geo = reinterpret_cast<const float *>(din + o_geo);
-    const EpnnCell *d_cells = reinterpret_cast<const EpnnCell *>(d_geo);
-    // ---- pair list: count and prefix sums first, then buffers of exactly that size, then the records and the incidence slots
-    FrontArgs F{};
-    F.xyz = d_xyz; F.mol_of = d_molof; F.moff = d_moff; F.mflag = reinterpret_cast<const int *>(din + o_mflag);
-    F.A = A;
-    F.cutoff = (double)h->cfg.cutoff; F.cut2 = cutoff_squared(F.cutoff); F.eta = (double)h->cfg.eta; F.tol = h->cfg.near_tol;
-    F.e_dim = h->cfg.e_dim;
-    F.mu = h->d_mu.as<double>();
-    F.row_cnt = reinterpret_cast<int *>(din + o_rowcnt); F.row_off = reinterpret_cast<int *>(din + o_rowoff);
-    F.deg = reinterpret_cast<int *>(din + o_deg); F.inc_off = reinterpret_cast<int *>(din + o_incoff);
-    F.status = reinterpret_cast<int *>(din + o_status);
-    F.pcap = 0x7fffffff;
-    const unsigned rows = (unsigned)((A + 3) / 4), gA = (unsigned)((A + 255) / 256);
-    if (cells) hipLaunchKernelGGL(k_front_count_cell, dim3(rows), dim3(256), 0, h->stream, F, d_cells);
-    else if (box) hipLaunchKernelGGL(k_front_count_pbc, dim3(rows), dim3(256), 0, h->stream, F, d_geo);
-    else hipLaunchKernelGGL(k_front_count, dim3(rows), dim3(256), 0, h->stream, F);
-    hipLaunchKernelGGL(k_front_scan_both, dim3(1), dim3(1024), 0, h->stream, F);
-    HIPCHK(hipGetLastError());
-    int *cnt = gl->pin_out.as<int>();
-    HIPCHK(hipMemcpyAsync(cnt, F.row_off + A, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cnt + 1, F.inc_off + A, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cnt + 2, F.status, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const int np = cnt[0];
-    if (cnt[2] != 0) EPNN_FAIL("%s (pair-list path): the pair count overflowed (status %d)", name, cnt[2]);
-    if (np < 0 || cnt[1] != 2 * np) EPNN_FAIL("%s (pair-list path): inconsistent pair count (%d pairs, %d incidences)", name, np, cnt[1]);
-    const size_t P1 = (size_t)std::max(np, 1), SL = 2 * P1, rowH = (size_t)A * GL_H * 4, rowE = (size_t)A * GL_E * 4;
-    at = 0;
-    const size_t o_pi = place(P1 * 4), o_pj = place(P1 * 4), o_psym = place(P1 * 4), o_pe = place(P1 * GL_E * 4), o_pwi = place(P1 * 4),
-                 o_pwj = place(P1 * 4), o_nbr = place(SL * 4), o_di = place(P1 * 4), o_dj = place(P1 * 4),
-                 o_prec = place(2 * (P1 + 256) * sizeof(int4)), o_h = place((size_t)(T + 1) * rowE), o_S = place((size_t)T * rowH),
-                 o_q = place((size_t)(T + 1) * A * 4), o_P = place(rowH), o_R = place(rowH), o_Yb = place(rowH), o_Yc = place(rowH),
-                 o_dS = place(rowH), o_partP = place((size_t)maxp * rowH), o_partR = place((size_t)maxp * rowH),
-                 o_slotP = place(SL * GL_H * 4), o_slotR = place(SL * GL_H * 4), o_slotq = place(SL * 4), o_gE = place(P1 * GL_E * 4),
-                 o_gh = place(rowE), o_ghp = place(rowE), o_slotx = place(SL * 72), o_share = place((size_t)A * 48),
-                 o_out = place(((size_t)A * 5 + 1 + (size_t)B * 9) * 4);
-    if (gl->work.ensure(at)) return 1;
-    h->stats[0] = np;
-    h->stats[1] = 0;
-    h->stats[3] = 0;
-    h->stats[2] = (int64_t)(at + gl->in.cap);                    // device scratch of this call, bytes
-    char *dw = gl->work.as<char>();
-    auto fp = [&](size_t o) { return reinterpret_cast<float *>(dw + o); };
-    auto ip = [&](size_t o) { return reinterpret_cast<int *>(dw + o); };
-    F.pcap = (int)P1;
-    F.pi = ip(o_pi); F.pj = ip(o_pj); F.psym = ip(o_psym); F.pe = fp(o_pe); F.pwi = fp(o_pwi); F.pwj = fp(o_pwj);
-    F.nbr = ip(o_nbr); F.dest_i = ip(o_di); F.dest_j = ip(o_dj); F.prec = reinterpret_cast<int4 *>(dw + o_prec);
-    if (np > 0) {
-        if (cells) hipLaunchKernelGGL(k_front_fill_cell, dim3(rows), dim3(256), 0, h->stream, F, d_cells);
-        else if (box) hipLaunchKernelGGL(k_front_fill_pbc, dim3(rows), dim3(256), 0, h->stream, F, d_geo);
-        else hipLaunchKernelGGL(k_front_fill, dim3(rows), dim3(256), 0, h->stream, F);
-        hipLaunchKernelGGL(k_front_link, dim3((unsigned)std::min<size_t>((P1 + 255) / 256, 1024)), dim3(256), 0, h->stream, F);
-        HIPCHK(hipGetLastError());
-    }
-    const GlGeom G{d_moff, d_molof, A, N, nx};
-    const GlPairs L{F.pi, F.pj, F.dest_i, F.dest_j, F.pe, F.pwi};
-    const int *inc = F.inc_off;
-    float *hck = fp(o_h), *Sck = fp(o_S), *qck = fp(o_q), *dP = fp(o_P), *dR = fp(o_R), *Yb = fp(o_Yb), *Yc = fp(o_Yc), *dS = fp(o_dS),
-          *partP = fp(o_partP), *partR = fp(o_partR), *slotP = fp(o_slotP), *slotR = fp(o_slotR), *slotq = fp(o_slotq), *gE = fp(o_gE),
-          *gh = fp(o_gh), *ghp = fp(o_ghp), *out = fp(o_out);
+    const std::string where = std::string(name) + " (pair-list path)";
+    const GlSpan span_g{g, (size_t)A * 4, false};
+    GlCall c;
+    if (gl_call_count(h, gl, where.c_str(), B, N, offsets, xyz, x, Q, box, cells, &span_g, 1, c)) return 1;
+    const size_t P1 = c.P1, SL = 2 * P1, rowH = (size_t)A * GL_H * 4, rowE = (size_t)A * GL_E * 4, maxp = (size_t)c.maxp;
+    const size_t o_h = c.place((size_t)(T + 1) * rowE), o_S = c.place((size_t)T * rowH),
+                 o_q = c.place((size_t)(T + 1) * A * 4), o_P = c.place(rowH), o_R = c.place(rowH), o_Yb = c.place(rowH), o_Yc = c.place(rowH),
+                 o_dS = c.place(rowH), o_partP = c.place(maxp * rowH), o_partR = c.place(maxp * rowH),
+                 o_slotP = c.place(SL * GL_H * 4), o_slotR = c.place(SL * GL_H * 4), o_slotq = c.place(SL * 4), o_gE = c.place(P1 * GL_E * 4),
+                 o_gh = c.place(rowE), o_ghp = c.place(rowE), o_slotx = c.place(SL * 72), o_share = c.place((size_t)A * 48),
+                 o_out = c.place(((size_t)A * 5 + 1 + (size_t)B * 9) * 4);
+    if (gl_call_fill(h, gl, c, gl->in.cap)) return 1;
+    const int np = c.np;
+    const unsigned nt = c.nt, gP = (unsigned)np, gA = c.gA;
+    const GlGeom &G = c.G;
+    const GlPairs &L = c.L;
+    const int *inc = c.inc;
+    const float *d_x = c.d_x, *d_Q = c.d_Q, *d_g = c.d_extra[0];
+    float *hck = c.fp(o_h), *Sck = c.fp(o_S), *qck = c.fp(o_q), *dP = c.fp(o_P), *dR = c.fp(o_R), *Yb = c.fp(o_Yb), *Yc = c.fp(o_Yc),
+          *dS = c.fp(o_dS), *partP = c.fp(o_partP), *partR = c.fp(o_partR), *slotP = c.fp(o_slotP), *slotR = c.fp(o_slotR),
+          *slotq = c.fp(o_slotq), *gE = c.fp(o_gE), *gh = c.fp(o_gh), *ghp = c.fp(o_ghp), *out = c.fp(o_out);
     const size_t nH = (size_t)A * GL_H, nE = (size_t)A * GL_E;
-    const unsigned nt = (unsigned)tasks.size(), gP = (unsigned)np;
     const dim3 w64(64);
-    // ---- forward with checkpoints
-    for (int t = 0; t < T; ++t) {
-        const float *ht = t ? hck + t * nE : nullptr;
-        hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, gl->msg[t], G, d_x, ht, (const float *)nullptr, d_Q, dP, dR, Yb, Yc);
-        hipLaunchKernelGGL(k_gl_sweep<0>, dim3(nt), w64, 0, h->stream, d_tasks, d_moff, A, gl->msg[t].W2, (const float *)dP, (const float *)dR,
-                           (const float *)Yb, (const float *)nullptr, partP, (int)nt, 1, (float *)nullptr);
-        if (np > 0)
-            hipLaunchKernelGGL(k_gl_gnn_pair<0>, dim3(gP), w64, 0, h->stream, gl->msg[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)nullptr, slotP, (float *)nullptr, (float *)nullptr, GlTape{});
-        hipLaunchKernelGGL(k_gl_gnn_tail, dim3(A), w64, 0, h->stream, gl->msg[t], gl->upd, G, inc, (const float *)partP, (const float *)slotP,
-                           (const float *)dP, ht, Sck + t * nH, hck + (t + 1) * nE);
-    }
-    HIPCHK(hipGetLastError());
+    if (gl_forward_ckpt(h, c, gl->msg, gl->pas, gl->upd, hck, Sck, qck, dP, dR, Yb, Yc, partP, slotP, slotq)) return 1;
     const float *feats = hck + T * nE;
-    hipLaunchKernelGGL(k_gl_q0, dim3(gA), dim3(256), 0, h->stream, G, d_Q, qck);
-    for (int t = 0; t < T; ++t) {
-        hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, gl->pas[t], G, d_x, feats, (const float *)(qck + (size_t)t * A), d_Q, dP, dR,
-                           (float *)nullptr, (float *)nullptr);
-        if (np > 0)
-            hipLaunchKernelGGL(k_gl_epn_pair<0>, dim3(gP), w64, 0, h->stream, gl->pas[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)nullptr, slotq, (float *)nullptr, (float *)nullptr, (float *)nullptr, GlTape{});
-        hipLaunchKernelGGL(k_gl_epn_atom, dim3(gA), dim3(256), 0, h->stream, A, inc, (const float *)slotq, (const float *)(qck + (size_t)t * A),
-                           qck + (size_t)(t + 1) * A);
-    }
-    HIPCHK(hipGetLastError());
     // ---- backward: EPN stack
     float *gq = out;                                             // [A] gq | [A] q | [A][3] gxyz | bad | [B][9] gstrain
     float *q_fin = out + A, *gx = out + 2 * (size_t)A;
@@ -245,9 +81,9 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
                                    (const float *)dS, (float *)nullptr, (float *)nullptr, gE, GlTape{});
             break;
         }
-        hipLaunchKernelGGL(k_gl_sweep<1>, dim3(nt), w64, 0, h->stream, d_tasks, d_moff, A, gl->msg[t].W2, (const float *)dP, (const float *)dR,
+        hipLaunchKernelGGL(k_gl_sweep<1>, dim3(nt), w64, 0, h->stream, c.d_tasks, c.d_moff, A, gl->msg[t].W2, (const float *)dP, (const float *)dR,
                            (const float *)Yb, (const float *)dS, partP, (int)nt, 1, (float *)nullptr);
-        hipLaunchKernelGGL(k_gl_sweep<2>, dim3(nt), w64, 0, h->stream, d_tasks, d_moff, A, gl->msg[t].W2, (const float *)dR, (const float *)dP,
+        hipLaunchKernelGGL(k_gl_sweep<2>, dim3(nt), w64, 0, h->stream, c.d_tasks, c.d_moff, A, gl->msg[t].W2, (const float *)dR, (const float *)dP,
                            (const float *)Yc, (const float *)dS, partR, (int)nt, 1, (float *)nullptr);
         if (np > 0)
             hipLaunchKernelGGL(k_gl_gnn_pair<1>, dim3(gP), w64, 0, h->stream, gl->msg[t], L, (const float *)dP, (const float *)dR,
@@ -258,16 +94,16 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
     }
     HIPCHK(hipGetLastError());
     // ---- edges -> coordinates
-    double *slotx = reinterpret_cast<double *>(dw + o_slotx), *share = gstrain_out ? reinterpret_cast<double *>(dw + o_share) : nullptr;
+    double *slotx = reinterpret_cast<double *>(c.dw + o_slotx), *share = gstrain_out ? reinterpret_cast<double *>(c.dw + o_share) : nullptr;
     if (np > 0) {
         const unsigned gp = (unsigned)((np + 255) / 256);
         const double cut = (double)h->cfg.cutoff, eta = (double)h->cfg.eta;
-        if (cells) hipLaunchKernelGGL(k_gl_pair_xyz<2>, dim3(gp), dim3(256), 0, h->stream, L, np, d_molof, d_xyz, d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
-        else if (box) hipLaunchKernelGGL(k_gl_pair_xyz<1>, dim3(gp), dim3(256), 0, h->stream, L, np, d_molof, d_xyz, d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
-        else hipLaunchKernelGGL(k_gl_pair_xyz<0>, dim3(gp), dim3(256), 0, h->stream, L, np, d_molof, d_xyz, d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
+        if (cells) hipLaunchKernelGGL(k_gl_pair_xyz<2>, dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
+        else if (box) hipLaunchKernelGGL(k_gl_pair_xyz<1>, dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
+        else hipLaunchKernelGGL(k_gl_pair_xyz<0>, dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
     }
     hipLaunchKernelGGL(k_gl_atom_xyz, dim3(gA), dim3(256), 0, h->stream, A, inc, (const double *)slotx, gx, share);
-    if (share) hipLaunchKernelGGL(k_g_strain_mol, dim3((unsigned)B), dim3(64), 0, h->stream, (const double *)share, d_moff, gs);
+    if (share) hipLaunchKernelGGL(k_g_strain_mol, dim3((unsigned)B), dim3(64), 0, h->stream, (const double *)share, c.d_moff, gs);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(q_fin, qck + (size_t)T * A, (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));
     const size_t nback = (size_t)A * 4 + 1 + (gstrain_out ? (size_t)B * 9 : 0);

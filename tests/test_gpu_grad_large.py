@@ -386,3 +386,41 @@ def test_routing_below_the_threshold_is_the_dense_path(gpu_engine_factory):
     eng.set_option("grad_path", 2)
     q2, g2 = eng.charges_vjp_xyz(offsets, xyz, x, Q, g, 80)
     assert not np.array_equal(g2, g1)
+
+
+def test_three_entries_share_one_handle(gpu_engine_factory):
+    """The gradient call, the JVP and the pair-list train step share the handle's GradLarge buffers: a smaller call after a larger
+    one, and one entry after another, see nothing of the previous call.  Four calls on one engine against the same four on a fresh
+    engine each: every output bit and the listed pairs."""
+    from test_gpu_train_cell import _batch as _train_batch, _periodic_case
+    nx, w, mols, cells, N = _periodic_case("batch")
+    t_off, t_xyz, t_x, t_Q, t_y, t_cell = _train_batch(mols, cells)
+    big, small = _lattice_molecule(300, nx, seed=300), _lattice_molecule(17, nx, seed=17)
+    rng = np.random.default_rng(12)
+    g300, g17, v17 = (rng.normal(size=s).astype(np.float32) for s in (300, 17, (17, 3)))
+
+    def vjp(eng, mol, g, N):
+        return eng.charges_vjp_xyz(np.int32([0, len(g)]), mol[0], mol[1], np.float32([mol[2]]), g, N)
+
+    def step(eng):
+        q, loss = eng.train_step_xyz(t_off, t_xyz, t_x, t_Q, t_y, N, apply=False, cell=t_cell)
+        return q, np.float32(loss), eng.get_gradients()
+
+    calls = [lambda e: vjp(e, big, g300, 300),
+             lambda e: e.charges_jvp_xyz(np.int32([0, 17]), small[0], small[1], np.float32([small[2]]), 24, v=v17, dQ=1.0),
+             step,
+             lambda e: vjp(e, small, g17, 24)]
+
+    def engine():
+        eng = _engine(gpu_engine_factory, w, nx)
+        eng.set_option("train_path", 2)
+        eng.train_init()
+        return eng
+
+    shared = engine()
+    for k, call in enumerate(calls):
+        got, pairs = call(shared), int(shared.last_stats()[0])
+        fresh = engine()
+        want = call(fresh)
+        assert pairs == int(fresh.last_stats()[0]) and pairs > 0, k
+        assert len(got) == len(want) and all(np.array_equal(a, b) for a, b in zip(got, want)), k
