@@ -38,6 +38,8 @@ SIGNATURES = {
     "epnn_create_fused": (C.c_int, [C.POINTER(EpnnConfig), C.c_int, C.POINTER(_vp)]),
     "epnn_destroy": (C.c_int, [_vp]),
     "epnn_skip_hw_queues": (C.c_int, [C.c_int, C.c_int]),
+    "epnn_stream_class": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "epnn_pick_stream_class": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int]),
     "epnn_set_weights": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "epnn_get_weights": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "epnn_weight_shape": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip]),
@@ -142,6 +144,8 @@ def load():
     # process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, one of them the null stream's): kernels of
     # streams that share a queue serialise.  Ask for 16 unless the caller decided otherwise (six batches in flight, and an
     # RCCL communicator in the same process takes queues of its own: with 8 the pipeline loses 15 %); read when HIP initialises.
+    # Where the caller did decide, on fewer queues than handles, epnn_create spreads the handles' streams over the runtime's
+    # priority classes, each of which has that many queues of its own (include/epnn.h at epnn_create; Engine.stream_class()).
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     try:
         lib = C.CDLL(LIB_PATH)

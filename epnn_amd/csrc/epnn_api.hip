@@ -1,7 +1,10 @@
 // C ABI of libepnn_hip.so (see include/epnn.h).  gfx950 only.
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
+#include <map>
 #include <mutex>
 #include <numeric>
 #include <sched.h>
@@ -53,15 +56,19 @@ extern "C" int epnn_destroy(epnn_handle *h);
 static void xyz_grad_release(epnn_handle *h);   // epnn_api_grad.hip.h
 static void grad_large_release(epnn_handle *h);
 
-// The HIP runtime maps a process's streams round-robin onto its hardware queues (GPU_MAX_HW_QUEUES of them) in the order the
-// streams are created, and which queues a pipeline's lanes sit on matters: eight lanes on every other queue run the bench batch at
+// The HIP runtime maps a process's streams round-robin onto its hardware queues in the order the streams are created -- onto the
+// queues of the stream's PRIORITY CLASS: it keeps one pool of up to GPU_MAX_HW_QUEUES queues for each of low, normal and high
+// priority -- and which queues a pipeline's lanes sit on matters: eight lanes on every other queue run the bench batch at
 // 220 M atoms/s, on eight consecutive queues at 213 M (round 4, measured both ways several times).  A caller that builds several
-// handles can therefore leave queues out between them: n placeholder streams are created here and kept in a process-level list;
-// n == 0 destroys every placeholder made so far on `device` (engine.Pipeline.close does: a long-lived process that builds many
-// pipelines does not accumulate them).  The placement is only defined for the FIRST pipeline a process builds -- later streams
-// land wherever the runtime's round robin has got to.
+// handles can therefore leave queues out between them: n placeholder streams (normal priority) are created here and kept in a
+// process-level list; n == 0 destroys every placeholder made so far on `device` (engine.Pipeline.close does: a long-lived process
+// that builds many pipelines does not accumulate them).  The placement within a class is only defined for the FIRST pipeline a
+// process builds -- later streams land wherever the runtime's round robin has got to.
+// Which class a handle's stream goes to is decided from g_class_live, the live streams per device and class (the placeholders
+// count as normal ones): epnn_host.h pick_stream_class, profiles/r11_lane_queues.txt.
 static std::mutex g_skip_mutex;
 static std::vector<std::pair<int, hipStream_t>> g_skip_streams;
+static std::map<int, std::array<int, 3>> g_class_live;       // device -> live streams of class 0 normal, 1 high, 2 low
 extern "C" int epnn_skip_hw_queues(int device, int n) {
     if (n < 0 || n > 64) EPNN_FAIL("epnn_skip_hw_queues: n must be in 0..64");
     HIPCHK(hipSetDevice(device));
@@ -71,6 +78,7 @@ extern "C" int epnn_skip_hw_queues(int device, int n) {
             if (g_skip_streams[k].first != device) { ++k; continue; }
             (void)hipStreamDestroy(g_skip_streams[k].second);
             g_skip_streams.erase(g_skip_streams.begin() + (long)k);
+            --g_class_live[device][0];
         }
         return 0;
     }
@@ -78,7 +86,57 @@ extern "C" int epnn_skip_hw_queues(int device, int n) {
         hipStream_t s;
         HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));      // (never used: it only holds its place)
         g_skip_streams.emplace_back(device, s);
+        ++g_class_live[device][0];
     }
+    return 0;
+}
+
+extern "C" int epnn_pick_stream_class(const int live[3], int limit, int nclasses) {
+    if (!live) return 0;
+    return pick_stream_class(live, limit, nclasses);
+}
+// queues per priority class, as the runtime reads it: the integer of GPU_MAX_HW_QUEUES, HIP's default of 4 without one.  Read ONCE,
+// like the runtime does when it starts: a process that changes the variable later does not change the runtime's pools either.
+static int hw_queue_limit() {
+    static const int limit = [] {
+        const char *v = getenv("GPU_MAX_HW_QUEUES");
+        if (!v || !*v) return 4;
+        char *end = nullptr;
+        const long q = strtol(v, &end, 10);
+        if (end == v || *end != '\0') return 4;
+        return (int)std::min(std::max(q, 1L), 1L << 20);
+    }();
+    return limit;
+}
+// The handle's stream, in the priority class pick_stream_class gives it (EPNN_STREAM_CLASSES=0: normal, as every stream was before).
+static int create_handle_stream(epnn_handle *h) {
+    int least = 0, greatest = 0;
+    const char *sw = getenv("EPNN_STREAM_CLASSES");
+    const bool on = !(sw && !strcmp(sw, "0"));
+    if (on) HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    // "normal" is HIP's default stream priority, 0: what hipStreamCreateWithFlags gives a stream and what the range's two ends are
+    // numbered around (greatest < 0 < least where the device has the levels); an end equal to 0 is no class of its own
+    int cls_of[3] = {0, 0, 0}, prio_of[3] = {0, 0, 0}, ncls = 1;          // the classes this device has, in the order they are tried
+    if (on && greatest != 0) { cls_of[ncls] = 1; prio_of[ncls] = greatest; ++ncls; }
+    if (on && least != 0 && least != greatest) { cls_of[ncls] = 2; prio_of[ncls] = least; ++ncls; }
+    std::lock_guard<std::mutex> lock(g_skip_mutex);
+    std::array<int, 3> &tab = g_class_live[h->device];
+    // one place of the normal class is the process's own: the null stream (the synchronous copies of epnn_create and the weight
+    // uploads run on it) holds a normal hardware queue, so the handles count from one there (profiles/r11_lane_queues.txt, 2a / 2g)
+    const int live[3] = {tab[cls_of[0]] + 1, tab[cls_of[1]], tab[cls_of[2]]};
+    const int k = pick_stream_class(live, hw_queue_limit(), ncls);
+    if (cls_of[k] == 0) HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    else HIPCHK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_of[k]));
+    h->stream_cls = cls_of[k];
+    h->stream_counted = true;
+    ++tab[h->stream_cls];
+    return 0;
+}
+extern "C" int epnn_stream_class(epnn_handle *h, int *cls, int *priority) {
+    if (!h || !cls || !priority) EPNN_FAIL("epnn_stream_class: null argument");
+    HIPCHK(hipSetDevice(h->device));
+    *cls = h->stream_cls;
+    HIPCHK(hipStreamGetPriority(h->stream, priority));
     return 0;
 }
 
@@ -122,7 +180,7 @@ static int create_impl(const epnn_config *cfg, int device, epnn_handle **out, in
 }
 static int create_resources(epnn_handle *h) {
     const epnn_config *cfg = &h->cfg;
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if (create_handle_stream(h)) return 1;
     HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     HIPCHK(hipEventCreate(&h->ev_t0));
@@ -277,6 +335,10 @@ extern "C" int epnn_destroy(epnn_handle *h) {
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->stream2) (void)hipStreamDestroy(h->stream2);
     if (h->stream) (void)hipStreamDestroy(h->stream);
+    if (h->stream_counted) {                     // its place in its priority class is free again (create_handle_stream)
+        std::lock_guard<std::mutex> lock(g_skip_mutex);
+        --g_class_live[h->device][h->stream_cls];
+    }
     delete h;
     return 0;
 }

@@ -95,12 +95,33 @@ struct Plan {                 // what the host derives from `offsets`
     bool valid = false;
 };
 
+// Which stream priority class the next handle's stream is created in (epnn_api.hip: create_resources; include/epnn.h at epnn_create).
+// The HIP runtime keeps one pool of at most GPU_MAX_HW_QUEUES hardware queues PER priority class, and kernels of streams that share
+// a queue serialise: a process with few queues per class gives its handles queues of their own by spreading them over the classes.
+// live[c] = live streams of class c, the classes in the order they are tried (normal, high, low; only the first `nclasses` exist);
+// limit = queues per class.  The first class with a free queue; with every class full the one with the fewest streams, the
+// earlier one on a tie (the sharing of one pool, spread evenly).  Pure: no HIP calls (tests/test_stream_classes.py).
+static inline int pick_stream_class(const int live[3], int limit, int nclasses) {
+    if (limit < 1) limit = 1;
+    if (nclasses < 1) nclasses = 1;
+    if (nclasses > 3) nclasses = 3;
+    for (int c = 0; c < nclasses; ++c)
+        if (live[c] < limit) return c;
+    int best = 0;
+    for (int c = 1; c < nclasses; ++c)
+        if (live[c] < live[best]) best = c;
+    return best;
+}
+
 struct epnn_handle {
     epnn_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
+    int stream_cls = 0;               // its priority class: 0 normal, 1 high, 2 low (pick_stream_class above)
+    bool stream_counted = false;      // ... and it holds a place in the process's table of live streams per class (epnn_destroy gives it back)
     hipStream_t stream2 = nullptr;    // side stream of a lone handle (the launch of the 33..64-atom molecules beside the others'), forked / joined by
-                                      // events; created at its first use
+                                      // events; created at its first use.  Always of normal priority and not counted in the
+                                      // table of streams per class: only lone handles have one, the placement is about pipelines
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
     std::vector<hipEvent_t> evpool;   // 4 stage events per profiled forward ("profile" option = pool size)

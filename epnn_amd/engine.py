@@ -547,6 +547,13 @@ class Engine:
         check(self.lib.epnn_timing_at(self.h, int(idx), fptr(out)), self.lib)
         return out
 
+    def stream_class(self):
+        """(class, priority) of the handle's stream: class 0 normal, 1 high, 2 low -- where epnn_create placed it so that handles
+        used side by side get a hardware queue each (include/epnn.h) --, priority as the HIP runtime reports it."""
+        cls, prio = C.c_int(), C.c_int()
+        check(self.lib.epnn_stream_class(self.h, C.byref(cls), C.byref(prio)), self.lib)
+        return cls.value, prio.value
+
     def last_stats(self):
         out = np.zeros(4, dtype=np.int64)
         check(self.lib.epnn_last_stats(self.h, out.ctypes.data_as(C.POINTER(C.c_int64))), self.lib)
@@ -559,7 +566,13 @@ class Pipeline:
     (8 per CU), so one batch of 1024 molecules fills half the machine and its largest molecules finish long after
     the smallest: the wavefronts of the next batches fill those slots.  A launch lasts as long as its largest molecule
     (~3x the mean under load), so six to ten batches in flight keep every slot busy (default 8); each needs its own hardware queue
-    (GPU_MAX_HW_QUEUES, raised to 16 in _lib.load(); with the runtime's default of 4 use depth 3).
+    (GPU_MAX_HW_QUEUES, raised to 16 in _lib.load() unless the caller set it).  Where the caller did set it, to fewer queues than
+    lanes, the library spreads the lanes' streams over the runtime's stream priority classes, each of which has that many queues of
+    its own: with 4, eight lanes are 3 normal + 4 high + 1 low (one normal queue is the null stream's), fourteen 3 + 4 + 4 and
+    three that share (include/epnn.h at epnn_create, `Engine.stream_class()`, switch EPNN_STREAM_CLASSES=0).
+    A process that shares its GPU with other jobs should set the switch: queue priority counts across processes.
+    Lanes of different classes are served in priority
+    order, so lanes may finish in another order than they were called; `map` collects in call order and results do not change.
     All handles carry the same weights.  Results of call k are complete after `sync()`."""
 
     def __init__(self, depth=8, queue_stride=None, **engine_kwargs):

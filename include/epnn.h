@@ -87,9 +87,36 @@ int epnn_create(const epnn_config *cfg, int device, epnn_handle **out);
  * so; the weight entries work as ever.  With nx <= 10 the handle is epnn_create's. */
 int epnn_create_fused(const epnn_config *cfg, int device, epnn_handle **out);
 int epnn_destroy(epnn_handle *h);
-/* Leaves out `n` of the process's hardware queues: the HIP runtime deals a process's streams onto its hardware queues in the order
- * they are created (every handle owns one stream), and a pipeline of several handles runs faster with its lanes on every other
- * queue (engine.Pipeline calls this between two handles; no counterpart in the reference, which runs one model call at a time). */
+/* WHERE A HANDLE'S STREAM RUNS.  Every handle owns one HIP stream, and handles used side by side (engine.Pipeline: a batch in
+ * flight per handle) only overlap on the GPU when their streams sit on different hardware queues: kernels of streams that share a
+ * queue serialise.  The HIP runtime keeps one pool of at most GPU_MAX_HW_QUEUES hardware queues (its default: 4) per stream
+ * PRIORITY CLASS -- normal, high, low -- so epnn_create places the stream by the process's count of live handle streams per
+ * device and class (the placeholders of epnn_skip_hw_queues count as normal ones; epnn_destroy and epnn_skip_hw_queues(device, 0)
+ * give their places back): with Q = the integer in GPU_MAX_HW_QUEUES (4 if unset or unparsable, at least 1) the classes are tried
+ * in the order normal, high, low and the first with fewer than Q live streams is taken; when all are full, the one with the fewest
+ * (normal first on a tie).  High / low are the `greatest` / `least` of hipDeviceGetStreamPriorityRange and exist only where they
+ * differ from the default priority; a device with one level keeps every stream normal.  One place of the normal class is counted
+ * for the process's null stream, which holds a normal hardware queue of its own (measured: four normal lanes share three queues).
+ * With Q = 4 eight handles become 3 normal + 4 high + 1 low, fourteen 3 + 4 + 4 and three that share; a process whose Q exceeds its
+ * handles and placeholders (this library's Python binding asks for 16 when the variable is unset) sees no change at all.  Never
+ * more than 3 Q queues per process.
+ * What a caller can see of it: lanes of different classes are served in priority order, so the order in which handles used side
+ * by side FINISH may differ from the order of the calls (engine.Pipeline.map collects in call order regardless); results do not
+ * change by a bit.  A stream's priority is the priority of its hardware queue, and the GPU's scheduler orders the queues of ALL
+ * processes on the device by it: a process that shares its GPU with other jobs takes precedence over their normal-priority work
+ * with its high lanes and yields to it with its low ones -- set EPNN_STREAM_CLASSES=0 there.  The side stream of a lone handle
+ * (33..64-atom molecules) stays normal and uncounted.
+ * Switch: the environment variable EPNN_STREAM_CLASSES, read when a handle is created; 0 = every stream normal, as before this
+ * placement existed; anything else, or unset, = on. */
+/* cls: 0 normal, 1 high, 2 low -- the class epnn_create chose; priority: what hipStreamGetPriority reports for the handle's stream. */
+int epnn_stream_class(epnn_handle *h, int *cls, int *priority);
+/* The rule above as a pure function (no GPU needed): live[c] = live streams of the c-th class in the order tried, of which
+ * the first `nclasses` (1..3) exist; limit = Q.  Returns the index of the class the next stream goes to. */
+int epnn_pick_stream_class(const int live[3], int limit, int nclasses);
+/* Leaves out `n` of the process's hardware queues: the HIP runtime deals a process's streams onto the hardware queues of their
+ * priority class in the order they are created, and a pipeline of several handles runs faster with its lanes on every other
+ * queue while there are twice as many queues as lanes (engine.Pipeline calls this between two handles; no counterpart in the
+ * reference, which runs one model call at a time).  The placeholders are normal-priority streams and hold places of that class. */
 int epnn_skip_hw_queues(int device, int n);
 
 /* model.load_weights / layer.set_weights (infer.py:57): one Dense layer of one MLP.
