@@ -386,6 +386,29 @@ class EPNNModel(_Stack):
         return self._eng().charges_jvp_xyz(offsets, xyz, x, Q, self.natom if N is None else N, v=v, strain=strain, dQ=dQ, box=box,
                                            cell=cell)
 
+    def charges_jvp_xyz_multi(self, offsets, xyz, x, Q, N=None, v=None, strain=None, dQ=None, box=None, cell=None):
+        """charges_jvp_xyz along K directions in one pass: (q (A,), tq (K, A)), row k with the bits of the single call on the k-th
+        slices.  v (K, A, 3), strain (K, 3, 3) or (K, B, 3, 3), dQ (K,) or (K, B); at least one, agreeing on K (1..16).  The
+        primal half of the work is paid once.  N defaults to the model's natom; box and cell as in predict_xyz."""
+        return self._eng().charges_jvp_xyz_multi(offsets, xyz, x, Q, self.natom if N is None else N, v=v, strain=strain, dQ=dQ,
+                                                 box=box, cell=cell)
+
+    def charge_strain_response(self, offsets, xyz, x, Q, N=None, box=None, cell=None):
+        """(q (A,), dq_deps (A, 3, 3)): the response of every charge to a homogeneous strain of coordinates and cell, from one
+        K = 6 forward-mode call on the symmetric unit strains (e_a e_b^T + e_b e_a^T) / 2, a <= b, filled in symmetrically:
+        (dq_deps[i] * E).sum() is dq_i along any symmetric strain E."""
+        pairs = [(a, b) for a in range(3) for b in range(a, 3)]
+        units = np.zeros((6, 3, 3), dtype=np.float32)
+        for k, (a, b) in enumerate(pairs):
+            units[k, a, b] += 0.5
+            units[k, b, a] += 0.5
+        q, tq = self.charges_jvp_xyz_multi(offsets, xyz, x, Q, N, strain=units, box=box, cell=cell)
+        out = np.empty((tq.shape[1], 3, 3), dtype=np.float32)
+        for k, (a, b) in enumerate(pairs):
+            out[:, a, b] = tq[k]
+            out[:, b, a] = tq[k]
+        return q, out
+
     def train_step_xyz(self, optimizer, offsets, xyz, x, Q, y, N=None, apply=True, box=None, cell=None):
         """One training step (loss = sum (y - q)^2 over the atoms, its gradient, one Adam step of `optimizer` unless apply=False) on a
         flat batch with reference charges y (A,): (q (A,), loss).  N defaults to the model's natom; box and cell as in predict_xyz:

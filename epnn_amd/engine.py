@@ -419,6 +419,58 @@ class Engine:
                                                  opt(strain), opt(dQ), fptr(q), fptr(tq)), self.lib)
         return q, tq
 
+    def charges_jvp_xyz_multi(self, offsets, xyz, x, Q, N, v=None, strain=None, dQ=None, box=None, cell=None):
+        """Forward mode along K directions in one pass (epnn_charges_jvp_multi_xyz_cell): (q (A,), tq (K, A)), row k being
+        charges_jvp_xyz's tq for the k-th slices, bit for bit, whatever K and the other rows are.  v (K, A, 3), strain (K, 3, 3)
+        or (K, B, 3, 3), dQ (K,) or (K, B); each may be None (= 0 for every direction), at least one must be given, and those
+        given must agree on K (1..16).  The primal, the pair list and every per-pair and per-atom primal statement run once;
+        box and cell as in charges_jvp_xyz."""
+        _one_periodic_argument(box, cell)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
+        B, A = len(offsets) - 1, int(offsets[-1])
+        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
+            raise EpnnError("charges_jvp_xyz_multi: array shapes do not match offsets")
+        Ks = {}
+        if v is not None:
+            v = _f32(v)
+            if v.ndim != 3 or v.shape[1:] != (A, 3):
+                raise ValueError(f"charges_jvp_xyz_multi: v must have shape (K, {A}, 3), got {v.shape}")
+            Ks["v"] = v.shape[0]
+        if strain is not None:
+            strain = np.asarray(strain, dtype=np.float32)
+            if strain.ndim == 3 and strain.shape[1:] == (3, 3):
+                strain = np.repeat(strain[:, None], B, axis=1)
+            if strain.ndim != 4 or strain.shape[1:] != (B, 3, 3):
+                raise ValueError(f"charges_jvp_xyz_multi: strain must have shape (K, 3, 3) or (K, {B}, 3, 3), got {strain.shape}")
+            strain = np.ascontiguousarray(strain)
+            Ks["strain"] = strain.shape[0]
+        if dQ is not None:
+            dQ = np.asarray(dQ, dtype=np.float32)
+            if dQ.ndim == 1:
+                dQ = np.repeat(dQ[:, None], B, axis=1)
+            if dQ.ndim != 2 or dQ.shape[1] != B:
+                raise ValueError(f"charges_jvp_xyz_multi: dQ must have shape (K,) or (K, {B}), got {dQ.shape}")
+            dQ = np.ascontiguousarray(dQ)
+            Ks["dQ"] = dQ.shape[0]
+        if not Ks:
+            raise ValueError("charges_jvp_xyz_multi: give at least one of v, strain and dQ (they carry K)")
+        if len(set(Ks.values())) != 1:
+            raise ValueError("charges_jvp_xyz_multi: the tangents disagree on K: " + ", ".join(f"{k} has {n}" for k, n in Ks.items()))
+        K = next(iter(Ks.values()))
+        if box is not None:
+            box = _box_rows(box, B)
+            cell = np.zeros((B, 3, 3), dtype=np.float32)
+            cell[:, [0, 1, 2], [0, 1, 2]] = box
+        if cell is not None:
+            cell = _cell_rows(cell, B)
+        opt = lambda a: None if a is None else fptr(a)
+        q = np.empty((A,), dtype=np.float32)
+        tq = np.empty((max(K, 1), A), dtype=np.float32)
+        check(self.lib.epnn_charges_jvp_multi_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), opt(cell), int(K),
+                                                       opt(v), opt(strain), opt(dQ), fptr(q), fptr(tq)), self.lib)
+        return q, tq
+
     def get_gradients(self):
         g = np.empty((self.param_count(),), dtype=np.float32)
         check(self.lib.epnn_get_gradients(self.h, fptr(g), g.size), self.lib)

@@ -348,6 +348,35 @@ int epnn_charges_vjp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offse
 int epnn_charges_jvp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                               const float *cell, const float *vxyz, const float *vstrain, const float *vQ, float *q_out,
                               float *tq_out);
+/* ---- forward mode, K directions in one pass: epnn_charges_jvp_xyz_cell with K tangents beside one primal.  K is in 1..16 (any
+ * other value is refused by name; the handle stays usable).  vxyz[K][A][3], vstrain[K][B][3][3], vQ[K][B]: each may be NULL (= 0 for
+ * every tangent; all three NULL gives tq = 0).  q_out[A] is computed once; tq_out[K][A]: row k has exactly the definition of
+ * epnn_charges_jvp_xyz_cell's tq_out for the k-th slices -- six unit strains give the full strain response dq_i/d eps_ab in one call,
+ * three Cartesian directions (or one per normal mode) a dipole derivative, 3 n directions a forward-mode Jacobian of a molecule.
+ * Contract: that of epnn_charges_jvp_xyz_cell, word for word: the pair-list path whatever "grad_path" says; works on a handle that
+ * never trained, uses the current weights, leaves weights, gradients, Adam state and step count untouched, waits first for a
+ * "train_async" step in flight; refuses by name update layers other than [32, 32], a partitioned handle, bad offsets, a molecule
+ * that does not fit N, null xyz / x / Q / outputs, coincident atoms or images (the handle stays usable); h_dim below 48 runs
+ * zero-padded; no float atomics and every sum in a fixed order; a molecule's rows do not depend on the rest of the batch at the
+ * same N.
+ * Bits: q_out has the bits of epnn_charges_jvp_xyz_cell (and so of the pair-list gradient path), and row k of tq_out the bits that
+ * entry gives for tangent k alone: every tangent statement is the single-tangent kernel's, looped over the tangents (the same MFMA
+ * order per tangent, the same pieces, slot order and closed-form padded term).  A row therefore does not depend on K, on its
+ * position, or on what the other rows hold.
+ * Cost: the front-end, the pair list, the primal projections, pair and atom kernels run once; the all-pairs sweep carries the
+ * tangents in chunks of 4, 2 or 1 (the widest that fits what is left: K = 7 is 4 + 2 + 1) and each chunk's launch repeats the 16
+ * primal MFMAs per partner for its masks: sum over chunks of (16 + 16 kc) MFMAs per partner and tile against 32 K for K single
+ * calls; measured, a K = 4 call on a 10 000-atom cell takes 0.68 of four single calls, while on batches of small molecules K single
+ * calls are faster from K = 4 on (profiles/r12_jvp_multi.txt).  Device scratch: the tangent rows (te, th, tP, tR, the sweep's
+ * tangent pieces, the tangent slots, tq) are K times the single call's, the primal rows and the pair list are not multiplied:
+ *     bytes = A (940 + 4 nx + 129 pieces + K (652 + 128 pieces)) + (524 + 456 K) listed pairs + 13 KB
+ *                                                              (12 K A more with vxyz; +- 256 per buffer of rounding)
+ * which at K = 1 is epnn_charges_jvp_xyz_cell's formula.  Shared with the gradient and single-tangent calls: the handle keeps the
+ * scratch of its largest call.  After a call epnn_last_stats gives out[0] = listed pairs, out[1] = 0, out[2] = bytes of device
+ * scratch the call used. */
+int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                    const float *cell, int K, const float *vxyz, const float *vstrain, const float *vQ, float *q_out,
+                                    float *tq_out);
 /* ---- training on periodic and large systems.  epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
  * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
  * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's
