@@ -40,6 +40,7 @@ SIGNATURES = {
     "epnn_skip_hw_queues": (C.c_int, [C.c_int, C.c_int]),
     "epnn_stream_class": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "epnn_pick_stream_class": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "epnn_reserve_null_stream": (C.c_int, [C.c_int, C.c_int]),
     "epnn_set_weights": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "epnn_get_weights": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "epnn_weight_shape": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip]),
@@ -142,7 +143,7 @@ def load():
         raise EpnnError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). There is no CPU fallback for the EPNN hot path.")
     # Several handles (= HIP streams) keep batches in flight concurrently (engine.Pipeline).  The HIP runtime maps a
-    # process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, one of them the null stream's): kernels of
+    # process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4 per stream priority class): kernels of
     # streams that share a queue serialise.  Ask for 16 unless the caller decided otherwise (six batches in flight, and an
     # RCCL communicator in the same process takes queues of its own: with 8 the pipeline loses 15 %); read when HIP initialises.
     # Where the caller did decide, on fewer queues than handles, epnn_create spreads the handles' streams over the runtime's

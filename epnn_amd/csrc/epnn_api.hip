@@ -65,10 +65,29 @@ static void grad_large_release(epnn_handle *h);
 // that builds many pipelines does not accumulate them).  The placement within a class is only defined for the FIRST pipeline a
 // process builds -- later streams land wherever the runtime's round robin has got to.
 // Which class a handle's stream goes to is decided from g_class_live, the live streams per device and class (the placeholders
-// count as normal ones): epnn_host.h pick_stream_class, profiles/r11_lane_queues.txt.
+// count as normal ones), and from the place kept for the process's null stream (g_null_place): epnn_host.h pick_stream_class,
+// profiles/r11_lane_queues.txt, profiles/r13_null_stream.txt.
 static std::mutex g_skip_mutex;
 static std::vector<std::pair<int, hipStream_t>> g_skip_streams;
 static std::map<int, std::array<int, 3>> g_class_live;       // device -> live streams of class 0 normal, 1 high, 2 low
+static std::map<int, int> g_null_place;                      // device -> what epnn_reserve_null_stream said (no entry: the environment decides)
+// The place of the normal class kept free for the process's null stream on `device`: 1 where the process uses that stream (the
+// runtime gives it a normal hardware queue at its first use: hipMemcpy, hipMemset, a launch without a stream, PyTorch's default
+// stream; not hipFree, hipEventSynchronize or hipDeviceSynchronize: tools/micro/null_stream_queue.hip), 0 where nothing does -- this library never does (epnn_host.h copy_sync).  No HIP call: it may
+// be the first thing a process says.  It is read when a handle's stream is created; streams that exist are not moved.
+extern "C" int epnn_reserve_null_stream(int device, int on) {
+    if (device < 0) EPNN_FAIL("epnn_reserve_null_stream: device must be >= 0");
+    if (on != 0 && on != 1) EPNN_FAIL("epnn_reserve_null_stream: on must be 0 or 1");
+    std::lock_guard<std::mutex> lock(g_skip_mutex);
+    g_null_place[device] = on;
+    return 0;
+}
+static int null_stream_place(int device) {                   // (g_skip_mutex held)
+    const auto it = g_null_place.find(device);
+    if (it != g_null_place.end()) return it->second;
+    const char *v = getenv("EPNN_NULL_STREAM_PLACE");
+    return v && !strcmp(v, "1") ? 1 : 0;
+}
 extern "C" int epnn_skip_hw_queues(int device, int n) {
     if (n < 0 || n > 64) EPNN_FAIL("epnn_skip_hw_queues: n must be in 0..64");
     HIPCHK(hipSetDevice(device));
@@ -121,9 +140,10 @@ static int create_handle_stream(epnn_handle *h) {
     if (on && least != 0 && least != greatest) { cls_of[ncls] = 2; prio_of[ncls] = least; ++ncls; }
     std::lock_guard<std::mutex> lock(g_skip_mutex);
     std::array<int, 3> &tab = g_class_live[h->device];
-    // one place of the normal class is the process's own: the null stream (the synchronous copies of epnn_create and the weight
-    // uploads run on it) holds a normal hardware queue, so the handles count from one there (profiles/r11_lane_queues.txt, 2a / 2g)
-    const int live[3] = {tab[cls_of[0]] + 1, tab[cls_of[1]], tab[cls_of[2]]};
+    // a process that uses its null stream has a normal hardware queue held by it, and the handles count from one there
+    // (profiles/r11_lane_queues.txt, 2a / 2g).  The library itself stays off that stream, so the place is the caller's to ask for
+    // (epnn_reserve_null_stream / EPNN_NULL_STREAM_PLACE=1); without it every normal queue takes a lane (profiles/r13_null_stream.txt)
+    const int live[3] = {tab[cls_of[0]] + null_stream_place(h->device), tab[cls_of[1]], tab[cls_of[2]]};
     const int k = pick_stream_class(live, hw_queue_limit(), ncls);
     if (cls_of[k] == 0) HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     else HIPCHK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_of[k]));
@@ -201,14 +221,14 @@ static int create_resources(epnn_handle *h) {
     for (int k = 0; k < ME; ++k) mu[k] = (double)k * step + start;
     if (ME > 1) mu[ME - 1] = stop;
     if (h->d_mu.ensure(mu.size() * sizeof(double))) return 1;
-    HIPCHK(hipMemcpy(h->d_mu.p, mu.data(), mu.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (copy_sync(h, h->d_mu.p, mu.data(), mu.size() * sizeof(double), hipMemcpyHostToDevice)) return 1;
     shape_layers(h);
     {
         std::vector<float> tab;
         h->edge_res = cfg->e_dim == EPNN_EDIM ? edge_basis(h->cfg, mu, h->edge_B, tab) : 1.0;
         if (!tab.empty()) {
             if (h->d_etab.ensure(tab.size() * sizeof(float))) return 1;
-            HIPCHK(hipMemcpy(h->d_etab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+            if (copy_sync(h, h->d_etab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice)) return 1;
         }
     }
     {   // dsafe: largest D up to which a lower bound of max_k e_k stays above 2 tol (every pair closer than that is a near
@@ -279,7 +299,7 @@ static int create_resources(epnn_handle *h) {
             h->nflip = (int)flips.size();
             flips.resize(EPNN_NFLIP_MAX, 1e300);
             if (h->d_flip.ensure(flips.size() * sizeof(double))) return 1;
-            HIPCHK(hipMemcpy(h->d_flip.p, flips.data(), flips.size() * sizeof(double), hipMemcpyHostToDevice));
+            if (copy_sync(h, h->d_flip.p, flips.data(), flips.size() * sizeof(double), hipMemcpyHostToDevice)) return 1;
         }
     }
     return 0;

@@ -381,7 +381,7 @@ extern "C" int epnn_mlp_forward_layers(epnn_handle *h, int rows, int n_layers, c
 extern "C" int epnn_debug_stamps(epnn_handle *h, unsigned long long *out, size_t count) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, h->l_nm.p, count * 8, hipMemcpyDeviceToHost));
+    if (copy_sync(h, out, h->l_nm.p, count * 8, hipMemcpyDeviceToHost)) return 1;
     return 0;
 }
 #endif

@@ -79,7 +79,7 @@ static int grad_large_weights(epnn_handle *h, GradLarge *gl) {
     for (int l = 0; l < 3; ++l) { ou[2 * l] = put(h->upd[l].W); ou[2 * l + 1] = put(h->upd[l].b); }
     HIPCHK(hipStreamSynchronize(h->stream));                      // (no call of this path is in flight: they all end with a wait)
     if (gl->w.ensure(flat.size() * 4)) return 1;
-    HIPCHK(hipMemcpy(gl->w.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
+    if (copy_sync(h, gl->w.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice)) return 1;
     const float *base = gl->w.as<float>();
     for (int t = 0; t < T; ++t) {
         gl_point_pair(gl->msg[t], base, om[t][0], om[t][1], om[t][2], om[t][3], om[t][4], om[t][5], F);

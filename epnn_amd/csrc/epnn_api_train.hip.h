@@ -556,7 +556,7 @@ extern "C" int epnn_comm_allreduce(epnn_handle *h, double *inout, int32_t n, int
 extern "C" int epnn_debug_large_clocks(epnn_handle *h, unsigned long long *dst, int n) {
     if (!h || !dst || !h->lg_clk.p) EPNN_FAIL("epnn_debug_large_clocks: bad argument");
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(dst, h->lg_clk.p, (size_t)std::min(n, 128 + 4 * 1024) * 8, hipMemcpyDeviceToHost));
+    if (copy_sync(h, dst, h->lg_clk.p, (size_t)std::min(n, 128 + 4 * 1024) * 8, hipMemcpyDeviceToHost)) return 1;
     return 0;
 }
 #endif
@@ -566,7 +566,7 @@ extern "C" int epnn_debug_train_clocks(epnn_handle *h, unsigned long long *dst, 
     if (!h || !dst || !h->train) EPNN_FAIL("epnn_debug_train_clocks: bad argument");
     TrainState *ts = train_state(h);
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(dst, ts->clk.p, (size_t)std::min(n, 64 * 16) * 8, hipMemcpyDeviceToHost));
+    if (copy_sync(h, dst, ts->clk.p, (size_t)std::min(n, 64 * 16) * 8, hipMemcpyDeviceToHost)) return 1;
     return 0;
 }
 #endif
@@ -577,12 +577,12 @@ extern "C" int epnn_debug_pairs(epnn_handle *h, int32_t *pi, int32_t *pj, float 
     if (finish_forward(h)) return 1;
     if (!h->plan.valid || !h->d_rowoff.p || !h->d_pi.p) EPNN_FAIL("epnn_debug_pairs: no pair list (the last forward used the in-kernel front-end)");
     int np = 0;
-    HIPCHK(hipMemcpy(&np, h->d_rowoff.as<int>() + h->plan.A, sizeof(int), hipMemcpyDeviceToHost));
+    if (copy_sync(h, &np, h->d_rowoff.as<int>() + h->plan.A, sizeof(int), hipMemcpyDeviceToHost)) return 1;
     if (np < 0 || np > h->pcap) EPNN_FAIL("epnn_debug_pairs: the list holds %d pairs, capacity %d", np, h->pcap);
     const size_t n = (size_t)std::min<int64_t>(np, cap);
-    HIPCHK(hipMemcpy(pi, h->d_pi.p, n * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pj, h->d_pj.p, n * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pwi, h->d_pwi.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (copy_sync(h, pi, h->d_pi.p, n * sizeof(int), hipMemcpyDeviceToHost)) return 1;
+    if (copy_sync(h, pj, h->d_pj.p, n * sizeof(int), hipMemcpyDeviceToHost)) return 1;
+    if (copy_sync(h, pwi, h->d_pwi.p, n * sizeof(float), hipMemcpyDeviceToHost)) return 1;
     *count_out = np;
     return 0;
 }

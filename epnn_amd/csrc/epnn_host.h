@@ -283,6 +283,17 @@ struct epnn_handle {
     int opt_train_path = 0;           // epnn_train_step_xyz_cell: the same choice for a training step
 };
 
+// The library's synchronous copies: on the handle's OWN stream, waited for -- never hipMemcpy / hipMemset, which run on the
+// process's null stream (nor hipDeviceSynchronize: a handle waits for its own work only).  The runtime makes that stream, and the normal-priority hardware queue it holds, at its first
+// use; a process with few queues per class wants that queue for a lane (create_handle_stream; profiles/r13_null_stream.txt).
+// Pageable `src` / `dst` may go out of scope as soon as this returns.
+static inline int copy_sync(epnn_handle *h, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+    if (!bytes) return 0;
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, kind, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 // ---- fail-closed collectives.  RCCL has no timeout: a rank that leaves an entry point with an error BEFORE a collective its peers
 // have already enqueued leaves them blocked for good.  Every payload collective of this library (the gradient all-reduce of a train
 // step, the row exchange of a partitioned system) is therefore preceded by a 4-byte ncclAllReduce(max) of a status word on the same

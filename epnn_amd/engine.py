@@ -612,6 +612,14 @@ class Engine:
         return out
 
 
+def reserve_null_stream(device=0, on=True):
+    """Say that this process uses the null (default) stream of `device` -- PyTorch work on its default stream, hipMemcpy, a launch
+    without a stream: the runtime then holds one normal hardware queue for it, and the handles created AFTERWARDS leave that place
+    free (include/epnn.h, epnn_reserve_null_stream; the same as EPNN_NULL_STREAM_PLACE=1 in the environment).  No HIP call."""
+    lib = _lib.load()
+    check(lib.epnn_reserve_null_stream(int(device), 1 if on else 0), lib)
+
+
 class Pipeline:
     """Keeps `depth` batches in flight on one GPU: `depth` handles (each with its own HIP stream and workspace) take
     the calls round robin.  The fused kernel runs one wavefront per molecule and an MI355X holds 2048 of them
@@ -620,18 +628,28 @@ class Pipeline:
     (~3x the mean under load), so six to ten batches in flight keep every slot busy (default 8); each needs its own hardware queue
     (GPU_MAX_HW_QUEUES, raised to 16 in _lib.load() unless the caller set it).  Where the caller did set it, to fewer queues than
     lanes, the library spreads the lanes' streams over the runtime's stream priority classes, each of which has that many queues of
-    its own: with 4, eight lanes are 3 normal + 4 high + 1 low (one normal queue is the null stream's), fourteen 3 + 4 + 4 and
-    three that share (include/epnn.h at epnn_create, `Engine.stream_class()`, switch EPNN_STREAM_CLASSES=0).
+    its own (include/epnn.h at epnn_create, `Engine.stream_class()`, switch EPNN_STREAM_CLASSES=0).  A
+    pipeline keeps one place of the normal class for the process's null stream unless it is told otherwise (`null_stream_place`
+    below): with 4, eight lanes are 3 normal + 4 high + 1 low, fourteen 3 + 4 + 4 and three that share -- the placement that was
+    measured (profiles/r11_lane_queues.txt) and that tests/test_gpu_stream_classes.py holds a pipeline to.  The library itself
+    never uses the null stream, so a process that does not either can give the pipeline every normal queue: `null_stream_place=0`
+    or EPNN_NULL_STREAM_PLACE=0 make it 4 normal + 4 high, and 4 + 4 + 4 and two that share.
     A process that shares its GPU with other jobs should set the switch: queue priority counts across processes.
     Lanes of different classes are served in priority
     order, so lanes may finish in another order than they were called; `map` collects in call order and results do not change.
     All handles carry the same weights.  Results of call k are complete after `sync()`."""
 
-    def __init__(self, depth=8, queue_stride=None, **engine_kwargs):
+    def __init__(self, depth=8, queue_stride=None, null_stream_place=None, **engine_kwargs):
         """queue_stride: hardware queues from one lane's to the next (the HIP runtime deals streams onto its hardware queues in
         creation order).  Measured on MI355X: up to eight lanes run 3 % faster on every other queue (stride 2, the default there);
-        more lanes than that need every queue (stride 1)."""
+        more lanes than that need every queue (stride 1).
+        null_stream_place: 1 keeps one normal hardware queue free for the process's null stream, 0 does not (`reserve_null_stream`:
+        it holds for the device from here on).  None: what EPNN_NULL_STREAM_PLACE says; without the variable, 1."""
         depth = max(1, int(depth))
+        if null_stream_place is None and os.environ.get("EPNN_NULL_STREAM_PLACE") is None:
+            null_stream_place = 1
+        if null_stream_place is not None:
+            reserve_null_stream(int(engine_kwargs.get("device", 0)), bool(null_stream_place))
         if queue_stride is None:
             # every other queue only while the lanes still get a queue each: with a user-set GPU_MAX_HW_QUEUES of 4 or 8 a stride of
             # 2 would fold eight lanes onto 2 or 4 queues (kernels of streams that share a queue serialise)

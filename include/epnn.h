@@ -95,11 +95,15 @@ int epnn_destroy(epnn_handle *h);
  * give their places back): with Q = the integer in GPU_MAX_HW_QUEUES (4 if unset or unparsable, at least 1) the classes are tried
  * in the order normal, high, low and the first with fewer than Q live streams is taken; when all are full, the one with the fewest
  * (normal first on a tie).  High / low are the `greatest` / `least` of hipDeviceGetStreamPriorityRange and exist only where they
- * differ from the default priority; a device with one level keeps every stream normal.  One place of the normal class is counted
- * for the process's null stream, which holds a normal hardware queue of its own (measured: four normal lanes share three queues).
- * With Q = 4 eight handles become 3 normal + 4 high + 1 low, fourteen 3 + 4 + 4 and three that share; a process whose Q exceeds its
- * handles and placeholders (this library's Python binding asks for 16 when the variable is unset) sees no change at all.  Never
- * more than 3 Q queues per process.
+ * differ from the default priority; a device with one level keeps every stream normal.  With Q = 4 eight handles become 4 normal
+ * + 4 high, fourteen 4 + 4 + 4 and two that share; a process whose Q exceeds its handles and placeholders (this library's Python
+ * binding asks for 16 when the variable is unset) sees no change at all.  Never more than 3 Q queues per process.
+ * THE NULL STREAM'S PLACE.  A process that uses its null stream -- hipMemcpy, hipMemset, a kernel launched without a stream,
+ * PyTorch's default stream -- has a normal hardware queue held by that stream from its first use on (measured:
+ * four normal lanes then share three queues).  This library never uses it: every copy and launch of its own runs on a handle's
+ * stream.  A caller whose process does says so BEFORE it creates its first handle on the device, with epnn_reserve_null_stream
+ * (device, 1) or EPNN_NULL_STREAM_PLACE=1 in the environment: one place of the normal class is then left to the null stream and
+ * eight handles become 3 normal + 4 high + 1 low, fourteen 3 + 4 + 4 and three that share.
  * What a caller can see of it: lanes of different classes are served in priority order, so the order in which handles used side
  * by side FINISH may differ from the order of the calls (engine.Pipeline.map collects in call order regardless); results do not
  * change by a bit.  A stream's priority is the priority of its hardware queue, and the GPU's scheduler orders the queues of ALL
@@ -113,6 +117,11 @@ int epnn_stream_class(epnn_handle *h, int *cls, int *priority);
 /* The rule above as a pure function (no GPU needed): live[c] = live streams of the c-th class in the order tried, of which
  * the first `nclasses` (1..3) exist; limit = Q.  Returns the index of the class the next stream goes to. */
 int epnn_pick_stream_class(const int live[3], int limit, int nclasses);
+/* on = 1: this process uses the null stream of `device`, keep one place of the normal class for it (see above); on = 0: it does
+ * not (the default; overrides EPNN_NULL_STREAM_PLACE=1, which is read when a handle is created on a device this was never called
+ * for).  Makes no HIP call and may come before anything else.  It decides about the handles created afterwards: streams that
+ * exist stay where they are, so call it before the first epnn_create on that device. */
+int epnn_reserve_null_stream(int device, int on);
 /* Leaves out `n` of the process's hardware queues: the HIP runtime deals a process's streams onto the hardware queues of their
  * priority class in the order they are created, and a pipeline of several handles runs faster with its lanes on every other
  * queue while there are twice as many queues as lanes (engine.Pipeline calls this between two handles; no counterpart in the
