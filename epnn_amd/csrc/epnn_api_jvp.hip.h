@@ -1,123 +1,10 @@
-// epnn_charges_jvp_xyz_cell: charges and their directional derivative along (vxyz, vstrain, vQ) of a flat coordinate batch
-// (kernels and arithmetic: epnn_jvp.hip.h).  Part of the one translation unit epnn_api.hip.
+// epnn_charges_jvp_xyz_cell, epnn_charges_jvp_multi_xyz_cell: charges and their directional derivatives along K tangents
+// (vxyz, vstrain, vQ) of a flat coordinate batch (kernels and arithmetic: epnn_jvp.hip.h).  Part of the one translation unit
+// epnn_api.hip.
 #pragma once
 #include "epnn_jvp.hip.h"
 
-// The call shares the pair-list gradient path's state (GradLarge: the weights in plain Keras layout, refreshed when weights_gen
-// moves on, and the input / scratch buffers, which keep the size of the largest call of either kind): neither the training state
-// nor the forward's plan and pair list are touched.
-static int charges_jvp_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                            const EpnnCell *cells, const float *vxyz, const float *vstrain, const float *vQ, float *q_out,
-                            float *tq_out) {
-    const char *name = "epnn_charges_jvp_xyz_cell";
-    GradLarge *gl = grad_large_state(h);
-    if (grad_large_weights(h, gl)) return 1;
-    const int T = h->cfg.T, A = offsets[B];
-    // the tangents: vQ as zeros when null, vxyz and vstrain left out
-    const GlSpan spans[3] = {{vQ, (size_t)B * 4, true}, {vxyz, vxyz ? (size_t)A * 12 : 0, false}, {vstrain, vstrain ? (size_t)B * 36 : 0, false}};
-    GlCall c;
-    if (gl_call_count(h, gl, name, B, N, offsets, xyz, x, Q, nullptr, cells, spans, 3, c)) return 1;
-    const size_t P1 = c.P1, SL = 2 * P1, rowH = (size_t)A * GL_H * 4, rowE = (size_t)A * GL_E * 4, maxp = (size_t)c.maxp;
-    const size_t o_te = c.place(P1 * GL_E * 4), o_h = c.place(2 * rowE), o_th = c.place(2 * rowE),
-                 o_P = c.place(rowH), o_R = c.place(rowH), o_Yb = c.place(rowH), o_Yc = c.place(rowH), o_tP = c.place(rowH), o_tR = c.place(rowH),
-                 o_partS = c.place(maxp * rowH), o_partT = c.place(maxp * rowH), o_slotS = c.place(SL * GL_H * 4),
-                 o_slotT = c.place(SL * GL_H * 4), o_slotq = c.place(SL * 4), o_slott = c.place(SL * 4), o_q = c.place(2 * (size_t)A * 4),
-                 o_tq = c.place(2 * (size_t)A * 4), o_out = c.place(((size_t)A * 2 + 1) * 4);
-    if (gl_call_fill(h, gl, c, c.in_total)) return 1;
-    const int np = c.np;
-    const unsigned gP = (unsigned)np, gA = c.gA;
-    const GlGeom &G = c.G;
-    const GlPairs &L = c.L;
-    const int *inc = c.inc;
-    const float *d_x = c.d_x, *d_Q = c.d_Q, *d_vQ = c.d_extra[0], *d_v = c.d_extra[1], *d_E = c.d_extra[2];
-    float *out = c.fp(o_out);                                      // [A] q | [A] tq | bad
-    int *bad = reinterpret_cast<int *>(out + 2 * (size_t)A);
-    HIPCHK(hipMemsetAsync(bad, 0, 4, h->stream));
-    float *te = c.fp(o_te);
-    if (np > 0) {
-        // ---- edge tangents
-        const unsigned gp = (unsigned)((np + 255) / 256);
-        const double cut = (double)h->cfg.cutoff, eta = (double)h->cfg.eta;
-        if (cells) hipLaunchKernelGGL(k_jv_edge<2>, dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, d_v, d_E, cut, eta, h->d_mu.as<double>(), te, bad);
-        else hipLaunchKernelGGL(k_jv_edge<0>, dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, d_v, d_E, cut, eta, h->d_mu.as<double>(), te, bad);
-        HIPCHK(hipGetLastError());
-    }
-    float *hb[2] = {c.fp(o_h), c.fp(o_h) + (size_t)A * GL_E}, *thb[2] = {c.fp(o_th), c.fp(o_th) + (size_t)A * GL_E};
-    float *qb[2] = {c.fp(o_q), c.fp(o_q) + A}, *tqb[2] = {c.fp(o_tq), c.fp(o_tq) + A};
-    float *dP = c.fp(o_P), *dR = c.fp(o_R), *Yb = c.fp(o_Yb), *Yc = c.fp(o_Yc), *tP = c.fp(o_tP), *tR = c.fp(o_tR), *partS = c.fp(o_partS), *partT = c.fp(o_partT),
-          *slotS = c.fp(o_slotS), *slotT = c.fp(o_slotT), *slotq = c.fp(o_slotq), *slott = c.fp(o_slott);
-    const unsigned nt = c.nt;
-    const dim3 w64(64);
-    // the charges before the first EPN step and their tangent: Q / n, vQ / n (every GNN step sees these)
-    hipLaunchKernelGGL(k_gl_q0, dim3(gA), dim3(256), 0, h->stream, G, d_Q, qb[0]);
-    hipLaunchKernelGGL(k_gl_q0, dim3(gA), dim3(256), 0, h->stream, G, d_vQ, tqb[0]);
-    // ---- GNN steps
-    for (int t = 0; t < T; ++t) {
-        const float *ht = t ? hb[t & 1] : nullptr, *tht = t ? thb[t & 1] : nullptr;
-        hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, gl->msg[t], G, d_x, ht, (const float *)nullptr, d_Q, dP, dR, Yb, Yc);
-        hipLaunchKernelGGL(k_jv_proj, dim3(A), w64, 0, h->stream, gl->msg[t], G, tht, (const float *)tqb[0], tP, tR);
-        hipLaunchKernelGGL(k_jv_sweep, dim3(nt), w64, 0, h->stream, c.d_tasks, c.d_moff, A, gl->msg[t].W2, (const float *)dP, (const float *)tP,
-                           (const float *)dR, (const float *)Yb, (const float *)tR, partS, partT, (int)nt);
-        if (np > 0)
-            hipLaunchKernelGGL(k_jv_gnn_pair, dim3(gP), w64, 0, h->stream, gl->msg[t], L, (const float *)te, (const float *)dP, (const float *)dR,
-                               (const float *)tP, (const float *)tR, slotS, slotT);
-        hipLaunchKernelGGL(k_jv_gnn_tail, dim3(A), w64, 0, h->stream, gl->msg[t], gl->upd, G, inc, (const float *)partS, (const float *)partT,
-                           (const float *)slotS, (const float *)slotT, (const float *)dP, (const float *)tP, ht, tht, hb[(t + 1) & 1],
-                           thb[(t + 1) & 1]);
-    }
-    HIPCHK(hipGetLastError());
-    // ---- EPN steps
-    const float *feats = hb[T & 1], *tfeats = thb[T & 1];
-    for (int t = 0; t < T; ++t) {
-        const float *qt = qb[t & 1], *tqt = tqb[t & 1];
-        hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, gl->pas[t], G, d_x, feats, qt, d_Q, dP, dR, (float *)nullptr, (float *)nullptr);
-        hipLaunchKernelGGL(k_jv_proj, dim3(A), w64, 0, h->stream, gl->pas[t], G, tfeats, tqt, tP, tR);
-        if (np > 0)
-            hipLaunchKernelGGL(k_jv_epn_pair, dim3(gP), w64, 0, h->stream, gl->pas[t], L, (const float *)te, (const float *)dP, (const float *)dR,
-                               (const float *)tP, (const float *)tR, slotq, slott);
-        hipLaunchKernelGGL(k_gl_epn_atom, dim3(gA), dim3(256), 0, h->stream, A, inc, (const float *)slotq, qt, qb[(t + 1) & 1]);
-        hipLaunchKernelGGL(k_gl_epn_atom, dim3(gA), dim3(256), 0, h->stream, A, inc, (const float *)slott, tqt, tqb[(t + 1) & 1]);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, qb[T & 1], (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(out + A, tqb[T & 1], (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));
-    const size_t nback = (size_t)A * 2 + 1;
-    if (gl->pin_out.ensure(nback * 4)) return 1;
-    float *back = gl->pin_out.as<float>();
-    HIPCHK(hipMemcpyAsync(back, out, nback * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const int flag = reinterpret_cast<const int *>(back)[2 * (size_t)A];
-    if (flag & 2) EPNN_FAIL("%s: the pair list is not symmetric", name);
-    if (flag != 0)
-        EPNN_FAIL("%s: two atoms of a molecule%s coincide (distance 0: the edge features have no derivative there)", name,
-                  cells ? " or their periodic images" : "");
-    memcpy(q_out, back, (size_t)A * 4);
-    memcpy(tq_out, back + A, (size_t)A * 4);
-    return 0;
-}
-
-extern "C" int epnn_charges_jvp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                                         const float *Q, const float *cell, const float *vxyz, const float *vstrain, const float *vQ,
-                                         float *q_out, float *tq_out) {
-    const char *name = "epnn_charges_jvp_xyz_cell";
-    if (!h || !offsets || !xyz || !x || !Q || !q_out || !tq_out) EPNN_FAIL("%s: null argument", name);
-    if (check_flat_batch(name, B, N, offsets)) return 1;
-    EPNN_NOT_FUSED_ONLY(h, name);
-    std::vector<EpnnCell> cells;
-    if (cell && check_cell(B, cell, (double)h->cfg.cutoff, name, cells)) return 1;
-    if (h->upd_generic) EPNN_FAIL("%s is built for update layers [32, 32] only (epnn_set_update_layers changed them)", name);
-    if (h->part_world != 1) EPNN_FAIL("%s does not run on a partitioned handle (epnn_set_partition)", name);
-    HIPCHK(hipSetDevice(h->device));
-    if (h->pending.active && finish_forward(h)) return 1;
-    // the weights epnn_forward_xyz would use: a training step still in flight is waited for, device masters it has updated are
-    // pulled into the host copies (what any inference call does first)
-    if (train_quiesce(h) || pack_weights(h)) return 1;
-    return charges_jvp_impl(h, B, N, offsets, xyz, x, Q, cell ? cells.data() : nullptr, vxyz, vstrain, vQ, q_out, tq_out);
-}
-
-// ------------------------------------------------------------------------------------------------ several tangents in one pass
-// epnn_charges_jvp_multi_xyz_cell: charges_jvp_impl with K tangents beside the one primal (kernels k_jvm_*).  The sweep carries the
-// tangents in chunks: the widest instantiated k_jvm_sweep<KC> that fits what is left, so K = 7 runs 4 + 2 + 1.
+// The sweep carries the tangents in chunks: the widest instantiated k_jvm_sweep<KC> that fits what is left, so K = 7 runs 4 + 2 + 1.
 static int jvm_chunk(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
 
 template <int KC>
@@ -138,20 +25,22 @@ static void jvm_bucket(int K, Launch &&launch) {
     else launch(std::integral_constant<int, 16>{});
 }
 
-static int charges_jvp_multi_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                  const EpnnCell *cells, int K, const float *vxyz, const float *vstrain, const float *vQ, float *q_out,
-                                  float *tq_out) {
-    const char *name = "epnn_charges_jvp_multi_xyz_cell";
+// K tangents beside the one primal; the single-tangent entry is K = 1.  The call shares the pair-list gradient path's state
+// (GradLarge: the weights in plain Keras layout, refreshed when weights_gen moves on, and the input / scratch buffers, which keep the
+// size of the largest call of either kind): neither the training state nor the forward's plan and pair list are touched.
+static int charges_jvp_multi_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                  const float *Q, const EpnnCell *cells, int K, const float *vxyz, const float *vstrain, const float *vQ,
+                                  float *q_out, float *tq_out) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
     const int T = h->cfg.T, A = offsets[B];
     const size_t Kz = (size_t)K;
-    // the tangents, K times the single-tangent sizes: vQ as zeros when null, vxyz and vstrain left out
+    // the tangents: vQ as zeros when null, vxyz and vstrain left out
     const GlSpan spans[3] = {{vQ, Kz * B * 4, true}, {vxyz, vxyz ? Kz * A * 12 : 0, false}, {vstrain, vstrain ? Kz * B * 36 : 0, false}};
     GlCall c;
     if (gl_call_count(h, gl, name, B, N, offsets, xyz, x, Q, nullptr, cells, spans, 3, c)) return 1;
     const size_t P1 = c.P1, SL = 2 * P1, nH = (size_t)A * GL_H, nE = (size_t)A * GL_E, rowH = nH * 4, rowE = nE * 4, maxp = (size_t)c.maxp;
-    // primal rows as in charges_jvp_impl; the tangent rows K times theirs (one buffer each, tangent t at t times the single size)
+    // the primal rows once, the tangent rows K times (one buffer each, tangent t at t times one tangent's size)
     const size_t o_te = c.place(Kz * P1 * GL_E * 4), o_h = c.place(2 * rowE), o_th = c.place(2 * Kz * rowE),
                  o_P = c.place(rowH), o_R = c.place(rowH), o_Yb = c.place(rowH), o_Yc = c.place(rowH), o_tP = c.place(Kz * rowH),
                  o_tR = c.place(Kz * rowH), o_partS = c.place(maxp * rowH), o_partT = c.place(Kz * maxp * rowH),
@@ -170,6 +59,7 @@ static int charges_jvp_multi_impl(epnn_handle *h, int B, int N, const int32_t *o
     HIPCHK(hipMemsetAsync(bad, 0, 4, h->stream));
     float *te = c.fp(o_te);
     if (np > 0) {
+        // ---- edge tangents
         const unsigned gp = (unsigned)((np + 255) / 256);
         const double cut = (double)h->cfg.cutoff, eta = (double)h->cfg.eta;
         const double *mu = h->d_mu.as<double>();
@@ -191,6 +81,7 @@ static int charges_jvp_multi_impl(epnn_handle *h, int B, int N, const int32_t *o
           *slotS = c.fp(o_slotS), *slotT = c.fp(o_slotT), *slotq = c.fp(o_slotq), *slott = c.fp(o_slott);
     const dim3 w64(64);
     const size_t pstride = maxp * nH;
+    // the charges before the first EPN step and their tangents: Q / n, vQ / n (every GNN step sees these)
     hipLaunchKernelGGL(k_gl_q0, dim3(gA), dim3(256), 0, h->stream, G, d_Q, qb[0]);
     hipLaunchKernelGGL(k_jvm_q0, dim3(gA), dim3(256), 0, h->stream, G, K, B, d_vQ, tqb[0]);
     // ---- GNN steps
@@ -258,20 +149,38 @@ static int charges_jvp_multi_impl(epnn_handle *h, int B, int N, const int32_t *o
     return 0;
 }
 
-extern "C" int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                                               const float *Q, const float *cell, int K, const float *vxyz, const float *vstrain,
-                                               const float *vQ, float *q_out, float *tq_out) {
-    const char *name = "epnn_charges_jvp_multi_xyz_cell";
+// What the two entries check and settle before the call (K = 1: the single-tangent entry); cells: the checked cell rows.
+static int charges_jvp_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                             const float *Q, const float *cell, int K, const float *q_out, const float *tq_out,
+                             std::vector<EpnnCell> &cells) {
     if (!h || !offsets || !xyz || !x || !Q || !q_out || !tq_out) EPNN_FAIL("%s: null argument", name);
     if (K < 1 || K > JVM_MAXK) EPNN_FAIL("%s: K must be in 1..%d, got %d", name, JVM_MAXK, K);
     if (check_flat_batch(name, B, N, offsets)) return 1;
     EPNN_NOT_FUSED_ONLY(h, name);
-    std::vector<EpnnCell> cells;
     if (cell && check_cell(B, cell, (double)h->cfg.cutoff, name, cells)) return 1;
     if (h->upd_generic) EPNN_FAIL("%s is built for update layers [32, 32] only (epnn_set_update_layers changed them)", name);
     if (h->part_world != 1) EPNN_FAIL("%s does not run on a partitioned handle (epnn_set_partition)", name);
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
-    if (train_quiesce(h) || pack_weights(h)) return 1;
-    return charges_jvp_multi_impl(h, B, N, offsets, xyz, x, Q, cell ? cells.data() : nullptr, K, vxyz, vstrain, vQ, q_out, tq_out);
+    // the weights epnn_forward_xyz would use: a training step still in flight is waited for, device masters it has updated are
+    // pulled into the host copies (what any inference call does first)
+    return train_quiesce(h) || pack_weights(h);
+}
+
+extern "C" int epnn_charges_jvp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                         const float *Q, const float *cell, const float *vxyz, const float *vstrain, const float *vQ,
+                                         float *q_out, float *tq_out) {
+    const char *name = "epnn_charges_jvp_xyz_cell";
+    std::vector<EpnnCell> cells;
+    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, 1, q_out, tq_out, cells)) return 1;
+    return charges_jvp_multi_impl(h, name, B, N, offsets, xyz, x, Q, cell ? cells.data() : nullptr, 1, vxyz, vstrain, vQ, q_out, tq_out);
+}
+
+extern "C" int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                               const float *Q, const float *cell, int K, const float *vxyz, const float *vstrain,
+                                               const float *vQ, float *q_out, float *tq_out) {
+    const char *name = "epnn_charges_jvp_multi_xyz_cell";
+    std::vector<EpnnCell> cells;
+    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, K, q_out, tq_out, cells)) return 1;
+    return charges_jvp_multi_impl(h, name, B, N, offsets, xyz, x, Q, cell ? cells.data() : nullptr, K, vxyz, vstrain, vQ, q_out, tq_out);
 }

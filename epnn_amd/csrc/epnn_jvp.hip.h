@@ -1,12 +1,14 @@
-// Forward-mode derivative of the charges (epnn_charges_jvp_xyz_cell): the kernels.  Part of the one translation unit epnn_api.hip.
+// Forward-mode derivative of the charges (epnn_charges_jvp_xyz_cell, epnn_charges_jvp_multi_xyz_cell): the kernels.  Part of the one
+// translation unit epnn_api.hip.
 //
 // The pair-list gradient path (epnn_grad_large.hip.h) runs the factorised form of DESIGN.md section 2 forward with checkpoints and
-// then backwards.  This file runs it forward once with a tangent beside every row: (h, th), (q, tq), (P, tP), (R, tR), (S, tS), and
-// per listed pair (e, te).  Nothing is checkpointed, nothing of size N^2 exists.  tests/jvp_ref.py is the same algebra in float64.
+// then backwards.  This file runs it forward once with K <= JVM_MAXK tangents beside every row: (h, th), (q, tq), (P, tP), (R, tR),
+// (S, tS), and per listed pair (e, te).  Nothing is checkpointed, nothing of size N^2 exists.  tests/jvp_ref.py is the same algebra
+// in float64.
 //
 //   edges                        te [P][48] = de/dD * tD, tD = d'.(v_j - v_i) / D + d'^T E d' / D, float64 per listed pair
 //   GNN step t                   projections (k_gl_proj) and their tangents tP = Wi^T ta, tR = Wj^T ta, ta = [0 | th | vQ / n];
-//                                tangent all-pairs sweep (k_jv_sweep, f32 MFMA): S_i and tS_i; listed pairs as correction rows
+//                                tangent all-pairs sweep (k_jvm_sweep, f32 MFMA): S_i and tS_i; listed pairs as correction rows
 //                                of both in the incidence slots; per atom the pieces, the (N - n) padded partners in closed form,
 //                                the slots, then the update MLP and its tangent
 //   EPN step t                   projections of (h_T, q_t) and (th_T, tq_t); listed pairs only, both orders of the pass MLP and of its
@@ -17,297 +19,29 @@
 // is taken from the pre-activation and by the comparison the backward kernels use (P > -R, z2pre > 0, z1pre > 0, ...).  The two
 // derivative modes are therefore transposes of one another up to float32 rounding of the sums, with no kink between them.
 //
+// Every tangent buffer is K copies of one tangent's, tangent t at t times that size (te [K][P][48], th [K][A][48], tP, tR [K][A][32],
+// partT [K][piece][A][32], slotT [K][slots][32], slott [K][slots], tq [K][A]).  The primal statements and the ReLU decisions stand
+// once; the tangent statements are looped over the tangents and none of them reads another tangent, so column t has the same bits
+// whatever K and the other columns are.  The single-tangent entry is K = 1 of these kernels.
+//
 // Plain float32, every sum in a fixed order, no float atomics: bit-reproducible, and a molecule's rows do not depend on the rest
 // of the batch.
 #pragma once
 #include "epnn_grad_large.hip.h"
 
-// ---------------------------------------------------------------------------------------------------------- edge tangents
-// One thread per listed pair, the displacement d' and D in float64 exactly as k_gl_pair_xyz (and the front-end) measure them.
-// v [A][3] or null, E [B][3][3] or null.  te [P][48] float32.  bad: bit 0 = two atoms or images coincide, bit 1 = a pair without
-// both incidence slots.
-template <int GEO>
-__global__ __launch_bounds__(256) void k_jv_edge(GlPairs L, int npairs, const int *mol_of, const float *xyz, const float *geo,
-                                                 const float *v, const float *E, double cutoff, double eta, const double *mu, float *te,
-                                                 int *bad) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= npairs) return;
-    const int i = L.pi[p], j = L.pj[p], b = mol_of[i];
-    double dx = (double)xyz[3 * j] - (double)xyz[3 * i], dy = (double)xyz[3 * j + 1] - (double)xyz[3 * i + 1],
-           dz = (double)xyz[3 * j + 2] - (double)xyz[3 * i + 2];
-    if (GEO == 1) {
-        dx = epnn_mic(dx, (double)geo[3 * b]); dy = epnn_mic(dy, (double)geo[3 * b + 1]); dz = epnn_mic(dz, (double)geo[3 * b + 2]);
-    }
-    if (GEO == 2) {
-        const EpnnCell &c = reinterpret_cast<const EpnnCell *>(geo)[b];
-        double a[9];
-        for (int k = 0; k < 9; ++k) a[k] = (double)c.a[k];
-        epnn_mic_cell(dx, dy, dz, c.g, a);
-    }
-    const double D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
-    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) atomicOr(bad, 2);
-    float *row = te + (size_t)p * GL_E;
-    if (!(D > 0.0)) atomicOr(bad, 1);
-    if (!(D > 0.0) || !(D < cutoff)) {
-        for (int k = 0; k < GL_E; ++k) row[k] = 0.f;
-        return;
-    }
-    double num = 0.0;
-    if (v)
-        num = dx * ((double)v[3 * j] - (double)v[3 * i]) + dy * ((double)v[3 * j + 1] - (double)v[3 * i + 1]) +
-              dz * ((double)v[3 * j + 2] - (double)v[3 * i + 2]);
-    if (E) {
-        const float *e = E + 9 * (size_t)b;
-        const double d[3] = {dx, dy, dz};
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) num += d[a] * (double)e[3 * a + c] * d[c];
-    }
-    const double tD = num / D;
-    const double pi_d = 3.141592653589793;
-    const double C = (cos(pi_d * D / cutoff) + 1.0) / 2.0, dC = -0.5 * (pi_d / cutoff) * sin(pi_d * D / cutoff);
-    for (int k = 0; k < GL_E; ++k) {
-        const double u = D - mu[k], ex = exp(-eta * (u * u));
-        row[k] = (float)((dC - 2.0 * eta * u * C) * ex * tD);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------- projection tangents
-// One wavefront per atom: ta = [0 | th | tq] (the atom features x are constants), tP = Wi^T ta (lanes 0..31), tR = Wj^T ta (lanes
-// 32..63), no bias.  th: rows [A][48] or null (zeros).
-__global__ __launch_bounds__(64) void k_jv_proj(GlPair M, GlGeom G, const float *th, const float *tq, float *tP, float *tR) {
-    __shared__ float av[GL_E + 1];
-    const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
-    if (lane < GL_E) av[lane] = th ? th[(size_t)a * GL_E + lane] : 0.f;
-    if (lane == 63) av[GL_E] = tq[a];
-    __syncthreads();
-    const float *W = (half ? M.Wj : M.Wi) + (size_t)G.nx * GL_H;
-    float acc = 0.f;
-    for (int k = 0; k < GL_E + 1; ++k) acc = fmaf(av[k], W[k * GL_H + f], acc);
-    (half ? tR : tP)[(size_t)a * GL_H + f] = acc;
-}
-
-// ---------------------------------------------------------------------------------------------------------- the tangent sweep
-// Tasks, lanes and layout of k_gl_sweep: one wavefront per (16 resident atoms as the columns of an MFMA tile, one piece of their
-// molecule's partner range), lane 16 qd + c owns column c and the features 16 rb + 4 qd + r.  Resident P_i, tP_i; streamed R_j,
-// Yb_j = b2 + W2^T R_j, tR_j.  Per partner, all element-wise work in front of the MFMAs:
-//     z1    = max(P, -R)              m1 = P > -R              tz1 = m1 ? tP + tR : 0
-//     z2pre = W2^T z1 + Yb            16 MFMAs, k_gl_sweep<0>'s, in its order
-//     tz2   = W2^T tz1                16 more, issued between them (four independent accumulators)
-//     S_i  += relu(z2pre)             tS_i += z2pre > 0 ? tz2 : 0
-// outS, outT [piece][A][32]: one row per (piece, resident atom), written by exactly one wavefront (an empty piece writes zeros).
-__global__ __launch_bounds__(64) void k_jv_sweep(const int4 *tasks, const int *moff, int A, const float *W2, const float *P,
-                                                 const float *tP, const float *R, const float *Yb, const float *tR, float *outS,
-                                                 float *outT, int ntask) {
-    const int lane = threadIdx.x, c = lane & 15, qd = lane >> 4;
-    const int task = blockIdx.x;
-    if (task >= ntask) return;
-    float wf[2][8];
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int kf = 16 * (s >> 2) + 4 * qd + (s & 3), m = 16 * rb + c;
-            wf[rb][s] = W2[kf * GL_H + m];                          // out[m] = sum_k W2[k][m] z1[k]
-        }
-    const int4 tk = tasks[task];                                    // (first resident atom, molecule, piece, pieces)
-    const int a0 = moff[tk.y], a1 = moff[tk.y + 1];
-    const int len = (a1 - a0 + tk.w - 1) / tk.w;
-    const int j0 = min(a0 + tk.z * len, a1), j1 = min(j0 + len, a1);
-    const int col = tk.x + c;
-    const bool valid = col < a1;
-    const int colc = valid ? col : a1 - 1;
-    float xr[8], tr[8], acc[8], tacc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int f = 16 * (e >> 2) + 4 * qd + (e & 3);
-        xr[e] = P[(size_t)colc * GL_H + f];
-        tr[e] = tP[(size_t)colc * GL_H + f];
-        acc[e] = 0.f;
-        tacc[e] = 0.f;
-    }
-    for (int j = j0; j < j1; ++j) {
-        const float *xs = R + (size_t)j * GL_H + 4 * qd, *ys = Yb + (size_t)j * GL_H + 4 * qd, *ts = tR + (size_t)j * GL_H + 4 * qd;
-        const f32x4 n0 = *reinterpret_cast<const f32x4 *>(xs), n1 = *reinterpret_cast<const f32x4 *>(xs + 16);
-        f32x4 o0 = *reinterpret_cast<const f32x4 *>(ys), o1 = *reinterpret_cast<const f32x4 *>(ys + 16);
-        const f32x4 s0 = *reinterpret_cast<const f32x4 *>(ts), s1 = *reinterpret_cast<const f32x4 *>(ts + 16);
-        float nn[8], z1[8], tz[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { nn[e] = -n0[e]; nn[4 + e] = -n1[e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) z1[e] = fmaxf(xr[e], nn[e]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            tz[e] = xr[e] > nn[e] ? tr[e] + s0[e] : 0.f;
-            tz[4 + e] = xr[4 + e] > nn[4 + e] ? tr[4 + e] + s1[e] : 0.f;
-        }
-        f32x4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[0][s], z1[s], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[1][s], z1[s], o1, 0, 0, 0);
-            t0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[0][s], tz[s], t0, 0, 0, 0);
-            t1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[1][s], tz[s], t1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc[e] += fmaxf(o0[e], 0.f);
-            acc[4 + e] += fmaxf(o1[e], 0.f);
-            tacc[e] += o0[e] > 0.f ? t0[e] : 0.f;
-            tacc[4 + e] += o1[e] > 0.f ? t1[e] : 0.f;
-        }
-    }
-    if (valid) {
-        float *o = outS + ((size_t)tk.z * A + col) * GL_H + 4 * qd, *t = outT + ((size_t)tk.z * A + col) * GL_H + 4 * qd;
-        *reinterpret_cast<f32x4 *>(o) = f32x4{acc[0], acc[1], acc[2], acc[3]};
-        *reinterpret_cast<f32x4 *>(o + 16) = f32x4{acc[4], acc[5], acc[6], acc[7]};
-        *reinterpret_cast<f32x4 *>(t) = f32x4{tacc[0], tacc[1], tacc[2], tacc[3]};
-        *reinterpret_cast<f32x4 *>(t + 16) = f32x4{tacc[4], tacc[5], tacc[6], tacc[7]};
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------- per listed pair
-// Lanes as in k_gl_gnn_pair: one wavefront per listed pair {i < j}, lanes 0..31 the order (i, j), lanes 32..63 the order (j, i),
-// a lane one hidden unit.  G = We^T e and tG = We^T te are the same for both orders.
-//
-// GNN step: the correction rows of S (k_gl_gnn_pair<0>'s) and of tS into the first atom's slot: with G the first layer's tangent
-// is tP_a + tR_b + tG, without it tP_a + tR_b.
-__global__ __launch_bounds__(64) void k_jv_gnn_pair(GlPair M, GlPairs L, const float *te, const float *P, const float *R, const float *tP,
-                                                    const float *tR, float *slotS, float *slotT) {
-    __shared__ float ev[GL_E], tv[GL_E], z[2][2][GL_H], tz[2][2][GL_H];
-    const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
-    const int i = L.pi[p], j = L.pj[p];
-    const int a = half ? j : i, b = half ? i : j;
-    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) return;               // (flagged by k_jv_edge: write nothing)
-    if (lane < GL_E) { ev[lane] = L.pe[(size_t)p * GL_E + lane]; tv[lane] = te[(size_t)p * GL_E + lane]; }
-    __syncthreads();
-    float g = 0.f, tg = 0.f;
-    for (int k = 0; k < GL_E; ++k) g = fmaf(ev[k], M.We[k * GL_H + f], g);
-    for (int k = 0; k < GL_E; ++k) tg = fmaf(tv[k], M.We[k * GL_H + f], tg);
-    const float base = P[(size_t)a * GL_H + f] + R[(size_t)b * GL_H + f];
-    const float z1g = base + g;
-    const float tb = tP[(size_t)a * GL_H + f] + tR[(size_t)b * GL_H + f];
-    z[half][0][f] = fmaxf(z1g, 0.f);
-    z[half][1][f] = fmaxf(base, 0.f);
-    tz[half][0][f] = z1g > 0.f ? tb + tg : 0.f;
-    tz[half][1][f] = base > 0.f ? tb : 0.f;
-    __syncthreads();
-    const float z2g = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half][0]), z2n = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half][1]);
-    const float t2g = gl_dotT(M.W2, GL_H, f, tz[half][0]), t2n = gl_dotT(M.W2, GL_H, f, tz[half][1]);
-    const int sa = half ? L.dest_j[p] : L.dest_i[p];
-    slotS[(size_t)sa * GL_H + f] = fmaxf(z2g, 0.f) - fmaxf(z2n, 0.f);
-    slotT[(size_t)sa * GL_H + f] = (z2g > 0.f ? t2g : 0.f) - (z2n > 0.f ? t2n : 0.f);
-}
-
-// EPN step: delta = (f(a_i, a_j, e) - f(a_j, a_i, e)) / 2 as k_gl_epn_pair<0> forms it, and its tangent
-// tf = W3 . ([z2pre > 0] W2^T ([z1pre > 0] (tP_a + tR_b + tG))), tdelta = (tf_ij - tf_ji) / 2; w delta, w tdelta into the first
-// atom's slots and their negatives into the second's.
-__global__ __launch_bounds__(64) void k_jv_epn_pair(GlPair M, GlPairs L, const float *te, const float *P, const float *R, const float *tP,
-                                                    const float *tR, float *slotq, float *slott) {
-    __shared__ float ev[GL_E], tv[GL_E], z[2][GL_H], tz[2][GL_H], red[2][GL_H], tred[2][GL_H];
-    const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
-    const int i = L.pi[p], j = L.pj[p];
-    const int a = half ? j : i, b = half ? i : j;
-    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) return;
-    if (lane < GL_E) { ev[lane] = L.pe[(size_t)p * GL_E + lane]; tv[lane] = te[(size_t)p * GL_E + lane]; }
-    __syncthreads();
-    float g = 0.f, tg = 0.f;
-    for (int k = 0; k < GL_E; ++k) g = fmaf(ev[k], M.We[k * GL_H + f], g);
-    for (int k = 0; k < GL_E; ++k) tg = fmaf(tv[k], M.We[k * GL_H + f], tg);
-    const float z1 = P[(size_t)a * GL_H + f] + R[(size_t)b * GL_H + f] + g;
-    z[half][f] = fmaxf(z1, 0.f);
-    tz[half][f] = z1 > 0.f ? tP[(size_t)a * GL_H + f] + tR[(size_t)b * GL_H + f] + tg : 0.f;
-    __syncthreads();
-    const float z2 = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half]);
-    const float t2 = z2 > 0.f ? gl_dotT(M.W2, GL_H, f, tz[half]) : 0.f;
-    const float w = L.pw[p];
-    const int sa = half ? L.dest_j[p] : L.dest_i[p];
-    red[half][f] = fmaxf(z2, 0.f) * M.W3[f];
-    tred[half][f] = t2 * M.W3[f];
-    __syncthreads();
-    if (f == 0) {
-        float fi = 0.f, fj = 0.f, ti = 0.f, tj = 0.f;             // (b3 cancels in the difference)
-        for (int k = 0; k < GL_H; ++k) { fi += red[0][k]; fj += red[1][k]; }
-        for (int k = 0; k < GL_H; ++k) { ti += tred[0][k]; tj += tred[1][k]; }
-        const float delta = 0.5f * (fi - fj), tdelta = 0.5f * (ti - tj);
-        slotq[sa] = half ? -(w * delta) : w * delta;
-        slott[sa] = half ? -(w * tdelta) : w * tdelta;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------- per atom
-// End of a GNN step, one wavefront per atom.  Primal: k_gl_gnn_tail's statements.  Tangent: tS = pieces in order +
-// (N - n) [W2^T relu(P) + b2 > 0] W2^T ([P > 0] tP) + the atom's slots in order; tM = W3^T tS; the update MLP's tangent on
-// [th | tM] with the ReLU decisions of its pre-activations.
-__global__ __launch_bounds__(64) void k_jv_gnn_tail(GlPair M, GlUpd U, GlGeom G, const int *inc_off, const float *part, const float *tpart,
-                                                    const float *corr, const float *tcorr, const float *P, const float *tP, const float *h,
-                                                    const float *th, float *h_out, float *th_out) {
-    __shared__ float v[GL_H], u0[GL_E + GL_H], u1[GL_H], u2[GL_H];
-    __shared__ float tv[GL_H], tu0[GL_E + GL_H], tu1[GL_H], tu2[GL_H];
-    const int a = blockIdx.x, lane = threadIdx.x;
-    const int b = G.mol_of[a], n = G.moff[b + 1] - G.moff[b];
-    if (lane < GL_H) {
-        const float pa = P[(size_t)a * GL_H + lane];
-        v[lane] = fmaxf(pa, 0.f);
-        tv[lane] = pa > 0.f ? tP[(size_t)a * GL_H + lane] : 0.f;
-    }
-    if (lane < GL_E) {
-        u0[lane] = h ? h[(size_t)a * GL_E + lane] : 0.f;
-        tu0[lane] = th ? th[(size_t)a * GL_E + lane] : 0.f;
-    }
-    __syncthreads();
-    if (lane < GL_H) {
-        float s = 0.f, ts = 0.f;
-        const int np = gl_pieces(n);
-        for (int k = 0; k < np; ++k) s += part[((size_t)k * G.A + a) * GL_H + lane];
-        const float zp = M.b2[lane] + gl_dotT(M.W2, GL_H, lane, v);
-        s += (float)(G.N - n) * fmaxf(zp, 0.f);
-        for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += corr[(size_t)k * GL_H + lane];
-        u1[lane] = s;
-        for (int k = 0; k < np; ++k) ts += tpart[((size_t)k * G.A + a) * GL_H + lane];
-        ts += (float)(G.N - n) * (zp > 0.f ? gl_dotT(M.W2, GL_H, lane, tv) : 0.f);
-        for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) ts += tcorr[(size_t)k * GL_H + lane];
-        tu1[lane] = ts;
-    }
-    __syncthreads();
-    if (lane < GL_H) {
-        u0[GL_E + lane] = (float)G.N * M.b3[lane] + gl_dotT(M.W3, GL_H, lane, u1);
-        tu0[GL_E + lane] = gl_dotT(M.W3, GL_H, lane, tu1);
-    }
-    __syncthreads();
-    float t = 0.f, tt = 0.f;
-    if (lane < GL_H) {
-        t = U.c1[lane];
-        for (int k = 0; k < GL_E + GL_H; ++k) t = fmaf(u0[k], U.U1[k * GL_H + lane], t);
-        for (int k = 0; k < GL_E + GL_H; ++k) tt = fmaf(tu0[k], U.U1[k * GL_H + lane], tt);
-    }
-    __syncthreads();
-    if (lane < GL_H) { u1[lane] = fmaxf(t, 0.f); tu1[lane] = t > 0.f ? tt : 0.f; }
-    __syncthreads();
-    if (lane < GL_H) {
-        const float u2pre = U.c2[lane] + gl_dotT(U.U2, GL_H, lane, u1);
-        u2[lane] = fmaxf(u2pre, 0.f);
-        tu2[lane] = u2pre > 0.f ? gl_dotT(U.U2, GL_H, lane, tu1) : 0.f;
-    }
-    __syncthreads();
-    if (lane < GL_E) {
-        h_out[(size_t)a * GL_E + lane] = U.c3[lane] + gl_dotT(U.U3, GL_E, lane, u2);
-        th_out[(size_t)a * GL_E + lane] = gl_dotT(U.U3, GL_E, lane, tu2);
-    }
-}
-
-// ================================================================================================== several tangents in one pass
-// epnn_charges_jvp_multi_xyz_cell: K <= JVM_MAXK tangents beside one primal.  Every tangent buffer is K copies of the
-// single-tangent one, tangent t at t times the single size (te [K][P][48], th [K][A][48], tP, tR [K][A][32], partT [K][piece][A][32],
-// slotT [K][slots][32], slott [K][slots], tq [K][A]).  The primal statements and the ReLU decisions stand once; each tangent
-// statement is the k_jv_* kernel's own, looped over the tangents: column t has the bits of a single-tangent call on tangent t.
 #define JVM_MAXK 16
 
-// acc[t] = sum_k v[t VS + k] W[k][col] for t < K: gl_dotT's fmaf chain per tangent (k ascending, from 0), each weight loaded once.
-// K is uniform over the block: the guards are scalar branches and acc stays in registers.  KM >= K is the kernel's bucket (1, 2, 4,
-// 8, 16): registers and LDS are sized for it, not for the maximum, so that a call with few tangents runs at the single-tangent
-// kernels' occupancy.
+// The per-pair and per-atom kernels are templated on KM >= K, the bucket of K (1, 2, 4, 8, 16): registers and LDS are sized for
+// it, not for the maximum.  K is uniform over the block, so the guards t < K are scalar branches; in the bucket KM = 1 every
+// kernel sets K = 1, the guards fold away and the instantiation is a single-tangent kernel.
+//
+// acc[t] = sum_k v[t VS + k] W[k][col] for t < K: gl_dotT's fmaf chain per tangent (k ascending, from 0), each weight loaded once,
+// acc in registers.  One tangent's 32-long sum is gl_dotT itself: its loop shape, unrolled by 8 beside the primal's, is what keeps
+// k_jvm_gnn_tail<1> at 7 waves per SIMD (the loop below, which the compiler unrolls in full, leaves 5: profiles/r14_jvp_one_path.txt).
 template <int KM, int VS>
 __device__ __forceinline__ void jvm_dotT(const float *W, int stride, int col, const float *v, int n, int K, float (&acc)[KM]) {
+    if constexpr (KM == 1)
+        if (n == GL_H) { acc[0] = gl_dotT(W, stride, col, v); return; }
 #pragma unroll
     for (int t = 0; t < KM; ++t) acc[t] = 0.f;
     for (int k = 0; k < n; ++k) {
@@ -319,13 +53,21 @@ __device__ __forceinline__ void jvm_dotT(const float *W, int stride, int col, co
 }
 
 // ---------------------------------------------------------------------------------------------------------- edge tangents
-// k_jv_edge with d', D and de/dD once per listed pair and tD, te per tangent.  v [K][A][3] or null, E [K][B][3][3] or null,
-// te [K][P1][48] (te_stride = P1 * 48).
+// One thread per listed pair, the displacement d' and D in float64 exactly as k_gl_pair_xyz (and the front-end) measure them; d', D
+// and de/dD once, tD and te per tangent (tD in LDS, a thread's column; in a register at KM = 1).  v [K][A][3] or null,
+// E [K][B][3][3] or null, te [K][P1][48] float32 (te_stride = P1 * 48).  bad: bit 0 = two atoms or images coincide, bit 1 = a pair
+// without both incidence slots.
 template <int GEO, int KM>
 __global__ __launch_bounds__(256) void k_jvm_edge(GlPairs L, int npairs, const int *mol_of, const float *xyz, const float *geo, int K,
                                                   int A, int B, const float *v, const float *E, double cutoff, double eta,
                                                   const double *mu, float *te, size_t te_stride, int *bad) {
     __shared__ double tDs[KM][256];
+    double tD1;
+    auto tD = [&](int t) -> double & {
+        if constexpr (KM == 1) return tD1;
+        else return tDs[t][threadIdx.x];
+    };
+    if (KM == 1) K = 1;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= npairs) return;
     const int i = L.pi[p], j = L.pj[p], b = mol_of[i];
@@ -362,22 +104,24 @@ __global__ __launch_bounds__(256) void k_jvm_edge(GlPairs L, int npairs, const i
             for (int a = 0; a < 3; ++a)
                 for (int c = 0; c < 3; ++c) num += d[a] * (double)e[3 * a + c] * d[c];
         }
-        tDs[t][threadIdx.x] = num / D;
+        tD(t) = num / D;
     }
     const double pi_d = 3.141592653589793;
     const double C = (cos(pi_d * D / cutoff) + 1.0) / 2.0, dC = -0.5 * (pi_d / cutoff) * sin(pi_d * D / cutoff);
     for (int k = 0; k < GL_E; ++k) {
         const double u = D - mu[k], ex = exp(-eta * (u * u));
         const double de = (dC - 2.0 * eta * u * C) * ex;
-        for (int t = 0; t < K; ++t) row[t * te_stride + k] = (float)(de * tDs[t][threadIdx.x]);
+        for (int t = 0; t < K; ++t) row[t * te_stride + k] = (float)(de * tD(t));
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------- projection tangents
-// k_jv_proj on K tangents: the weights pass once.  th [K][A][48] or null, tq [K][A]; tP, tR [K][A][32].
+// One wavefront per atom: ta = [0 | th | tq] per tangent (the atom features x are constants), tP = Wi^T ta (lanes 0..31),
+// tR = Wj^T ta (lanes 32..63), no bias; the weights pass once.  th [K][A][48] or null (zeros), tq [K][A]; tP, tR [K][A][32].
 template <int KM>
 __global__ __launch_bounds__(64) void k_jvm_proj(GlPair M, GlGeom G, int K, const float *th, const float *tq, float *tP, float *tR) {
     __shared__ float av[KM][GL_E + 1];
+    if (KM == 1) K = 1;
     const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     for (int t = 0; t < K; ++t) {
         if (lane < GL_E) av[t][lane] = th ? th[((size_t)t * G.A + a) * GL_E + lane] : 0.f;
@@ -394,10 +138,17 @@ __global__ __launch_bounds__(64) void k_jvm_proj(GlPair M, GlGeom G, int K, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------- the tangent sweep
-// k_jv_sweep carrying KC tangents: tasks, lanes and layout are its own.  Per partner z1, the mask P > -R and the 16 primal MFMAs
-// stand once; each carried tangent has its tz1, its own accumulator pair (16 MFMAs, k_jv_sweep's order in s) and its tS.
-// tP, tR: the chunk's first tangent, the next at tstride floats; outT likewise at ostride.  outS null: the primal rows are
-// another launch's to store (every launch needs z2pre for its masks).
+// Tasks, lanes and layout of k_gl_sweep: one wavefront per (16 resident atoms as the columns of an MFMA tile, one piece of their
+// molecule's partner range), lane 16 qd + c owns column c and the features 16 rb + 4 qd + r.  A launch carries KC tangents.
+// Resident P_i and tP_i per tangent; streamed R_j, Yb_j = b2 + W2^T R_j and tR_j per tangent.  Per partner, all element-wise work
+// in front of the MFMAs:
+//     z1    = max(P, -R)              m1 = P > -R              tz1 = m1 ? tP + tR : 0        (z1 and m1 once, tz1 per tangent)
+//     z2pre = W2^T z1 + Yb            16 MFMAs, k_gl_sweep<0>'s, in its order
+//     tz2   = W2^T tz1                16 more per tangent, issued between them (an accumulator pair of its own each)
+//     S_i  += relu(z2pre)             tS_i += z2pre > 0 ? tz2 : 0
+// outS [piece][A][32], outT the same per tangent: one row per (piece, resident atom), written by exactly one wavefront (an empty
+// piece writes zeros).  tP, tR: the chunk's first tangent, the next at tstride floats; outT likewise at ostride.  outS null: the
+// primal rows are another launch's to store (every launch needs z2pre for its masks).
 template <int KC>
 __global__ __launch_bounds__(64) void k_jvm_sweep(const int4 *tasks, const int *moff, int A, const float *W2, const float *P,
                                                   const float *tP, const float *R, const float *Yb, const float *tR, size_t tstride,
@@ -490,16 +241,21 @@ __global__ __launch_bounds__(64) void k_jvm_sweep(const int4 *tasks, const int *
 }
 
 // ---------------------------------------------------------------------------------------------------------- per listed pair
-// k_jv_gnn_pair on K tangents: G, the two first-layer rows and their ReLU decisions once; tG, tz1, tz2 per tangent.
-// te [K][P1][48], tP, tR [K][A][32], slotT [K][SL][32].
+// Lanes as in k_gl_gnn_pair: one wavefront per listed pair {i < j}, lanes 0..31 the order (i, j), lanes 32..63 the order (j, i),
+// a lane one hidden unit.  G = We^T e and tG = We^T te are the same for both orders.
+//
+// GNN step: the correction rows of S (k_gl_gnn_pair<0>'s) and of tS into the first atom's slot: with G the first layer's tangent
+// is tP_a + tR_b + tG, without it tP_a + tR_b.  G, the two first-layer rows and their ReLU decisions once; tG, tz1, tz2 per
+// tangent.  te [K][P1][48], tP, tR [K][A][32], slotT [K][SL][32].
 template <int KM>
 __global__ __launch_bounds__(64) void k_jvm_gnn_pair(GlPair M, GlPairs L, int K, int A, size_t P1, size_t SL, const float *te, const float *P,
                                                      const float *R, const float *tP, const float *tR, float *slotS, float *slotT) {
     __shared__ float ev[GL_E], tv[KM][GL_E], z[2][2][GL_H], tz[KM][2][2][GL_H];
+    if (KM == 1) K = 1;
     const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     const int i = L.pi[p], j = L.pj[p];
     const int a = half ? j : i, b = half ? i : j;
-    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) return;
+    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) return;               // (flagged by k_jvm_edge: write nothing)
     if (lane < GL_E) {
         ev[lane] = L.pe[(size_t)p * GL_E + lane];
         for (int t = 0; t < K; ++t) tv[t][lane] = te[((size_t)t * P1 + p) * GL_E + lane];
@@ -531,11 +287,14 @@ __global__ __launch_bounds__(64) void k_jvm_gnn_pair(GlPair M, GlPairs L, int K,
         if (t < K) slotT[((size_t)t * SL + sa) * GL_H + f] = (z2g > 0.f ? t2g[t] : 0.f) - (z2n > 0.f ? t2n[t] : 0.f);
 }
 
-// k_jv_epn_pair on K tangents: delta once, tdelta per tangent.  slott [K][SL].
+// EPN step: delta = (f(a_i, a_j, e) - f(a_j, a_i, e)) / 2 as k_gl_epn_pair<0> forms it, once, and per tangent
+// tf = W3 . ([z2pre > 0] W2^T ([z1pre > 0] (tP_a + tR_b + tG))), tdelta = (tf_ij - tf_ji) / 2; w delta, w tdelta into the first
+// atom's slots and their negatives into the second's.  slott [K][SL].
 template <int KM>
 __global__ __launch_bounds__(64) void k_jvm_epn_pair(GlPair M, GlPairs L, int K, int A, size_t P1, size_t SL, const float *te, const float *P,
                                                      const float *R, const float *tP, const float *tR, float *slotq, float *slott) {
     __shared__ float ev[GL_E], tv[KM][GL_E], z[2][GL_H], tz[KM][2][GL_H], red[2][GL_H], tred[KM][2][GL_H];
+    if (KM == 1) K = 1;
     const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     const int i = L.pi[p], j = L.pj[p];
     const int a = half ? j : i, b = half ? i : j;
@@ -568,7 +327,7 @@ __global__ __launch_bounds__(64) void k_jvm_epn_pair(GlPair M, GlPairs L, int K,
         }
     __syncthreads();
     if (f == 0) {
-        float fi = 0.f, fj = 0.f;
+        float fi = 0.f, fj = 0.f;                                   // (b3 cancels in the difference)
         for (int k = 0; k < GL_H; ++k) { fi += red[0][k]; fj += red[1][k]; }
         const float delta = 0.5f * (fi - fj);
         slotq[sa] = half ? -(w * delta) : w * delta;
@@ -582,8 +341,10 @@ __global__ __launch_bounds__(64) void k_jvm_epn_pair(GlPair M, GlPairs L, int K,
 }
 
 // ---------------------------------------------------------------------------------------------------------- per atom
-// k_jv_gnn_tail on K tangents.  tpart [K][maxp][A][32] (tp_stride = maxp * A * 32), tcorr [K][SL][32], tP [K][A][32],
-// th, th_out [K][A][48].
+// End of a GNN step, one wavefront per atom.  Primal: k_gl_gnn_tail's statements.  Per tangent: tS = pieces in order +
+// (N - n) [W2^T relu(P) + b2 > 0] W2^T ([P > 0] tP) + the atom's slots in order; tM = W3^T tS; the update MLP's tangent on
+// [th | tM] with the ReLU decisions of its pre-activations.  tpart [K][maxp][A][32] (tp_stride = maxp * A * 32),
+// tcorr [K][SL][32], tP [K][A][32], th, th_out [K][A][48].
 template <int KM>
 __global__ __launch_bounds__(64) void k_jvm_gnn_tail(GlPair M, GlUpd U, GlGeom G, int K, size_t tp_stride, size_t SL, const int *inc_off,
                                                      const float *part, const float *tpart, const float *corr, const float *tcorr,
@@ -591,6 +352,7 @@ __global__ __launch_bounds__(64) void k_jvm_gnn_tail(GlPair M, GlUpd U, GlGeom G
                                                      float *th_out) {
     __shared__ float v[GL_H], u0[GL_E + GL_H], u1[GL_H], u2[GL_H];
     __shared__ float tv[KM][GL_H], tu0[KM][GL_E + GL_H], tu1[KM][GL_H], tu2[KM][GL_H];
+    if (KM == 1) K = 1;
     const int a = blockIdx.x, lane = threadIdx.x;
     const int b = G.mol_of[a], n = G.moff[b + 1] - G.moff[b];
     if (lane < GL_H) {

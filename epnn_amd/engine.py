@@ -374,6 +374,23 @@ class Engine:
                                                     fptr(q), fptr(gxyz)), self.lib)
         return q, gxyz
 
+    def _jvp_batch(self, name, offsets, xyz, x, Q, box, cell):
+        """What charges_jvp_xyz and charges_jvp_xyz_multi do to the batch: the arrays as the C entries take them, box or cell as
+        cell rows (B, 3, 3) or None -> (offsets, xyz, x, Q, cell, B, A)."""
+        _one_periodic_argument(box, cell)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
+        B, A = len(offsets) - 1, int(offsets[-1])
+        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
+            raise EpnnError(f"{name}: array shapes do not match offsets")
+        if box is not None:
+            box = _box_rows(box, B)
+            cell = np.zeros((B, 3, 3), dtype=np.float32)
+            cell[:, [0, 1, 2], [0, 1, 2]] = box
+        if cell is not None:
+            cell = _cell_rows(cell, B)
+        return offsets, xyz, x, Q, cell, B, A
+
     def charges_jvp_xyz(self, offsets, xyz, x, Q, N, v=None, strain=None, dQ=None, box=None, cell=None):
         """Forward mode: flat batch and a direction -> (q (A,), tq (A,)), tq the derivative of the charges along it
         (epnn_charges_jvp_xyz_cell): v (A, 3) a tangent of the coordinates (an MD velocity: tq = dq/dt), strain (3, 3) or
@@ -382,12 +399,7 @@ class Engine:
         None (= 0); the three add up.  box (3,) or (B, 3), cell (3, 3) or (B, 3, 3) as in forward_xyz; neither: open molecules.
         One call costs about one forward of the pair-list gradient path, whose charges q has bit for bit; it touches no training
         state and works without train_init."""
-        _one_periodic_argument(box, cell)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
-        B, A = len(offsets) - 1, int(offsets[-1])
-        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
-            raise EpnnError("charges_jvp_xyz: array shapes do not match offsets")
+        offsets, xyz, x, Q, cell, B, A = self._jvp_batch("charges_jvp_xyz", offsets, xyz, x, Q, box, cell)
         if v is not None:
             v = _f32(v)
             if v.shape != (A, 3):
@@ -406,12 +418,6 @@ class Engine:
             if dQ.shape != (B,):
                 raise ValueError(f"charges_jvp_xyz: dQ must be a scalar or have shape ({B},), got {dQ.shape}")
             dQ = np.ascontiguousarray(dQ)
-        if box is not None:
-            box = _box_rows(box, B)
-            cell = np.zeros((B, 3, 3), dtype=np.float32)
-            cell[:, [0, 1, 2], [0, 1, 2]] = box
-        if cell is not None:
-            cell = _cell_rows(cell, B)
         opt = lambda a: None if a is None else fptr(a)
         q = np.empty((A,), dtype=np.float32)
         tq = np.empty((A,), dtype=np.float32)
@@ -425,12 +431,7 @@ class Engine:
         or (K, B, 3, 3), dQ (K,) or (K, B); each may be None (= 0 for every direction), at least one must be given, and those
         given must agree on K (1..16).  The primal, the pair list and every per-pair and per-atom primal statement run once;
         box and cell as in charges_jvp_xyz."""
-        _one_periodic_argument(box, cell)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
-        B, A = len(offsets) - 1, int(offsets[-1])
-        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
-            raise EpnnError("charges_jvp_xyz_multi: array shapes do not match offsets")
+        offsets, xyz, x, Q, cell, B, A = self._jvp_batch("charges_jvp_xyz_multi", offsets, xyz, x, Q, box, cell)
         Ks = {}
         if v is not None:
             v = _f32(v)
@@ -458,12 +459,6 @@ class Engine:
         if len(set(Ks.values())) != 1:
             raise ValueError("charges_jvp_xyz_multi: the tangents disagree on K: " + ", ".join(f"{k} has {n}" for k, n in Ks.items()))
         K = next(iter(Ks.values()))
-        if box is not None:
-            box = _box_rows(box, B)
-            cell = np.zeros((B, 3, 3), dtype=np.float32)
-            cell[:, [0, 1, 2], [0, 1, 2]] = box
-        if cell is not None:
-            cell = _cell_rows(cell, B)
         opt = lambda a: None if a is None else fptr(a)
         q = np.empty((A,), dtype=np.float32)
         tq = np.empty((max(K, 1), A), dtype=np.float32)

@@ -369,7 +369,7 @@ int epnn_charges_jvp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offse
  * zero-padded; no float atomics and every sum in a fixed order; a molecule's rows do not depend on the rest of the batch at the
  * same N.
  * Bits: q_out has the bits of epnn_charges_jvp_xyz_cell (and so of the pair-list gradient path), and row k of tq_out the bits that
- * entry gives for tangent k alone: every tangent statement is the single-tangent kernel's, looped over the tangents (the same MFMA
+ * entry gives for tangent k alone: that entry is K = 1 of this one, and no tangent statement reads another tangent (the same MFMA
  * order per tangent, the same pieces, slot order and closed-form padded term).  A row therefore does not depend on K, on its
  * position, or on what the other rows hold.
  * Cost: the front-end, the pair list, the primal projections, pair and atom kernels run once; the all-pairs sweep carries the

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""The bits of the three pair-list entries (charges_vjp_xyz at "grad_path" 2, train_step_xyz at "train_path" 2 with apply=False,
-charges_jvp_xyz) on the smallest systems that reach each branch of their shared set-up (csrc/epnn_api_pairlist.hip.h):
+"""The bits of the pair-list entries (charges_vjp_xyz at "grad_path" 2, train_step_xyz at "train_path" 2 with apply=False,
+charges_jvp_xyz, charges_jvp_xyz_multi at K = 1 and at K = 3, which runs sweep chunks 2 + 1) on the smallest systems that reach each
+branch of their shared set-up (csrc/epnn_api_pairlist.hip.h):
     python tools/pairlist_bits.py record FILE      # on the build to compare against
     python tools/pairlist_bits.py compare FILE     # on the build under test: every array, hash and last_stats() must be equal
 Random weights (random_weights(9, 2, ...)), fixed seeds, the generators of the GPU tests.  The bits belong to a build and a card:
@@ -66,6 +67,14 @@ def run():
             tangents.update(v=dict(v=v), strain=dict(strain=E), dQ=dict(dQ=dQ))
         for tag, tan in tangents.items():
             keep("jvp_" + tag, ("q", "tq"), eng.charges_jvp_xyz(offsets, xyz, x, Q, N, **tan, **geo))
+        cols = [dict(v=v, strain=E, dQ=dQ)]                                 # the multi entry's columns: the tangent above, two more seeds
+        for seed in (2000 + k, 3000 + k):
+            r = np.random.default_rng(seed)
+            cols.append(dict(v=r.normal(size=(A, 3)).astype(np.float32), strain=(0.3 * r.normal(size=(B, 3, 3))).astype(np.float32),
+                             dQ=r.normal(size=B).astype(np.float32)))
+        for K in (1, 3):
+            tan = {nm: np.stack([c[nm] for c in cols[:K]]) for nm in ("v", "strain", "dQ")}
+            keep(f"jvp_multi_K{K}", ("q", "tq"), eng.charges_jvp_xyz_multi(offsets, xyz, x, Q, N, **tan, **geo))
         eng.close()
     return out
 
