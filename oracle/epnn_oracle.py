@@ -197,9 +197,10 @@ def gnn_layer(h, e, x, q, mask, msg, upd, dtype=np.float32, row_block=64):
     return h
 
 
-def epn_layer(h, e, x, q, mask, pas, dtype=np.float32, row_block=64, return_transfer=False):
-    """reference charge_gn.py:87-119 (EPN_layer.call)."""
-    tol = np.float32(1e-5)
+def epn_layer(h, e, x, q, mask, pas, dtype=np.float32, row_block=64, return_transfer=False, near_tol=1e-5):
+    """reference charge_gn.py:87-119 (EPN_layer.call).  (near_tol is the reference's constant 1e-5, charge_gn.py:90; a parameter
+    here because the C ABI's config has it.)"""
+    tol = np.float32(near_tol)
     h, x, q, mask = (np.asarray(a, dtype=dtype) for a in (h, x, q, mask))
     B, N = e.shape[0], e.shape[1]
     pad = mask.max(axis=-1)                                             # :116 reduce_max(mask, -1)
@@ -244,7 +245,7 @@ def model_reduce(h_inp, x_inp, q_inp, mask_inp, dtype=np.float32):
     return red(h_inp), red(x_inp), red(q_inp), mask_inp
 
 
-def model_forward(h_inp, e_inp, x_inp, q_inp, mask_inp, weights, dtype=np.float32, row_block=64):
+def model_forward(h_inp, e_inp, x_inp, q_inp, mask_inp, weights, dtype=np.float32, row_block=64, near_tol=1e-5):
     """reference charge_gn.py:369-391 (make_model graph): model([h, e, x, q, mask]) -> (B,N,1).
 
     Inputs are first cast to float32 like Keras does for float64 arrays fed to float32 Inputs."""
@@ -252,20 +253,20 @@ def model_forward(h_inp, e_inp, x_inp, q_inp, mask_inp, weights, dtype=np.float3
     h_inp, e_inp, x_inp, q_inp, mask_inp = f32
     h, x, q, mask = model_reduce(h_inp, x_inp, q_inp, mask_inp, dtype)
     feats = gnn_layer(h, e_inp, x, q, mask, weights["msg"], weights["upd"], dtype, row_block)   # :386
-    return epn_layer(feats, e_inp, x, q, mask, weights["pas"], dtype, row_block)                 # :387
+    return epn_layer(feats, e_inp, x, q, mask, weights["pas"], dtype, row_block, near_tol=near_tol)   # :387
 
 
-def forward_xyz(xyz, x, Q, weights, N=None, dtype=np.float32, row_block=64, cutoff=3.0, eta=2.0, h_dim=48):
+def forward_xyz(xyz, x, Q, weights, N=None, dtype=np.float32, row_block=64, cutoff=3.0, eta=2.0, h_dim=48, near_tol=1e-5):
     """Featurise one molecule like gen_padded_init_state and run the model; returns (N,) charges.  (h_dim: the channels of h and of
     e -- make_model gives both h_dim, charge_gn.py:376-377; infer.py:42-43 uses 48.)"""
     n = x.shape[0]
     N = n if N is None else N
     h_p, e_p, x_p, q_p, mask = dense_inputs(xyz, x, Q, N, h_dim=h_dim, e_dim=h_dim, cutoff=cutoff, eta=eta)
-    out = model_forward(h_p[None], e_p[None], x_p[None], q_p[None], mask[None], weights, dtype, row_block)
+    out = model_forward(h_p[None], e_p[None], x_p[None], q_p[None], mask[None], weights, dtype, row_block, near_tol)
     return out[0, :, 0]
 
 
-def forward_xyz_large(xyz, x, Q, weights, dtype=np.float64, row_block=64, cutoff=3.0, eta=2.0):
+def forward_xyz_large(xyz, x, Q, weights, dtype=np.float64, row_block=64, cutoff=3.0, eta=2.0, near_tol=1e-5):
     """forward_xyz for one UNPADDED system (N = n) too large for its dense (n,n,.) inputs: the per-atom x, h = 0 and
     q = Q/n are what make_model's reductions (:382-384) return for gen_padded_init_state's tiled arrays (:335-338), the
     mask is all ones, and the edge tensor is produced a block of rows at a time.  Same layer functions, same operations
@@ -278,4 +279,4 @@ def forward_xyz_large(xyz, x, Q, weights, dtype=np.float64, row_block=64, cutoff
     e = EdgeRows(xyz, 48, cutoff, eta)
     xx = x[None].astype(dtype)
     feats = gnn_layer(h, e, xx, q, mask, weights["msg"], weights["upd"], dtype, row_block)
-    return epn_layer(feats, e, xx, q, mask, weights["pas"], dtype, row_block)[0, :, 0]
+    return epn_layer(feats, e, xx, q, mask, weights["pas"], dtype, row_block, near_tol=near_tol)[0, :, 0]

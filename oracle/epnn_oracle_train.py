@@ -65,7 +65,8 @@ def _acc(dst, src):
         dst[k] = (dst[k][0] + dW, dst[k][1] + db)
 
 
-def loss_and_grads(h_inp, e_inp, x_inp, q_inp, mask_inp, y, weights, dtype=np.float64, kink_shift=0.0, kink_where="all"):
+def loss_and_grads(h_inp, e_inp, x_inp, q_inp, mask_inp, y, weights, dtype=np.float64, kink_shift=0.0, kink_where="all",
+                   near_tol=1e-5):
     """Batch of B molecules (dense make_model inputs).  Returns (loss_sum, predictions (B,N,1), grads dict);
     loss_sum = sum over molecules and atoms of (y - p)^2, i.e. what tape.gradient differentiates when the B
     molecules' gradients are summed (data-parallel training: one molecule per rank, all-reduce sum).
@@ -79,12 +80,12 @@ def loss_and_grads(h_inp, e_inp, x_inp, q_inp, mask_inp, y, weights, dtype=np.fl
     global _KINK_SHIFT, _KINK_WHERE
     _KINK_SHIFT, _KINK_WHERE = float(kink_shift), kink_where
     try:
-        return _loss_and_grads(h_inp, e_inp, x_inp, q_inp, mask_inp, y, weights, dtype)
+        return _loss_and_grads(h_inp, e_inp, x_inp, q_inp, mask_inp, y, weights, dtype, near_tol)
     finally:
         _KINK_SHIFT, _KINK_WHERE = 0.0, "all"
 
 
-def _loss_and_grads(h_inp, e_inp, x_inp, q_inp, mask_inp, y, weights, dtype):
+def _loss_and_grads(h_inp, e_inp, x_inp, q_inp, mask_inp, y, weights, dtype, near_tol=1e-5):
     w = _cast(weights, dtype)
     f32 = [np.asarray(t, dtype=np.float32) for t in (h_inp, e_inp, x_inp, q_inp, mask_inp)]
     h0, x, q0, mask = orc.model_reduce(f32[0], f32[2], f32[3], f32[4], dtype)
@@ -108,7 +109,7 @@ def _loss_and_grads(h_inp, e_inp, x_inp, q_inp, mask_inp, y, weights, dtype):
         tape_g.append((acts, uacts, F))
         h = hn.reshape(B, N, -1) * nm
     feats = h
-    tol = np.float32(1e-5)
+    tol = np.float32(near_tol)
     near = (np.clip(f32[1], tol, np.float32(1e5)).max(-1) != tol).astype(dtype)
     wgt = mask.max(-1) * near                                               # (B,N,N)
     q = q0

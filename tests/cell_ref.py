@@ -106,7 +106,7 @@ class EdgeRowsCell(orc.EdgeRows):
         return self._blocks[key]
 
 
-def forward_cell(xyz, x, Q, cell, weights, N=None, dtype=np.float64, h_dim=48, cutoff=3.0, eta=2.0):
+def forward_cell(xyz, x, Q, cell, weights, N=None, dtype=np.float64, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):
     """One molecule padded to N in the cell (3,3): orc.dense_inputs with the cell's edges, orc.model_forward.  (N,) charges."""
     x = np.asarray(x, dtype=np.float32)
     n = x.shape[0]
@@ -114,10 +114,10 @@ def forward_cell(xyz, x, Q, cell, weights, N=None, dtype=np.float64, h_dim=48, c
     h_p, e_p, x_p, q_p, mask = orc.dense_inputs(xyz, x, Q, N, h_dim=h_dim, e_dim=h_dim, cutoff=cutoff, eta=eta)
     e, _ = get_init_edges_cell(xyz, cell, num=h_dim, cutoff=cutoff, eta=eta)
     e_p[:n, :n] = e
-    return orc.model_forward(h_p[None], e_p[None], x_p[None], q_p[None], mask[None], weights, dtype)[0, :, 0]
+    return orc.model_forward(h_p[None], e_p[None], x_p[None], q_p[None], mask[None], weights, dtype, near_tol=near_tol)[0, :, 0]
 
 
-def forward_large_cell(xyz, x, Q, cell, weights, dtype=np.float64, cutoff=3.0, eta=2.0):
+def forward_large_cell(xyz, x, Q, cell, weights, dtype=np.float64, cutoff=3.0, eta=2.0, near_tol=1e-5):
     """orc.forward_xyz_large in the cell (3,3): one unpadded system, edge rows a block at a time."""
     x = np.asarray(x, dtype=np.float32)
     n = x.shape[0]
@@ -127,7 +127,7 @@ def forward_large_cell(xyz, x, Q, cell, weights, dtype=np.float64, cutoff=3.0, e
     e = EdgeRowsCell(xyz, cell, 48, cutoff, eta)
     xx = x[None].astype(dtype)
     feats = orc.gnn_layer(h, e, xx, q, mask, weights["msg"], weights["upd"], dtype)
-    return orc.epn_layer(feats, e, xx, q, mask, weights["pas"], dtype)[0, :, 0]
+    return orc.epn_layer(feats, e, xx, q, mask, weights["pas"], dtype, near_tol=near_tol)[0, :, 0]
 
 
 def pairs_cell(xyz, cell, cutoff=3.0, eta=2.0, tol=1e-5, num=48, block=64):
@@ -205,23 +205,23 @@ def _cell_grad_ref(cell, outer=False):
         xgr.edges64, xgr.orc = saved
 
 
-def vjp64_cell(xyz, x, Q, g, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0):
+def vjp64_cell(xyz, x, Q, g, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5):
     """(q (N,), gxyz (n, 3)) of one molecule in the cell (3,3): xgr.vjp64 on the cell's edges."""
     with _cell_grad_ref(cell):
-        return xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift)
+        return xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol)
 
 
-def strain64(xyz, x, Q, g, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0):
+def strain64(xyz, x, Q, g, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5):
     """(q (N,), gxyz (n, 3), gstrain (3, 3)): gstrain[a][c] = d(sum_i g_i q_i)/d eps_ac under r -> (1 + eps) r, a_k -> (1 + eps) a_k,
     = sum over pairs i < j with D < cutoff of (dF/dD_ij) d'_a d'_c / D_ij.  xgr sums over ordered pairs: half of it."""
     with _cell_grad_ref(cell, outer=True):
-        q, ext = xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift)
+        q, ext = xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol)
     return q, ext[:, :3], 0.5 * ext[:, 3:].sum(0).reshape(3, 3)
 
 
-def forward64_cell(xyz, x, Q, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0):
+def forward64_cell(xyz, x, Q, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):
     with _cell_grad_ref(cell):
-        return xgr.forward64(xyz, x, Q, weights, N, h_dim, cutoff, eta)
+        return xgr.forward64(xyz, x, Q, weights, N, h_dim, cutoff, eta, near_tol=near_tol)
 
 
 def random_cell(rng, n, cell, min_sep=0.9):

@@ -30,7 +30,7 @@ def _image(box=None, cell=None):
     return lambda d: d
 
 
-def pair_list(xyz, num, cutoff=3.0, eta=2.0, box=None, cell=None, block=256):
+def pair_list(xyz, num, cutoff=3.0, eta=2.0, box=None, cell=None, block=256, near_tol=1e-5):
     """Every ORDERED pair (i, j), j != i, with D < cutoff, sorted by (i, j): dict of i, j, rev (index of (j, i)), e and de/dD
     (float64, num channels), d = image of r_i - r_j, D, near (the float32 decision of charge_gn.py:90-94)."""
     r = np.asarray(xyz, dtype=np.float32).astype(np.float64)
@@ -61,7 +61,7 @@ def pair_list(xyz, num, cutoff=3.0, eta=2.0, box=None, cell=None, block=256):
     ex = np.exp(-eta * u * u)
     e = C[:, None] * ex
     de = (dC[:, None] - 2.0 * eta * u * C[:, None]) * ex
-    near = e.astype(np.float32).max(-1) > np.float32(1e-5)
+    near = e.astype(np.float32).max(-1) > np.float32(near_tol)
     return {"i": I, "j": J, "rev": rev, "e": e, "de": de, "d": d, "D": D, "near": near, "n": n}
 
 
@@ -135,7 +135,7 @@ def _sweep_backward(P, R, dS, W2, b2, pl, G, N, s, block):
 
 
 def vjp64_large(xyz, x, Q, g, weights, N=None, box=None, cell=None, strain=False, h_dim=48, cutoff=3.0, eta=2.0,
-                kink_shift=0.0, block=64):
+                kink_shift=0.0, block=64, near_tol=1e-5):
     """(q (n,), gxyz (n, 3)[, gstrain (3, 3)]) of one molecule padded to N: open, in the box (3,) or in the cell (3, 3)."""
     w = _cast(weights)
     s = float(kink_shift)
@@ -144,7 +144,7 @@ def vjp64_large(xyz, x, Q, g, weights, N=None, box=None, cell=None, strain=False
     N = n if N is None else N
     nh = h_dim
     F = nx + nh + 1
-    pl = pair_list(xyz, h_dim, cutoff, eta, box, cell)
+    pl = pair_list(xyz, h_dim, cutoff, eta, box, cell, near_tol=near_tol)
     pi, pj, rev, e = pl["i"], pl["j"], pl["rev"], pl["e"]
     q0 = np.full((n, 1), np.float64(np.float32(np.float32(Q) / np.float32(n))))
     T = len(w["msg"])

@@ -30,10 +30,10 @@ def cell_of(box=None, cell=None):
     return np.zeros((3, 3), dtype=np.float32)
 
 
-def near_flags(xyz, cell, h_dim=48, cutoff=3.0, eta=2.0):
+def near_flags(xyz, cell, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):
     """is_near of charge_gn.py:90-94 from the float32 edge tensor (n, n) bool."""
     e32, _ = cell_ref.get_init_edges_cell(xyz, cell, num=h_dim, cutoff=cutoff, eta=eta)
-    tol = np.float32(1e-5)
+    tol = np.float32(near_tol)
     return np.clip(e32, tol, np.float32(1e5)).max(-1) != tol
 
 
@@ -115,7 +115,7 @@ def edge_tangents(r, a, v=None, strain=None, num=48, cutoff=3.0, eta=2.0):
 
 
 def jvp64(xyz, x, Q, weights, N=None, v=None, strain=None, dQ=None, box=None, cell=None, h_dim=48, cutoff=3.0, eta=2.0,
-          kink_shift=0.0):
+          kink_shift=0.0, near_tol=1e-5):
     """(q (n,), tq (n,)) of one molecule padded to N: open, in the box (3,) or in the cell (3, 3); v (n, 3), strain (3, 3), dQ a
     scalar, each or all None (= 0)."""
     c = cell_of(box, cell)
@@ -126,7 +126,7 @@ def jvp64(xyz, x, Q, weights, N=None, v=None, strain=None, dQ=None, box=None, ce
     e, te = edge_tangents(r, cell_ref.duals(c)[0], v, strain, h_dim, cutoff, eta)
     q0 = np.float64(np.float32(np.float32(Q) / np.float32(n)))
     tq0 = 0.0 if dQ is None else float(dQ) / n
-    return model_jvp(e, te, near_flags(xyz, c, h_dim, cutoff, eta), x, q0, tq0, weights, N, kink_shift)
+    return model_jvp(e, te, near_flags(xyz, c, h_dim, cutoff, eta, near_tol), x, q0, tq0, weights, N, kink_shift)
 
 
 def forward64_at(r, a, x, Q, near, weights, N, h_dim=48, cutoff=3.0, eta=2.0):
@@ -137,7 +137,8 @@ def forward64_at(r, a, x, Q, near, weights, N, h_dim=48, cutoff=3.0, eta=2.0):
     return model_jvp(e, np.zeros_like(e), near, x, float(Q) / x.shape[0], 0.0, weights, N)[0]
 
 
-def jvp64_factorised(xyz, x, Q, weights, N=None, v=None, strain=None, dQ=None, box=None, cell=None, h_dim=48, cutoff=3.0, eta=2.0):
+def jvp64_factorised(xyz, x, Q, weights, N=None, v=None, strain=None, dQ=None, box=None, cell=None, h_dim=48, cutoff=3.0, eta=2.0,
+                     near_tol=1e-5):
     """jvp64 in the form the kernels of epnn_jvp.hip.h run it (float64): per-atom rows P, R, tP, tR; the all-pairs sweep on
     z1 = max(P_i, -R_j), Yb_j = b2 + W2^T R_j and tz1 = [P_i > -R_j] (tP_i + tR_j); the listed pairs as correction rows (with G minus
     without G) of S and tS; the (N - n) padded partners in closed form; EPN steps over the listed pairs only."""
@@ -148,7 +149,7 @@ def jvp64_factorised(xyz, x, Q, weights, N=None, v=None, strain=None, dQ=None, b
     n, nx = x.shape
     N = n if N is None else N
     F = nx + h_dim + 1
-    pl = pair_list(xyz, h_dim, cutoff, eta, cell=c)
+    pl = pair_list(xyz, h_dim, cutoff, eta, cell=c, near_tol=near_tol)
     pi, pj, rev, e, d, D = pl["i"], pl["j"], pl["rev"], pl["e"], pl["d"], pl["D"]
     tnum = np.zeros(len(pi))
     if v is not None:

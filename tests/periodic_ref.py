@@ -66,7 +66,7 @@ class EdgeRowsPBC(orc.EdgeRows):
         return self._blocks[key]
 
 
-def forward_pbc(xyz, x, Q, box, weights, N=None, dtype=np.float64, h_dim=48, cutoff=3.0, eta=2.0):
+def forward_pbc(xyz, x, Q, box, weights, N=None, dtype=np.float64, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):
     """One molecule padded to N in the cell box (3,): orc.dense_inputs with periodic edges, orc.model_forward.  (N,) charges."""
     x = np.asarray(x, dtype=np.float32)
     n = x.shape[0]
@@ -74,10 +74,10 @@ def forward_pbc(xyz, x, Q, box, weights, N=None, dtype=np.float64, h_dim=48, cut
     h_p, e_p, x_p, q_p, mask = orc.dense_inputs(xyz, x, Q, N, h_dim=h_dim, e_dim=h_dim, cutoff=cutoff, eta=eta)
     e, _ = get_init_edges_pbc(xyz, box, num=h_dim, cutoff=cutoff, eta=eta)
     e_p[:n, :n] = e
-    return orc.model_forward(h_p[None], e_p[None], x_p[None], q_p[None], mask[None], weights, dtype)[0, :, 0]
+    return orc.model_forward(h_p[None], e_p[None], x_p[None], q_p[None], mask[None], weights, dtype, near_tol=near_tol)[0, :, 0]
 
 
-def forward_large_pbc(xyz, x, Q, box, weights, dtype=np.float64, cutoff=3.0, eta=2.0):
+def forward_large_pbc(xyz, x, Q, box, weights, dtype=np.float64, cutoff=3.0, eta=2.0, near_tol=1e-5):
     """orc.forward_xyz_large in the cell box (3,): one unpadded system, edge rows a block at a time."""
     x = np.asarray(x, dtype=np.float32)
     n = x.shape[0]
@@ -87,16 +87,16 @@ def forward_large_pbc(xyz, x, Q, box, weights, dtype=np.float64, cutoff=3.0, eta
     e = EdgeRowsPBC(xyz, box, 48, cutoff, eta)
     xx = x[None].astype(dtype)
     feats = orc.gnn_layer(h, e, xx, q, mask, weights["msg"], weights["upd"], dtype)
-    return orc.epn_layer(feats, e, xx, q, mask, weights["pas"], dtype)[0, :, 0]
+    return orc.epn_layer(feats, e, xx, q, mask, weights["pas"], dtype, near_tol=near_tol)[0, :, 0]
 
 
-def forward_batch_pbc(offsets, xyz, x, Q, box, weights, N, dtype=np.float64):
+def forward_batch_pbc(offsets, xyz, x, Q, box, weights, N, dtype=np.float64, **kw):
     """A flat batch, molecule by molecule: (A,) charges."""
     rows = box_rows(box, len(offsets) - 1)
     out = []
     for b in range(len(offsets) - 1):
         a0, a1 = int(offsets[b]), int(offsets[b + 1])
-        out.append(forward_pbc(xyz[a0:a1], x[a0:a1], Q[b], rows[b], weights, N, dtype)[:a1 - a0])
+        out.append(forward_pbc(xyz[a0:a1], x[a0:a1], Q[b], rows[b], weights, N, dtype, **kw)[:a1 - a0])
     return np.concatenate(out)
 
 
@@ -170,15 +170,15 @@ def _periodic_grad_ref(box):
         xgr.edges64, xgr.orc = saved
 
 
-def vjp64_pbc(xyz, x, Q, g, box, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0):
+def vjp64_pbc(xyz, x, Q, g, box, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5):
     """(q (N,), gxyz (n, 3)) of one molecule in the cell box (3,): xgr.vjp64 on minimum-image edges."""
     with _periodic_grad_ref(box):
-        return xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift)
+        return xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol)
 
 
-def forward64_pbc(xyz, x, Q, box, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0):
+def forward64_pbc(xyz, x, Q, box, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):
     with _periodic_grad_ref(box):
-        return xgr.forward64(xyz, x, Q, weights, N, h_dim, cutoff, eta)
+        return xgr.forward64(xyz, x, Q, weights, N, h_dim, cutoff, eta, near_tol=near_tol)
 
 
 def random_cell(rng, n, L, min_sep=0.9):

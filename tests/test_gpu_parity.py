@@ -546,7 +546,8 @@ def test_near_flag_at_other_tolerances_fused_front_end_vs_pair_list(gpu_engine_f
     front-end does not evaluate max_k e_k per pair: epnn_create finds, with the reference's float64 expression, the distances at
     which the flag changes and the kernel counts how many lie below D.  With a large tolerance the change sits well inside the
     cutoff (1.9 .. 2.8 A), where QM9 molecules have many pairs: the charges must equal those of the 48-channel front-end,
-    which forms the e rows and takes their maximum like the reference does."""
+    which forms the e rows and takes their maximum like the reference does; and both equal the float64 oracle run at that tolerance."""
+    from oracle import epnn_oracle as orc
     nx, T, N = 9, 3, 33
     w = random_weights(nx, T, seed=23, scale=0.35)
     names = [nm for nm in val_names if nm.startswith("dsgdb9nsd")][:40]
@@ -566,6 +567,9 @@ def test_near_flag_at_other_tolerances_fused_front_end_vs_pair_list(gpu_engine_f
     print(f"eta {eta} near_tol {near_tol}: fused vs pair-list front-end {np.abs(q[0] - q[1]).max():.2e}; effect of the tolerance {np.abs(q[0] - q_ref_tol).max():.2e}")
     assert np.abs(q[0] - q_ref_tol).max() > 1e-3
     assert np.abs(q[0] - q[1]).max() <= 5e-6
+    ref = np.concatenate([orc.forward_xyz(m[0], m[1], m[2], w, N=N, dtype=np.float64, eta=eta, near_tol=near_tol)[:m[1].shape[0]] for m in mols])
+    print(f"    vs the float64 oracle at that tolerance: fused front-end {np.abs(q[0] - ref).max():.2e}, pair-list front-end {np.abs(q[1] - ref).max():.2e}")
+    assert np.abs(q[0] - ref).max() <= TOL and np.abs(q[1] - ref).max() <= TOL
 
 
 _PART_WORKER = r'''

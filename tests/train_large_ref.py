@@ -64,7 +64,8 @@ def _sweep_backward_w(P, R, dS, W2, b2, pl, G, N, s, block):
     return dP + _scatter(i, corr, n), dR + _scatter(j, corr, n), dzg, dW2, db2
 
 
-def loss_and_grads_large(xyz, x, Q, y, weights, N=None, box=None, cell=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, block=64):
+def loss_and_grads_large(xyz, x, Q, y, weights, N=None, box=None, cell=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, block=64,
+                         near_tol=1e-5):
     """(loss, q (n,), grads) of one molecule padded to N: open, in the box (3,) or in the cell (3, 3)."""
     w = _cast(weights)
     s = float(kink_shift)
@@ -74,7 +75,7 @@ def loss_and_grads_large(xyz, x, Q, y, weights, N=None, box=None, cell=None, h_d
     N = n if N is None else N
     nh = h_dim
     F = nx + nh + 1
-    pl = pair_list(xyz, h_dim, cutoff, eta, box, cell)
+    pl = pair_list(xyz, h_dim, cutoff, eta, box, cell, near_tol=near_tol)
     pi, pj, rev = pl["i"], pl["j"], pl["rev"]
     # the edge features are an INPUT of the model, float32 (get_init_edges and the library's front-end round them): the same
     # expression as cell_ref._edge_rows_cell, rounded, so that this file and the dense oracle differentiate the same function

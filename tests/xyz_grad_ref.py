@@ -37,13 +37,13 @@ def edges64(xyz, num, cutoff=3.0, eta=2.0):
     return e, de, d, D
 
 
-def _inputs(xyz, x, Q, N, h_dim, cutoff, eta):
+def _inputs(xyz, x, Q, N, h_dim, cutoff, eta, near_tol=1e-5):
     n = x.shape[0]
     e32, _ = orc.get_init_edges(xyz, num=h_dim, cutoff=cutoff, eta=eta)
     e64, de, d, D = edges64(xyz, h_dim, cutoff, eta)
     E = np.zeros((1, N, N, h_dim))
     E[0, :n, :n] = e64
-    tol = np.float32(1e-5)
+    tol = np.float32(near_tol)
     near32 = np.zeros((N, N), dtype=bool)
     near32[:n, :n] = np.clip(e32, tol, np.float32(1e5)).max(-1) != tol
     xs = np.zeros((1, N, x.shape[1]))
@@ -55,25 +55,25 @@ def _inputs(xyz, x, Q, N, h_dim, cutoff, eta):
     return E, de, d, D, near32, xs, q0, mask
 
 
-def forward64(xyz, x, Q, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0):
+def forward64(xyz, x, Q, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):
     """(N,) charges from the float64 forward with float64 edges."""
-    return vjp64(xyz, x, Q, np.zeros(x.shape[0]), weights, N, h_dim, cutoff, eta)[0]
+    return vjp64(xyz, x, Q, np.zeros(x.shape[0]), weights, N, h_dim, cutoff, eta, near_tol=near_tol)[0]
 
 
-def vjp64(xyz, x, Q, g, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, kink_where="all"):
+def vjp64(xyz, x, Q, g, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, kink_where="all", near_tol=1e-5):
     """(q (N,), gxyz (n, 3) = sum_i g[i] dq_i/dxyz) for one molecule padded to N."""
     otr._KINK_SHIFT, otr._KINK_WHERE = float(kink_shift), kink_where
     try:
-        return _vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta)
+        return _vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, near_tol)
     finally:
         otr._KINK_SHIFT, otr._KINK_WHERE = 0.0, "all"
 
 
-def _vjp64(xyz, x_at, Q, g, weights, N, h_dim, cutoff, eta):
+def _vjp64(xyz, x_at, Q, g, weights, N, h_dim, cutoff, eta, near_tol=1e-5):
     n = x_at.shape[0]
     N = n if N is None else N
     w = otr._cast(weights, np.float64)
-    e, de, dvec, Dm, near32, x, q0, mask = _inputs(xyz, x_at, Q, N, h_dim, cutoff, eta)
+    e, de, dvec, Dm, near32, x, q0, mask = _inputs(xyz, x_at, Q, N, h_dim, cutoff, eta, near_tol)
     B = 1
     nm = np.clip(mask.sum(axis=1), 0, 1)[..., None]                         # (1,N,1)
     h0 = np.zeros((1, N, h_dim))
