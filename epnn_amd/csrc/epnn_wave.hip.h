@@ -290,6 +290,11 @@ __device__ __forceinline__ f32x4 w16_lds_ld4(unsigned a) { return *(w16_lds_cf4 
 __device__ __forceinline__ unsigned w16_lds_ldu16(unsigned a) { return *(w16_lds_cu16 *)(size_t)a; }
 typedef __attribute__((address_space(3))) const unsigned w16_lds_cu32;
 __device__ __forceinline__ unsigned w16_lds_ldu32(unsigned a) { return *(w16_lds_cu32 *)(size_t)a; }
+typedef __attribute__((address_space(3))) u32x4 w16_lds_u4;
+typedef __attribute__((address_space(3))) float w16_lds_f1;
+__device__ __forceinline__ u32x4 w16_lds_ldu4(unsigned a) { return *(const w16_lds_u4 *)(size_t)a; }
+__device__ __forceinline__ void w16_lds_stu4(unsigned a, u32x4 v) { *(w16_lds_u4 *)(size_t)a = v; }
+__device__ __forceinline__ void w16_lds_stf(unsigned a, float v) { *(w16_lds_f1 *)(size_t)a = v; }
 __device__ __forceinline__ f32x2 w16_lo(f32x4 v) { return __builtin_shufflevector(v, v, 0, 1); }
 __device__ __forceinline__ f32x2 w16_hi(f32x4 v) { return __builtin_shufflevector(v, v, 2, 3); }
 __device__ __forceinline__ f32x4 w16_cat(f32x2 a, f32x2 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3); }
@@ -1205,6 +1210,45 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         wave_sync_lds();
+        // ---- What an EPN block needs of a pair and no step changes, built ONCE for all T steps (in-kernel front-end with G on the
+        //      bf16 pipe): the three bf16 pieces of the pair's edge coordinates as the B operand of w16_mm_bfk16 (w16_split3k16 of
+        //      the same row: the same bits as the split every step made), the LDS addresses of the P rows of li and lj, and the
+        //      address of the transfer-matrix entry this lane group stores (~0: none -- q >= 2, or a pair beyond the near
+        //      tolerance, whose weight is 0 and whose entry is never written; the weights of this front-end are exactly 0 or 1).
+        //      Per pair and lane group q two 16-byte halves:  a = piece 1 | piece 2,  IN PLACE of the lane group's quarter of the
+        //      pair's f32 row (every lane overwrites exactly what it read: no order to watch);  b = piece 3 | P address of li |
+        //      of lj << 16 | store address,  16 ptl words further down (below the last row, above the EPN layout's tables).
+        //      The first `ktab` pairs have one -- all of them where 32 np words fit, else whole blocks of 16 as far as the room
+        //      below the rows goes; the blocks behind them run as before from their f32 rows (untouched) and records.
+        //      (32-unit update MLPs: the kernel for wider ones has no registers to spare, its blocks stay as they were.)
+        constexpr bool TB = GB && NRU == 2;
+        int ktab = 0;
+        const unsigned tb_off = 4u * EPNN_ER * (unsigned)ptl;
+        if constexpr (TB) {
+            const int kfit = min(ptl, max(0, A.lds_words - (o_x + n * (EPNN_PST + DMS)) - EPNN_ER * ptl) / 16);
+            ktab = kfit >= np ? np : (kfit & ~15);
+            const unsigned pl_a = w16_lds_addr(Pl) + 16u * (unsigned)q, dm_a = w16_lds_addr(Dm);
+            for (int s0 = 0; s0 < ktab; s0 += 16) {
+                const bool ok = s0 + n16 < ktab;
+                const int sl = ok ? s0 + n16 : 0;
+                const unsigned ra = pt_top - 64u * (unsigned)(sl + 1);
+                const f32x4 v = w16_lds_ld4(ra);
+                const unsigned ij = eij[sl];
+                w16_u32x2 z[3];
+                w16_split3k16(v, z[0], z[1], z[2]);
+                const unsigned li = ij & 0x7Fu, lj = ij >> 8;
+                const unsigned to = q == 0 ? li : lj, from = q == 0 ? lj : li;
+                const unsigned rows = (pl_a + 4u * EPNN_PST * li) | (pl_a + 4u * EPNN_PST * lj) << 16;
+                const unsigned st = (q < 2 && (ij & 0x80u)) ? dm_a + 4u * (to * DMS + ((from & 3u) << 3) + (from >> 2)) : ~0u;
+                asm volatile("" ::: "memory");
+                if (ok) {
+                    w16_lds_stu4(ra, u32x4{z[0][0], z[0][1], z[1][0], z[1][1]});
+                    w16_lds_stu4(ra - tb_off, u32x4{z[2][0], z[2][1], rows, st});
+                }
+                asm volatile("" ::: "memory");
+            }
+            wave_sync_lds();
+        }
         const int qs = (nx + 1) >> 2, ql = (nx + 1) & 3;    // step / lane group of xq that holds q
 #pragma unroll 1
         for (int t = 0; t < Te; ++t) {
@@ -1277,8 +1321,10 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 const int nblk = (np + 15) >> 4;
                 struct Rec { int ij; float wi, wj; };
                 struct Rows { float e[KE]; f32x4 pi_[2], rj_[2], pj_[2], ri_[2]; };
+                // (lanes beyond the last pair read the first pair that runs this way: its f32 row is still one)
+                const int sl_pad = ktab < np ? ktab : 0;
                 auto load_rec = [&](int blk, Rec &r_) {
-                    const int sl = blk * 16 + n16 < np ? blk * 16 + n16 : 0;
+                    const int sl = blk * 16 + n16 < np ? blk * 16 + n16 : sl_pad;
                     r_.ij = eij[sl];
                     if (FRONT) {
                         r_.wi = r_.wj = (r_.ij & 0x80) ? 1.f : 0.f;
@@ -1289,7 +1335,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                     }
                 };
                 auto load_rows = [&](int blk, const Rec &r_, Rows &w_) {
-                    const int sl = blk * 16 + n16 < np ? blk * 16 + n16 : 0;
+                    const int sl = blk * 16 + n16 < np ? blk * 16 + n16 : sl_pad;
                     const int li = r_.ij & 0xFF, lj = r_.ij >> 8;
                     load_e1(sl, w_.e);          // the G term is computed in the block, it never goes through memory
 #pragma unroll
@@ -1300,11 +1346,8 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                         w_.ri_[rb] = w16_ld(Rl + li * EPNN_PST + 16 * rb + fo);
                     }
                 };
-                auto block = [&](int blk, const Rec &r_, const Rows &w_) {
-                    const bool valid = blk * 16 + n16 < np;
-                    const int li = r_.ij & 0xFF, lj = r_.ij >> 8;
-                    f32x4 g[2] = {w16_splat(0.f), w16_splat(0.f)};       // G = We^T e of the 16 pairs (charge_gn.py:105, e block)
-                    g_mm(w_.e, g);
+                // the pair MLP behind G for the 16 pairs of a block, both directions: half the antisymmetric transfer (charge_gn.py:105-116)
+                auto pair_d = [&](const f32x4 (&g)[2], const auto &w_) -> float {
                     const f32x4 ua = w16_relu((g[0] + w_.pi_[0]) + w_.rj_[0]), ub = w16_relu((g[1] + w_.pi_[1]) + w_.rj_[1]);
                     const f32x4 va = w16_relu((g[0] + w_.pj_[0]) + w_.ri_[0]), vb = w16_relu((g[1] + w_.pj_[1]) + w_.ri_[1]);
                     const float zu[8] = {ua[0], ua[1], ua[2], ua[3], ub[0], ub[1], ub[2], ub[3]};
@@ -1330,7 +1373,14 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
 #pragma unroll
                         for (int r = 0; r < 4; ++r) fd = fmaf(w3[rb][r], t[r], fd);
                     }
-                    const float d = 0.5f * w16_sumq(fd);               // charge_gn.py:116; all lanes take part
+                    return 0.5f * w16_sumq(fd);                        // charge_gn.py:116; all lanes take part
+                };
+                auto block = [&](int blk, const Rec &r_, const Rows &w_) {
+                    const bool valid = blk * 16 + n16 < np;
+                    const int li = r_.ij & 0xFF, lj = r_.ij >> 8;
+                    f32x4 g[2] = {w16_splat(0.f), w16_splat(0.f)};       // G = We^T e of the 16 pairs (charge_gn.py:105, e block)
+                    g_mm(w_.e, g);
+                    const float d = pair_d(g, w_);
                     // entries with weight 0 are never written (they stay 0): a one-sided entry (j,i) of the dense
                     // front-end must not clear what the entry (i,j) wrote
                     // (ONE store instruction: lane group q = 0 writes what i receives, q = 1 what j receives)
@@ -1338,13 +1388,68 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                     const int to = q == 0 ? li : lj, from = q == 0 ? lj : li;
                     if (q < 2 && valid && wq != 0.f) Dm[to * DMS + ((from & 3) << 3) + (from >> 2)] = q == 0 ? wq * d : -(wq * d);
                 };
-                if (nblk > 0) {
+                // the same for the pairs with ready operands (ktab): no decode, no address arithmetic, no split
+                const int nbt = (ktab + 15) >> 4;
+                if constexpr (TB) {
+                    struct RecT { u32x4 a, b; };
+                    struct RowsT { f32x4 pi_[2], rj_[2], pj_[2], ri_[2]; };
+                    const unsigned pr_d = 4u * EPNN_PST * (unsigned)n;          // P row -> R row of the same atom
+                    auto load_rec_t = [&](int blk, RecT &r_) {
+                        const int sl = blk * 16 + n16 < ktab ? blk * 16 + n16 : 0;
+                        const unsigned ra = pt_top - 64u * (unsigned)(sl + 1);
+                        r_.a = w16_lds_ldu4(ra);
+                        r_.b = w16_lds_ldu4(ra - tb_off);
+                    };
+                    auto load_rows_t = [&](const RecT &r_, RowsT &w_) {
+                        const unsigned pi = r_.b[2] & 0xFFFFu, pj = r_.b[2] >> 16, ri = pi - pr_d, rj = pj - pr_d;
+#pragma unroll
+                        for (int rb = 0; rb < 2; ++rb) {
+                            w_.pi_[rb] = w16_lds_ld4(pi + 64u * rb);
+                            w_.rj_[rb] = w16_lds_ld4(rj + 64u * rb);
+                            w_.pj_[rb] = w16_lds_ld4(pj + 64u * rb);
+                            w_.ri_[rb] = w16_lds_ld4(ri + 64u * rb);
+                        }
+                    };
+                    auto block_t = [&](int blk, const RecT &r_, const RowsT &w_) {
+                        const bool valid = blk * 16 + n16 < ktab;
+                        f32x4 g[2] = {w16_splat(0.f), w16_splat(0.f)};
+                        const w16_u32x2 z[3] = {{r_.a[0], r_.a[1]}, {r_.a[2], r_.a[3]}, {r_.b[0], r_.b[1]}};
+                        w16_mm_bfk16(gwb, z, g);
+                        const float d = pair_d(g, w_);
+                        // (ONE store instruction, lane group 0 what i receives, 1 what j receives; weight 1: d and -d as they are)
+                        if (valid && r_.b[3] != ~0u) w16_lds_stf(r_.b[3], q == 0 ? d : -d);
+                    };
+                    if (nbt > 0) {
+                        RecT r0, r1;
+                        RowsT w0, w1;
+                        load_rec_t(0, r0);
+                        load_rec_t(min(1, nbt - 1), r1);
+                        load_rows_t(r0, w0);
+                        int blk = 0;
+#pragma unroll 1
+                        for (; blk + 1 < nbt; blk += 2) {
+                            RecT r2, r3;
+                            load_rows_t(r1, w1);
+                            load_rec_t(min(blk + 2, nbt - 1), r2);
+                            WAVE_FENCE();
+                            block_t(blk, r0, w0);
+                            load_rows_t(r2, w0);
+                            load_rec_t(min(blk + 3, nbt - 1), r3);
+                            WAVE_FENCE();
+                            block_t(blk + 1, r1, w1);
+                            r0 = r2;
+                            r1 = r3;
+                        }
+                        if (blk < nbt) block_t(blk, r0, w0);
+                    }
+                }
+                if (nbt < nblk) {
                     Rec r0, r1;
                     Rows w0, w1;
-                    load_rec(0, r0);
-                    load_rec(min(1, nblk - 1), r1);
-                    load_rows(0, r0, w0);
-                    int blk = 0;
+                    load_rec(nbt, r0);
+                    load_rec(min(nbt + 1, nblk - 1), r1);
+                    load_rows(nbt, r0, w0);
+                    int blk = nbt;
 #pragma unroll 1
                     for (; blk + 1 < nblk; blk += 2) {
                         Rec r2, r3;
