@@ -241,7 +241,11 @@ int epnn_train_apply(epnn_handle *h);
  * ReLU decisions within it apart) under the same contract; the pair-list path is built for update layers [32, 32] on a handle
  * without epnn_set_partition.  The handle keeps the scratch of its largest call on either path until epnn_destroy.  After a
  * call on the pair-list path epnn_last_stats gives out[0] = listed pairs, out[1] = 0,
- * out[2] = bytes of device scratch the call used. */
+ * out[2] = bytes of device scratch the call used: the checkpoints of every step (h_t, S_t, q_t), the per-atom rows and partial
+ * sums of one step, the pair list and the per-pair slots; with A atoms, T steps and `pieces` = the most pieces of a molecule's
+ * partner range (1 up to 32768 atoms),
+ *     bytes = A (1324 + 4 nx + 324 T + 257 pieces) + 1120 listed pairs + 13 KB      (+- 256 per buffer of rounding)
+ * on a handle whose first pair-list call this is (the staged inputs count with their buffer's capacity). */
 int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                          const float *g, float *q_out, float *gxyz_out);
 
