@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import checkpoint
-from .engine import Engine, EpnnError
+from .engine import KE_EV_ANGSTROM, Engine, EpnnError
 
 atom_num_dict = {'H': 1, 'C': 6, 'N': 7, 'O': 8, 'F': 9, 'P': 15, 'S': 16, 'Cl': 17, 'Br': 35}
 elem_dict = {'H': 0, 'C': 1, 'N': 2, 'O': 3, 'F': 4, 'P': 5, 'S': 6, 'Cl': 7, 'Br': 8}
@@ -385,6 +385,14 @@ class EPNNModel(_Stack):
         and cell as in predict_xyz."""
         return self._eng().charges_jvp_xyz(offsets, xyz, x, Q, self.natom if N is None else N, v=v, strain=strain, dQ=dQ, box=box,
                                            cell=cell)
+
+    def coulomb_xyz(self, offsets, xyz, x, Q, N=None, ke=KE_EV_ANGSTROM, alpha=0.0, parts=False):
+        """Charges, electrostatic potential, Coulomb energy and total forces in one call: (q (A,), phi (A,), E (B,) float64,
+        F (A, 3)), F = -dE/dxyz including the part through dq/dxyz; parts=True appends its two parts ffix and fq.  ke is the unit
+        constant (default KE_EV_ANGSTROM), alpha = 0 the bare 1 / D, alpha > 0 erf(alpha D) / D.  Open systems only, no
+        self-energy, no bonded exclusions.  One call costs about one charges_vjp_xyz call of the pair-list path.  N defaults to
+        the model's natom."""
+        return self._eng().coulomb_xyz(offsets, xyz, x, Q, self.natom if N is None else N, ke=ke, alpha=alpha, parts=parts)
 
     def charges_jvp_xyz_multi(self, offsets, xyz, x, Q, N=None, v=None, strain=None, dQ=None, box=None, cell=None):
         """charges_jvp_xyz along K directions in one pass: (q (A,), tq (K, A)), row k with the bits of the single call on the k-th

@@ -19,17 +19,24 @@ static void xyz_grad_release(epnn_handle *h) {
 
 // ------------------------------------------------------------------------------------------------ pair-list path ("grad_path")
 // State, weights, the call's set-up and the checkpointed forward: epnn_api_pairlist.hip.h.  Here: this entry's scratch and its backward.
-static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                  const float *g, float *q_out, float *gxyz_out, const float *box, const EpnnCell *cells,
-                                  float *gstrain_out) {
-    GradLarge *gl = grad_large_state(h);
-    if (grad_large_weights(h, gl)) return 1;
-    const int T = h->cfg.T, A = offsets[B];
-    const char *name = cells ? "epnn_charges_vjp_xyz_cell" : box ? "epnn_charges_vjp_xyz_pbc" : "epnn_charges_vjp_xyz";
-    const std::string where = std::string(name) + " (pair-list path)";
-    const GlSpan span_g{g, (size_t)A * 4, false};
+// One call of a reverse-mode entry, in the two pieces its entries share: gl_grad_forward (set-up, scratch, checkpointed forward) and
+// gl_grad_backward (the backward from a seed already on the device, in r.gq).  Between the two an entry writes its seed.
+struct GlGrad {
     GlCall c;
-    if (gl_call_count(h, gl, where.c_str(), B, N, offsets, xyz, x, Q, box, cells, &span_g, 1, c)) return 1;
+    size_t o_slotx, o_share, o_more[2];                          // o_more: the entry's own buffers, placed behind the shared ones
+    float *hck, *Sck, *qck, *dP, *dR, *Yb, *Yc, *dS, *partP, *partR, *slotP, *slotR, *slotq, *gE, *gh, *ghp;
+    float *out, *gq, *q_fin, *gx, *gs;                           // out: [A] gq | [A] q | [A][3] gxyz | bad | [B][9] gstrain
+    int *bad;
+};
+
+// spans: the entry's own staged inputs (r.c.d_extra); more[k] bytes: buffers of the entry alone (r.o_more[k]; the first one follows
+// `out` directly); in_cap: epnn_last_stats counts the staged inputs with their buffer's capacity, not with this call's bytes.
+static int gl_grad_forward(epnn_handle *h, GradLarge *gl, const char *where, int B, int N, const int32_t *offsets, const float *xyz,
+                           const float *x, const float *Q, const float *box, const EpnnCell *cells, const GlSpan *spans, int n_spans,
+                           const size_t *more, int n_more, bool in_cap, GlGrad &r) {
+    const int T = h->cfg.T, A = offsets[B];
+    GlCall &c = r.c;
+    if (gl_call_count(h, gl, where, B, N, offsets, xyz, x, Q, box, cells, spans, n_spans, c)) return 1;
     const size_t P1 = c.P1, SL = 2 * P1, rowH = (size_t)A * GL_H * 4, rowE = (size_t)A * GL_E * 4, maxp = (size_t)c.maxp;
     const size_t o_h = c.place((size_t)(T + 1) * rowE), o_S = c.place((size_t)T * rowH),
                  o_q = c.place((size_t)(T + 1) * A * 4), o_P = c.place(rowH), o_R = c.place(rowH), o_Yb = c.place(rowH), o_Yc = c.place(rowH),
@@ -37,26 +44,37 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
                  o_slotP = c.place(SL * GL_H * 4), o_slotR = c.place(SL * GL_H * 4), o_slotq = c.place(SL * 4), o_gE = c.place(P1 * GL_E * 4),
                  o_gh = c.place(rowE), o_ghp = c.place(rowE), o_slotx = c.place(SL * 72), o_share = c.place((size_t)A * 48),
                  o_out = c.place(((size_t)A * 5 + 1 + (size_t)B * 9) * 4);
-    if (gl_call_fill(h, gl, c, gl->in.cap)) return 1;
-    const int np = c.np;
+    for (int k = 0; k < n_more; ++k) r.o_more[k] = c.place(more[k]);
+    if (gl_call_fill(h, gl, c, in_cap ? gl->in.cap : c.in_total)) return 1;
+    r.o_slotx = o_slotx; r.o_share = o_share;
+    r.hck = c.fp(o_h); r.Sck = c.fp(o_S); r.qck = c.fp(o_q); r.dP = c.fp(o_P); r.dR = c.fp(o_R); r.Yb = c.fp(o_Yb); r.Yc = c.fp(o_Yc);
+    r.dS = c.fp(o_dS); r.partP = c.fp(o_partP); r.partR = c.fp(o_partR); r.slotP = c.fp(o_slotP); r.slotR = c.fp(o_slotR);
+    r.slotq = c.fp(o_slotq); r.gE = c.fp(o_gE); r.gh = c.fp(o_gh); r.ghp = c.fp(o_ghp); r.out = c.fp(o_out);
+    r.gq = r.out;
+    r.q_fin = r.out + A; r.gx = r.out + 2 * (size_t)A;
+    r.bad = reinterpret_cast<int *>(r.out + 5 * (size_t)A);
+    r.gs = r.out + 5 * (size_t)A + 1;
+    return gl_forward_ckpt(h, c, gl->msg, gl->pas, gl->upd, r.hck, r.Sck, r.qck, r.dP, r.dR, r.Yb, r.Yc, r.partP, r.slotP, r.slotq);
+}
+
+// The backward from the seed in r.gq (overwritten), down to gxyz (r.gx), the strain derivative (r.gs; want_strain) and the final
+// charges beside them (r.q_fin): everything up to the entry's download.
+static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, const float *box, const EpnnCell *cells, bool want_strain) {
+    const GlCall &c = r.c;
+    const int T = h->cfg.T, A = c.G.A, np = c.np;
+    const size_t P1 = c.P1;
     const unsigned nt = c.nt, gP = (unsigned)np, gA = c.gA;
     const GlGeom &G = c.G;
     const GlPairs &L = c.L;
     const int *inc = c.inc;
-    const float *d_x = c.d_x, *d_Q = c.d_Q, *d_g = c.d_extra[0];
-    float *hck = c.fp(o_h), *Sck = c.fp(o_S), *qck = c.fp(o_q), *dP = c.fp(o_P), *dR = c.fp(o_R), *Yb = c.fp(o_Yb), *Yc = c.fp(o_Yc),
-          *dS = c.fp(o_dS), *partP = c.fp(o_partP), *partR = c.fp(o_partR), *slotP = c.fp(o_slotP), *slotR = c.fp(o_slotR),
-          *slotq = c.fp(o_slotq), *gE = c.fp(o_gE), *gh = c.fp(o_gh), *ghp = c.fp(o_ghp), *out = c.fp(o_out);
+    const float *d_x = c.d_x, *d_Q = c.d_Q;
+    float *hck = r.hck, *Sck = r.Sck, *qck = r.qck, *dP = r.dP, *dR = r.dR, *Yb = r.Yb, *Yc = r.Yc, *dS = r.dS, *partP = r.partP,
+          *partR = r.partR, *slotP = r.slotP, *slotR = r.slotR, *gE = r.gE, *gh = r.gh, *ghp = r.ghp, *gq = r.gq, *gx = r.gx, *gs = r.gs;
+    int *bad = r.bad;
     const size_t nH = (size_t)A * GL_H, nE = (size_t)A * GL_E;
     const dim3 w64(64);
-    if (gl_forward_ckpt(h, c, gl->msg, gl->pas, gl->upd, hck, Sck, qck, dP, dR, Yb, Yc, partP, slotP, slotq)) return 1;
     const float *feats = hck + T * nE;
     // ---- backward: EPN stack
-    float *gq = out;                                             // [A] gq | [A] q | [A][3] gxyz | bad | [B][9] gstrain
-    float *q_fin = out + A, *gx = out + 2 * (size_t)A;
-    int *bad = reinterpret_cast<int *>(out + 5 * (size_t)A);
-    float *gs = out + 5 * (size_t)A + 1;
-    HIPCHK(hipMemcpyAsync(gq, d_g, (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemsetAsync(gh, 0, nE * 4, h->stream));
     HIPCHK(hipMemsetAsync(gE, 0, P1 * GL_E * 4, h->stream));
     HIPCHK(hipMemsetAsync(bad, 0, 4, h->stream));
@@ -94,7 +112,7 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
     }
     HIPCHK(hipGetLastError());
     // ---- edges -> coordinates
-    double *slotx = reinterpret_cast<double *>(c.dw + o_slotx), *share = gstrain_out ? reinterpret_cast<double *>(c.dw + o_share) : nullptr;
+    double *slotx = reinterpret_cast<double *>(c.dw + r.o_slotx), *share = want_strain ? reinterpret_cast<double *>(c.dw + r.o_share) : nullptr;
     if (np > 0) {
         const unsigned gp = (unsigned)((np + 255) / 256);
         const double cut = (double)h->cfg.cutoff, eta = (double)h->cfg.eta;
@@ -105,7 +123,24 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
     hipLaunchKernelGGL(k_gl_atom_xyz, dim3(gA), dim3(256), 0, h->stream, A, inc, (const double *)slotx, gx, share);
     if (share) hipLaunchKernelGGL(k_g_strain_mol, dim3((unsigned)B), dim3(64), 0, h->stream, (const double *)share, c.d_moff, gs);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(q_fin, qck + (size_t)T * A, (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(r.q_fin, qck + (size_t)T * A, (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
+static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                  const float *g, float *q_out, float *gxyz_out, const float *box, const EpnnCell *cells,
+                                  float *gstrain_out) {
+    GradLarge *gl = grad_large_state(h);
+    if (grad_large_weights(h, gl)) return 1;
+    const int A = offsets[B];
+    const char *name = cells ? "epnn_charges_vjp_xyz_cell" : box ? "epnn_charges_vjp_xyz_pbc" : "epnn_charges_vjp_xyz";
+    const std::string where = std::string(name) + " (pair-list path)";
+    const GlSpan span_g{g, (size_t)A * 4, false};
+    GlGrad r;
+    if (gl_grad_forward(h, gl, where.c_str(), B, N, offsets, xyz, x, Q, box, cells, &span_g, 1, nullptr, 0, true, r)) return 1;
+    HIPCHK(hipMemcpyAsync(r.gq, r.c.d_extra[0], (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));    // the seed: the staged g
+    if (gl_grad_backward(h, gl, r, B, box, cells, gstrain_out != nullptr)) return 1;
+    const float *q_fin = r.q_fin;
     const size_t nback = (size_t)A * 4 + 1 + (gstrain_out ? (size_t)B * 9 : 0);
     if (gl->pin_out.ensure(nback * 4)) return 1;
     float *back = gl->pin_out.as<float>();

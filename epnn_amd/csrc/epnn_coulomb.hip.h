@@ -1,0 +1,129 @@
+// Electrostatics of the predicted charges (epnn_coulomb_xyz): the kernels.  Part of the one translation unit epnn_api.hip.
+//
+// Per molecule, over its real atoms only (open systems: no cell, no images):
+//     kappa(D) = 1 / D  (alpha == 0)   or   erf(alpha D) / D  (alpha > 0)
+//     phi_i    = ke sum_{j != i} q_j kappa(D_ij)
+//     ffix_i   = -ke q_i sum_{j != i} q_j kappa'(D_ij) (r_i - r_j) / D_ij        kappa' = -g(alpha D) / D^2,
+//                g = 1 (alpha == 0),  g(u) = erf(u) - 2 / sqrt(pi) u exp(-u^2) (alpha > 0)
+//     E_b      = 1/2 sum_i q_i phi_i
+// k_cl_sweep is the all-pairs part: one wavefront per task = (up to 64 atoms, one per lane; one piece of a partner range), the
+// partners staged 64 at a time in LDS and read at a wave-uniform address (a broadcast).  A molecule above 64 atoms is cut into
+// blocks of 64 atoms times cl_pieces(n) pieces of its partner range; molecules of up to 64 atoms are packed whole, several to a
+// wavefront, and every lane skips the partners of the other molecules.  Either way a lane meets the partners of its own molecule
+// in index order, and the number of pieces depends on the molecule's size alone: a molecule's rows do not depend on the batch.
+// Arithmetic: the displacement is the float64 difference of the float32 coordinates rounded once (exact far from the origin);
+// the per-pair terms are float32 (one reciprocal square root, plus erff and expf or a short series when alpha > 0); every running
+// sum is float64.  part [pieces][A][4] = (sum q_j kappa, sum q_j g dx / D^3, .. dy .., .. dz ..) is written by exactly one wavefront
+// per (piece, atom); k_cl_atom adds an atom's pieces in piece order and k_cl_energy a molecule's atoms, as k_g_strain_mol does.
+// No atomics on floats; the only atomic is the OR into the coincident-atoms flag.
+#pragma once
+#include "epnn_host.h"
+
+#define CL_BLOCK 64               // atoms of a task: one per lane
+#define CL_TILE 64                // partners staged in LDS at a time: one per lane
+#define CL_MINPIECE 128           // a partner range is not cut into pieces shorter than this ...
+#define CL_MAXP 32                // ... nor into more pieces than this
+#define CL_WANT 2048              // wavefronts a single molecule should bring
+
+// pieces of the partner range of a molecule of n atoms: enough for CL_WANT wavefronts, within the two limits above
+__host__ __device__ __forceinline__ int cl_pieces(int n) {
+    if (n <= CL_BLOCK) return 1;
+    const int blocks = (n + CL_BLOCK - 1) / CL_BLOCK, want = (CL_WANT + blocks - 1) / blocks, cap = (n + CL_MINPIECE - 1) / CL_MINPIECE;
+    const int np = want < cap ? want : cap;
+    return np < 1 ? 1 : (np > CL_MAXP ? CL_MAXP : np);
+}
+
+// g(u) = erf(u) - 2 / sqrt(pi) u exp(-u^2), erf_u = erf(u).  Below 1 the two terms cancel (g ~ 4 / (3 sqrt(pi)) u^3): the series
+// 2 / sqrt(pi) sum_{k >= 1} (-1)^(k + 1) 2 k / ((2 k + 1) k!) u^(2 k + 1), whose 12th term is below 5e-9 of the sum at u = 1.
+__device__ __forceinline__ float cl_g(float u, float erf_u) {
+    const float two_rpi = 1.1283791670955126f;
+    if (u >= 1.f) return erf_u - two_rpi * u * expf(-u * u);
+    const float w = u * u;
+    float s = 22.f / 918086400.f;
+    s = fmaf(s, w, -20.f / 76204800.f);
+    s = fmaf(s, w, 18.f / 6894720.f);
+    s = fmaf(s, w, -16.f / 685440.f);
+    s = fmaf(s, w, 14.f / 75600.f);
+    s = fmaf(s, w, -12.f / 9360.f);
+    s = fmaf(s, w, 10.f / 1320.f);
+    s = fmaf(s, w, -8.f / 216.f);
+    s = fmaf(s, w, 6.f / 42.f);
+    s = fmaf(s, w, -4.f / 10.f);
+    s = fmaf(s, w, 2.f / 3.f);
+    return two_rpi * (u * w) * s;
+}
+
+// task = (first atom, atoms | piece << 8, first partner, end of the partners); atoms and partners are flat atom indices
+template <bool ERF>
+__global__ __launch_bounds__(64) void k_cl_sweep(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q, int A,
+                                                 float alpha, double *part, int *bad) {
+    __shared__ double tx[CL_TILE], ty[CL_TILE], tz[CL_TILE];
+    __shared__ float tq[CL_TILE];
+    const int4 tk = tasks[blockIdx.x];
+    const int lane = threadIdx.x, na = tk.y & 255, piece = tk.y >> 8;
+    const bool valid = lane < na;
+    const int i = tk.x + (valid ? lane : 0);
+    const int b = mol_of[i], lo = moff[b], hi = moff[b + 1];
+    const double xi = (double)xyz[3 * (size_t)i], yi = (double)xyz[3 * (size_t)i + 1], zi = (double)xyz[3 * (size_t)i + 2];
+    double sp = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    bool hit = false;
+    for (int t0 = tk.z; t0 < tk.w; t0 += CL_TILE) {
+        const int cnt = min(CL_TILE, tk.w - t0);
+        __syncthreads();
+        if (lane < cnt) {
+            const size_t j = (size_t)(t0 + lane);
+            tx[lane] = (double)xyz[3 * j]; ty[lane] = (double)xyz[3 * j + 1]; tz[lane] = (double)xyz[3 * j + 2];
+            tq[lane] = q[j];
+        }
+        __syncthreads();
+        for (int jj = 0; jj < cnt; ++jj) {
+            const int j = t0 + jj;
+            const float dx = (float)(xi - tx[jj]), dy = (float)(yi - ty[jj]), dz = (float)(zi - tz[jj]), qj = tq[jj];
+            const float r2 = dx * dx + dy * dy + dz * dz;
+            const bool use = valid && j != i && j >= lo && j < hi;        // the self term goes by index
+            hit |= use && r2 == 0.f;
+            const float rinv = (use && r2 > 0.f) ? rsqrtf(r2) : 0.f;
+            float kap = rinv, g = 1.f;
+            if (ERF) {
+                const float u = alpha * (r2 * rinv), e = erff(u);
+                kap = e * rinv;
+                g = cl_g(u, e);
+            }
+            const float s = qj * g * (rinv * rinv * rinv);
+            sp += (double)(qj * kap);
+            sx += (double)(s * dx);
+            sy += (double)(s * dy);
+            sz += (double)(s * dz);
+        }
+    }
+    if (valid) {
+        double *o = part + ((size_t)piece * A + i) * 4;
+        o[0] = sp; o[1] = sx; o[2] = sy; o[3] = sz;
+    }
+    if (hit) atomicOr(bad, 1);
+}
+
+// every atom adds its pieces in piece order: phi [A] (float32, written twice: the backward's seed and the output), ffix [A][3],
+// and its share of the energy, 1/2 q_i phi_i, in float64
+__global__ __launch_bounds__(256) void k_cl_atom(int A, const int *moff, const int *mol_of, const float *q, const double *part, double ke,
+                                                 float *seed, float *phi, float *ffix, double *share) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= A) return;
+    const int b = mol_of[i], np = cl_pieces(moff[b + 1] - moff[b]);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < np; ++k)
+        for (int c = 0; c < 4; ++c) s[c] += part[((size_t)k * A + i) * 4 + c];
+    const double p = ke * s[0], qi = (double)q[i];
+    seed[i] = phi[i] = (float)p;
+    for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
+    share[i] = 0.5 * qi * p;
+}
+
+// E_b: a molecule's shares, lane by lane in atom order, then across the lanes (the order of k_g_strain_mol)
+__global__ __launch_bounds__(64) void k_cl_energy(const double *share, const int *moff, double *e_out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double v = 0.0;
+    for (int a = moff[b] + lane; a < moff[b + 1]; a += 64) v += share[a];
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    if (lane == 0) e_out[b] = v;
+}

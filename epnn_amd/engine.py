@@ -9,6 +9,7 @@ import numpy as np
 from . import _lib
 from ._lib import W_MSG, W_PAS, W_UPD, EpnnConfig, EpnnError, check, fptr, iptr
 
+KE_EV_ANGSTROM = 14.3996454784255      # e^2 / (4 pi eps0) in eV Angstrom: coulomb_xyz's default ke (332.0637: kcal/mol)
 _WHICH = {"msg": W_MSG, "upd": W_UPD, "pas": W_PAS}
 
 
@@ -465,6 +466,31 @@ class Engine:
         check(self.lib.epnn_charges_jvp_multi_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), opt(cell), int(K),
                                                        opt(v), opt(strain), opt(dQ), fptr(q), fptr(tq)), self.lib)
         return q, tq
+
+    def coulomb_xyz(self, offsets, xyz, x, Q, N, ke=KE_EV_ANGSTROM, alpha=0.0, parts=False):
+        """Electrostatics of the predicted charges in one call (epnn_coulomb_xyz): flat batch -> (q (A,), phi (A,), E (B,) float64,
+        F (A, 3)) with phi_i = ke sum_{j != i} q_j kappa(D_ij) = dE/dq_i, E = 1/2 sum_i q_i phi_i per molecule and F = -dE/dxyz in
+        total: the part at fixed charges plus the part through dq/dxyz.  kappa(D) = 1 / D for alpha = 0 (bare Coulomb) and
+        erf(alpha D) / D for alpha > 0 (Gaussian charges of width sigma, alpha = 1 / (2 sigma)); ke is the unit constant
+        (KE_EV_ANGSTROM, the default: eV, Angstrom, e; 332.0637: kcal/mol).  parts=True appends ffix (A, 3) and fq (A, 3),
+        F = ffix + fq; fq is -gxyz of charges_vjp_xyz(g=phi) on "grad_path" 2, bit for bit, and q has that path's bits.  Open
+        systems only (no box or cell), no self-energy term, no bonded exclusions: alpha is the only short-range handle.  One
+        call costs about one gradient call of the pair-list path; it touches no training state and works without train_init."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
+        B, A = len(offsets) - 1, int(offsets[-1])
+        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
+            raise EpnnError("coulomb_xyz: array shapes do not match offsets")
+        q = np.empty((A,), dtype=np.float32)
+        phi = np.empty((A,), dtype=np.float32)
+        E = np.empty((B,), dtype=np.float64)
+        F = np.empty((A, 3), dtype=np.float32)
+        ffix = np.empty((A, 3), dtype=np.float32) if parts else None
+        fq = np.empty((A, 3), dtype=np.float32) if parts else None
+        check(self.lib.epnn_coulomb_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), float(ke), float(alpha), fptr(q),
+                                        fptr(phi), E.ctypes.data_as(C.POINTER(C.c_double)), fptr(F), fptr(ffix) if parts else None,
+                                        fptr(fq) if parts else None), self.lib)
+        return (q, phi, E, F, ffix, fq) if parts else (q, phi, E, F)
 
     def get_gradients(self):
         g = np.empty((self.param_count(),), dtype=np.float32)

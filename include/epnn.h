@@ -390,7 +390,51 @@ int epnn_charges_jvp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offse
 int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                     const float *cell, int K, const float *vxyz, const float *vstrain, const float *vQ, float *q_out,
                                     float *tq_out);
-/* ---- training on periodic and large systems.  epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
+/* ---- electrostatics of the predicted charges in one call: charges, potential, Coulomb energy and total forces.  Replaces the three
+ * steps of INTEGRATION.md, "Forces from the charges" (a forward, the caller's own all-pairs sum for g = dE/dq, a gradient call with
+ * a second forward inside) for the potential most used with a charge model.  Per molecule b of the flat batch, over its real atoms
+ * only (the N - n padded partners have no coordinates: they enter the model's message sums as in every entry, not these sums):
+ *     kappa(D) = 1 / D                  alpha == 0: bare Coulomb
+ *              = erf(alpha D) / D       alpha  > 0: Gaussian-smeared charges of equal width sigma, alpha = 1 / (2 sigma)
+ *     phi_i    = ke sum_{j != i} q_j kappa(D_ij)                                         = dE/dq_i
+ *     E_b      = 1/2 sum_i q_i phi_i                                                     = ke sum_{i<j} q_i q_j kappa(D_ij)
+ *     ffix_i   = -ke q_i sum_{j != i} q_j kappa'(D_ij) (r_i - r_j) / D_ij                = -dE/dr_i at fixed q
+ *     fq_i     = -sum_k phi_k dq_k/dr_i        = -gxyz_out of epnn_charges_vjp_xyz with g = phi
+ *     f_i      = ffix_i + fq_i  (one float32 add per component)                          = -dE/dr_i, total
+ * ke is the caller's unit constant (14.3996454784255 eV A / e^2, 332.0637 kcal A / mol e^2).  q is the model's output, so sum q = Q
+ * holds by construction and no constraint term appears.  Open systems only: the entry takes no box or cell (periodic electrostatics
+ * need an Ewald or PME sum whose real-space range is far beyond the model's cutoff).  No self-energy term (for alpha > 0 the
+ * Gaussians' self-energy -ke alpha / sqrt(pi) sum q_i^2 is left out; it depends on q alone), no bonded exclusions or scaling of
+ * near neighbours: every pair of a molecule counts in full, and alpha is the only short-range handle.
+ * Outputs (host): q_out[A], phi_out[A], e_out[B] in float64 (a float32 energy of a 100 000-atom system loses the digits its forces
+ * live in), f_out[A][3]; ffix_out[A][3] and fq_out[A][3] may each be NULL, and the other outputs have the same bits either way.
+ * Contract: that of epnn_charges_jvp_xyz_cell, word for word where it applies: the pair-list path whatever "grad_path" says; works
+ * on a handle that never trained, uses the current weights, leaves weights, gradients, Adam state and step count untouched, waits
+ * first for a "train_async" step in flight; refuses by name update layers other than [32, 32], a partitioned handle, bad offsets,
+ * a molecule that does not fit N, a null required pointer, ke not finite, alpha negative or not finite, two coincident atoms (the
+ * handle stays usable); h_dim below 48 runs zero-padded; bit-reproducible (no float atomics, every sum in a fixed order); a
+ * molecule's rows do not depend on the rest of the batch at the same N.
+ * Bits: q_out has the bits of epnn_charges_vjp_xyz on "grad_path" 2; fq_out is bit for bit -gxyz_out of that entry called with
+ * g = phi_out; f_out == ffix_out + fq_out in float32.  The call is that entry's pair-list call with one forward: set-up and
+ * checkpointed forward, an all-pairs Coulomb sweep on that forward's charges which writes phi into the backward's seed on the
+ * device, the backward, one download.  Pair terms are float32 (one reciprocal square root per pair; erff, and expf or a series,
+ * for alpha > 0) of displacements taken in float64 and rounded once, so atoms far from the origin lose nothing; phi, ffix and E
+ * accumulate in float64: each is within 2e-6 of the sum of its absolute terms, whatever n.
+ * Device scratch: the gradient path's rows (the formula at epnn_charges_vjp_xyz, without the 4 A bytes of its staged g) plus what
+ * the Coulomb sweep adds -- its float64 partial rows [cpieces][A][4], the atoms' energy shares, phi and ffix, E, the task table:
+ *     bytes = gradient path's + A (20 + 32 cpieces) + 8 B + 16 ctasks
+ * and, term by term, with the staged inputs counted with this call's bytes (not with their buffer's capacity):
+ *     bytes = A (1344 + 4 nx + 324 T + 256 pieces + 32 cpieces) + 16 (gtasks + ctasks) + 1116 max(listed pairs, 1) + 56 B + 8240
+ *                                                                  (plus up to 256 per buffer of rounding; 44 buffers)
+ * pieces and gtasks as on the gradient path: pieces = max over the molecules of p(n) = min(16, ceil(2048 / ceil(n / 16))), gtasks =
+ * sum of ceil(n / 16) p(n); cpieces = max of c(n) = 1 up to 64 atoms, else min(32, ceil(n / 128), ceil(2048 / ceil(n / 64)));
+ * ctasks = one per wavefront of molecules of up to 64 atoms packed in batch order plus ceil(n / 64) c(n) per larger molecule.
+ * Shared with the other pair-list calls: the handle keeps the scratch of its largest call.  After a call epnn_last_stats gives
+ * out[0] = listed pairs, out[1] = 0, out[2] = bytes of device scratch the call used. */
+int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                     double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out,
+                     float *ffix_out, float *fq_out);
+/* ---- training on periodic and large systems. epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
  * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
  * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's
  * flat vector (epnn_get_gradients); apply != 0 adds the guarded all-reduce and the Adam step, as in epnn_train_step_xyz.  Two

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""The electrostatics call coulomb_xyz beside the pair-list gradient call charges_vjp_xyz ("grad_path" = 2) of the same system, on
+one handle (profiles/r16_coulomb.txt):
+  * the 2220-atom protein (open);
+  * a 10 000-atom open cluster (synth.periodic_box_system's atoms without its box, as tools/bench_grad_large.py runs them);
+  * 1024 QM9-sized molecules at N = 29.
+    python tools/bench_coulomb.py [--systems protein,cluster10000,qm9] [--rounds 5] [--alpha 0.0]
+The two calls alternate, `--rounds` times; every figure is wall clock per blocking host call (uploads, the pair count's round
+trip and downloads included) over enough calls for a window of about half a second, after a warm-up call of each kind.  Printed
+per system: the median and the range over the rounds, the ratio of the medians coulomb / gradient, the device scratch the library
+reports (epnn_last_stats()[2]) beside the formula of include/epnn.h, and checks of what was timed: q of the two calls (bits), fq
+against -gxyz of the gradient call seeded with phi (bits), and sum_i f_i over the batch.
+    python tools/bench_coulomb.py --trace [--systems ...]
+makes three calls of coulomb_xyz per system and nothing else: the run to put under a kernel trace, whose k_cl_* rows are the Coulomb
+kernels."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from epnn_amd import charge_gn, checkpoint, synth  # noqa: E402
+from epnn_amd.engine import Engine  # noqa: E402
+
+
+def gl_pieces(n):
+    tiles = (n + 15) // 16
+    return min(16, max(1, (2048 + tiles - 1) // tiles))
+
+
+def cl_pieces(n):
+    return 1 if n <= 64 else max(1, min(32, (n + 127) // 128, (2048 + (n + 63) // 64 - 1) // ((n + 63) // 64)))
+
+
+def cl_tasks(ns):
+    """the Coulomb sweep's wavefronts: molecules of up to 64 atoms packed in batch order, blocks x pieces for larger ones"""
+    tasks, b = 0, 0
+    while b < len(ns):
+        if ns[b] <= 64:
+            tot = 0
+            while b < len(ns) and ns[b] <= 64 and tot + ns[b] <= 64:
+                tot += ns[b]
+                b += 1
+            tasks += 1
+        else:
+            tasks += (ns[b] + 63) // 64 * cl_pieces(ns[b])
+            b += 1
+    return tasks
+
+
+def scratch_formula(ns, P, nx, T):
+    A, B = sum(ns), len(ns)
+    gtasks = sum((n + 15) // 16 * gl_pieces(n) for n in ns)
+    return (A * (1344 + 4 * nx + 324 * T + 256 * max(map(gl_pieces, ns)) + 32 * max(map(cl_pieces, ns))) + 16 * (gtasks + cl_tasks(ns))
+            + 1116 * max(P, 1) + 56 * B + 8240)
+
+
+def window(fn, seconds=0.5):
+    """seconds per call over a window of about `seconds` (at least 3 calls), the first call's time deciding the count"""
+    t0 = time.perf_counter()
+    out = fn()
+    one = time.perf_counter() - t0
+    reps = max(3, int(seconds / max(one, 1e-6)))
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        out = fn()
+    return (time.perf_counter() - t0) / reps, out
+
+
+def load(system):
+    if system == "protein":
+        xyz, x, Q, _ = charge_gn.read_xyz(os.path.join(ROOT, "tests/golden/protein/6qlp_capped.xyz"), 9)
+        return "protein 6qlp_capped, open", np.array([0, len(x)], np.int32), xyz, x, np.array([Q], np.float32), len(x)
+    if system.startswith("cluster"):
+        offsets, xyz, x, Q, N, _ = synth.periodic_box_system(int(system[7:]), seed=0)
+        return f"{int(system[7:])} atoms, open cluster", offsets, xyz, x, Q, N
+    if system == "qm9":
+        offsets, xyz, x, Q, N = synth.qm9_like_batch(B=1024, seed=0, N=29)
+        return "1024 QM9-sized molecules, N = 29", offsets, xyz, x, Q, N
+    raise SystemExit(f"unknown system {system}")
+
+
+def main():
+    arg = lambda name, default: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+    systems = arg("--systems", "protein,cluster10000,qm9").split(",")
+    rounds, alpha = int(arg("--rounds", "5")), float(arg("--alpha", "0.0"))
+    w = checkpoint.load_epnn_weights(os.path.join(ROOT, "models/decay_model_weights"))
+    T = len(w["msg"])
+    eng = Engine(nx=9, T=T)
+    eng.set_weights(w)
+    eng.set_option("grad_path", 2)
+    for system in systems:
+        name, offsets, xyz, x, Q, N = load(system)
+        A = int(offsets[-1])
+        if "--trace" in sys.argv:
+            for _ in range(3):
+                eng.coulomb_xyz(offsets, xyz, x, Q, N, alpha=alpha)
+            print(json.dumps({"workload": name, "atoms": A, "calls": 3, "alpha": alpha}), flush=True)
+            continue
+        g = np.random.default_rng(0).normal(size=A).astype(np.float32)
+        calls = {"coulomb": lambda: eng.coulomb_xyz(offsets, xyz, x, Q, N, alpha=alpha, parts=True),
+                 "gradient": lambda: eng.charges_vjp_xyz(offsets, xyz, x, Q, g, N)}
+        for fn in calls.values():                                    # warm-up: code objects, scratch of the largest call
+            fn()
+        times = {k: [] for k in calls}
+        outs = {}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t, outs[k] = window(fn)
+                times[k].append(t * 1e3)
+        q, phi, E, F, ffix, fq = outs["coulomb"]
+        st = eng.last_stats() if calls["coulomb"]() else None
+        seeded = eng.charges_vjp_xyz(offsets, xyz, x, Q, phi, N)
+        sg = eng.last_stats()
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        ns = [int(n) for n in np.diff(offsets)]
+        line = {"workload": name, "atoms": A, "molecules": len(ns), "near_pairs": int(st[0]), "rounds": rounds, "alpha": alpha}
+        for k, t in times.items():
+            line[k + "_ms_median"] = round(med[k], 3)
+            line[k + "_ms_range"] = [round(min(t), 3), round(max(t), 3)]
+        line.update({"coulomb_over_gradient": round(med["coulomb"] / med["gradient"], 3), "coulomb_scratch_bytes": int(st[2]),
+                     "coulomb_scratch_formula_bytes": scratch_formula(ns, int(st[0]), 9, T), "gradient_scratch_bytes": int(sg[2]),
+                     "q_bits_equal_gradient_call": bool(np.array_equal(q, outs["gradient"][0])),
+                     "fq_bits_equal_minus_gxyz_of_phi": bool(np.array_equal(fq, -seeded[1])),
+                     "energy_sum": float(E.sum()), "max_abs_f": float(np.abs(F).max()), "max_abs_ffix": float(np.abs(ffix).max()),
+                     "max_abs_fq": float(np.abs(fq).max()), "max_abs_sum_f": float(np.abs(F.sum(0, dtype=np.float64)).max())})
+        print(json.dumps(line), flush=True)
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
