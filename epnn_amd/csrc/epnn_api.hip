@@ -17,6 +17,7 @@
 #include "epnn_large.hip.h"
 #include "epnn_dense.hip.h"
 #include "epnn_train.hip.h"
+#include "epnn_geometry.h"
 
 thread_local std::string g_epnn_err;
 

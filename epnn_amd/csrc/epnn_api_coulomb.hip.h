@@ -33,7 +33,7 @@ static int cl_build_tasks(int B, const int32_t *offsets, std::vector<int4> &task
 }
 
 static int coulomb_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                        const float *Q, double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
+                        const float *Q, const HostGeo &geo, double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
                         float *fq_out) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
@@ -46,7 +46,7 @@ static int coulomb_impl(epnn_handle *h, const char *name, int B, int N, const in
     const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), co_bytes = o_E + (size_t)B * 8;
     const size_t more[2] = {co_bytes, (cpieces * 4 + 1) * (size_t)A * 8};
     GlGrad r;
-    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, nullptr, nullptr, &span_t, 1, more, 2, false, r)) return 1;
+    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, &span_t, 1, more, 2, false, r)) return 1;
     const GlCall &c = r.c;
     char *co = c.dw + r.o_more[0];
     float *phi = reinterpret_cast<float *>(co), *ffix = phi + A;
@@ -67,7 +67,7 @@ static int coulomb_impl(epnn_handle *h, const char *name, int B, int N, const in
                        share);
     hipLaunchKernelGGL(k_cl_energy, dim3((unsigned)B), dim3(64), 0, h->stream, (const double *)share, c.d_moff, E);
     HIPCHK(hipGetLastError());
-    if (gl_grad_backward(h, gl, r, B, nullptr, nullptr, false)) return 1;
+    if (gl_grad_backward(h, gl, r, B, false)) return 1;
     // ---- one download: q | gxyz | flag | (the unused strain rows and the step to the next buffer) | phi | ffix | flag | E
     const char *from = reinterpret_cast<const char *>(r.q_fin);
     const size_t nbytes = (size_t)(co + co_bytes - from), at_co = (size_t)(co - from);
@@ -109,7 +109,7 @@ extern "C" int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *off
     if ((kbits & expo) == expo) EPNN_FAIL("%s: ke must be finite", name);
     if ((abits & expo) == expo || ((abits >> 63) && (abits << 1)))
         EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
-    std::vector<EpnnCell> cells;
-    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, nullptr, 1, q_out, f_out, cells)) return 1;
-    return coulomb_impl(h, name, B, N, offsets, xyz, x, Q, ke, alpha, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
+    GeoArg arg;                                                  // (open molecules: the entry takes no cell)
+    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, nullptr, 1, q_out, f_out, arg)) return 1;
+    return coulomb_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
 }

@@ -375,40 +375,31 @@ static int make_front_args(epnn_handle *h, const float *d_xyz, FrontArgs &F) {
     }
     return 0;
 }
-// d_box: the box rows [B][3] of a periodic forward (minimum-image distances), null for open molecules; cell_kind 2: d_box points
-// to the EpnnCell records [B] of general cells instead
-static int run_frontend_xyz(epnn_handle *h, const FrontArgs &F, const float *d_box = nullptr, int cell_kind = 1) {
-    const unsigned rows = (unsigned)((F.A + 3) / 4);
-    const EpnnCell *d_cell = reinterpret_cast<const EpnnCell *>(d_box);
-    if (d_box && cell_kind == 2) hipLaunchKernelGGL(k_front_count_cell, dim3(rows), dim3(256), 0, h->stream, F, d_cell);
-    else if (d_box) hipLaunchKernelGGL(k_front_count_pbc, dim3(rows), dim3(256), 0, h->stream, F, d_box);
-    else hipLaunchKernelGGL(k_front_count, dim3(rows), dim3(256), 0, h->stream, F);
-    hipLaunchKernelGGL(k_front_scan_both, dim3(1), dim3(1024), 0, h->stream, F);
-    if (d_box && cell_kind == 2) hipLaunchKernelGGL(k_front_fill_cell, dim3(rows), dim3(256), 0, h->stream, F, d_cell);
-    else if (d_box) hipLaunchKernelGGL(k_front_fill_pbc, dim3(rows), dim3(256), 0, h->stream, F, d_box);
-    else hipLaunchKernelGGL(k_front_fill, dim3(rows), dim3(256), 0, h->stream, F);
-    hipLaunchKernelGGL(k_front_link, dim3((unsigned)std::min<size_t>(((size_t)h->pcap + 255) / 256, 1024)), dim3(256), 0, h->stream, F);
+// geo: the forward's geometry, its rows [B] on the device (minimum-image distances in a box or a cell)
+static int run_frontend_xyz(epnn_handle *h, const FrontArgs &F, const DevGeo &geo) {
+    launch_front_count(h, F, geo);
+    launch_front_fill(h, F, geo);                   // (F.pcap is the handle's pcap: make_front_args)
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 static bool wave_front_ok(const epnn_handle *h) { return h->opt_wave_front && h->cfg.e_dim == EPNN_EDIM && h->edge_res < 1e-8; }
 static int enqueue_forward_planned(epnn_handle *h, const float *d_xyz, const float *d_x, const float *d_Q, float *d_q, bool front_ok,
-                                   const float *d_box, int cell_kind);
-// d_box: box rows [B][3] on the device (periodic forward) or null.  A periodic forward always takes the separate front-end: the
-// fused kernels read its pair list (molecules of up to 32 atoms), everything larger is tiled, as with "wave_front" 0.
+                                   const DevGeo &geo);
+// A periodic forward (geo: a box or a cell) always takes the separate front-end: the fused kernels read its pair list (molecules
+// of up to 32 atoms), everything larger is tiled, as with "wave_front" 0.
 static int enqueue_forward_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz,
-                               const float *d_x, const float *d_Q, float *d_q, const float *d_box = nullptr, int cell_kind = 1) {
+                               const float *d_x, const float *d_Q, float *d_q, const DevGeo &geo) {
     HIPCHK(hipSetDevice(h->device));
     if (pack_weights(h)) return 1;
-    const bool front_ok = !d_box && wave_front_ok(h);
+    const bool front_ok = !geo.periodic() && wave_front_ok(h);
     if (build_plan(h, B, N, offsets, front_ok)) return 1;
     // from here to the first row exchange of a partitioned system a failure is reported to the other processes (comm_guard)
     if (large_exchanges_over_rccl(h, 1)) h->guard_pending = true;
-    return comm_guard_exit(h, enqueue_forward_planned(h, d_xyz, d_x, d_Q, d_q, front_ok, d_box, cell_kind), "partitioned forward (row exchange)");
+    return comm_guard_exit(h, enqueue_forward_planned(h, d_xyz, d_x, d_Q, d_q, front_ok, geo), "partitioned forward (row exchange)");
 }
 static int enqueue_forward_planned(epnn_handle *h, const float *d_xyz, const float *d_x, const float *d_Q, float *d_q, bool front_ok,
-                                   const float *d_box, int cell_kind) {
+                                   const DevGeo &geo) {
     const Plan &P = h->plan;
     // Small molecules (fused kernel): the wavefront builds its molecule's pair list itself (slots for every i<j pair, so
     // nothing can overflow; G products in the 16-dimensional edge basis, used only when it represents the features to
@@ -443,9 +434,9 @@ static int enqueue_forward_planned(epnn_handle *h, const float *d_xyz, const flo
     const FrontArgs *front_later = nullptr;
     if (!pure) {
         if (make_front_args(h, d_xyz, F)) return 1;
-        if (!d_box && h->opt_large_merge && !P.large_list.empty() && (front_small || P.fused_count() == 0)) front_later = &F;
+        if (!geo.periodic() && h->opt_large_merge && !P.large_list.empty() && (front_small || P.fused_count() == 0)) front_later = &F;
         else {
-            if (run_frontend_xyz(h, F, d_box, cell_kind)) return 1;
+            if (run_frontend_xyz(h, F, geo)) return 1;
             if (ev) { HIPCHK(hipEventRecord(ev[1], h->stream)); *ev_has |= 1; }
         }
     }
@@ -515,139 +506,52 @@ static int finish_forward(epnn_handle *h) {
     EPNN_FAIL("forward: capacity regrow did not converge");
 }
 
-// Box rows of a periodic forward (include/epnn.h): finite, >= 0, and a periodic length of at least twice the cutoff
-static int check_box(int B, const float *box, double cutoff, const char *what) {
-    if (!box) EPNN_FAIL("%s: null box", what);
-    for (int b = 0; b < B; ++b)
-        for (int k = 0; k < 3; ++k) {
-            const float L = box[3 * b + k];
-            uint32_t bits;                        // (the library is built with -ffinite-math-only: std::isfinite would fold to true)
-            memcpy(&bits, &L, 4);
-            if ((bits & 0x7f800000u) == 0x7f800000u || L < 0.f)
-                EPNN_FAIL("%s: box[%d][%d] = %g: a length must be finite and >= 0 (0: open axis)", what, b, k, (double)L);
-            if (L > 0.f && (double)L < 2.0 * cutoff)
-                EPNN_FAIL("%s: box[%d][%d] = %g is shorter than twice the cutoff (%g)", what, b, k, (double)L, 2.0 * cutoff);
+// Every enqueue of a device-resident forward, a redo too: its geometry's rows onto the device in the status slot it uses (the forward
+// two calls back, which used that slot, has been waited for), then the enqueue.  rows empty: open, or rows on the device already.
+static int enqueue_forward_rows(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz, const float *d_x, const float *d_Q,
+                                float *d_q, DevGeo geo, const std::vector<char> &rows) {
+    if (!rows.empty()) {
+        const size_t stride = (rows.size() + 255) & ~size_t(255);
+        bool ok = (h->pin_box.cap >= 2 * stride && h->d_box.cap >= 2 * stride) ||
+                  (hipStreamSynchronize(h->stream) == hipSuccess && !h->pin_box.ensure(2 * stride) && !h->d_box.ensure(2 * stride));
+        if (ok) {
+            char *hp = h->pin_box.as<char>() + h->st_slot * stride, *dp = h->d_box.as<char>() + h->st_slot * stride;
+            memcpy(hp, rows.data(), rows.size());
+            ok = hipMemcpyAsync(dp, hp, rows.size(), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+            geo.rows = dp;
         }
-    return 0;
-}
-
-// General cells (include/epnn.h): validates cell [B][3][3] and prepares what the device needs of every molecule (EpnnCell: the
-// entries, the dual vectors in float64, the constants of the front-end's float32 pre-test).  Refused, naming molecule and axis: a
-// NaN or infinite entry, linearly dependent non-zero rows, a periodic axis whose perpendicular width 1 / |g_k| is below 2 * cutoff.
-static int check_cell(int B, const float *cell, double cutoff, const char *what, std::vector<EpnnCell> &out) {
-    if (!cell) EPNN_FAIL("%s: null cell", what);
-    out.assign((size_t)B, EpnnCell());
-    for (int b = 0; b < B; ++b) {
-        EpnnCell &c = out[b];
-        memset(&c, 0, sizeof(c));
-        double a[3][3], g[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, len[3];
-        int per[3], m = 0;
-        for (int k = 0; k < 3; ++k) {
-            bool nz = false;
-            for (int x = 0; x < 3; ++x) {
-                const float v = cell[9 * b + 3 * k + x];
-                uint32_t bits;                    // (-ffinite-math-only: std::isfinite would fold to true)
-                memcpy(&bits, &v, 4);
-                if ((bits & 0x7f800000u) == 0x7f800000u)
-                    EPNN_FAIL("%s: cell[%d][%d][%d] is not finite (molecule %d, axis %d)", what, b, k, x, b, k);
-                a[k][x] = (double)v;
-                c.a[3 * k + x] = v;
-                nz = nz || v != 0.f;
-            }
-            len[k] = sqrt(a[k][0] * a[k][0] + a[k][1] * a[k][1] + a[k][2] * a[k][2]);
-            if (nz) per[m++] = k;
-        }
-        auto cross = [](const double *u, const double *v, double *o) {
-            o[0] = u[1] * v[2] - u[2] * v[1]; o[1] = u[2] * v[0] - u[0] * v[2]; o[2] = u[0] * v[1] - u[1] * v[0];
-        };
-        auto dot = [](const double *u, const double *v) { return u[0] * v[0] + u[1] * v[1] + u[2] * v[2]; };
-        if (m == 3) {
-            double c12[3], c20[3], c01[3];
-            cross(a[1], a[2], c12); cross(a[2], a[0], c20); cross(a[0], a[1], c01);
-            const double det = dot(a[0], c12);
-            if (!(fabs(det) > 1e-12 * len[0] * len[1] * len[2]))
-                EPNN_FAIL("%s: the rows of cell[%d] (molecule %d) are linearly dependent (axis 2 lies in the plane of axes 0 and 1)", what, b, b);
-            for (int x = 0; x < 3; ++x) { g[0][x] = c12[x] / det; g[1][x] = c20[x] / det; g[2][x] = c01[x] / det; }
-        } else if (m == 2) {
-            const int p = per[0], q = per[1];
-            double n[3], t[3];
-            cross(a[p], a[q], n);
-            const double n2 = dot(n, n);
-            if (!(sqrt(n2) > 1e-12 * len[p] * len[q]))
-                EPNN_FAIL("%s: rows %d and %d of cell[%d] (molecule %d) are linearly dependent (axis %d is parallel to axis %d)", what, p, q, b, b, q, p);
-            cross(a[q], n, t);
-            for (int x = 0; x < 3; ++x) g[p][x] = t[x] / n2;
-            cross(n, a[p], t);
-            for (int x = 0; x < 3; ++x) g[q][x] = t[x] / n2;
-        } else if (m == 1) {
-            const int p = per[0];
-            for (int x = 0; x < 3; ++x) g[p][x] = a[p][x] / (len[p] * len[p]);
-        }
-        double S = 0.0, wmin = 0.0;
-        for (int i = 0; i < m; ++i) {
-            const int k = per[i];
-            const double w = 1.0 / sqrt(dot(g[k], g[k]));
-            if (!(w >= 2.0 * cutoff))
-                EPNN_FAIL("%s: cell[%d] (molecule %d): the perpendicular width of periodic axis %d is %g, below twice the cutoff (%g)", what, b, b,
-                          k, w, 2.0 * cutoff);
-            S += len[k];
-            wmin = i == 0 ? w : std::min(wmin, w);
-        }
-        for (int k = 0; k < 3; ++k)
-            for (int x = 0; x < 3; ++x) c.g[3 * k + x] = g[k][x];
-        // the front-end's pre-test (front_scan_row): X bounds the components of a pre-tested position (S, plus 1024 A along open
-        // directions where there are any), u = 2^-24, pre_eps = 32 u X / w, margin 1.0001 + 96 r + 1024 r^2, r = u X / cutoff
-        const double X = S + (m < 3 ? 1024.0 : 0.0), r = 0x1p-24 * X / cutoff;
-        c.pre_ext = (float)X;
-        c.pre_eps = m ? (float)std::min(0.5, 32.0 * 0x1p-24 * X / wmin * 1.000001) : 0.f;
-        c.pre_margin = (float)((1.0001 + r * (96.0 + 1024.0 * r)) * 1.000001);
+        if (!ok) EPNN_FAIL(geo.kind == GEO_CELL ? "epnn_forward_xyz_cell_dev: cell upload failed" : "epnn_forward_xyz_pbc_dev: box upload failed");
     }
-    return 0;
+    return enqueue_forward_xyz(h, B, N, offsets, d_xyz, d_x, d_Q, d_q, geo);
 }
 
-// the box rows of a forward of the device-resident entry, in the status slot it uses (the forward two calls back, which used the
-// same slot, has been waited for): page-locked copy, one upload on the stream
-static const float *upload_box(epnn_handle *h, int slot, const std::vector<float> &box) {
-    const size_t stride = (box.size() * 4 + 255) & ~size_t(255);
-    if (h->pin_box.cap < 2 * stride || h->d_box.cap < 2 * stride) {
-        if (hipStreamSynchronize(h->stream) != hipSuccess || h->pin_box.ensure(2 * stride) || h->d_box.ensure(2 * stride)) return nullptr;
-    }
-    char *hp = h->pin_box.as<char>() + slot * stride;
-    char *dp = h->d_box.as<char>() + slot * stride;
-    memcpy(hp, box.data(), box.size() * 4);
-    if (hipMemcpyAsync(dp, hp, box.size() * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return nullptr;
-    return reinterpret_cast<const float *>(dp);
-}
-
-// h_box: host box rows of a periodic forward, uploaded by every enqueue of it (a redo too); d_box: box rows already on the device
-// (staged with the host entry's inputs).  Both null: open molecules.
+// h_geo: a periodic forward's rows on the host, uploaded by every enqueue of it; staged: its rows already on the device (staged
+// with the host entry's inputs).  At most one of them is periodic; neither: open molecules.
 static int forward_xyz_dev_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz, const float *d_x,
-                                const float *d_Q, float *d_q_out, const float *h_box, const float *d_box, int cell_kind = 1) {
+                                const float *d_Q, float *d_q_out, const HostGeo &h_geo, const DevGeo &staged) {
     auto &pd = h->pending;
     const void *key[4] = {d_xyz, d_x, d_Q, d_q_out};
-    std::vector<float> boxv;
-    // (cell_kind 2: h_box / d_box are EpnnCell records, 30 words a molecule, handled as the box rows are)
-    if (h_box) boxv.assign(h_box, h_box + (size_t)B * (cell_kind == 2 ? sizeof(EpnnCell) / 4 : 3));
+    const DevGeo geo = h_geo.periodic() ? geo_on_device(h_geo, nullptr) : staged;      // (h_geo's rows get their place at the enqueue)
+    std::vector<char> rows;
+    if (h_geo.periodic()) rows.assign(h_geo.raw(), h_geo.raw() + h_geo.bytes(B));
     // The SAME forward again (same batch, same device buffers: a trajectory, a benchmark loop) while the previous one may still need
     // a look at its status: enqueue first, check after -- nothing is (re)allocated for a plan that is reused, the two forwards
     // report through two status slots, and a forward that did overflow is redone with its successor behind it.  (Waiting for the
     // previous forward before enqueueing left the GPU idle for the host's 15 us between any two forwards of the tiled path.)
     const Plan &P0 = h->plan;
-    // (a periodic forward is the same forward only in the same cells: a changed box, as in an NPT run, waits for the one before)
+    // (a periodic forward is the same forward only in the same geometry, kind and rows: a changed box, as in an NPT run, waits for
+    // the one before)
     const bool ahead = h->opt_forward_ahead && pd.active && memcmp(pd.key, key, sizeof(key)) == 0 && P0.valid && P0.B == B && P0.N == N &&
                        (int)P0.offsets.size() == B + 1 && memcmp(P0.offsets.data(), offsets, (B + 1) * sizeof(int)) == 0 && h->part_world == 1 &&
-                       !d_box && pd.box.size() == boxv.size() &&
-                       (boxv.empty() || memcmp(pd.box.data(), boxv.data(), boxv.size() * 4) == 0);      // (bytes: cell records hold doubles)
+                       !staged.periodic() && pd.geo_kind == h_geo.kind && pd.geo_rows.size() == rows.size() &&
+                       (rows.empty() || memcmp(pd.geo_rows.data(), rows.data(), rows.size()) == 0);      // (bytes: cell records hold doubles)
     if (!ahead && pd.active && finish_forward(h)) return 1;     // previous call may still need a regrow
     const int old_slot = pd.slot;
     std::function<int()> old_redo;
     if (ahead) old_redo = pd.redo;
     h->st_slot = ahead ? (old_slot ^ 1) : h->st_slot;
     h->h_status = h->h_status_base + 4 * h->st_slot;
-    const float *db = d_box;
-    if (!boxv.empty() && !(db = upload_box(h, h->st_slot, boxv)))
-        EPNN_FAIL(cell_kind == 2 ? "epnn_forward_xyz_cell_dev: cell upload failed" : "epnn_forward_xyz_pbc_dev: box upload failed");
-    if (enqueue_forward_xyz(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, db, cell_kind)) return 1;
+    if (enqueue_forward_rows(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, geo, rows)) return 1;
     if (h->last_front && !ahead) {            // nothing can overflow with the in-kernel front-end: no need to look at this forward
         pd.active = false;                    // again, the caller may queue the next one right away (the headline loop: nothing else
         return 0;                             // is done per call)
@@ -655,11 +559,8 @@ static int forward_xyz_dev_impl(epnn_handle *h, int B, int N, const int32_t *off
     HIPCHK(hipEventRecord(h->ev_done[h->st_slot], h->stream));
     const bool new_active = !h->last_front;
     std::vector<int> offs(offsets, offsets + B + 1);
-    auto redo = [h, B, N, offs, d_xyz, d_x, d_Q, d_q_out, boxv, d_box, cell_kind]() {
-        const float *db = d_box;
-        if (!boxv.empty() && !(db = upload_box(h, h->st_slot, boxv)))
-            EPNN_FAIL(cell_kind == 2 ? "epnn_forward_xyz_cell_dev: cell upload failed" : "epnn_forward_xyz_pbc_dev: box upload failed");
-        const int rc = enqueue_forward_xyz(h, B, N, offs.data(), d_xyz, d_x, d_Q, d_q_out, db, cell_kind);
+    auto redo = [h, B, N, offs, d_xyz, d_x, d_Q, d_q_out, geo, rows]() {
+        const int rc = enqueue_forward_rows(h, B, N, offs.data(), d_xyz, d_x, d_Q, d_q_out, geo, rows);
         if (!rc) (void)hipEventRecord(h->ev_done[h->st_slot], h->stream);
         return rc;
     };
@@ -693,31 +594,33 @@ static int forward_xyz_dev_impl(epnn_handle *h, int B, int N, const int32_t *off
     pd.redo = redo;
     pd.slot = h->st_slot;
     memcpy(pd.key, key, sizeof(key));
-    pd.box.swap(boxv);
+    pd.geo_kind = h_geo.kind;
+    pd.geo_rows.swap(rows);
     return 0;
 }
 
 extern "C" int epnn_forward_xyz_dev(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz,
                                     const float *d_x, const float *d_Q, float *d_q_out) {
     if (!h || !offsets || !d_xyz || !d_x || !d_Q || !d_q_out) EPNN_FAIL("epnn_forward_xyz_dev: null argument");
-    return forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, nullptr, nullptr);
+    return forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, HostGeo{}, DevGeo{});
 }
 
 extern "C" int epnn_forward_xyz_cell_dev(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz, const float *d_x,
                                          const float *d_Q, const float *cell, float *d_q_out) {
     if (!h || !offsets || !d_xyz || !d_x || !d_Q || !d_q_out) EPNN_FAIL("epnn_forward_xyz_cell_dev: null argument");
     if (B < 1) EPNN_FAIL("epnn_forward_xyz_cell_dev: empty batch");
-    std::vector<EpnnCell> cells;
-    if (check_cell(B, cell, (double)h->cfg.cutoff, "epnn_forward_xyz_cell_dev", cells)) return 1;
-    return forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, reinterpret_cast<const float *>(cells.data()), nullptr, 2);
+    GeoArg arg;
+    if (arg.cell(B, cell, (double)h->cfg.cutoff, "epnn_forward_xyz_cell_dev")) return 1;
+    return forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, arg.geo, DevGeo{});
 }
 
 extern "C" int epnn_forward_xyz_pbc_dev(epnn_handle *h, int B, int N, const int32_t *offsets, const float *d_xyz, const float *d_x,
                                         const float *d_Q, const float *box, float *d_q_out) {
     if (!h || !offsets || !d_xyz || !d_x || !d_Q || !d_q_out) EPNN_FAIL("epnn_forward_xyz_pbc_dev: null argument");
     if (B < 1) EPNN_FAIL("epnn_forward_xyz_pbc_dev: empty batch");
-    if (check_box(B, box, (double)h->cfg.cutoff, "epnn_forward_xyz_pbc_dev")) return 1;
-    return forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, box, nullptr);
+    GeoArg arg;
+    if (arg.box(B, box, (double)h->cfg.cutoff, "epnn_forward_xyz_pbc_dev")) return 1;
+    return forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, d_q_out, arg.geo, DevGeo{});
 }
 
 // Row-block partition of a SINGLE large system over `world` processes: the all-pairs sweep -- all of
@@ -748,10 +651,9 @@ extern "C" int epnn_sync(epnn_handle *h) {
 // its arrays at once), uploads + kernel + download of the charges are queued, and the call returns without waiting for
 // the GPU.  end: waits and hands the charges over.  One forward per handle between begin and end; several handles
 // (engine.Pipeline) keep several batches in flight.
-// box: host box rows [B][3] of a periodic forward (staged with the other inputs), or null; cell_kind 2: the EpnnCell records [B] of
-// general cells instead
+// geo: the forward's geometry, its rows [B] on the host (staged with the other inputs)
 static int forward_xyz_begin_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                  const float *box, int cell_kind = 1) {
+                                  const HostGeo &geo) {
     HIPCHK(hipSetDevice(h->device));
     if (h->hostcall.active) EPNN_FAIL("epnn_forward_xyz_begin: collect the previous forward with epnn_forward_xyz_end first");
     if (B < 1) EPNN_FAIL("epnn_forward_xyz: empty batch");
@@ -761,8 +663,8 @@ static int forward_xyz_begin_impl(epnn_handle *h, int B, int N, const int32_t *o
     if (h->pending.active && finish_forward(h)) return 1;
     auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
     const size_t n_xyz = (size_t)A * 3, n_x = (size_t)A * nx;
-    const size_t o_x = up256(n_xyz * 4), o_Q = o_x + up256(n_x * 4), o_box = o_Q + up256((size_t)B * 4),
-                 box_bytes = (size_t)B * (cell_kind == 2 ? sizeof(EpnnCell) : 12), in_bytes = box ? o_box + box_bytes : o_Q + (size_t)B * 4;
+    const size_t o_x = up256(n_xyz * 4), o_Q = o_x + up256(n_x * 4), o_geo = o_Q + up256((size_t)B * 4),
+                 in_bytes = geo.periodic() ? o_geo + geo.bytes(B) : o_Q + (size_t)B * 4;
     // ONE host-to-device copy per forward: the inputs are staged behind the plan's index arrays in the same page-locked
     // buffer, whose device mirror has the same layout.  (Separate copies for xyz, x, Q and the index arrays kept the copy
     // engine busy 73 us per batch of 1024 molecules -- of the 86 us the GPU needs for it -- and the kernels of different
@@ -779,7 +681,7 @@ static int forward_xyz_begin_impl(epnn_handle *h, int B, int N, const int32_t *o
     memcpy(stage, xyz, n_xyz * 4);
     memcpy(stage + o_x, x, n_x * 4);
     memcpy(stage + o_Q, Q, (size_t)B * 4);
-    if (box) memcpy(stage + o_box, box, box_bytes);
+    if (geo.periodic()) memcpy(stage + o_geo, geo.rows, geo.bytes(B));
     const size_t from = fresh ? 0 : off;
     HIPCHK(hipMemcpyAsync(h->d_ctl.as<char>() + from, h->pin_ctl.as<char>() + from, off + in_bytes - from, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipEventRecord(h->ev_ctl, h->stream));
@@ -791,8 +693,7 @@ static int forward_xyz_begin_impl(epnn_handle *h, int B, int N, const int32_t *o
     // no device-to-host copy is queued.  With one, the copy engine's queue holds "results of batch k" (which waits for
     // kernel k) in front of "inputs of batch k+1", and the kernels of different handles run one after the other instead
     // of side by side (kernel trace: 0.75 instead of 4.2 kernels in flight).
-    const float *d_box = box ? reinterpret_cast<const float *>(dev + o_box) : nullptr;
-    if (forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, h->pin_out.as<float>(), nullptr, d_box, cell_kind)) return 1;
+    if (forward_xyz_dev_impl(h, B, N, offsets, d_xyz, d_x, d_Q, h->pin_out.as<float>(), HostGeo{}, geo_on_device(geo, dev + o_geo))) return 1;
     h->hostcall.active = true;
     h->hostcall.A = A;
     return 0;
@@ -800,7 +701,7 @@ static int forward_xyz_begin_impl(epnn_handle *h, int B, int N, const int32_t *o
 extern "C" int epnn_forward_xyz_begin(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz,
                                       const float *x, const float *Q) {
     if (!h || !offsets || !xyz || !x || !Q) EPNN_FAIL("epnn_forward_xyz_begin: null argument");
-    return forward_xyz_begin_impl(h, B, N, offsets, xyz, x, Q, nullptr);
+    return forward_xyz_begin_impl(h, B, N, offsets, xyz, x, Q, HostGeo{});
 }
 
 extern "C" int epnn_forward_xyz_end(epnn_handle *h, float *q_out) {
@@ -824,9 +725,10 @@ extern "C" int epnn_forward_xyz_pbc(epnn_handle *h, int B, int N, const int32_t 
                                     const float *Q, const float *box, float *q_out) {
     if (!h || !offsets || !xyz || !x || !Q || !q_out) EPNN_FAIL("epnn_forward_xyz_pbc: null argument");
     if (B < 1) EPNN_FAIL("epnn_forward_xyz_pbc: empty batch");
-    if (check_box(B, box, (double)h->cfg.cutoff, "epnn_forward_xyz_pbc")) return 1;
+    GeoArg arg;
+    if (arg.box(B, box, (double)h->cfg.cutoff, "epnn_forward_xyz_pbc")) return 1;
     if (h->hostcall.active) EPNN_FAIL("epnn_forward_xyz_pbc: collect the forward begun with epnn_forward_xyz_begin first");
-    if (forward_xyz_begin_impl(h, B, N, offsets, xyz, x, Q, box)) return 1;
+    if (forward_xyz_begin_impl(h, B, N, offsets, xyz, x, Q, arg.geo)) return 1;
     return epnn_forward_xyz_end(h, q_out);
 }
 
@@ -834,34 +736,26 @@ extern "C" int epnn_forward_xyz_cell(epnn_handle *h, int B, int N, const int32_t
                                      const float *Q, const float *cell, float *q_out) {
     if (!h || !offsets || !xyz || !x || !Q || !q_out) EPNN_FAIL("epnn_forward_xyz_cell: null argument");
     if (B < 1) EPNN_FAIL("epnn_forward_xyz_cell: empty batch");
-    std::vector<EpnnCell> cells;
-    if (check_cell(B, cell, (double)h->cfg.cutoff, "epnn_forward_xyz_cell", cells)) return 1;
+    GeoArg arg;
+    if (arg.cell(B, cell, (double)h->cfg.cutoff, "epnn_forward_xyz_cell")) return 1;
     if (h->hostcall.active) EPNN_FAIL("epnn_forward_xyz_cell: collect the forward begun with epnn_forward_xyz_begin first");
-    if (forward_xyz_begin_impl(h, B, N, offsets, xyz, x, Q, reinterpret_cast<const float *>(cells.data()), 2)) return 1;
+    if (forward_xyz_begin_impl(h, B, N, offsets, xyz, x, Q, arg.geo)) return 1;
     return epnn_forward_xyz_end(h, q_out);
 }
 
 // ------------------------------------------------------------------------------------------------ edges
-// box: the cell [3] of a periodic call (staged behind the coordinates, minimum-image distances), or null
+// geo: the ONE row of the call's cell (staged behind the coordinates, minimum-image distances)
 static int edges_impl(epnn_handle *h, int n, const float *xyz, int num, double cutoff, double eta, const double *d_mu,
-                      float *e_out, double *c_out, const float *box = nullptr, const EpnnCell *cell = nullptr) {
+                      float *e_out, double *c_out, const HostGeo &geo) {
     const size_t total = (size_t)n * n * num, nn = (size_t)n * n;
-    const size_t o_cell = ((size_t)n * 3 * 4 + 7) & ~size_t(7);         // cell: one EpnnCell record behind the coordinates
-    if (h->s_xyz.ensure(cell ? o_cell + sizeof(EpnnCell) : (size_t)n * 3 * 4 + (box ? 12 : 0)) || h->s_misc.ensure(total * 4 + (c_out ? nn * 8 + 8 : 0))) return 1;
+    const size_t o_geo = geo.kind == GEO_CELL ? ((size_t)n * 3 * 4 + 7) & ~size_t(7) : (size_t)n * 3 * 4;      // (a cell record holds doubles)
+    if (h->s_xyz.ensure(o_geo + geo.bytes(1)) || h->s_misc.ensure(total * 4 + (c_out ? nn * 8 + 8 : 0))) return 1;
     double *d_c = c_out ? reinterpret_cast<double *>(h->s_misc.as<char>() + ((total * 4 + 7) & ~size_t(7))) : nullptr;
     HIPCHK(hipMemcpyAsync(h->s_xyz.p, xyz, (size_t)n * 3 * 4, hipMemcpyHostToDevice, h->stream));
-    if (box) HIPCHK(hipMemcpyAsync(h->s_xyz.as<float>() + (size_t)n * 3, box, 12, hipMemcpyHostToDevice, h->stream));
-    if (cell) HIPCHK(hipMemcpyAsync(h->s_xyz.as<char>() + o_cell, cell, sizeof(EpnnCell), hipMemcpyHostToDevice, h->stream));
+    if (geo.periodic()) HIPCHK(hipMemcpyAsync(h->s_xyz.as<char>() + o_geo, geo.rows, geo.bytes(1), hipMemcpyHostToDevice, h->stream));
     const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 16);
-    if (cell)
-        hipLaunchKernelGGL(k_edges_dense_cell, dim3(grid), dim3(256), 0, h->stream, h->s_xyz.as<float>(),
-                           reinterpret_cast<const EpnnCell *>(h->s_xyz.as<char>() + o_cell), n, num, cutoff, eta, d_mu, h->s_misc.as<float>(), d_c);
-    else if (box)
-        hipLaunchKernelGGL(k_edges_dense_pbc, dim3(grid), dim3(256), 0, h->stream, h->s_xyz.as<float>(), h->s_xyz.as<float>() + (size_t)n * 3,
-                           n, num, cutoff, eta, d_mu, h->s_misc.as<float>(), d_c);
-    else
-        hipLaunchKernelGGL(k_edges_dense, dim3(grid), dim3(256), 0, h->stream, h->s_xyz.as<float>(), n, num, cutoff, eta, d_mu,
-                           h->s_misc.as<float>(), d_c);
+    launch_edges_dense(h, grid, h->s_xyz.as<float>(), geo_on_device(geo, h->s_xyz.as<char>() + o_geo), n, num, cutoff, eta, d_mu,
+                       h->s_misc.as<float>(), d_c);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(e_out, h->s_misc.p, total * 4, hipMemcpyDeviceToHost, h->stream));
     if (c_out) HIPCHK(hipMemcpyAsync(c_out, d_c, nn * 8, hipMemcpyDeviceToHost, h->stream));
@@ -873,13 +767,13 @@ extern "C" int epnn_edges(epnn_handle *h, int n, const float *xyz, float *e_out)
     if (!h || !xyz || !e_out || n < 1) EPNN_FAIL("epnn_edges: bad argument");
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
-    return edges_impl(h, n, xyz, h->model_dim, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), e_out, nullptr);
+    return edges_impl(h, n, xyz, h->model_dim, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), e_out, nullptr, HostGeo{});
 }
 
 // get_init_edges with the reference's own parameters (charge_gn.py:122: num, and the constants 3.0 / 2.0 of :148-161 as
 // arguments): any number of channels, plus the cutoff weights C[n][n] (float64) the reference returns tiled.
 static int edges_ex_impl(epnn_handle *h, int n, const float *xyz, int num, double cutoff, double eta, float *e_out, double *c_out,
-                         const float *box, const EpnnCell *cell = nullptr) {
+                         const HostGeo &geo) {
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
     // mu = np.linspace(0.1, cutoff, num): arange(num)*step + start, last element forced to stop
@@ -890,25 +784,26 @@ static int edges_ex_impl(epnn_handle *h, int n, const float *xyz, int num, doubl
     if (h->d_mu_ex.ensure((size_t)num * sizeof(double))) return 1;
     HIPCHK(hipMemcpyAsync(h->d_mu_ex.p, mu.data(), (size_t)num * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));      // mu is a local
-    return edges_impl(h, n, xyz, num, cutoff, eta, h->d_mu_ex.as<double>(), e_out, c_out, box, cell);
+    return edges_impl(h, n, xyz, num, cutoff, eta, h->d_mu_ex.as<double>(), e_out, c_out, geo);
 }
 extern "C" int epnn_edges_ex(epnn_handle *h, int n, const float *xyz, int num, double cutoff, double eta, float *e_out,
                              double *c_out) {
     if (!h || !xyz || !e_out || n < 1 || num < 2 || !(cutoff > 0.1)) EPNN_FAIL("epnn_edges_ex: bad argument");
-    return edges_ex_impl(h, n, xyz, num, cutoff, eta, e_out, c_out, nullptr);
+    return edges_ex_impl(h, n, xyz, num, cutoff, eta, e_out, c_out, HostGeo{});
 }
 // epnn_edges_ex in the periodic cell box[3]
 extern "C" int epnn_edges_pbc(epnn_handle *h, int n, const float *xyz, const float *box, int num, double cutoff, double eta,
                               float *e_out, double *c_out) {
     if (!h || !xyz || !e_out || n < 1 || num < 2 || !(cutoff > 0.1)) EPNN_FAIL("epnn_edges_pbc: bad argument");
-    if (check_box(1, box, cutoff, "epnn_edges_pbc")) return 1;
-    return edges_ex_impl(h, n, xyz, num, cutoff, eta, e_out, c_out, box);
+    GeoArg arg;
+    if (arg.box(1, box, cutoff, "epnn_edges_pbc")) return 1;
+    return edges_ex_impl(h, n, xyz, num, cutoff, eta, e_out, c_out, arg.geo);
 }
 // epnn_edges_ex in the general cell cell[3][3]
 extern "C" int epnn_edges_cell(epnn_handle *h, int n, const float *xyz, const float *cell, int num, double cutoff, double eta,
                                float *e_out, double *c_out) {
     if (!h || !xyz || !e_out || n < 1 || num < 2 || !(cutoff > 0.1)) EPNN_FAIL("epnn_edges_cell: bad argument");
-    std::vector<EpnnCell> cells;
-    if (check_cell(1, cell, cutoff, "epnn_edges_cell", cells)) return 1;
-    return edges_ex_impl(h, n, xyz, num, cutoff, eta, e_out, c_out, nullptr, cells.data());
+    GeoArg arg;
+    if (arg.cell(1, cell, cutoff, "epnn_edges_cell")) return 1;
+    return edges_ex_impl(h, n, xyz, num, cutoff, eta, e_out, c_out, arg.geo);
 }

@@ -32,11 +32,11 @@ struct GlGrad {
 // spans: the entry's own staged inputs (r.c.d_extra); more[k] bytes: buffers of the entry alone (r.o_more[k]; the first one follows
 // `out` directly); in_cap: epnn_last_stats counts the staged inputs with their buffer's capacity, not with this call's bytes.
 static int gl_grad_forward(epnn_handle *h, GradLarge *gl, const char *where, int B, int N, const int32_t *offsets, const float *xyz,
-                           const float *x, const float *Q, const float *box, const EpnnCell *cells, const GlSpan *spans, int n_spans,
-                           const size_t *more, int n_more, bool in_cap, GlGrad &r) {
+                           const float *x, const float *Q, const HostGeo &geo, const GlSpan *spans, int n_spans, const size_t *more, int n_more,
+                           bool in_cap, GlGrad &r) {
     const int T = h->cfg.T, A = offsets[B];
     GlCall &c = r.c;
-    if (gl_call_count(h, gl, where, B, N, offsets, xyz, x, Q, box, cells, spans, n_spans, c)) return 1;
+    if (gl_call_count(h, gl, where, B, N, offsets, xyz, x, Q, geo, spans, n_spans, c)) return 1;
     const size_t P1 = c.P1, SL = 2 * P1, rowH = (size_t)A * GL_H * 4, rowE = (size_t)A * GL_E * 4, maxp = (size_t)c.maxp;
     const size_t o_h = c.place((size_t)(T + 1) * rowE), o_S = c.place((size_t)T * rowH),
                  o_q = c.place((size_t)(T + 1) * A * 4), o_P = c.place(rowH), o_R = c.place(rowH), o_Yb = c.place(rowH), o_Yc = c.place(rowH),
@@ -57,9 +57,11 @@ static int gl_grad_forward(epnn_handle *h, GradLarge *gl, const char *where, int
     return gl_forward_ckpt(h, c, gl->msg, gl->pas, gl->upd, r.hck, r.Sck, r.qck, r.dP, r.dR, r.Yb, r.Yc, r.partP, r.slotP, r.slotq);
 }
 
+static void launch_gl_pair_xyz(epnn_handle *h, const GlCall &c, const float *gE, double *slotx, int *bad);      // (below)
+
 // The backward from the seed in r.gq (overwritten), down to gxyz (r.gx), the strain derivative (r.gs; want_strain) and the final
 // charges beside them (r.q_fin): everything up to the entry's download.
-static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, const float *box, const EpnnCell *cells, bool want_strain) {
+static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, bool want_strain) {
     const GlCall &c = r.c;
     const int T = h->cfg.T, A = c.G.A, np = c.np;
     const size_t P1 = c.P1;
@@ -113,13 +115,7 @@ static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, con
     HIPCHK(hipGetLastError());
     // ---- edges -> coordinates
     double *slotx = reinterpret_cast<double *>(c.dw + r.o_slotx), *share = want_strain ? reinterpret_cast<double *>(c.dw + r.o_share) : nullptr;
-    if (np > 0) {
-        const unsigned gp = (unsigned)((np + 255) / 256);
-        const double cut = (double)h->cfg.cutoff, eta = (double)h->cfg.eta;
-        if (cells) hipLaunchKernelGGL(k_gl_pair_xyz<2>, dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
-        else if (box) hipLaunchKernelGGL(k_gl_pair_xyz<1>, dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
-        else hipLaunchKernelGGL(k_gl_pair_xyz<0>, dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, (const float *)gE, cut, eta, h->d_mu.as<double>(), slotx, bad);
-    }
+    if (np > 0) launch_gl_pair_xyz(h, c, gE, slotx, bad);
     hipLaunchKernelGGL(k_gl_atom_xyz, dim3(gA), dim3(256), 0, h->stream, A, inc, (const double *)slotx, gx, share);
     if (share) hipLaunchKernelGGL(k_g_strain_mol, dim3((unsigned)B), dim3(64), 0, h->stream, (const double *)share, c.d_moff, gs);
     HIPCHK(hipGetLastError());
@@ -127,19 +123,29 @@ static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, con
     return 0;
 }
 
-static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                  const float *g, float *q_out, float *gxyz_out, const float *box, const EpnnCell *cells,
-                                  float *gstrain_out) {
+// The listed pairs' edge gradients gE -> their coordinate slots, in the call's geometry.  (Behind its caller: kernels are emitted in the
+// order the host code first names them, and a build's device listing is compared with its parent's.)
+static void launch_gl_pair_xyz(epnn_handle *h, const GlCall &c, const float *gE, double *slotx, int *bad) {
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((c.np + 255) / 256)), dim3(256), 0, h->stream, c.L, c.np, c.d_molof, c.d_xyz, c.geo.words(),
+                           gE, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), slotx, bad);
+    };
+    if (c.geo.kind == GEO_CELL) launch(k_gl_pair_xyz<GEO_CELL>);
+    else if (c.geo.kind == GEO_BOX) launch(k_gl_pair_xyz<GEO_BOX>);
+    else launch(k_gl_pair_xyz<GEO_OPEN>);
+}
+
+static int charges_vjp_large_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                  const float *g, float *q_out, float *gxyz_out, const HostGeo &geo, float *gstrain_out) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
     const int A = offsets[B];
-    const char *name = cells ? "epnn_charges_vjp_xyz_cell" : box ? "epnn_charges_vjp_xyz_pbc" : "epnn_charges_vjp_xyz";
     const std::string where = std::string(name) + " (pair-list path)";
     const GlSpan span_g{g, (size_t)A * 4, false};
     GlGrad r;
-    if (gl_grad_forward(h, gl, where.c_str(), B, N, offsets, xyz, x, Q, box, cells, &span_g, 1, nullptr, 0, true, r)) return 1;
+    if (gl_grad_forward(h, gl, where.c_str(), B, N, offsets, xyz, x, Q, geo, &span_g, 1, nullptr, 0, true, r)) return 1;
     HIPCHK(hipMemcpyAsync(r.gq, r.c.d_extra[0], (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));    // the seed: the staged g
-    if (gl_grad_backward(h, gl, r, B, box, cells, gstrain_out != nullptr)) return 1;
+    if (gl_grad_backward(h, gl, r, B, gstrain_out != nullptr)) return 1;
     const float *q_fin = r.q_fin;
     const size_t nback = (size_t)A * 4 + 1 + (gstrain_out ? (size_t)B * 9 : 0);
     if (gl->pin_out.ensure(nback * 4)) return 1;
@@ -149,19 +155,29 @@ static int charges_vjp_large_impl(epnn_handle *h, int B, int N, const int32_t *o
     if (reinterpret_cast<const int *>(back)[4 * (size_t)A] & 2) EPNN_FAIL("%s (pair-list path): the pair list is not symmetric", name);
     if (reinterpret_cast<const int *>(back)[4 * (size_t)A] != 0)
         EPNN_FAIL("%s: two atoms of a molecule%s coincide (distance 0: the edge features have no derivative there)", name,
-                  (cells || box) ? " or their periodic images" : "");
+                  geo.periodic() ? " or their periodic images" : "");
     memcpy(q_out, back, (size_t)A * 4);
     memcpy(gxyz_out, back + A, (size_t)A * 12);
     if (gstrain_out) memcpy(gstrain_out, back + 4 * (size_t)A + 1, (size_t)B * 9 * 4);
     return 0;
 }
 
-// box: host box rows [B][3] of periodic cells (minimum-image distances; staged with the other inputs), or null.  cells: the
-// EpnnCell records [B] of general cells (check_cell) instead, staged the same way; gstrain_out [B][3][3]: with cells, the strain
-// derivative (k_g_xyz_cell / k_g_strain_mol), or null.
-static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                const float *g, float *q_out, float *gxyz_out, const float *box, const EpnnCell *cells = nullptr,
-                                float *gstrain_out = nullptr) {
+// the edge gradients gE [B][N][N][48] -> gxyz, a wavefront per atom, in the call's geometry; share: with cells, the atoms' strain shares, or null
+static void launch_g_xyz(epnn_handle *h, int A, const float *d_xyz, const int *d_moff, int B, int N, const float *gE, float *gxyz, int *bad,
+                         const DevGeo &geo, double *share) {
+    auto launch = [&](auto kernel, auto... rows) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)A), dim3(64), 0, h->stream, d_xyz, d_moff, B, N, gE, (double)h->cfg.cutoff, (double)h->cfg.eta,
+                           h->d_mu.as<double>(), gxyz, bad, rows...);
+    };
+    if (geo.kind == GEO_CELL) launch(k_g_xyz_cell, geo.cells(), share);
+    else if (geo.kind == GEO_BOX) launch(k_g_xyz_pbc, geo.box());
+    else launch(k_g_xyz);
+}
+
+// name: the entry's; geo: the batch's geometry, its rows on the host (staged with the other inputs); gstrain_out [B][3][3]:
+// with cells, the strain derivative (k_g_xyz_cell / k_g_strain_mol), or null.
+static int charges_vjp_xyz_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                const float *g, float *q_out, float *gxyz_out, const HostGeo &geo, float *gstrain_out) {
     for (int b = 0; b < B; ++b)
         if (offsets[b + 1] - offsets[b] > N || offsets[b + 1] - offsets[b] < 1) EPNN_FAIL("epnn_charges_vjp_xyz: molecule %d does not fit N=%d", b, N);
     EPNN_NOT_FUSED_ONLY(h, "epnn_charges_vjp_xyz");
@@ -176,7 +192,7 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
     if (h->opt_grad_path == 2 && h->part_world != 1)
         EPNN_FAIL("epnn_charges_vjp_xyz: grad_path = 2 (pair-list path) does not run on a partitioned handle (epnn_set_partition)");
     if (h->opt_grad_path == 2 || (h->opt_grad_path == 0 && grad_large_possible(h) && grad_large_auto(B, N)))
-        return charges_vjp_large_impl(h, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, box, cells, gstrain_out);
+        return charges_vjp_large_impl(h, name, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, geo, gstrain_out);
     TrainState *xs = xyz_grad_state(h);
     if (!xs->ready || xs->step != h->weights_gen) {
         train_layout(h, xs);
@@ -188,49 +204,19 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
         xs->step = h->weights_gen;                              // (this state takes no optimizer steps: `step` keeps the generation)
         xs->ready = true;
     }
-    const int nx = h->cfg.nx, A = offsets[B];
-    const size_t pairs = (size_t)B * N * N, slots = (size_t)B * N;
-    // the train path's inputs, staged and padded as epnn_train_step_xyz does; the label slot carries -g / 2 (see XyzGrad)
-    auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t o_xyz = up256((size_t)(B + 1) * 4), o_x = o_xyz + up256((size_t)A * 3 * 4), o_Q = o_x + up256((size_t)A * nx * 4),
-                 o_y = o_Q + up256((size_t)B * 4), o_box = o_y + up256((size_t)A * 4), in_bytes = cells ? o_box + (size_t)B * sizeof(EpnnCell) : (box ? o_box + (size_t)B * 12 : o_y + (size_t)A * 4);
-    if (h->pin_train.ensure(in_bytes) || h->s_train.ensure(in_bytes) || h->sd_e.ensure(pairs * EPNN_EDIM * 4) ||
-        h->sd_mask.ensure(pairs * 4) || h->dn_xs.ensure(slots * nx * 4) || h->dn_hs.ensure(slots * EPNN_EDIM * 4) ||
-        h->dn_qs.ensure(slots * 4) || h->sd_out.ensure(slots * 4) || h->tr_realbuf.ensure(slots * 4))
-        return 1;
+    const int A = offsets[B];
+    // the train path's inputs, staged and padded as epnn_train_step_xyz does (dense_in_stage); the label slot carries -g / 2 (see XyzGrad)
+    const DenseIn L(h, B, N, A, geo);
+    const size_t pairs = L.pairs, slots = L.slots;
+    if (dense_in_ensure(h, L)) return 1;
     // [BN] loss terms | [BN] predictions | [BN] zeros | [A][3] gxyz | the coincident-atoms flag;  gE [R][48]
     // ... | [B][9] gstrain (when asked for); behind them, not downloaded, the atoms' strain shares [A][6] float64
     const size_t o_zero = 2 * slots, o_gx = 3 * slots, o_bad = o_gx + (size_t)A * 3, o_gs = o_bad + 1,
                  nout = o_gs + (gstrain_out ? (size_t)B * 9 : 0), o_share = (nout * 4 + 7) & ~size_t(7);
     if (xs->loss.ensure(gstrain_out ? o_share + (size_t)A * 48 : nout * 4) || xs->grad.ensure(pairs * 48 * 4)) return 1;
-    char *stage = h->pin_train.as<char>();
-    memcpy(stage, offsets, (size_t)(B + 1) * 4);
-    memcpy(stage + o_xyz, xyz, (size_t)A * 3 * 4);
-    memcpy(stage + o_x, x, (size_t)A * nx * 4);
-    memcpy(stage + o_Q, Q, (size_t)B * 4);
-    float *ystage = reinterpret_cast<float *>(stage + o_y);
-    for (int a = 0; a < A; ++a) ystage[a] = -0.5f * g[a];
-    if (cells) memcpy(stage + o_box, cells, (size_t)B * sizeof(EpnnCell));
-    else if (box) memcpy(stage + o_box, box, (size_t)B * 12);
-    HIPCHK(hipMemcpyAsync(h->s_train.p, stage, in_bytes, hipMemcpyHostToDevice, h->stream));
-    const float *dev = h->s_train.as<float>();
-    const int *d_moff = h->s_train.as<int>();
-    if (cells)
-        hipLaunchKernelGGL(k_t_pad_inputs_cell, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
-                           (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), (int)(o_box / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff,
-                           (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(),
-                           h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
-    else if (box)
-        hipLaunchKernelGGL(k_t_pad_inputs_pbc, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
-                           (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), (int)(o_box / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff,
-                           (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(),
-                           h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
-    else
-        hipLaunchKernelGGL(k_t_pad_inputs, dim3(t_grid(pairs * ((h->cfg.e_dim + 3) / 4))), dim3(256), 0, h->stream, dev, (int)(o_xyz / 4),
-                           (int)(o_x / 4), (int)(o_Q / 4), (int)(o_y / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta,
-                           h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
-                           h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+    if (dense_in_stage(h, L, B, N, offsets, xyz, x, Q, geo, [&](float *ys) { for (int a = 0; a < A; ++a) ys[a] = -0.5f * g[a]; })) return 1;
     HIPCHK(hipGetLastError());
+    const int *d_moff = h->s_train.as<int>();
     float *out = xs->loss.as<float>();
     HIPCHK(hipMemsetAsync(out + o_zero, 0, (slots + (size_t)A * 3 + 1) * 4, h->stream));
     HIPCHK(hipMemsetAsync(xs->grad.p, 0, pairs * 48 * 4, h->stream));
@@ -247,20 +233,10 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
     h->tr_moff = nullptr;
     h->tr_real = nullptr;
     if (rc) return 1;
-    if (cells) {
-        double *share = gstrain_out ? reinterpret_cast<double *>(xs->loss.as<char>() + o_share) : nullptr;
-        hipLaunchKernelGGL(k_g_xyz_cell, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B,
-                           N, xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
-                           reinterpret_cast<int *>(out + o_bad), reinterpret_cast<const EpnnCell *>(dev + o_box / 4), share);
-        if (share) hipLaunchKernelGGL(k_g_strain_mol, dim3((unsigned)B), dim3(64), 0, h->stream, share, d_moff, out + o_gs);
-    } else if (box)
-        hipLaunchKernelGGL(k_g_xyz_pbc, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B,
-                           N, xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
-                           reinterpret_cast<int *>(out + o_bad), reinterpret_cast<const float *>(dev + o_box / 4));
-    else
-        hipLaunchKernelGGL(k_g_xyz, dim3((unsigned)A), dim3(64), 0, h->stream, reinterpret_cast<const float *>(dev + o_xyz / 4), d_moff, B, N,
-                           xs->grad.as<float>(), (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), out + o_gx,
-                           reinterpret_cast<int *>(out + o_bad));
+    double *share = gstrain_out && geo.kind == GEO_CELL ? reinterpret_cast<double *>(xs->loss.as<char>() + o_share) : nullptr;
+    launch_g_xyz(h, A, reinterpret_cast<const float *>(h->s_train.as<char>() + L.o_xyz), d_moff, B, N, xs->grad.as<float>(), out + o_gx,
+                 reinterpret_cast<int *>(out + o_bad), geo_on_device(geo, h->s_train.as<char>() + L.o_geo), share);
+    if (share) hipLaunchKernelGGL(k_g_strain_mol, dim3((unsigned)B), dim3(64), 0, h->stream, share, d_moff, out + o_gs);
     HIPCHK(hipGetLastError());
     // predictions | zeros | gxyz | flag: one download
     if (h->pin_tout.ensure((nout - slots) * 4)) return 1;
@@ -268,9 +244,8 @@ static int charges_vjp_xyz_impl(epnn_handle *h, int B, int N, const int32_t *off
     HIPCHK(hipMemcpyAsync(back, out + slots, (nout - slots) * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (reinterpret_cast<const int *>(back)[o_bad - slots] != 0)
-        EPNN_FAIL(cells ? "epnn_charges_vjp_xyz_cell: two atoms of a molecule or their periodic images coincide (distance 0: the edge features have no derivative there)"
-                  : box ? "epnn_charges_vjp_xyz_pbc: two atoms of a molecule or their periodic images coincide (distance 0: the edge features have no derivative there)"
-                      : "epnn_charges_vjp_xyz: two atoms of a molecule coincide (distance 0: the edge features have no derivative there)");
+        EPNN_FAIL("%s: two atoms of a molecule%s coincide (distance 0: the edge features have no derivative there)", name,
+                  geo.periodic() ? " or their periodic images" : "");
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < offsets[b + 1] - offsets[b]; ++i) q_out[offsets[b] + i] = back[(size_t)b * N + i];
     memcpy(gxyz_out, back + (o_gx - slots), (size_t)A * 3 * 4);
@@ -282,15 +257,16 @@ extern "C" int epnn_charges_vjp_xyz(epnn_handle *h, int B, int N, const int32_t 
                                     const float *Q, const float *g, float *q_out, float *gxyz_out) {
     if (!h || !offsets || !xyz || !x || !Q || !g || !q_out || !gxyz_out) EPNN_FAIL("epnn_charges_vjp_xyz: null argument");
     if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz: B and N must be positive and offsets[0] must be 0");
-    return charges_vjp_xyz_impl(h, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, nullptr);
+    return charges_vjp_xyz_impl(h, "epnn_charges_vjp_xyz", B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, HostGeo{}, nullptr);
 }
 
 extern "C" int epnn_charges_vjp_xyz_pbc(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                                         const float *Q, const float *box, const float *g, float *q_out, float *gxyz_out) {
     if (!h || !offsets || !xyz || !x || !Q || !g || !q_out || !gxyz_out) EPNN_FAIL("epnn_charges_vjp_xyz_pbc: null argument");
     if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz_pbc: B and N must be positive and offsets[0] must be 0");
-    if (check_box(B, box, (double)h->cfg.cutoff, "epnn_charges_vjp_xyz_pbc")) return 1;
-    return charges_vjp_xyz_impl(h, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, box);
+    GeoArg arg;
+    if (arg.box(B, box, (double)h->cfg.cutoff, "epnn_charges_vjp_xyz_pbc")) return 1;
+    return charges_vjp_xyz_impl(h, "epnn_charges_vjp_xyz_pbc", B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, arg.geo, nullptr);
 }
 
 extern "C" int epnn_charges_vjp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
@@ -298,7 +274,7 @@ extern "C" int epnn_charges_vjp_xyz_cell(epnn_handle *h, int B, int N, const int
                                          float *gstrain_out) {
     if (!h || !offsets || !xyz || !x || !Q || !g || !q_out || !gxyz_out) EPNN_FAIL("epnn_charges_vjp_xyz_cell: null argument");
     if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_charges_vjp_xyz_cell: B and N must be positive and offsets[0] must be 0");
-    std::vector<EpnnCell> cells;
-    if (check_cell(B, cell, (double)h->cfg.cutoff, "epnn_charges_vjp_xyz_cell", cells)) return 1;
-    return charges_vjp_xyz_impl(h, B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, nullptr, cells.data(), gstrain_out);
+    GeoArg arg;
+    if (arg.cell(B, cell, (double)h->cfg.cutoff, "epnn_charges_vjp_xyz_cell")) return 1;
+    return charges_vjp_xyz_impl(h, "epnn_charges_vjp_xyz_cell", B, N, offsets, xyz, x, Q, g, q_out, gxyz_out, arg.geo, gstrain_out);
 }

@@ -25,12 +25,24 @@ static void jvm_bucket(int K, Launch &&launch) {
     else launch(std::integral_constant<int, 16>{});
 }
 
+// The listed pairs' edge tangents te in the call's geometry: open molecules or cells, as the entries take (charges_jvp_multi_impl refuses box rows)
+template <int KM>
+static void launch_jvm_edge(epnn_handle *h, const GlCall &c, int K, int B, const float *d_v, const float *d_E, float *te, int *bad) {
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((c.np + 255) / 256)), dim3(256), 0, h->stream, c.L, c.np, c.d_molof, c.d_xyz, c.geo.words(), K,
+                           c.G.A, B, d_v, d_E, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), te, c.P1 * GL_E, bad);
+    };
+    if (c.geo.kind == GEO_CELL) launch(k_jvm_edge<GEO_CELL, KM>);
+    else launch(k_jvm_edge<GEO_OPEN, KM>);
+}
+
 // K tangents beside the one primal; the single-tangent entry is K = 1.  The call shares the pair-list gradient path's state
 // (GradLarge: the weights in plain Keras layout, refreshed when weights_gen moves on, and the input / scratch buffers, which keep the
 // size of the largest call of either kind): neither the training state nor the forward's plan and pair list are touched.
 static int charges_jvp_multi_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                                  const float *Q, const EpnnCell *cells, int K, const float *vxyz, const float *vstrain, const float *vQ,
+                                  const float *Q, const HostGeo &geo, int K, const float *vxyz, const float *vstrain, const float *vQ,
                                   float *q_out, float *tq_out) {
+    if (geo.kind == GEO_BOX) EPNN_FAIL("%s: internal error (box rows: the tangent kernels take cells)", name);
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
     const int T = h->cfg.T, A = offsets[B];
@@ -38,7 +50,7 @@ static int charges_jvp_multi_impl(epnn_handle *h, const char *name, int B, int N
     // the tangents: vQ as zeros when null, vxyz and vstrain left out
     const GlSpan spans[3] = {{vQ, Kz * B * 4, true}, {vxyz, vxyz ? Kz * A * 12 : 0, false}, {vstrain, vstrain ? Kz * B * 36 : 0, false}};
     GlCall c;
-    if (gl_call_count(h, gl, name, B, N, offsets, xyz, x, Q, nullptr, cells, spans, 3, c)) return 1;
+    if (gl_call_count(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, 3, c)) return 1;
     const size_t P1 = c.P1, SL = 2 * P1, nH = (size_t)A * GL_H, nE = (size_t)A * GL_E, rowH = nH * 4, rowE = nE * 4, maxp = (size_t)c.maxp;
     // the primal rows once, the tangent rows K times (one buffer each, tangent t at t times one tangent's size)
     const size_t o_te = c.place(Kz * P1 * GL_E * 4), o_h = c.place(2 * rowE), o_th = c.place(2 * Kz * rowE),
@@ -60,19 +72,7 @@ static int charges_jvp_multi_impl(epnn_handle *h, const char *name, int B, int N
     float *te = c.fp(o_te);
     if (np > 0) {
         // ---- edge tangents
-        const unsigned gp = (unsigned)((np + 255) / 256);
-        const double cut = (double)h->cfg.cutoff, eta = (double)h->cfg.eta;
-        const double *mu = h->d_mu.as<double>();
-        const size_t tes = P1 * GL_E;
-        jvm_bucket(K, [&](auto km) {
-            constexpr int KM = decltype(km)::value;
-            if (cells)
-                hipLaunchKernelGGL((k_jvm_edge<2, KM>), dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, K, A, B, d_v, d_E,
-                                   cut, eta, mu, te, tes, bad);
-            else
-                hipLaunchKernelGGL((k_jvm_edge<0, KM>), dim3(gp), dim3(256), 0, h->stream, L, np, c.d_molof, c.d_xyz, c.d_geo, K, A, B, d_v, d_E,
-                                   cut, eta, mu, te, tes, bad);
-        });
+        jvm_bucket(K, [&](auto km) { launch_jvm_edge<decltype(km)::value>(h, c, K, B, d_v, d_E, te, bad); });
         HIPCHK(hipGetLastError());
     }
     float *hb[2] = {c.fp(o_h), c.fp(o_h) + nE}, *thb[2] = {c.fp(o_th), c.fp(o_th) + Kz * nE};
@@ -143,21 +143,20 @@ static int charges_jvp_multi_impl(epnn_handle *h, const char *name, int B, int N
     if (flag & 2) EPNN_FAIL("%s: the pair list is not symmetric", name);
     if (flag != 0)
         EPNN_FAIL("%s: two atoms of a molecule%s coincide (distance 0: the edge features have no derivative there)", name,
-                  cells ? " or their periodic images" : "");
+                  geo.periodic() ? " or their periodic images" : "");
     memcpy(q_out, back, (size_t)A * 4);
     memcpy(tq_out, back + A, Kz * A * 4);
     return 0;
 }
 
-// What the two entries check and settle before the call (K = 1: the single-tangent entry); cells: the checked cell rows.
+// What the two entries check and settle before the call (K = 1: the single-tangent entry); arg: the checked cell (a null cell: open molecules).
 static int charges_jvp_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                             const float *Q, const float *cell, int K, const float *q_out, const float *tq_out,
-                             std::vector<EpnnCell> &cells) {
+                             const float *Q, const float *cell, int K, const float *q_out, const float *tq_out, GeoArg &arg) {
     if (!h || !offsets || !xyz || !x || !Q || !q_out || !tq_out) EPNN_FAIL("%s: null argument", name);
     if (K < 1 || K > JVM_MAXK) EPNN_FAIL("%s: K must be in 1..%d, got %d", name, JVM_MAXK, K);
     if (check_flat_batch(name, B, N, offsets)) return 1;
     EPNN_NOT_FUSED_ONLY(h, name);
-    if (cell && check_cell(B, cell, (double)h->cfg.cutoff, name, cells)) return 1;
+    if (cell && arg.cell(B, cell, (double)h->cfg.cutoff, name)) return 1;
     if (h->upd_generic) EPNN_FAIL("%s is built for update layers [32, 32] only (epnn_set_update_layers changed them)", name);
     if (h->part_world != 1) EPNN_FAIL("%s does not run on a partitioned handle (epnn_set_partition)", name);
     HIPCHK(hipSetDevice(h->device));
@@ -171,16 +170,16 @@ extern "C" int epnn_charges_jvp_xyz_cell(epnn_handle *h, int B, int N, const int
                                          const float *Q, const float *cell, const float *vxyz, const float *vstrain, const float *vQ,
                                          float *q_out, float *tq_out) {
     const char *name = "epnn_charges_jvp_xyz_cell";
-    std::vector<EpnnCell> cells;
-    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, 1, q_out, tq_out, cells)) return 1;
-    return charges_jvp_multi_impl(h, name, B, N, offsets, xyz, x, Q, cell ? cells.data() : nullptr, 1, vxyz, vstrain, vQ, q_out, tq_out);
+    GeoArg arg;
+    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, 1, q_out, tq_out, arg)) return 1;
+    return charges_jvp_multi_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, 1, vxyz, vstrain, vQ, q_out, tq_out);
 }
 
 extern "C" int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                                                const float *Q, const float *cell, int K, const float *vxyz, const float *vstrain,
                                                const float *vQ, float *q_out, float *tq_out) {
     const char *name = "epnn_charges_jvp_multi_xyz_cell";
-    std::vector<EpnnCell> cells;
-    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, K, q_out, tq_out, cells)) return 1;
-    return charges_jvp_multi_impl(h, name, B, N, offsets, xyz, x, Q, cell ? cells.data() : nullptr, K, vxyz, vstrain, vQ, q_out, tq_out);
+    GeoArg arg;
+    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, K, q_out, tq_out, arg)) return 1;
+    return charges_jvp_multi_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, K, vxyz, vstrain, vQ, q_out, tq_out);
 }

@@ -33,13 +33,6 @@ static bool grad_large_possible(const epnn_handle *h) { return !h->upd_generic &
 // is above it, so every call that ran before takes the path it took)
 static bool grad_large_auto(int B, int N) { return (size_t)B * (size_t)N * (size_t)N > ((size_t)1 << 22); }
 
-static int check_flat_batch(const char *name, int B, int N, const int32_t *offsets) {
-    if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("%s: B and N must be positive and offsets[0] must be 0", name);
-    for (int b = 0; b < B; ++b)
-        if (offsets[b + 1] - offsets[b] > N || offsets[b + 1] - offsets[b] < 1) EPNN_FAIL("%s: molecule %d does not fit N=%d", name, b, N);
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------ weights
 // Dense: HostDense (the handle's host copies) or TDense (the training state's flat vector); F = nx + 48 + 1 input features per atom
 template <class Dense>
@@ -96,13 +89,13 @@ struct GlSpan { const void *src; size_t bytes; bool zero; };
 struct GlCall {
     const int *d_moff, *d_molof;  // the staged inputs, on the device
     const int4 *d_tasks;          // sweep tasks: 16 resident atoms x one piece of their molecule's partner range
-    const float *d_xyz, *d_x, *d_Q, *d_geo, *d_extra[3];      // d_geo: box rows or EpnnCell records; d_extra[k]: span k, null if it is empty
-    int geo;                      // 0 open molecules, 1 box rows, 2 cells
+    const float *d_xyz, *d_x, *d_Q, *d_extra[3];      // d_extra[k]: span k, null if it is empty
+    DevGeo geo;                   // the call's geometry, its rows staged behind the spans
     FrontArgs F;
     GlGeom G;
     GlPairs L;
     const int *inc;               // [A + 1] incidence rows
-    unsigned nt, rows, gA;        // tasks; grids of the front-end's rows and of one thread per atom
+    unsigned nt, gA;              // tasks; grid of one thread per atom
     int maxp, np;                 // most pieces of a partner range; listed pairs
     size_t P1;                    // max(np, 1)
     size_t in_total;              // bytes of the input block with the front-end's counts
@@ -116,8 +109,7 @@ struct GlCall {
 // Stages the inputs (one upload), counts the pairs and checks the counts; `where` opens the two failure texts.  Afterwards the
 // entry places its scratch behind the pair list (c.place) and calls gl_call_fill.
 static int gl_call_count(epnn_handle *h, GradLarge *gl, const char *where, int B, int N, const int32_t *offsets, const float *xyz,
-                         const float *x, const float *Q, const float *box, const EpnnCell *cells, const GlSpan *extras, int n_extras,
-                         GlCall &c) {
+                         const float *x, const float *Q, const HostGeo &geo, const GlSpan *extras, int n_extras, GlCall &c) {
     const int nx = h->cfg.nx, A = offsets[B];
     std::vector<int4> tasks;
     c.maxp = 1;
@@ -128,7 +120,6 @@ static int gl_call_count(epnn_handle *h, GradLarge *gl, const char *where, int B
             for (int k = 0; k < np; ++k) tasks.push_back(make_int4(a0, b, k, np));
     }
     c.nt = (unsigned)tasks.size();
-    c.geo = cells ? 2 : box ? 1 : 0;
     // ---- inputs and the front-end's per-atom counts: one upload
     c.at = 0;
     const size_t o_off = c.place((size_t)(B + 1) * 4), o_molof = c.place((size_t)A * 4), o_mflag = c.place((size_t)B * 4),
@@ -136,7 +127,7 @@ static int gl_call_count(epnn_handle *h, GradLarge *gl, const char *where, int B
                  o_Q = c.place((size_t)B * 4);
     size_t o_extra[3] = {0, 0, 0};
     for (int k = 0; k < n_extras; ++k) o_extra[k] = c.place(extras[k].bytes);
-    const size_t o_geo = c.place(cells ? (size_t)B * sizeof(EpnnCell) : box ? (size_t)B * 12 : 0), in_bytes = c.at;
+    const size_t o_geo = c.place(geo.bytes(B)), in_bytes = c.at;
     const size_t o_rowcnt = c.place((size_t)(A + 1) * 4), o_rowoff = c.place((size_t)(A + 1) * 4), o_deg = c.place((size_t)(A + 1) * 4),
                  o_incoff = c.place((size_t)(A + 1) * 4), o_status = c.place(16);
     c.in_total = c.at;
@@ -156,8 +147,7 @@ static int gl_call_count(epnn_handle *h, GradLarge *gl, const char *where, int B
         if (extras[k].src) memcpy(st + o_extra[k], extras[k].src, extras[k].bytes);
         else if (extras[k].zero) memset(st + o_extra[k], 0, extras[k].bytes);
     }
-    if (cells) memcpy(st + o_geo, cells, (size_t)B * sizeof(EpnnCell));
-    else if (box) memcpy(st + o_geo, box, (size_t)B * 12);
+    if (geo.periodic()) memcpy(st + o_geo, geo.rows, geo.bytes(B));
     char *din = gl->in.as<char>();
     HIPCHK(hipMemcpyAsync(din, st, in_bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(din + o_status, 0, 16, h->stream));
@@ -165,7 +155,8 @@ static int gl_call_count(epnn_handle *h, GradLarge *gl, const char *where, int B
     auto dip = [&](size_t o) { return reinterpret_cast<int *>(din + o); };
     c.d_moff = dip(o_off); c.d_molof = dip(o_molof);
     c.d_tasks = reinterpret_cast<const int4 *>(din + o_task);
-    c.d_xyz = dfp(o_xyz); c.d_x = dfp(o_x); c.d_Q = dfp(o_Q); c.d_geo = dfp(o_geo);
+    c.d_xyz = dfp(o_xyz); c.d_x = dfp(o_x); c.d_Q = dfp(o_Q);
+    c.geo = geo_on_device(geo, din + o_geo);
     for (int k = 0; k < 3; ++k) c.d_extra[k] = k < n_extras && extras[k].bytes ? dfp(o_extra[k]) : nullptr;
     // ---- pair list: count and prefix sums first, then buffers of exactly that size (gl_call_fill)
     FrontArgs &F = c.F;
@@ -177,12 +168,8 @@ static int gl_call_count(epnn_handle *h, GradLarge *gl, const char *where, int B
     F.mu = h->d_mu.as<double>();
     F.row_cnt = dip(o_rowcnt); F.row_off = dip(o_rowoff); F.deg = dip(o_deg); F.inc_off = dip(o_incoff); F.status = dip(o_status);
     F.pcap = 0x7fffffff;
-    c.rows = (unsigned)((A + 3) / 4);
     c.gA = (unsigned)((A + 255) / 256);
-    if (cells) hipLaunchKernelGGL(k_front_count_cell, dim3(c.rows), dim3(256), 0, h->stream, F, reinterpret_cast<const EpnnCell *>(c.d_geo));
-    else if (box) hipLaunchKernelGGL(k_front_count_pbc, dim3(c.rows), dim3(256), 0, h->stream, F, c.d_geo);
-    else hipLaunchKernelGGL(k_front_count, dim3(c.rows), dim3(256), 0, h->stream, F);
-    hipLaunchKernelGGL(k_front_scan_both, dim3(1), dim3(1024), 0, h->stream, F);
+    launch_front_count(h, F, c.geo);
     HIPCHK(hipGetLastError());
     int *cnt = gl->pin_out.as<int>();
     HIPCHK(hipMemcpyAsync(cnt, F.row_off + A, 4, hipMemcpyDeviceToHost, h->stream));
@@ -218,10 +205,7 @@ static int gl_call_fill(epnn_handle *h, GradLarge *gl, GlCall &c, size_t in_byte
     F.pi = ip(0); F.pj = ip(1); F.psym = ip(2); F.pe = c.fp(c.o_pair[3]); F.pwi = c.fp(c.o_pair[4]); F.pwj = c.fp(c.o_pair[5]);
     F.nbr = ip(6); F.dest_i = ip(7); F.dest_j = ip(8); F.prec = reinterpret_cast<int4 *>(c.dw + c.o_pair[9]);
     if (c.np > 0) {
-        if (c.geo == 2) hipLaunchKernelGGL(k_front_fill_cell, dim3(c.rows), dim3(256), 0, h->stream, F, reinterpret_cast<const EpnnCell *>(c.d_geo));
-        else if (c.geo == 1) hipLaunchKernelGGL(k_front_fill_pbc, dim3(c.rows), dim3(256), 0, h->stream, F, c.d_geo);
-        else hipLaunchKernelGGL(k_front_fill, dim3(c.rows), dim3(256), 0, h->stream, F);
-        hipLaunchKernelGGL(k_front_link, dim3((unsigned)std::min<size_t>((c.P1 + 255) / 256, 1024)), dim3(256), 0, h->stream, F);
+        launch_front_fill(h, F, c.geo);             // (F.pcap is c.P1)
         HIPCHK(hipGetLastError());
     }
     c.L = GlPairs{F.pi, F.pj, F.dest_i, F.dest_j, F.pe, F.pwi};

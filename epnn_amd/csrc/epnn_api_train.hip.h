@@ -407,52 +407,86 @@ static int train_step_dense_impl(epnn_handle *h, int B, int N, const float *h_in
     return train_step_slots(h, B, N, D.e_in, D.mask_in, D.xs, D.hs, D.qs, d_y, pred_out, loss_out, apply);
 }
 
-// train_step from a flat coordinate batch: y_flat / q_out_flat are per real atom [A]
-// cells: the EpnnCell records [B] of general cells (epnn_train_step_xyz_cell: minimum-image distances, k_t_pad_inputs_cell), or null
-static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                               const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply,
-                               const EpnnCell *cells = nullptr);
-extern "C" int epnn_train_step_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                                   const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply) {
-    if (!train_step_guarded(h, apply)) return train_step_xyz_impl(h, B, N, offsets, xyz, x, Q, y_flat, q_out_flat, loss_out, apply);
-    h->guard_pending = true;
-    return comm_guard_exit(h, train_step_xyz_impl(h, B, N, offsets, xyz, x, Q, y_flat, q_out_flat, loss_out, apply), "train step (gradient all-reduce)");
+// ---- the dense path's inputs from a flat coordinate batch, shared by the coordinate train step and the dense branch of
+// epnn_charges_vjp_xyz (epnn_api_grad.hip.h).  ONE upload per call: offsets | xyz | x | Q | labels | geometry rows staged in page-locked
+// memory, every section at a multiple of 256 bytes, the same layout on the device (five separate copies from pageable memory were
+// ~50 us of a 0.5 ms step before its first kernel could start); the padding kernel makes the dense tensors of them.
+struct DenseIn {
+    size_t o_xyz, o_x, o_Q, o_y, o_geo, in_bytes;      // bytes into the block
+    size_t pairs, slots;                               // B N N, B N
+    unsigned pgrid;                                    // the padding kernel's grid
+    DenseIn(const epnn_handle *h, int B, int N, int A, const HostGeo &geo) {
+        auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+        o_xyz = up256((size_t)(B + 1) * 4); o_x = o_xyz + up256((size_t)A * 3 * 4); o_Q = o_x + up256((size_t)A * h->cfg.nx * 4);
+        o_y = o_Q + up256((size_t)B * 4); o_geo = o_y + up256((size_t)A * 4);
+        in_bytes = geo.periodic() ? o_geo + geo.bytes(B) : o_y + (size_t)A * 4;
+        pairs = (size_t)B * N * N; slots = (size_t)B * N;
+        pgrid = t_grid(pairs * ((h->cfg.e_dim + 3) / 4));
+    }
+};
+static int dense_in_ensure(epnn_handle *h, const DenseIn &L) {
+    return h->pin_train.ensure(L.in_bytes) || h->s_train.ensure(L.in_bytes) || h->sd_e.ensure(L.pairs * EPNN_EDIM * 4) ||
+           h->sd_mask.ensure(L.pairs * 4) || h->dn_xs.ensure(L.slots * h->cfg.nx * 4) || h->dn_hs.ensure(L.slots * EPNN_EDIM * 4) ||
+           h->dn_qs.ensure(L.slots * 4) || h->sd_out.ensure(L.slots * 4) || h->tr_realbuf.ensure(L.slots * 4);
 }
+// the padding kernel on the uploaded block: the entry point of the geometry's kind (a periodic one takes the word its rows start at)
+static void launch_pad_inputs(epnn_handle *h, const DenseIn &L, int B, int N, GeoKind kind) {
+    auto launch = [&](auto kernel, auto... w_geo) {
+        hipLaunchKernelGGL(kernel, dim3(L.pgrid), dim3(256), 0, h->stream, h->s_train.as<float>(), (int)(L.o_xyz / 4), (int)(L.o_x / 4),
+                           (int)(L.o_Q / 4), (int)(L.o_y / 4), w_geo..., B, N, h->cfg.nx, h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta,
+                           h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
+                           h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+    };
+    if (kind == GEO_CELL) launch(k_t_pad_inputs_cell, (int)(L.o_geo / 4));
+    else if (kind == GEO_BOX) launch(k_t_pad_inputs_pbc, (int)(L.o_geo / 4));
+    else launch(k_t_pad_inputs);
+}
+// The copies into page-locked memory (labels(slot) writes the A words of the label section: what it holds is the caller's), the
+// upload and the padding launch, after dense_in_ensure.  (The previous call on these buffers ended with a stream synchronisation.)
+template <class Labels>
+static int dense_in_stage(epnn_handle *h, const DenseIn &L, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                          const float *Q, const HostGeo &geo, Labels &&labels) {
+    const int A = offsets[B];
+    char *stage = h->pin_train.as<char>();
+    memcpy(stage, offsets, (size_t)(B + 1) * 4);
+    memcpy(stage + L.o_xyz, xyz, (size_t)A * 3 * 4);
+    memcpy(stage + L.o_x, x, (size_t)A * h->cfg.nx * 4);
+    memcpy(stage + L.o_Q, Q, (size_t)B * 4);
+    labels(reinterpret_cast<float *>(stage + L.o_y));
+    if (geo.periodic()) memcpy(stage + L.o_geo, geo.rows, geo.bytes(B));
+    HIPCHK(hipMemcpyAsync(h->s_train.p, stage, L.in_bytes, hipMemcpyHostToDevice, h->stream));
+    launch_pad_inputs(h, L, B, N, geo.kind);
+    return 0;
+}
+
+static int check_flat_batch(const char *name, int B, int N, const int32_t *offsets) {
+    if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("%s: B and N must be positive and offsets[0] must be 0", name);
+    for (int b = 0; b < B; ++b)
+        if (offsets[b + 1] - offsets[b] > N || offsets[b + 1] - offsets[b] < 1) EPNN_FAIL("%s: molecule %d does not fit N=%d", name, b, N);
+    return 0;
+}
+
+// train_step from a flat coordinate batch: y_flat / q_out_flat are per real atom [A]
+// geo: the batch's geometry (epnn_train_step_xyz_cell: minimum-image distances in its cells)
 static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                               const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply,
-                               const EpnnCell *cells) {
+                               const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply, const HostGeo &geo) {
     if (!h || !offsets || !xyz || !x || !Q || !y_flat) EPNN_FAIL("epnn_train_step_xyz: null argument");
     EPNN_NOT_FUSED_ONLY(h, "epnn_train_step_xyz");
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
-    if (B < 1 || N < 1 || offsets[0] != 0) EPNN_FAIL("epnn_train_step_xyz: B and N must be positive and offsets[0] must be 0");
+    if (check_flat_batch("epnn_train_step_xyz", B, N, offsets)) return 1;
     const int nx = h->cfg.nx, A = offsets[B];
-    for (int b = 0; b < B; ++b)
-        if (offsets[b + 1] - offsets[b] > N || offsets[b + 1] - offsets[b] < 1) EPNN_FAIL("epnn_train_step_xyz: molecule %d does not fit N=%d", b, N);
-    const size_t pairs = (size_t)B * N * N, slots = (size_t)B * N;
-    // ONE upload per step: offsets | xyz | x | Q | y staged in page-locked memory, same layout on the device (five separate
-    // copies from pageable memory were ~50 us of a 0.5 ms step before its first kernel could start)
-    auto up256 = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t o_xyz = up256((size_t)(B + 1) * 4), o_x = o_xyz + up256((size_t)A * 3 * 4), o_Q = o_x + up256((size_t)A * nx * 4),
-                 o_y = o_Q + up256((size_t)B * 4), o_cell = o_y + up256((size_t)A * 4),
-                 in_bytes = cells ? o_cell + (size_t)B * sizeof(EpnnCell) : o_y + (size_t)A * 4;
+    const DenseIn L(h, B, N, A, geo);
     if (h->train) {
         // the previous step's backward pass may still be running ("train_async"): it reads the buffers below
         TrainState *ts0 = train_state(h);
-        if ((B != ts0->last_B || N != ts0->last_N || in_bytes > h->s_train.cap || in_bytes > h->pin_train.cap) && train_quiesce(h)) return 1;
+        if ((B != ts0->last_B || N != ts0->last_N || L.in_bytes > h->s_train.cap || L.in_bytes > h->pin_train.cap) && train_quiesce(h)) return 1;
     }
-    if (h->pin_train.ensure(in_bytes) || h->s_train.ensure(in_bytes) || h->sd_e.ensure(pairs * EPNN_EDIM * 4) ||
-        h->sd_mask.ensure(pairs * 4) || h->dn_xs.ensure(slots * nx * 4) || h->dn_hs.ensure(slots * EPNN_EDIM * 4) ||
-        h->dn_qs.ensure(slots * 4) || h->sd_out.ensure(slots * 4) || h->tr_realbuf.ensure(slots * 4))
-        return 1;
-    char *stage = h->pin_train.as<char>();
-    const char *dev = h->s_train.as<char>();
-    const int w_xyz = (int)(o_xyz / 4), w_x = (int)(o_x / 4), w_Q = (int)(o_Q / 4), w_y = (int)(o_y / 4);
-    const unsigned pgrid = t_grid(pairs * ((h->cfg.e_dim + 3) / 4));
+    if (dense_in_ensure(h, L)) return 1;
     // one molecule (or two small ones): the inputs are few enough to ride in the padding kernel's argument block, packed (no 256-byte
     // sections) -- no upload; otherwise ONE upload of the staged block
     const size_t packed_words = (size_t)(B + 1) + (size_t)A * (3 + nx + 1) + B;
-    if (h->opt_train_inline && packed_words <= EPNN_PAD_INLINE_WORDS && !cells) {
+    if (h->opt_train_inline && packed_words <= EPNN_PAD_INLINE_WORDS && !geo.periodic()) {
         PadInline P;
         int k = 0;
         memcpy(P.w + k, offsets, (size_t)(B + 1) * 4); k += B + 1;
@@ -460,32 +494,17 @@ static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offs
         const int p_x = k; memcpy(P.w + k, x, (size_t)A * nx * 4); k += A * nx;
         const int p_Q = k; memcpy(P.w + k, Q, (size_t)B * 4); k += B;
         const int p_y = k; memcpy(P.w + k, y_flat, (size_t)A * 4); k += A;
-        hipLaunchKernelGGL(k_t_pad_inputs_inline, dim3(pgrid), dim3(256), 0, h->stream, P, p_xyz, p_x, p_Q, p_y, B, N, nx, h->cfg.e_dim,
+        hipLaunchKernelGGL(k_t_pad_inputs_inline, dim3(L.pgrid), dim3(256), 0, h->stream, P, p_xyz, p_x, p_Q, p_y, B, N, nx, h->cfg.e_dim,
                            (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(),
                            h->dn_xs.as<float>(), h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>(),
                            reinterpret_cast<int *>(h->s_train.p));
-    } else {
-        memcpy(stage, offsets, (size_t)(B + 1) * 4);             // (the previous step ended with a stream synchronisation)
-        memcpy(stage + o_xyz, xyz, (size_t)A * 3 * 4);
-        memcpy(stage + o_x, x, (size_t)A * nx * 4);
-        memcpy(stage + o_Q, Q, (size_t)B * 4);
-        memcpy(stage + o_y, y_flat, (size_t)A * 4);
-        if (cells) memcpy(stage + o_cell, cells, (size_t)B * sizeof(EpnnCell));
-        HIPCHK(hipMemcpyAsync(h->s_train.p, stage, in_bytes, hipMemcpyHostToDevice, h->stream));
-        if (cells)
-            hipLaunchKernelGGL(k_t_pad_inputs_cell, dim3(pgrid), dim3(256), 0, h->stream, reinterpret_cast<const float *>(dev), w_xyz, w_x, w_Q, w_y,
-                               (int)(o_cell / 4), B, N, nx, h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(),
-                               h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(), h->dn_qs.as<float>(),
-                               h->sd_out.as<float>(), h->tr_realbuf.as<int>());
-        else
-            hipLaunchKernelGGL(k_t_pad_inputs, dim3(pgrid), dim3(256), 0, h->stream, reinterpret_cast<const float *>(dev), w_xyz, w_x, w_Q, w_y, B, N, nx,
-                               h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(),
-                               h->dn_xs.as<float>(), h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
+    } else if (dense_in_stage(h, L, B, N, offsets, xyz, x, Q, geo, [&](float *ys) { memcpy(ys, y_flat, (size_t)A * 4); })) {
+        return 1;
     }
     HIPCHK(hipGetLastError());
-    std::vector<float> pred(q_out_flat ? slots : 0);
+    std::vector<float> pred(q_out_flat ? L.slots : 0);
     // the padded slots of a coordinate batch are exact zeros in every input: the matrix-pipe kernels skip their workgroups
-    if (h->opt_train_skip_padded) { h->tr_moff = reinterpret_cast<const int *>(dev); h->tr_real = h->tr_realbuf.as<int>(); }
+    if (h->opt_train_skip_padded) { h->tr_moff = h->s_train.as<int>(); h->tr_real = h->tr_realbuf.as<int>(); }
     const int rc_step = train_step_slots(h, B, N, h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
                                          h->dn_qs.as<float>(), h->sd_out.as<float>(), q_out_flat ? pred.data() : nullptr, loss_out, apply);
     h->tr_moff = nullptr;
@@ -495,6 +514,14 @@ static int train_step_xyz_impl(epnn_handle *h, int B, int N, const int32_t *offs
         for (int b = 0; b < B; ++b)
             for (int i = 0; i < offsets[b + 1] - offsets[b]; ++i) q_out_flat[offsets[b] + i] = pred[(size_t)b * N + i];
     return 0;
+}
+
+extern "C" int epnn_train_step_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                                   const float *Q, const float *y_flat, float *q_out_flat, float *loss_out, int apply) {
+    if (!train_step_guarded(h, apply)) return train_step_xyz_impl(h, B, N, offsets, xyz, x, Q, y_flat, q_out_flat, loss_out, apply, HostGeo{});
+    h->guard_pending = true;
+    return comm_guard_exit(h, train_step_xyz_impl(h, B, N, offsets, xyz, x, Q, y_flat, q_out_flat, loss_out, apply, HostGeo{}),
+                           "train step (gradient all-reduce)");
 }
 
 // RCCL communicator for the gradient all-reduce (one rank per GPU).  The 128-byte id is created on rank 0 and

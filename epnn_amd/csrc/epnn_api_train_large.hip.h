@@ -9,7 +9,7 @@
 // (the flat vector has the layout GlPair / GlUpd point into), adds into the state's gradient vector, and returns when all of it is
 // done.  Inputs, pair list and scratch are those of the gradient path (GradLarge).
 static int train_step_large_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                 const EpnnCell *cells, const float *y, float *q_out, float *loss_out, int apply) {
+                                 const HostGeo &geo, const float *y, float *q_out, float *loss_out, int apply) {
     const char *name = "epnn_train_step_xyz_cell";
     TrainState *ts = train_state(h);
     GradLarge *gl = grad_large_state(h);
@@ -26,7 +26,7 @@ static int train_step_large_impl(epnn_handle *h, int B, int N, const int32_t *of
                     theta + ts->upd[2].offW, theta + ts->upd[2].offB};
     const GlSpan span_y{y, (size_t)A * 4, false};
     GlCall c;
-    if (gl_call_count(h, gl, "epnn_train_step_xyz_cell (pair-list path)", B, N, offsets, xyz, x, Q, nullptr, cells, &span_y, 1, c)) return 1;
+    if (gl_call_count(h, gl, "epnn_train_step_xyz_cell (pair-list path)", B, N, offsets, xyz, x, Q, geo, &span_y, 1, c)) return 1;
     const int np = c.np;
     const size_t P1 = c.P1, SL = 2 * P1, rowH = (size_t)A * GL_H * 4, rowE = (size_t)A * GL_E * 4, maxp = (size_t)c.maxp;
     const unsigned nt = c.nt;
@@ -177,8 +177,8 @@ static int train_step_xyz_cell_impl(epnn_handle *h, int B, int N, const int32_t 
     HIPCHK(hipSetDevice(h->device));
     if (h->pending.active && finish_forward(h)) return 1;
     if (check_flat_batch(name, B, N, offsets)) return 1;
-    std::vector<EpnnCell> cells;
-    if (cell && check_cell(B, cell, (double)h->cfg.cutoff, name, cells)) return 1;
+    GeoArg arg;                                                  // (a null cell: open molecules)
+    if (cell && arg.cell(B, cell, (double)h->cfg.cutoff, name)) return 1;
     if (!train_state(h)->ready) EPNN_FAIL("train step: call epnn_train_init first");
     // "train_path": 0 = by size, 1 = the dense path, 2 = the pair-list path (refused where it is not built)
     if (h->opt_train_path == 2 && h->upd_generic)
@@ -187,9 +187,9 @@ static int train_step_xyz_cell_impl(epnn_handle *h, int B, int N, const int32_t 
         EPNN_FAIL("%s: train_path = 2 (pair-list path) does not run on a partitioned handle (epnn_set_partition)", name);
     if (h->opt_train_path == 2 || (h->opt_train_path == 0 && grad_large_possible(h) && grad_large_auto(B, N))) {
         if (train_quiesce(h)) return 1;                          // a dense "train_async" step may still be reading the masters' gradients
-        return train_step_large_impl(h, B, N, offsets, xyz, x, Q, cell ? cells.data() : nullptr, y_flat, q_out_flat, loss_out, apply);
+        return train_step_large_impl(h, B, N, offsets, xyz, x, Q, arg.geo, y_flat, q_out_flat, loss_out, apply);
     }
-    return train_step_xyz_impl(h, B, N, offsets, xyz, x, Q, y_flat, q_out_flat, loss_out, apply, cell ? cells.data() : nullptr);
+    return train_step_xyz_impl(h, B, N, offsets, xyz, x, Q, y_flat, q_out_flat, loss_out, apply, arg.geo);
 }
 extern "C" int epnn_train_step_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                                         const float *Q, const float *cell, const float *y_flat, float *q_out_flat, float *loss_out,

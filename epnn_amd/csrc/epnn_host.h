@@ -72,6 +72,8 @@ struct PinBuf {               // page-locked host memory: asynchronous copies re
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+enum GeoKind { GEO_OPEN = 0, GEO_BOX = 1, GEO_CELL = 2 };     // the geometry of a call (epnn_geometry.h): the kernels' PBC / GEO template argument
+
 struct HostDense {            // one Keras Dense: kernel [in][out], bias [out]
     int n_in = 0, n_out = 0;
     std::vector<float> W, b;
@@ -166,7 +168,7 @@ struct epnn_handle {
     DevBuf d_pi, d_pj, d_psym, d_pe, d_pwi, d_pwj;
     DevBuf d_deg, d_incoff, d_nbr, d_desti, d_destj, d_prec;   // incidence rows of the pair list (epnn_frontend.hip.h)
     DevBuf d_nearbits;                // the count pass's D < cutoff decisions, a bit per candidate (FrontArgs::bits)
-    DevBuf d_box;                     // box rows of epnn_forward_xyz_pbc_dev, two slots (the status slot of the forward: st_slot)
+    DevBuf d_box;                     // geometry rows of epnn_forward_xyz_pbc_dev / _cell_dev, two slots (the status slot of the forward: st_slot)
     PinBuf pin_box;                   // ... and their page-locked staging
     int opt_front_inline = 1;         // developer switch: 0 = the prefix sums of the pair list always in a launch of their own
     int opt_front_bits = 1;           // developer switch: 0 = the fill pass measures every distance again
@@ -269,7 +271,7 @@ struct epnn_handle {
         std::function<int()> redo;    // re-enqueues the same forward after a capacity regrow
         int slot = 0;                 // its status slot / completion event
         const void *key[4] = {nullptr, nullptr, nullptr, nullptr};      // the device buffers of a device-resident compact forward
-        std::vector<float> box;       // its box rows (periodic forward; empty: open molecules)
+        GeoKind geo_kind = GEO_OPEN; std::vector<char> geo_rows;      // its geometry: the kind and the bytes of its rows, compared together
     } pending;
     // dense front-end workspace (epnn_dense.hip.h)
     DevBuf dn_den;

@@ -11,6 +11,7 @@ from ._lib import W_MSG, W_PAS, W_UPD, EpnnConfig, EpnnError, check, fptr, iptr
 
 KE_EV_ANGSTROM = 14.3996454784255      # e^2 / (4 pi eps0) in eV Angstrom: coulomb_xyz's default ke (332.0637: kcal/mol)
 _WHICH = {"msg": W_MSG, "upd": W_UPD, "pas": W_PAS}
+_FORWARD_SHAPES = "forward_xyz: shapes xyz {xyz} x {x} Q {Q} do not match offsets (A={A}, B={B}, nx={nx})"
 
 
 def _box_rows(box, B):
@@ -38,6 +39,20 @@ def _cell_rows(cell, B):
 def _one_periodic_argument(box, cell):
     if box is not None and cell is not None:
         raise ValueError("box and cell are two descriptions of the same thing: give one of them")
+
+
+def _geometry(box, cell, B, cells_only=False):
+    """box= / cell= (at most one: _one_periodic_argument) -> what the C entry of that geometry is named after and takes: ("", None),
+    ("_pbc", (B, 3) rows) or ("_cell", (B, 3, 3) rows).  cells_only (entries that take a cell or nothing): a box becomes its diagonal cell."""
+    if box is not None:
+        box = _box_rows(box, B)
+        if not cells_only:
+            return "_pbc", box
+        cell = np.zeros((B, 3, 3), dtype=np.float32)
+        cell[:, [0, 1, 2], [0, 1, 2]] = box
+    if cell is not None:
+        return "_cell", _cell_rows(cell, B)
+    return "", None
 
 
 def _f32(a):
@@ -182,33 +197,27 @@ class Engine:
         (include/epnn.h: > 0 periodic length, 0 open axis).  cell (3, 3) or (B, 3, 3): general (triclinic) cells, row k the
         lattice vector a_k, a zero row an open axis."""
         _one_periodic_argument(box, cell)
+        offsets, xyz, x, Q, _, B, A = self._flat_batch(_FORWARD_SHAPES, offsets, xyz, x, Q)
+        suffix, rows = _geometry(box, cell, B)
+        out = np.empty((A,), dtype=np.float32)
+        check(getattr(self.lib, "epnn_forward_xyz" + suffix)(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q),
+                                                            *([] if rows is None else [fptr(rows)]), fptr(out)), self.lib)
+        return out
+
+    def _flat_batch(self, message, offsets, xyz, x, Q, per_atom=None):
+        """A flat batch as the C entries take it: offsets int32 (B+1,), xyz (A, 3), x (A, nx), Q (B,), a per-atom array (A,) where the method
+        has one, float32 and contiguous -> (offsets, xyz, x, Q, per_atom, B, A); message: the method's text for shapes that do not match."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
         xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
-        B = len(offsets) - 1
-        A = int(offsets[-1])
-        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
-            raise EpnnError(f"forward_xyz: shapes xyz {xyz.shape} x {x.shape} Q {Q.shape} do not match offsets (A={A}, B={B}, nx={self.nx})")
-        out = np.empty((A,), dtype=np.float32)
-        if cell is not None:
-            cell = _cell_rows(cell, B)
-            check(self.lib.epnn_forward_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), fptr(out)),
-                  self.lib)
-        elif box is None:
-            check(self.lib.epnn_forward_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(out)), self.lib)
-        else:
-            box = _box_rows(box, B)
-            check(self.lib.epnn_forward_xyz_pbc(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(box), fptr(out)),
-                  self.lib)
-        return out
+        per_atom = None if per_atom is None else _f32(per_atom)
+        B, A = len(offsets) - 1, int(offsets[-1])
+        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,) or (per_atom is not None and per_atom.shape != (A,)):
+            raise EpnnError(message.format(xyz=xyz.shape, x=x.shape, Q=Q.shape, A=A, B=B, nx=self.nx))
+        return offsets, xyz, x, Q, per_atom, B, A
 
     def forward_xyz_begin(self, offsets, xyz, x, Q, N):
         """First half of forward_xyz: returns as soon as the work is queued (the arrays may be reused at once)."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
-        B = len(offsets) - 1
-        A = int(offsets[-1])
-        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
-            raise EpnnError(f"forward_xyz: shapes xyz {xyz.shape} x {x.shape} Q {Q.shape} do not match offsets (A={A}, B={B}, nx={self.nx})")
+        offsets, xyz, x, Q, _, B, A = self._flat_batch(_FORWARD_SHAPES, offsets, xyz, x, Q)
         check(self.lib.epnn_forward_xyz_begin(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q)), self.lib)
         self._begun = A
 
@@ -322,24 +331,13 @@ class Engine:
         the pairs under the cutoff only: large systems) above that, 1 / 2 force one of them.  Without box and cell it is the dense
         step of epnn_train_step_xyz at any size."""
         _one_periodic_argument(box, cell)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        xyz, x, Q, y = _f32(xyz), _f32(x), _f32(Q), _f32(y)
-        B, A = len(offsets) - 1, int(offsets[-1])
-        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,) or y.shape != (A,):
-            raise EpnnError("train_step_xyz: array shapes do not match offsets")
+        offsets, xyz, x, Q, y, B, A = self._flat_batch("train_step_xyz: array shapes do not match offsets", offsets, xyz, x, Q, y)
         q = np.empty((A,), dtype=np.float32)
         loss = C.c_float()
-        if box is not None or cell is not None:
-            if cell is None:
-                box = _box_rows(box, B)
-                cell = np.zeros((B, 3, 3), dtype=np.float32)
-                cell[:, [0, 1, 2], [0, 1, 2]] = box
-            cell = _cell_rows(cell, B)
-            check(self.lib.epnn_train_step_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), fptr(y),
-                                                    fptr(q), C.byref(loss), int(bool(apply))), self.lib)
-            return q, loss.value
-        check(self.lib.epnn_train_step_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(y), fptr(q),
-                                           C.byref(loss), int(bool(apply))), self.lib)
+        suffix, cell = _geometry(box, cell, B, cells_only=True)
+        check(getattr(self.lib, "epnn_train_step_xyz" + suffix)(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q),
+                                                               *([] if cell is None else [fptr(cell)]), fptr(y), fptr(q), C.byref(loss),
+                                                               int(bool(apply))), self.lib)
         return q, loss.value
 
     def charges_vjp_xyz(self, offsets, xyz, x, Q, g, N, box=None, cell=None, strain=False):
@@ -353,44 +351,15 @@ class Engine:
         _one_periodic_argument(box, cell)
         if strain and box is not None:
             raise ValueError("charges_vjp_xyz: strain=True takes the cell as cell= (np.diag(box) for an orthorhombic one)")
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        xyz, x, Q, g = _f32(xyz), _f32(x), _f32(Q), _f32(g)
-        B, A = len(offsets) - 1, int(offsets[-1])
-        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,) or g.shape != (A,):
-            raise EpnnError("charges_vjp_xyz: array shapes do not match offsets")
+        offsets, xyz, x, Q, g, B, A = self._flat_batch("charges_vjp_xyz: array shapes do not match offsets", offsets, xyz, x, Q, g)
         q = np.empty((A,), dtype=np.float32)
         gxyz = np.empty((A, 3), dtype=np.float32)
-        if cell is not None or strain:
-            cell = _cell_rows(np.zeros((3, 3), np.float32) if cell is None else cell, B)
-            gs = np.empty((B, 3, 3), dtype=np.float32) if strain else None
-            check(self.lib.epnn_charges_vjp_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), fptr(g),
-                                                     fptr(q), fptr(gxyz), fptr(gs) if strain else None), self.lib)
-            return (q, gxyz, gs) if strain else (q, gxyz)
-        if box is None:
-            check(self.lib.epnn_charges_vjp_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(g), fptr(q),
-                                                fptr(gxyz)), self.lib)
-        else:
-            box = _box_rows(box, B)
-            check(self.lib.epnn_charges_vjp_xyz_pbc(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(box), fptr(g),
-                                                    fptr(q), fptr(gxyz)), self.lib)
-        return q, gxyz
-
-    def _jvp_batch(self, name, offsets, xyz, x, Q, box, cell):
-        """What charges_jvp_xyz and charges_jvp_xyz_multi do to the batch: the arrays as the C entries take them, box or cell as
-        cell rows (B, 3, 3) or None -> (offsets, xyz, x, Q, cell, B, A)."""
-        _one_periodic_argument(box, cell)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
-        B, A = len(offsets) - 1, int(offsets[-1])
-        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
-            raise EpnnError(f"{name}: array shapes do not match offsets")
-        if box is not None:
-            box = _box_rows(box, B)
-            cell = np.zeros((B, 3, 3), dtype=np.float32)
-            cell[:, [0, 1, 2], [0, 1, 2]] = box
-        if cell is not None:
-            cell = _cell_rows(cell, B)
-        return offsets, xyz, x, Q, cell, B, A
+        suffix, rows = _geometry(box, np.zeros((3, 3), np.float32) if strain and cell is None else cell, B)
+        gs = np.empty((B, 3, 3), dtype=np.float32) if strain else None
+        check(getattr(self.lib, "epnn_charges_vjp_xyz" + suffix)(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q),
+                                                                *([] if rows is None else [fptr(rows)]), fptr(g), fptr(q), fptr(gxyz),
+                                                                *([fptr(gs) if strain else None] if suffix == "_cell" else [])), self.lib)
+        return (q, gxyz, gs) if strain else (q, gxyz)
 
     def charges_jvp_xyz(self, offsets, xyz, x, Q, N, v=None, strain=None, dQ=None, box=None, cell=None):
         """Forward mode: flat batch and a direction -> (q (A,), tq (A,)), tq the derivative of the charges along it
@@ -400,7 +369,9 @@ class Engine:
         None (= 0); the three add up.  box (3,) or (B, 3), cell (3, 3) or (B, 3, 3) as in forward_xyz; neither: open molecules.
         One call costs about one forward of the pair-list gradient path, whose charges q has bit for bit; it touches no training
         state and works without train_init."""
-        offsets, xyz, x, Q, cell, B, A = self._jvp_batch("charges_jvp_xyz", offsets, xyz, x, Q, box, cell)
+        _one_periodic_argument(box, cell)
+        offsets, xyz, x, Q, _, B, A = self._flat_batch("charges_jvp_xyz: array shapes do not match offsets", offsets, xyz, x, Q)
+        _, cell = _geometry(box, cell, B, cells_only=True)
         if v is not None:
             v = _f32(v)
             if v.shape != (A, 3):
@@ -432,7 +403,9 @@ class Engine:
         or (K, B, 3, 3), dQ (K,) or (K, B); each may be None (= 0 for every direction), at least one must be given, and those
         given must agree on K (1..16).  The primal, the pair list and every per-pair and per-atom primal statement run once;
         box and cell as in charges_jvp_xyz."""
-        offsets, xyz, x, Q, cell, B, A = self._jvp_batch("charges_jvp_xyz_multi", offsets, xyz, x, Q, box, cell)
+        _one_periodic_argument(box, cell)
+        offsets, xyz, x, Q, _, B, A = self._flat_batch("charges_jvp_xyz_multi: array shapes do not match offsets", offsets, xyz, x, Q)
+        _, cell = _geometry(box, cell, B, cells_only=True)
         Ks = {}
         if v is not None:
             v = _f32(v)
@@ -476,11 +449,7 @@ class Engine:
         F = ffix + fq; fq is -gxyz of charges_vjp_xyz(g=phi) on "grad_path" 2, bit for bit, and q has that path's bits.  Open
         systems only (no box or cell), no self-energy term, no bonded exclusions: alpha is the only short-range handle.  One
         call costs about one gradient call of the pair-list path; it touches no training state and works without train_init."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        xyz, x, Q = _f32(xyz), _f32(x), _f32(Q)
-        B, A = len(offsets) - 1, int(offsets[-1])
-        if xyz.shape != (A, 3) or x.shape != (A, self.nx) or Q.shape != (B,):
-            raise EpnnError("coulomb_xyz: array shapes do not match offsets")
+        offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz: array shapes do not match offsets", offsets, xyz, x, Q)
         q = np.empty((A,), dtype=np.float32)
         phi = np.empty((A,), dtype=np.float32)
         E = np.empty((B,), dtype=np.float64)
@@ -584,17 +553,13 @@ class Engine:
     def forward_xyz_dev(self, offsets, d_xyz, d_x, d_Q, d_q, N, box=None, cell=None):
         _one_periodic_argument(box, cell)
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        if cell is not None:
-            cell = _cell_rows(cell, len(offsets) - 1)
-            check(self.lib.epnn_forward_xyz_cell_dev(self.h, len(offsets) - 1, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr,
-                                                     d_Q.ptr, fptr(cell), d_q.ptr), self.lib)
-        elif box is None:
-            check(self.lib.epnn_forward_xyz_dev(self.h, len(offsets) - 1, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr,
-                                                d_Q.ptr, d_q.ptr), self.lib)
-        else:
-            box = _box_rows(box, len(offsets) - 1)
-            check(self.lib.epnn_forward_xyz_pbc_dev(self.h, len(offsets) - 1, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr,
-                                                    d_Q.ptr, fptr(box), d_q.ptr), self.lib)
+        B = len(offsets) - 1
+        if box is None and cell is None:                           # (a trajectory's or a benchmark's loop: nothing else per call)
+            check(self.lib.epnn_forward_xyz_dev(self.h, B, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr, d_Q.ptr, d_q.ptr), self.lib)
+            return
+        suffix, rows = _geometry(box, cell, B)
+        check(getattr(self.lib, "epnn_forward_xyz" + suffix + "_dev")(self.h, B, int(N), iptr(offsets), d_xyz.ptr, d_x.ptr, d_Q.ptr,
+                                                                     fptr(rows), d_q.ptr), self.lib)
 
     def sync(self):
         check(self.lib.epnn_sync(self.h), self.lib)

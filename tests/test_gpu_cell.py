@@ -307,6 +307,44 @@ def test_device_entry_with_a_changing_cell(gpu_engine_factory):
     assert np.array_equal(boxed, eng.forward_xyz(offsets, xyz, x, Q, 64, box=np.float32([8, 8, 8])))
 
 
+def test_one_handle_through_every_geometry(gpu_engine_factory):
+    """One handle and one set of device buffers, forward_xyz_dev as open molecules, in a box, in the diagonal cell of that box, in a
+    sheared cell and as open molecules again: every result has the bits of the same call on a fresh handle, the first and the last
+    are equal.  Once with a wait behind every call and once for every prefix of the sequence back to back, where the handle decides
+    from the kind and the rows of the forward before whether the next one is the same forward enqueued ahead."""
+    w = random_weights(9, 2, seed=12, scale=0.35)
+    box = np.float32([13.0, 12.0, 12.5])
+    mols = [_cell(70 + k, n, cr.SHEARED) for k, n in enumerate([9, 20])]
+    offsets, xyz, x = _batch(mols)
+    Q = np.float32([0, -1])
+    A = int(offsets[-1])
+    geos = [{}, {"box": box}, {"cell": np.diag(box).astype(np.float32)}, {"cell": cr.SHEARED}, {}]
+
+    def handle():
+        eng = gpu_engine_factory(nx=9, T=2)
+        eng.set_weights(w)
+        return eng, (eng.to_device(xyz), eng.to_device(x), eng.to_device(Q), eng.alloc(A * 4))
+
+    want = []
+    for geo in geos:
+        fresh, (dx, dX, dQ, dq) = handle()
+        fresh.forward_xyz_dev(offsets, dx, dX, dQ, dq, 24, **geo)
+        fresh.sync()
+        want.append(dq.download((A,)))
+    eng, (dx, dX, dQ, dq) = handle()
+    for k, geo in enumerate(geos):
+        eng.forward_xyz_dev(offsets, dx, dX, dQ, dq, 24, **geo)
+        eng.sync()
+        assert np.array_equal(dq.download((A,)), want[k]), k
+    for k in range(len(geos)):
+        for geo in geos[:k + 1]:                               # back to back, no wait in between
+            eng.forward_xyz_dev(offsets, dx, dX, dQ, dq, 24, **geo)
+        eng.sync()
+        assert np.array_equal(dq.download((A,)), want[k]), k
+    assert np.array_equal(want[0], want[4])
+    assert not np.array_equal(want[1], want[3])                # (the atoms fill the sheared cell: its images are other neighbours than the box's)
+
+
 # ------------------------------------------------------------------------------------------------ 9. gradients and strain
 @pytest.mark.parametrize("N,ns,name", [(24, [20, 9], "sheared"), (96, [40], "slab"), (100, [40, 30], "sheared"), (24, [18, 10], "open")])
 def test_charge_gradients_and_strain_in_cells(gpu_engine_factory, N, ns, name):
