@@ -436,10 +436,12 @@ static int pack_weights(epnn_handle *h) {
             return off;
         };
         auto frag_bf3 = [&](auto &&fn) { return frag_bf3s([&](int q, int s, int out) { return fn(accf(s, q), out); }); };
-        // a K = 16 kernel as three bf16 pieces per weight for v_mfma_f32_16x16x16_bf16, [2][3][64 lanes][2 dwords]: lane (q, m) of row
-        // block rb: K slots s = 0..3 = fn(q, s, 16 rb + m); dword j = slots 2j | 2j+1 << 16
+        // a K = 16 kernel as three bf16 pieces w1, w2, w3 per weight, [2][2][64 lanes][4 dwords]: lane (q, m) of row block rb: K slots
+        // s = 0..3 = fn(q, s, 16 rb + m), a piece is two dwords (dword j = slots 2j | 2j+1 << 16).  A lane's row block is the 32-byte
+        // string w1 w2 w3 w1, stored as its two 16-byte halves w1 w2 | w3 w1: the two K = 32 operands of w16_mm_bfk16
+        // (epnn_wave.hip.h: two K = 16 products per v_mfma_f32_16x16x32_bf16)
         auto frag_bf3k16 = [&](auto &&fn) {
-            const int off = alloc((size_t)2 * 3 * 64 * 2);
+            const int off = alloc((size_t)2 * 2 * 64 * 4);
             for (int rb = 0; rb < 2; ++rb)
                 for (int l = 0; l < 64; ++l) {
                     uint32_t pc[3][4];
@@ -455,10 +457,12 @@ static int pack_weights(epnn_handle *h) {
                             v = v - top;
                         }
                     }
-                    for (int k = 0; k < 3; ++k)
+                    static const int order[4] = {0, 1, 2, 0};                   // w1 w2 | w3 w1
+                    for (int i = 0; i < 4; ++i)
                         for (int j = 0; j < 2; ++j) {
+                            const int k = order[i];
                             const uint32_t word = pc[k][2 * j] | pc[k][2 * j + 1] << 16;
-                            memcpy(&buf[off + ((rb * 3 + k) * 64 + l) * 2 + j], &word, 4);
+                            memcpy(&buf[off + ((rb * 2 + i / 2) * 64 + l) * 4 + 2 * (i & 1) + j], &word, 4);
                         }
                 }
             return off;

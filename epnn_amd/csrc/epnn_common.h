@@ -74,7 +74,7 @@ struct WeightIndex {
 struct WaveGnnPack {           // GNN step t
     int we;               // [2][12][64]  e order       We_t
     int we16;             // [2][4][64]   k = 4q + s    B^T We_t   (edge features in the 16-dimensional basis)
-    int we16b;            // [2][3][64][2] dwords       the same as three bf16 pieces per weight (v_mfma_f32_16x16x16_bf16: K slot s of lane q = coefficient 4q + s)
+    int we16b;            // [2][2][64][4] dwords       the same as three bf16 pieces per weight, a lane's row block = w1 w2 | w3 w1 (w16_mm_bfk16: K slot s of lane q = coefficient 4q + s)
     int w2;               // [2][8][64]   acc order     W2_t
     int w2b;              // [2][3][64][4] dwords       W2_t as three bf16 pieces per weight (w16_split3 / pack_bf16x3), K slot s of lane q = acc order
     int b2;               // [32]
@@ -87,7 +87,7 @@ struct WaveGnnPack {           // GNN step t
     int cu3;              // [32]         Wu1_H^T bu3
     // the same kernels as three bf16 pieces per weight (32-unit update MLPs only): the per-atom chains on the bf16 matrix pipe.
     // `..hb` = the K = 32 block that multiplies nm u2 (acc order), [2][3][64][4] dwords each (w2b's layout); `..xb` = the xq block,
-    // a K = 16 operand in the slot order of wave_xq_slot, [2][3][64][2] dwords each (we16b's layout, v_mfma_f32_16x16x16_bf16)
+    // a K = 16 operand in the slot order of wave_xq_slot, [2][2][64][4] dwords each (we16b's layout: w1 w2 | w3 w1, w16_mm_bfk16)
     int u1sb, u2b, pu1b, pwihb, pwixb, pwjhb, pwjxb;
 };
 // K slot (lane group q, slot s of the lane: K index 4q + s of v_mfma_f32_16x16x16_bf16) of the xq block's operand -> index into xq
@@ -103,7 +103,7 @@ struct WaveEpnPack {           // EPN step t
     int we, w2, b2, w3;   // w3: [32]
     int w2b;              // [2][3][64][4] dwords: W2_t as three bf16 pieces per weight (see WaveGnnPack)
     int we16;             // [2][4][64]   B^T We_t
-    int we16b;            // [2][3][64][2] dwords: B^T We_t as three bf16 pieces per weight (see WaveGnnPack)
+    int we16b;            // [2][2][64][4] dwords: B^T We_t as three bf16 pieces per weight (see WaveGnnPack)
     int wi, wj;           // [2][XS+12][64]  xq rows, then h rows (acc order over 48 features): h given by the caller
     int wif, wjf;         // [2][8+XS][64]   acc rows: Wu3 M_h;  xq rows: [M_h^T bu3, M_x, M_q, b1]: h = nm (Wu3^T u2 + bu3) of the GNN stack
     int wifhb, wifxb, wjfhb, wjfxb;      // wif / wjf as bf16 pieces (see WaveGnnPack: ..hb K = 32, ..xb K = 16)
@@ -112,7 +112,7 @@ struct WaveIndex {
     WaveGnnPack g[EPNN_MAXT];
     WaveEpnPack e[EPNN_MAXT];
     int wi0, wj0;         // [2][XS+12][64]  first GNN step (h given by the caller, usually zeros)
-    int wi0xb, wj0xb;     // [2][3][64][2] dwords: the xq rows of wi0 / wj0 as bf16 pieces (see WaveGnnPack's ..xb; 32-unit update MLPs only)
+    int wi0xb, wj0xb;     // [2][2][64][4] dwords: the xq rows of wi0 / wj0 as bf16 pieces (see WaveGnnPack's ..xb; 32-unit update MLPs only)
     int u1h0;             // [2][12][64]     acc order over 48 features  Wu1_H
     int u3;               // [3][8][64]      acc order  Wu3 (48 outputs = 3 row blocks)
     int bu3;              // [48]

@@ -167,8 +167,9 @@ __device__ __forceinline__ f32x4 w16_mfma_bf(u32x4 a, u32x4 b, f32x4 c) {
 // as the accumulator (rows 4 q + r = v[r]), D = C + A B with A = -I (lane 16 qa + ma holds -1 in slot ma % 4 when qa = ma / 4) is
 // "x - piece" in place: 2 MFMAs per 8 values and level instead of 8 v_and + 8 v_sub -- 12 vector instructions per split instead
 // of 44, the SAME pieces bit for bit (round 5: bench 321 -> 327 M atoms/s; protein 0.382 -> 0.372 ms with the tiled sweep's own
-// arrangement, epnn_large.hip.h).  The K = 16 instruction takes half the pipe time of the K = 32 one (a row block's four values
-// are two dwords of the packed piece) and its operand is two registers, the same for both row blocks.
+// arrangement, epnn_large.hip.h).  The K = 16 instruction's operand is two registers (a row block's four values are two dwords of
+// the packed piece), the same for both row blocks.  (It was taken for half the pipe time of the K = 32 one; the counters say it
+// keeps the pipe busy just as long, 16 cycles: profiles/r18_k16_pairs.txt section 2.)
 typedef short w16_s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned w16_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ w16_u32x2 w16_ident() {
@@ -240,34 +241,46 @@ __device__ __forceinline__ void w16_mm_bf(const u32x4 (&w)[2][3], u32x4 z1, u32x
     _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_)                                                         \
         _Pragma("unroll") for (int pc_ = 0; pc_ < 3; ++pc_)                                                     \
             (dst)[rb_][pc_] = reinterpret_cast<const u32x4 *>(wp + (size_t)(unsigned)(off))[(rb_ * 3 + pc_) * 64 + lane];
-// ---- the same at K = 16 (v_mfma_f32_16x16x16_bf16, half the pipe time): operands of up to 16 values -- the pair coordinates of a G
-// product and the xq block (node mask, one, charge, x: wave_xq_slot).  Lane 16 q + m holds row / column m and the K slots
-// 4 q .. 4 q + 3 as two dwords of bf16 pairs; the split of a lane's four values is one remainder MFMA per level.
-__device__ __forceinline__ void w16_split3k16(f32x4 x, w16_u32x2 &p1, w16_u32x2 &p2, w16_u32x2 &p3) {
-    const w16_u32x2 I = w16_ident();
-    p1 = w16_pack_hi2(x);
-    x = w16_rem(I, p1[0], p1[1], x);
-    p2 = w16_pack_hi2(x);
-    x = w16_rem(I, p2[0], p2[1], x);
-    p3 = w16_pack_hi2(x);
+// ---- the same at K = 16: operands of up to 16 values -- the pair coordinates of a G product and the xq block
+// (node mask, one, charge, x: wave_xq_slot).  Lane 16 q + m holds row / column m and the K slots 4 q .. 4 q + 3 as two dwords of
+// bf16 pairs; the split of a lane's four values is one remainder MFMA (v_mfma_f32_16x16x16_bf16) per level.
+// The six partial products are issued as THREE v_mfma_f32_16x16x32_bf16: two K = 16 operands side by side in four consecutive
+// registers are one K = 32 operand (lane 16 q + m: K slots 8 q .. 8 q + 3 from the first, 8 q + 4 .. 8 q + 7 from the second), so
+//     (w1|w2) . (z3|z1) = w1 z3 + w2 z1,    (w3|w1) . (z1|z2) = w3 z1 + w1 z2,    (w1|w2) . (z1|z2) = w1 z1 + w2 z2
+// are the same six products, each once, the smallest terms in the first two, in half the instructions and half the links of the
+// accumulate chain (measured: a K = 16 instruction keeps the pipe busy as long as a K = 32 one, profiles/r18_k16_pairs.txt: the
+// pipe's busy cycles fell with the instruction count).  This pairing needs TWO four-register tuples
+// on either side and none that overlap: the compiler gives every MFMA operand a register tuple of its own (it copies registers
+// where two operands share some), so a third tuple is four registers or four v_mov.  Each side carries its first piece twice:
+// the activation as a = z3|z1, b = z1|z2 (W16K16 holds a and z2), the kernel's row block as the 32 bytes w1 w2 | w3 w1 (the host's
+// frag_bf3k16).
+struct W16K16 { u32x4 a; w16_u32x2 z2; };              // (b = z1|z2 is put together where it is used: two copies, no registers held)
+__device__ __forceinline__ W16K16 w16_k16(w16_u32x2 p1, w16_u32x2 p2, w16_u32x2 p3) {
+    return W16K16{u32x4{p3[0], p3[1], p1[0], p1[1]}, p2};
 }
-// D[rb] += W[rb] z, the partial products in w16_mm_bf's order (smallest terms first)
-__device__ __forceinline__ void w16_mm_bfk16(const w16_u32x2 (&w)[2][3], const w16_u32x2 (&z)[3], f32x4 (&d)[2]) {
+__device__ __forceinline__ W16K16 w16_split3k16(f32x4 x) {
+    const w16_u32x2 I = w16_ident();
+    const w16_u32x2 p1 = w16_pack_hi2(x);
+    x = w16_rem(I, p1[0], p1[1], x);
+    const w16_u32x2 p2 = w16_pack_hi2(x);
+    x = w16_rem(I, p2[0], p2[1], x);
+    return w16_k16(p1, p2, w16_pack_hi2(x));
+}
+// D[rb] += W[rb] z: w[rb][0] = w1|w2, w[rb][1] = w3|w1
+__device__ __forceinline__ void w16_mm_bfk16(const u32x4 (&w)[2][2], const W16K16 &z, f32x4 (&d)[2]) {
+    const u32x4 zb = {z.a[2], z.a[3], z.z2[0], z.z2[1]};
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
-        d[rb] = w16_rem(w[rb][0], z[2][0], z[2][1], d[rb]);
-        d[rb] = w16_rem(w[rb][1], z[1][0], z[1][1], d[rb]);
-        d[rb] = w16_rem(w[rb][2], z[0][0], z[0][1], d[rb]);
-        d[rb] = w16_rem(w[rb][0], z[1][0], z[1][1], d[rb]);
-        d[rb] = w16_rem(w[rb][1], z[0][0], z[0][1], d[rb]);
-        d[rb] = w16_rem(w[rb][0], z[0][0], z[0][1], d[rb]);
+        d[rb] = w16_mfma_bf(w[rb][0], z.a, d[rb]);
+        d[rb] = w16_mfma_bf(w[rb][1], zb, d[rb]);
+        d[rb] = w16_mfma_bf(w[rb][0], zb, d[rb]);
     }
 }
-// a K = 16 three-piece kernel: [2 row blocks][3 pieces][64 lanes][2 dwords], one 8-byte load each
+// a K = 16 three-piece kernel: [2 row blocks][2 halves][64 lanes][4 dwords] (w1 w2 | w3 w1), one 16-byte load per half
 #define W16_LDB16(dst, off)                                                                                     \
     _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_)                                                         \
-        _Pragma("unroll") for (int pc_ = 0; pc_ < 3; ++pc_)                                                     \
-            (dst)[rb_][pc_] = reinterpret_cast<const w16_u32x2 *>(wp + (size_t)(unsigned)(off))[(rb_ * 3 + pc_) * 64 + lane];
+        _Pragma("unroll") for (int hf_ = 0; hf_ < 2; ++hf_)                                                     \
+            (dst)[rb_][hf_] = reinterpret_cast<const u32x4 *>(wp + (size_t)(unsigned)(off))[(rb_ * 2 + hf_) * 64 + lane];
 __device__ __forceinline__ f32x4 w16_relu(f32x4 v) {
     return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
 }
@@ -351,8 +364,9 @@ __device__ __forceinline__ void w16_feed(const f32x4 (&a)[NRB], float (&in)[4 * 
 // between steps is nm * u2 (4 NRU K steps), the pair sweep and the EPN stack are the same for every NRU.
 // ---- the edge products G = We^T pt of the in-kernel front-end (K = 16 coordinates per pair, §2 of DESIGN.md) on the bf16 pipe as well:
 // pt split into three pieces (remainders on the matrix pipe, like every activation), We as three bf16 pieces from the host
-// (WaveGnnPack::we16b), six v_mfma_f32_16x16x16_bf16 per row block (48 cycles against 4 x 32 of v_mfma_f32_16x16x4_f32): bench
-// 331.6 -> 337.8 M atoms/s.  Pair lists from outside (K = 48, !FRONT) keep the f32 MFMAs; -DEPNN_G_F32 builds them everywhere.
+// (WaveGnnPack::we16b), six partial products per row block (first as six v_mfma_f32_16x16x16_bf16 against four
+// v_mfma_f32_16x16x4_f32 of 32 cycles: bench 331.6 -> 337.8 M atoms/s; now two per v_mfma_f32_16x16x32_bf16, three instructions
+// of 16 cycles, w16_mm_bfk16).  Pair lists from outside (K = 48, !FRONT) keep the f32 MFMAs; -DEPNN_G_F32 builds them everywhere.
 // Both macros are used inside the kernels (k_wave_forward, k_wave_forward2), where FRONT, KE, gw, wp, lane exist.
 #ifdef EPNN_G_F32
 #define W16_G_BF 0
@@ -361,12 +375,10 @@ __device__ __forceinline__ void w16_feed(const f32x4 (&a)[NRB], float (&in)[4 * 
 #endif
 #define W16_G_DECL                                                                                                        \
     constexpr bool GB = FRONT && W16_G_BF;                                                                                \
-    w16_u32x2 gwb[2][3];                                                                                                  \
+    u32x4 gwb[2][2];                                                                                                      \
     auto g_mm = [&](const float (&e)[KE], f32x4 (&d)[2]) {      /* d[rb] += We[rb] e for 16 pairs (columns) */            \
         if constexpr (GB) {                                                                                               \
-            w16_u32x2 z[3];                                                                                               \
-            w16_split3k16(f32x4{e[0], e[1], e[2], e[3]}, z[0], z[1], z[2]);                                               \
-            w16_mm_bfk16(gwb, z, d);                                                                                      \
+            w16_mm_bfk16(gwb, w16_split3k16(f32x4{e[0], e[1], e[2], e[3]}), d);                                           \
         } else {                                                                                                          \
             w16_mm<2, KE>(gw, e, d);                                                                                      \
         }                                                                                                                 \
@@ -656,9 +668,10 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
     constexpr bool CHB = NRU == 2 && GNN;
 #endif
     u32x4 Bp0[3], Bp1[3];                                  // nm u2 of the last step as pieces (CHB)
-    w16_u32x2 xqb0[3], xqb1[3];                            // the xq operand's pieces (CHB)
+    W16K16 xqb0, xqb1;                                     // the xq operand's pieces (CHB): w16_mm_bfk16
     // (slots: wave_xq_slot -- lane group 0: mask, one, charge, x[0]; q >= 1: x[4q - 3 .. 4q].  Only the charge changes, between EPN
-    //  steps: its three pieces go into the low half of dword 1 of the three operand pieces of lane group 0; nothing else is kept)
+    //  steps: its three pieces go into the low half of dword 1 of the three operand pieces of lane group 0 -- the odd dwords
+    //  of a = z3|z1 and of z2; nothing else is kept)
     float qc0 = 0.f, qc1 = 0.f;                            // the columns' charges, the same bits in every lane
     auto xq_charge = [&]() {
         if (q != 0) return;
@@ -666,15 +679,12 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
         const float b0_ = __uint_as_float(__float_as_uint(r0_) & 0xffff0000u), c0_ = r0_ - b0_;
         const float a1_ = __uint_as_float(__float_as_uint(qc1) & 0xffff0000u), r1_ = qc1 - a1_;
         const float b1_ = __uint_as_float(__float_as_uint(r1_) & 0xffff0000u), c1_ = r1_ - b1_;
-        const float pc0[3] = {a0_, b0_, c0_}, pc1[3] = {a1_, b1_, c1_};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            xqb0[k][1] = (xqb0[k][1] & 0xffff0000u) | (__float_as_uint(pc0[k]) >> 16);
-            xqb1[k][1] = (xqb1[k][1] & 0xffff0000u) | (__float_as_uint(pc1[k]) >> 16);
-        }
+        auto put = [](unsigned w, float pc) { return (w & 0xffff0000u) | (__float_as_uint(pc) >> 16); };
+        xqb0.a[1] = put(xqb0.a[1], c0_); xqb0.a[3] = put(xqb0.a[3], a0_); xqb0.z2[1] = put(xqb0.z2[1], b0_);
+        xqb1.a[1] = put(xqb1.a[1], c1_); xqb1.a[3] = put(xqb1.a[3], a1_); xqb1.z2[1] = put(xqb1.z2[1], b1_);
     };
     // d += W xq for the two column blocks (wx: a K = 16 pack in the slot order of wave_xq_slot)
-    auto xq_mm = [&](const w16_u32x2 (&wx)[2][3], f32x4 (&d0)[2], f32x4 (&d1)[2]) {
+    auto xq_mm = [&](const u32x4 (&wx)[2][2], f32x4 (&d0)[2], f32x4 (&d1)[2]) {
         w16_mm_bfk16(wx, xqb0, d0);
         if (two) w16_mm_bfk16(wx, xqb1, d1);
     };
@@ -695,8 +705,8 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             xs0[s_] = v0;
             xs1[s_] = v1;
         }
-        w16_split3k16(xs0, xqb0[0], xqb0[1], xqb0[2]);
-        w16_split3k16(xs1, xqb1[0], xqb1[1], xqb1[2]);
+        xqb0 = w16_split3k16(xs0);
+        xqb1 = w16_split3k16(xs1);
     }
     WAVE_STAMP();   // init done
     const float Nf = (float)A.N, padw = (float)(A.N - n);
@@ -772,7 +782,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
         {
             // the xq block of Wi / Wj: its K = 16 bf16 pieces (CHB), or the f32 xq steps; the h steps only when h is given
             float wa[2][EPNN_XS], wc[2][EPNN_XS];
-            w16_u32x2 wax[2][3], wcx[2][3];
+            u32x4 wax[2][2], wcx[2][2];
             if constexpr (CHB) {
                 W16_LDB16(wax, X.wi0xb);
                 W16_LDB16(wcx, X.wj0xb);
@@ -1088,7 +1098,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
               if (!lastg) {
                 // next step: G rows, then P / R / u1pre from (nm u2 pieces | xq operand) through the folded matrices' pieces
                 u32x4 wh[2][3];
-                w16_u32x2 wx[2][3];
+                u32x4 wx[2][2];
                 W16_LDB(wh, M.pwihb);
                 W16_LDB16(wx, M.pwixb);
                 WAVE_FENCE();
@@ -1215,8 +1225,8 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
         //      the same row: the same bits as the split every step made), the LDS addresses of the P rows of li and lj, and the
         //      address of the transfer-matrix entry this lane group stores (~0: none -- q >= 2, or a pair beyond the near
         //      tolerance, whose weight is 0 and whose entry is never written; the weights of this front-end are exactly 0 or 1).
-        //      Per pair and lane group q two 16-byte halves:  a = piece 1 | piece 2,  IN PLACE of the lane group's quarter of the
-        //      pair's f32 row (every lane overwrites exactly what it read: no order to watch);  b = piece 3 | P address of li |
+        //      Per pair and lane group q two 16-byte halves:  a = piece 3 | piece 1,  IN PLACE of the lane group's quarter of the
+        //      pair's f32 row (every lane overwrites exactly what it read: no order to watch);  b = piece 2 | P address of li |
         //      of lj << 16 | store address,  16 ptl words further down (below the last row, above the EPN layout's tables).
         //      The first `ktab` pairs have one -- all of them where 32 np words fit, else whole blocks of 16 as far as the room
         //      below the rows goes; the blocks behind them run as before from their f32 rows (untouched) and records.
@@ -1234,16 +1244,15 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 const unsigned ra = pt_top - 64u * (unsigned)(sl + 1);
                 const f32x4 v = w16_lds_ld4(ra);
                 const unsigned ij = eij[sl];
-                w16_u32x2 z[3];
-                w16_split3k16(v, z[0], z[1], z[2]);
+                const W16K16 z = w16_split3k16(v);
                 const unsigned li = ij & 0x7Fu, lj = ij >> 8;
                 const unsigned to = q == 0 ? li : lj, from = q == 0 ? lj : li;
                 const unsigned rows = (pl_a + 4u * EPNN_PST * li) | (pl_a + 4u * EPNN_PST * lj) << 16;
                 const unsigned st = (q < 2 && (ij & 0x80u)) ? dm_a + 4u * (to * DMS + ((from & 3u) << 3) + (from >> 2)) : ~0u;
                 asm volatile("" ::: "memory");
                 if (ok) {
-                    w16_lds_stu4(ra, u32x4{z[0][0], z[0][1], z[1][0], z[1][1]});
-                    w16_lds_stu4(ra - tb_off, u32x4{z[2][0], z[2][1], rows, st});
+                    w16_lds_stu4(ra, z.a);
+                    w16_lds_stu4(ra - tb_off, u32x4{z.z2[0], z.z2[1], rows, st});
                 }
                 asm volatile("" ::: "memory");
             }
@@ -1256,7 +1265,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             if constexpr (CHB && FOLD) {
                 // P / R of this step from (nm u2 pieces | xq operand): the bf16 pipe (see CHB)
                 u32x4 wh[2][3];
-                w16_u32x2 wx[2][3];
+                u32x4 wx[2][2];
                 W16_LDB(wh, M.wifhb);
                 W16_LDB16(wx, M.wifxb);
                 WAVE_FENCE();
@@ -1413,8 +1422,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                     auto block_t = [&](int blk, const RecT &r_, const RowsT &w_) {
                         const bool valid = blk * 16 + n16 < ktab;
                         f32x4 g[2] = {w16_splat(0.f), w16_splat(0.f)};
-                        const w16_u32x2 z[3] = {{r_.a[0], r_.a[1]}, {r_.a[2], r_.a[3]}, {r_.b[0], r_.b[1]}};
-                        w16_mm_bfk16(gwb, z, g);
+                        w16_mm_bfk16(gwb, W16K16{r_.a, w16_u32x2{r_.b[0], r_.b[1]}}, g);
                         const float d = pair_d(g, w_);
                         // (ONE store instruction, lane group 0 what i receives, 1 what j receives; weight 1: d and -d as they are)
                         if (valid && r_.b[3] != ~0u) w16_lds_stf(r_.b[3], q == 0 ? d : -d);

@@ -138,15 +138,14 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
     constexpr bool CHB = true;
 #endif
     u32x4 Bp[3];
-    w16_u32x2 xqb[3];                                       // (a K = 16 operand: wave_xq_slot)
+    W16K16 xqb;                                             // (a K = 16 operand: wave_xq_slot)
     float qc = cat ? qa : 0.f;                              // the column's charge, the same bits in every lane
-    auto xq_charge = [&]() {                                // (k_wave_forward: the charge's pieces into the low half of dword 1)
+    auto xq_charge = [&]() {                                // (k_wave_forward: the charge's pieces into the low half of the odd dwords)
         if (q != 0) return;
         const float a_ = __uint_as_float(__float_as_uint(qc) & 0xffff0000u), r_ = qc - a_;
         const float b_ = __uint_as_float(__float_as_uint(r_) & 0xffff0000u), c_ = r_ - b_;
-        const float pc[3] = {a_, b_, c_};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xqb[k][1] = (xqb[k][1] & 0xffff0000u) | (__float_as_uint(pc[k]) >> 16);
+        auto put = [](unsigned w, float pc) { return (w & 0xffff0000u) | (__float_as_uint(pc) >> 16); };
+        xqb.a[1] = put(xqb.a[1], c_); xqb.a[3] = put(xqb.a[3], a_); xqb.z2[1] = put(xqb.z2[1], b_);
     };
     if constexpr (CHB) {
         f32x4 xs_;
@@ -160,7 +159,7 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
             if (q == 0 && s_ == 2) v = qc;
             xs_[s_] = v;
         }
-        w16_split3k16(xs_, xqb[0], xqb[1], xqb[2]);
+        xqb = w16_split3k16(xs_);
     }
     const bool have_h = !FRONT && A.h_in != nullptr;        // h given by the caller (make_model's h_inp); zeros with the compact entry
     f32x4 hk[3] = {w16_splat(0.f), w16_splat(0.f), w16_splat(0.f)};
@@ -329,7 +328,7 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
         f32x4 b2v[2];
         {
             float wa[2][EPNN_XS], wc[2][EPNN_XS];
-            w16_u32x2 wax[2][3], wcx[2][3];
+            u32x4 wax[2][2], wcx[2][2];
             if constexpr (CHB) {
                 W16_LDB16(wax, X.wi0xb);
                 W16_LDB16(wcx, X.wj0xb);
@@ -542,7 +541,7 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
             if constexpr (CHB) {
               if (!lastg) {
                 u32x4 wh[2][3];
-                w16_u32x2 wx[2][3];
+                u32x4 wx[2][2];
                 W16_LDB(wh, M.pwihb);
                 W16_LDB16(wx, M.pwixb);
                 WAVE_FENCE();
@@ -622,7 +621,7 @@ __global__ __launch_bounds__(64 * NW, EPNN_WAVES_PER_SIMD) void k_wave_forward2(
             const WaveEpnPack &M = X.e[t];
             if constexpr (CHB) {
                 u32x4 wh[2][3];
-                w16_u32x2 wx[2][3];
+                u32x4 wx[2][2];
                 W16_LDB(wh, M.wifhb);
                 W16_LDB16(wx, M.wifxb);
                 WAVE_FENCE();

@@ -3,7 +3,7 @@
 // (v_mfma_f32_16x16x32_bf16, 16 cycles each on gfx950 against 8 x 32 cycles of v_mfma_f32_16x16x4_f32 for the same K = 32).
 // Checks the operand layout (lane 16q + m: row / column m, K slots 8q .. 8q + 7 as four dwords of bf16 pairs) and the accuracy
 // against float64 and against the f32 MFMA, then times both forms with the split's VALU work included.
-//   hipcc --offload-arch=gfx950 -O3 -o bf16x6 bf16x6.hip && ./bf16x6
+//   hipcc --offload-arch=gfx950 -O3 -o bf16x6 bf16x6.hip && ./bf16x6            (./bf16x6 k16pairs: only the K = 16 pairing)
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -195,7 +195,132 @@ __global__ __launch_bounds__(64, 2) void k_time(const float *src, float *dst, in
     }
     for (int r = 0; r < 4; ++r) dst[(blockIdx.x * 64 + lane) * 8 + r] = S[0][r], dst[(blockIdx.x * 64 + lane) * 8 + 4 + r] = S[1][r];
 }
-int main() {
+// The K = 16 products of the fused kernels (w16_mm_bfk16, epnn_wave.hip.h): C[16x16] = W[16x16] * Z[16x16], six partial products.
+// Six-instruction form (what the kernels issued before): six v_mfma_f32_16x16x16_bf16.  Paired form, instruction for instruction
+// and register for register what w16_mm_bfk16 issues: two K = 16 operands side by side in four consecutive registers are one
+// K = 32 operand, so three v_mfma_f32_16x16x32_bf16 take the same six products two at a time --
+//     (w1|w2) . (z3|z1),   (w3|w1) . (z1|z2),   (w1|w2) . (z1|z2)
+// with the kernel's row block as the two tuples w1 w2 | w3 w1 (the host's pack) and the activation as a = z3|z1 plus z2, b = z1|z2
+// being a's upper half and z2 (W16K16).  Every block takes its own 16x16 pair of operands; `zs` receives the six operand dwords
+// a, z2 (MFMA-remainder split), `zp` the pieces of the v_and / v_sub form in the same order.
+__device__ __forceinline__ void split3k16_valu(const float (&v)[4], u32x2 &p1, u32x2 &p2, u32x2 &p3) {
+    float r1[4], r2[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        r1[s] = v[s] - __uint_as_float(__float_as_uint(v[s]) & 0xffff0000u);
+        r2[s] = r1[s] - __uint_as_float(__float_as_uint(r1[s]) & 0xffff0000u);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        p1[j] = __builtin_amdgcn_perm(__float_as_uint(v[2 * j + 1]), __float_as_uint(v[2 * j]), 0x07060302u);
+        p2[j] = __builtin_amdgcn_perm(__float_as_uint(r1[2 * j + 1]), __float_as_uint(r1[2 * j]), 0x07060302u);
+        p3[j] = __builtin_amdgcn_perm(__float_as_uint(r2[2 * j + 1]), __float_as_uint(r2[2 * j]), 0x07060302u);
+    }
+}
+__device__ __forceinline__ u32x2 pack_hi2(const f32x4 &v) {
+    return u32x2{__builtin_amdgcn_perm(__float_as_uint(v[1]), __float_as_uint(v[0]), 0x07060302u),
+                 __builtin_amdgcn_perm(__float_as_uint(v[3]), __float_as_uint(v[2]), 0x07060302u)};
+}
+__global__ void k_check16(const float *Wa, const float *Za, float *C6, float *C3, float *C32, unsigned *zs, unsigned *zp) {
+    const int lane = threadIdx.x, q = lane >> 4, m = lane & 15, t = blockIdx.x;
+    const float *W = Wa + t * 256, *Z = Za + t * 256;
+    float w[4], z[4];
+    for (int s = 0; s < 4; ++s) { w[s] = W[m * 16 + 4 * q + s]; z[s] = Z[(4 * q + s) * 16 + m]; }
+    u32x2 w1, w2, w3, y1, y2, y3;
+    split3k16_valu(w, w1, w2, w3);         // the weights' pieces come from the host: truncation
+    split3k16_valu(z, y1, y2, y3);
+    // the activation's split as the kernels do it: one remainder MFMA per level, the pieces in the order z3 z1 z2
+    const int qa = lane >> 4, ma = lane & 15;
+    u32x2 I;
+    for (int d = 0; d < 2; ++d) I[d] = (qa == (ma >> 2) && d == ((ma & 3) >> 1)) ? (0xbf80u << (16 * (ma & 1))) : 0u;
+    f32x4 x = {z[0], z[1], z[2], z[3]};
+    const u32x2 z1 = pack_hi2(x);
+    x = mm16(I, z1, x);
+    const u32x2 z2 = pack_hi2(x);
+    x = mm16(I, z2, x);
+    const u32x2 z3 = pack_hi2(x);
+    const u32x4 za = {z3[0], z3[1], z1[0], z1[1]};                        // W16K16::a
+    const u32x4 zb = {za[2], za[3], z2[0], z2[1]};                        // put together where it is used
+    const u32x4 w12 = {w1[0], w1[1], w2[0], w2[1]}, w31 = {w3[0], w3[1], w1[0], w1[1]};      // the pack's two halves
+    f32x4 a6 = {0.f, 0.f, 0.f, 0.f};
+    a6 = mm16(w1, z3, a6); a6 = mm16(w2, z2, a6); a6 = mm16(w3, z1, a6);
+    a6 = mm16(w1, z2, a6); a6 = mm16(w2, z1, a6); a6 = mm16(w1, z1, a6);
+    f32x4 a3 = {0.f, 0.f, 0.f, 0.f};
+    a3 = mm(w12, za, a3);
+    a3 = mm(w31, zb, a3);
+    a3 = mm(w12, zb, a3);
+    f32x4 a32 = {0.f, 0.f, 0.f, 0.f};
+    for (int k4 = 0; k4 < 4; ++k4)
+        a32 = __builtin_amdgcn_mfma_f32_16x16x4f32(W[m * 16 + 4 * k4 + q], Z[(4 * k4 + q) * 16 + m], a32, 0, 0, 0);
+    for (int r = 0; r < 4; ++r) {
+        C6[t * 256 + (4 * q + r) * 16 + m] = a6[r];
+        C3[t * 256 + (4 * q + r) * 16 + m] = a3[r];
+        C32[t * 256 + (4 * q + r) * 16 + m] = a32[r];
+    }
+    const unsigned yy[6] = {y3[0], y3[1], y1[0], y1[1], y2[0], y2[1]};
+    const unsigned zz[6] = {za[0], za[1], za[2], za[3], z2[0], z2[1]};
+    for (int j = 0; j < 6; ++j) { zs[(t * 64 + lane) * 6 + j] = zz[j]; zp[(t * 64 + lane) * 6 + j] = yy[j]; }
+}
+static bool three_pieces(float v) {        // all three truncated bf16 pieces of v are non-zero
+    for (int k = 0; k < 3; ++k) {
+        unsigned b; memcpy(&b, &v, 4); b &= 0xffff0000u;
+        float top; memcpy(&top, &b, 4);
+        if (top == 0.f) return false;
+        v -= top;
+    }
+    return true;
+}
+static void pieces3(float v, double (&p)[3]) {        // the truncated pieces of v
+    for (int k = 0; k < 3; ++k) {
+        unsigned b; memcpy(&b, &v, 4); b &= 0xffff0000u;
+        float top; memcpy(&top, &b, 4);
+        p[k] = top;
+        v -= top;
+    }
+}
+static int check_k16_pairs() {
+    const int T = 64;
+    std::vector<float> W(T * 256), Z(T * 256), C6(T * 256), C3(T * 256), C32(T * 256);
+    srand(16);
+    for (auto &v : W) do v = (rand() / (float)RAND_MAX - 0.5f) * 2.f; while (!three_pieces(v));
+    for (auto &v : Z) do v = (rand() / (float)RAND_MAX - 0.25f) * 4.f; while (!three_pieces(v));
+    float *dW, *dZ, *d6, *d3, *d32; unsigned *ds, *dp;
+    const size_t nb = (size_t)T * 1024, np = (size_t)T * 64 * 6;
+    hipMalloc(&dW, nb); hipMalloc(&dZ, nb); hipMalloc(&d6, nb); hipMalloc(&d3, nb); hipMalloc(&d32, nb);
+    hipMalloc(&ds, np * 4); hipMalloc(&dp, np * 4);
+    hipMemcpy(dW, W.data(), nb, hipMemcpyHostToDevice); hipMemcpy(dZ, Z.data(), nb, hipMemcpyHostToDevice);
+    hipLaunchKernelGGL(k_check16, dim3(T), dim3(64), 0, 0, dW, dZ, d6, d3, d32, ds, dp);
+    std::vector<unsigned> zs(np), zp(np);
+    if (hipMemcpy(C6.data(), d6, nb, hipMemcpyDeviceToHost) != hipSuccess) { printf("K = 16 pairs: the kernel failed\n"); return 1; }
+    hipMemcpy(C3.data(), d3, nb, hipMemcpyDeviceToHost); hipMemcpy(C32.data(), d32, nb, hipMemcpyDeviceToHost);
+    hipMemcpy(zs.data(), ds, np * 4, hipMemcpyDeviceToHost); hipMemcpy(zp.data(), dp, np * 4, hipMemcpyDeviceToHost);
+    double e6 = 0, e3 = 0, e32 = 0, scale = 0, s6 = 0, s3 = 0;
+    long bits = 0, words = 0;
+    for (int t = 0; t < T; ++t)
+        for (int i = 0; i < 16; ++i)
+            for (int j = 0; j < 16; ++j) {
+                double ref = 0, six = 0;       // six: the six partial products w_a z_b, a + b <= 4, summed in float64 (each is exact there)
+                for (int k = 0; k < 16; ++k) {
+                    ref += (double)W[t * 256 + i * 16 + k] * (double)Z[t * 256 + k * 16 + j];
+                    double wp[3], zq[3];
+                    pieces3(W[t * 256 + i * 16 + k], wp); pieces3(Z[t * 256 + k * 16 + j], zq);
+                    six += wp[0] * zq[2] + wp[1] * zq[1] + wp[2] * zq[0] + wp[0] * zq[1] + wp[1] * zq[0] + wp[0] * zq[0];
+                }
+                const int o = t * 256 + i * 16 + j;
+                s6 = fmax(s6, fabs(C6[o] - six)); s3 = fmax(s3, fabs(C3[o] - six));
+                e6 = fmax(e6, fabs(C6[o] - ref)); e3 = fmax(e3, fabs(C3[o] - ref)); e32 = fmax(e32, fabs(C32[o] - ref)); scale = fmax(scale, fabs(ref));
+                bits += memcmp(&C6[o], &C3[o], 4) != 0;
+            }
+    for (size_t i = 0; i < np; ++i) words += zs[i] != zp[i];
+    printf("K = 16 pairs: max |C - float64|: paired (three K = 32 MFMAs) %.3e, six K = 16 MFMAs %.3e, f32 MFMA %.3e (largest |C| %.2f, %d outputs)\n", e3, e6, e32, scale, T * 256);
+    printf("K = 16 pairs: max |C - the six partial products summed in float64|: paired %.3e, six K = 16 MFMAs %.3e\n", s3, s6);
+    printf("K = 16 pairs: %ld of %d outputs differ in bits from the six-instruction form\n", bits, T * 256);
+    printf("K = 16 pairs: %ld of %zu piece words differ from the v_and / v_sub form's\n", words, np);
+    hipFree(dW); hipFree(dZ); hipFree(d6); hipFree(d3); hipFree(d32); hipFree(ds); hipFree(dp);
+    return 0;
+}
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "k16pairs")) return check_k16_pairs();      // only the K = 16 pairing (tests/test_gpu_k16_pairs.py)
     std::vector<float> W(16 * 32), Z(32 * 16), C6(256), C32(256);
     srand(1);
     for (auto &v : W) v = (rand() / (float)RAND_MAX - 0.5f) * 2.f;
@@ -267,6 +392,7 @@ int main() {
             printf("%s pieces: %ld of %d values not reproduced exactly by x1 + x2 + x3 (worst relative %.3g)\n", sp == 3 ? "truncated / MFMA remainders, K = 16" : sp == 2 ? "truncated / MFMA remainders" : sp ? "nearest / dot2c" : "truncated", bad, nv, worst);
         }
     }
+    check_k16_pairs();
     const int blocks = 2048, tiles = 4000;
     float *src, *dst;
     hipMalloc(&src, 1536 * 4); hipMalloc(&dst, (size_t)blocks * 512 * 4);
