@@ -149,6 +149,21 @@ def test_vjp_equals_central_differences(name):
     assert np.abs(xr.vjp64(xyz, x, Q, g, w, N=N, h_dim=s.h_dim, cutoff=s.cutoff, eta=s.eta)[1] - gxyz).max() > 1e-3 * np.abs(gxyz).max()
 
 
+@pytest.mark.parametrize("name", list(ec.SETS))
+def test_the_coulomb_cases_are_usable(name):
+    """The Coulomb call's case of tests/test_gpu_edge_constants.py at sets A, B and C: admissible, fq a usable derivative case that the
+    constants move; the reference's keywords reach both of its halves (q by forward64, fq by vjp64 at the same constants)."""
+    from coulomb_ref import coulomb64
+    from test_gpu_coulomb import KE
+    from test_gpu_edge_constants import COULOMB_ALPHA, _coulomb_case
+    s, w, mol, N, q, phi, fq, kink = _coulomb_case(name)
+    kw = ec.ref_kwargs(s)
+    n = len(q)
+    assert np.array_equal(q, xr.forward64(*mol, w, N=N, **kw)[:n])
+    assert np.array_equal(phi, coulomb64(mol[0], q, KE, COULOMB_ALPHA)[0])
+    assert np.array_equal(fq, -xr.vjp64(*mol, phi, w, N=N, **kw)[1]) and np.abs(fq).max() > 0
+
+
 @pytest.mark.parametrize("geo", ["open", "cell"])
 @pytest.mark.parametrize("name", NON_DEFAULT)
 def test_the_factorised_gradient_is_the_literal_one(name, geo):

@@ -24,6 +24,7 @@ BOUND = 2e-6          # about ten float32 roundings per term (10 * 2^-24 = 6e-7)
 #                       two pieces of 129 are of 65 and 64 partners: a full tile and one partner more
 #   CL_MINPIECE = 128   pieces of the partner range, ceil(n / 128) at these sizes: 1 piece up to 128 | 2 from 129, 2 up to 256 | 3 from 257
 #   CL_MAXP, CL_WANT    limit the pieces from 4097 atoms on only; the 2220-atom protein runs 18 pieces of 124 (35 blocks)
+#                       (4100 and 8250 atoms, the packing of small molecules and single pairs over alpha and D: test_gpu_coulomb_domain.py)
 SIZES = [(1, 8), (2, 8), (17, 24), (63, 64), (64, 64), (65, 72), (129, 136),
          (127, 128), (128, 128), (192, 192), (193, 200), (256, 256), (257, 264)]
 CASES = [f"{n}-{N}" for n, N in SIZES] + ["batch", "far", "protein"]
@@ -81,6 +82,30 @@ def _run(factory, name, alpha):
 
 
 # ---------------------------------------------------------------------------------------------------- 1: the fixed-charge parts
+def _check_fixed_parts(what, alpha, xyz, Qb, q, phi, Eb, F, ffix, fq):
+    """One molecule's phi, ffix and E against coulomb64 on its device charges q: each within BOUND of the sum of its absolute terms;
+    a lone atom has zeros and q == Q.  Returns the three errors as shares of the absolute sums."""
+    n = len(q)
+    phi64, E64, ffix64, sphi, sff = coulomb64(xyz, q, KE, alpha)
+    sE = 0.5 * float(np.abs(q.astype(np.float64)) @ sphi)
+    ephi, eff, eE = np.abs(phi - phi64), np.abs(ffix - ffix64), abs(Eb - E64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rp = np.where(sphi > 0, ephi / sphi, 0.0).max()
+        rf = np.where(sff > 0, eff.max(1) / sff, 0.0).max()
+    re = eE / sE if sE else 0.0
+    print(f"{what}, alpha {alpha} (n = {n}): phi {rp:.2e}, ffix {rf:.2e}, E {re:.2e} of the absolute sums "
+          f"(|phi| {np.abs(phi64).max():.3e}, |ffix| {np.abs(ffix64).max():.3e}, E {E64:.6e})")
+    if n == 1:
+        assert not phi.any() and not ffix.any() and Eb == 0.0 and not F.any() and not fq.any()
+        assert q[0] == Qb
+        return rp, rf, re
+    assert np.abs(phi64).max() > 0
+    assert (ephi <= BOUND * sphi).all()
+    assert (eff <= BOUND * sff[:, None]).all()
+    assert eE <= BOUND * sE
+    return rp, rf, re
+
+
 @pytest.mark.parametrize("alpha", ALPHAS)
 @pytest.mark.parametrize("name", CASES)
 def test_fixed_charge_parts_against_float64_on_the_device_charges(gpu_engine_factory, name, alpha):
@@ -89,22 +114,7 @@ def test_fixed_charge_parts_against_float64_on_the_device_charges(gpu_engine_fac
     assert E.dtype == np.float64 and E.shape == (len(offsets) - 1,)
     for b in range(len(offsets) - 1):
         a0, a1 = offsets[b], offsets[b + 1]
-        phi64, E64, ffix64, sphi, sff = coulomb64(xyz[a0:a1], q[a0:a1], KE, alpha)
-        sE = 0.5 * float(np.abs(q[a0:a1].astype(np.float64)) @ sphi)
-        ephi, eff, eE = np.abs(phi[a0:a1] - phi64), np.abs(ffix[a0:a1] - ffix64), abs(E[b] - E64)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            rp = np.where(sphi > 0, ephi / sphi, 0.0).max()
-            rf = np.where(sff > 0, eff.max(1) / sff, 0.0).max()
-        print(f"{name}, alpha {alpha}, molecule {b} (n = {a1 - a0}): phi {rp:.2e}, ffix {rf:.2e}, E {eE / sE if sE else 0.0:.2e} of the absolute sums "
-              f"(|phi| {np.abs(phi64).max():.3e}, |ffix| {np.abs(ffix64).max():.3e}, E {E64:.6e})")
-        if a1 - a0 == 1:
-            assert not phi[a0:a1].any() and not ffix[a0:a1].any() and E[b] == 0.0 and not F[a0:a1].any() and not fq[a0:a1].any()
-            assert q[a0] == Q[b]
-            continue
-        assert np.abs(phi64).max() > 0
-        assert (ephi <= BOUND * sphi).all()
-        assert (eff <= BOUND * sff[:, None]).all()
-        assert eE <= BOUND * sE
+        _check_fixed_parts(f"{name}, molecule {b}", alpha, xyz[a0:a1], Q[b], q[a0:a1], phi[a0:a1], E[b], F[a0:a1], ffix[a0:a1], fq[a0:a1])
 
 
 # ---------------------------------------------------------------------------------------------------- 2: composition bits
@@ -122,6 +132,21 @@ def test_composition_with_the_gradient_call_bit_for_bit(gpu_engine_factory, name
     assert len(out) == 4
     for got, want in zip(out, (q, phi, E, F)):
         assert np.array_equal(got, want)
+
+
+def _check_call(eng, mol, N, alpha, what):
+    """One molecule through the call on an engine of any shape or edge constants, "grad_path" 2 set: the fixed-charge parts against
+    coulomb64 on the device charges (test 1) and the composition bits (test 2).  Returns (q, phi, E, F, ffix, fq)."""
+    batch = _batch([mol])
+    out = eng.coulomb_xyz(*batch, N, ke=KE, alpha=alpha, parts=True)
+    q, phi, E, F, ffix, fq = out
+    _check_fixed_parts(what, alpha, mol[0], batch[3][0], q, phi, E[0], F, ffix, fq)
+    q2, gxyz = eng.charges_vjp_xyz(*batch, phi, N)
+    assert np.array_equal(q2, q) and np.array_equal(fq, -gxyz)
+    assert np.array_equal(F, ffix + fq) and F.dtype == np.float32
+    for got, want in zip(eng.coulomb_xyz(*batch, N, ke=KE, alpha=alpha), (q, phi, E, F)):
+        assert np.array_equal(got, want)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------- 3: the charges' part

@@ -1,9 +1,13 @@
 """cutoff, eta and near_tol away from the reference's 3.0 / 2.0 / 1e-5 on every kernel family, against the float64 references run at
-the same constants (tests/edge_constants.py: the sets A, B, C and what makes an input a usable case).  GPU only.
+the same constants (tests/edge_constants.py: the sets A, B, C and what makes an input a usable case): the forward on its routes, open
+and periodic, the dense entries, both gradient paths with strain, the Coulomb call (coulomb_xyz), the forward mode and the training
+steps.  GPU only.
 
 No tolerance of its own: the forward within TOL = 1e-5 (tests/test_gpu_parity.py); derivatives within 2e-4 max |ref| + the ReLU-kink
 bracket at TAU = 2e-5 (tests/test_gpu_grad_large.py, per atom for the forward mode as in tests/test_gpu_jvp.py); training gradients by
-the per-tensor rule of tests/test_gpu_train_cell.py; the adjoint identity within test_gpu_jvp._adjoint's bound.
+the per-tensor rule of tests/test_gpu_train_cell.py; the adjoint identity within test_gpu_jvp._adjoint's bound; the Coulomb call's
+phi, ffix and E within BOUND = 2e-6 of their absolute sums on the device charges (tests/test_gpu_coulomb.py), its fq = -vjp(g = phi) by
+the derivatives' rule per component.
 
 Every case first passes, on the references alone: no listed pair within 1e-5 (relative, in max_k e_k / near_tol) of a flip of the near
 flag; for set C at least 5 listed pairs in each of the four flag intervals; the reference at the set differs from the reference at the
@@ -27,11 +31,18 @@ largest bracket; in the forward mode, whose bound is per atom, over the atoms in
           gstrain   A 100 %, 1.3e-4, 2258;  B 100 %, 1.6e-4, 799;   C 100 %, 1.5e-5, 4148
     (set A on the lattice (40, 40) and in the box with seed 40 has brackets of 2.9e-2 and 7.2e-2 of the scale and a sensitivity of
     only 34 and 18 bounds: not usable, replaced by the cases above)
+  coulomb, alpha = 0.3, on the open molecules of the gradients (margin; pairs per flag interval; q against the default constants; fq:
+    share inside the bracket, largest bracket / scale, sensitivity in bounds of the components inside):
+    A (48, 48)  9.4e-1; 423 / 2;            q 2.19;    fq 95 %, 5.1e-4, 3044
+    B (33, 40)  1.1e-2; 349 / 31;           q 0.137;   fq 94 %, 2.3e-3, 1197
+    C (33, 40)  1.0e-4; 186/17/41/136;      q 1.19;    fq 98 %, 7.7e-4, 830
   training (one open 13-atom molecule and 24 atoms in a 7.0 x 7.2 x 7.5 cell, N = 24): margins 4.8e-2 / 3.9e-3 / 4.9e-3; set C
     63 / 16 / 23 / 80 pairs per interval; the gradient differs from the default constants' by 744 .. 4770 tolerances
 
 Measured on an MI355X: set C edge basis residual 8.2e-11; forward worst |dq| 5.3e-7 over all sets and routes; gxyz, gstrain and tq
-errors below 1e-6 of their scale; training gradients below 1e-6 per tensor.
+errors below 1e-6 of their scale; training gradients below 1e-6 per tensor; the Coulomb call's phi / ffix / E 3.3e-8 / 6.1e-8 /
+1.2e-9 (A), 5.1e-8 / 8.7e-8 / 9.7e-9 (B) and 3.7e-8 / 8.5e-8 / 6.2e-9 (C) of their absolute sums, q within 1.7e-6, fq within 3.3e-7,
+5.3e-7 and 7.6e-7 of its scale.
 """
 import functools
 
@@ -368,6 +379,51 @@ def test_gradient_strain(gpu_engine_factory, name):
         print(f"set {name}, grad_path {path}: gstrain {err:.3e} of {scale:.3e}, kink {kink:.3e}")
         assert err <= 2e-4 * scale + kink
     assert np.abs(gs[2] - gs[1]).max() <= 4e-4 * scale + kink
+
+
+# ---------------------------------------------------------------------------------------------------- the Coulomb call
+COULOMB_ALPHA = 0.3
+
+
+@functools.lru_cache(maxsize=None)
+def _coulomb_case(name):
+    """(s, w, molecule, N, q, phi, fq, kink per component) of the Coulomb call on the open molecule of the gradient tests, the
+    reference (coulomb_forces64) at the set's constants and h_dim; admitted on the reference alone: margin and flag intervals, the kink
+    rule per component for fq = -vjp64(g = phi), and its sensitivity to the constants over the components inside the bracket (the
+    comparison's bound is per component)."""
+    from coulomb_ref import coulomb_forces64
+    from test_gpu_coulomb import KE
+    s = ec.SETS[name]
+    w = _deriv_weights(s)
+    n, N, seed = GRAD_OPEN[name]
+    mol = _lattice_molecule(n, NX, seed=seed)
+    what = f"set {name}, coulomb ({n}, {N})"
+    ec.assert_admissible([mol], s, least=5 if name == "C" else 0, what=what)
+    kw = ec.ref_kwargs(s)
+    q, phi, E, f, ffix, fq = coulomb_forces64(*mol, w, N, KE, COULOMB_ALPHA, **kw)
+    lo = coulomb_forces64(*mol, w, N, KE, COULOMB_ALPHA, kink_shift=+TAU, **kw)[5]
+    hi = coulomb_forces64(*mol, w, N, KE, COULOMB_ALPHA, kink_shift=-TAU, **kw)[5]
+    dflt = coulomb_forces64(*mol, w, N, KE, COULOMB_ALPHA, h_dim=s.h_dim)
+    kink = np.abs(lo - hi)
+    ec.assert_sensitive(q, dflt[0], 2e-4, f"{what}, q")
+    _, inside = ec.assert_derivative_case(fq, kink, dflt[5], f"{what}, fq")
+    assert inside > 100, (what, inside)
+    return s, w, mol, N, q, phi, fq, kink
+
+
+@pytest.mark.parametrize("name", list(ec.SETS))
+def test_coulomb(gpu_engine_factory, name):
+    """coulomb_xyz at alpha = 0.3 at the set's constants: phi, ffix and E against coulomb64 on the device charges at test_gpu_coulomb's
+    BOUND, the bits of charges_vjp_xyz(g=phi) on the pair-list path, q within 2e-4 of the reference and fq per component."""
+    from test_gpu_coulomb import _check_call
+    s, w, mol, N, q_ref, phi_ref, fq_ref, kink = _coulomb_case(name)
+    eng = _engine(gpu_engine_factory, s, w, grad_path=2)
+    q, phi, E, F, ffix, fq = _check_call(eng, mol, N, COULOMB_ALPHA, f"set {name} coulomb")
+    scale, err = np.abs(fq_ref).max(), np.abs(fq - fq_ref)
+    print(f"set {name}: q {np.abs(q - q_ref).max():.3e}, phi {np.abs(phi - phi_ref).max():.3e} of {np.abs(phi_ref).max():.3e}; fq max error "
+          f"{err.max():.3e} of {scale:.3e}, worst excess over the component's bound {(err - 2e-4 * scale - kink).max():.3e}")
+    assert np.abs(q - q_ref).max() <= 2e-4
+    assert scale > 0 and (err <= 2e-4 * scale + kink).all(), (np.argmax(err - kink), err.max(), scale)
 
 
 # ---------------------------------------------------------------------------------------------------- forward mode

@@ -1,68 +1,82 @@
 """Every entry at nx = 1..10 and T = 1..8 (the ten (nx, T) pairs of tests/model_shapes.py) against the float64 references run at the same
 shape: the forward on its five routes and on the tiled kernels' row tiles, the dense entries, both gradient paths with strain, the
-forward mode (single and K = 5), the three training routes, and the scratch the pair-list entries report at T = 1 and T = 8.  GPU only.
+forward mode (single and K = 5), the Coulomb call (coulomb_xyz), the three training routes, and the scratch the pair-list entries
+report at T = 1 and T = 8.  GPU only.
 
 No tolerance of its own: the forward within TOL = 1e-5 (tests/test_gpu_parity.py); the layer calls within max(TOL, 3 x float32-oracle
 noise) (tests/test_gpu_api.py); derivatives within 2e-4 max |ref| + the ReLU-kink bracket at TAU = 2e-5, here per component
 (|got - ref|_i <= 2e-4 max |ref| + kink_i) beside the whole-array bound of test_gpu_grad_large._check; the adjoint identity within
 test_gpu_jvp._adjoint's bound; training gradients by the per-tensor rule of tests/test_gpu_train_cell.py, which the x rows of each
-first-layer gradient also meet on their own; scratch within 1 % of the formulas of include/epnn.h.
+first-layer gradient also meet on their own; scratch within 1 % of the formulas of include/epnn.h; the Coulomb call's phi, ffix and E
+within BOUND = 2e-6 of their absolute sums on the device charges (tests/test_gpu_coulomb.py), its fq by the derivatives' rule.
 
 Every case first passes the conditions of tests/model_shapes.py on the references alone.  The chosen seeds and what they measure:
 forward (weight seed, scale): float32 noise and the smallest of the three sensitivities (last step, column 0, column nx - 1) in q
 for the batches at N = 32 / N = 64 / the 150-atom molecule; derivatives (weight seed, scale, molecule seed): share of the components
 (atoms for tq) inside the bracket, largest bracket / scale, smallest sensitivity in bounds of the components inside (> 100 asked);
-training (weights seed 13, scale 0.4): the smallest x row of a first-layer gradient over its tensor's largest entry.
+training (weights seed 13, scale 0.4): the smallest x row of a first-layer gradient over its tensor's largest entry; coulomb: fq of
+the Coulomb call at alpha = 0.3, the same three figures.
 
   nx = 1, T = 8
     forward (17, 0.25): noise 4.4e-07 / 4.9e-07 / 1.2e-06; sensitivity 3.3e-01 / 4.9e-01 / 9.3e-01
     gxyz, open (17, 24) (8, 0.6, 43): 92 %, 3.5e-04, 2424;  tq (17, 24) (5, 0.6, 40): 100 %, 1.3e-04, 1594
     gxyz, open (33, 40) (6, 0.6, 44): 85 %, 6.3e-03, 1019;  tq (33, 40) (9, 0.6, 43): 85 %, 8.9e-04, 1356
     box (20, 24) (7, 0.6, 41): gxyz 100 %, 2.1e-08, 2527; gstrain 100 %, 7.6e-09, 2338;  training x rows 5.0e-01
+    coulomb fq, open (17, 24) (8, 0.6, 43): 92 %, 3.7e-04, 2503
   nx = 2, T = 1
     forward (18, 0.35): noise 7.4e-07 / 6.7e-07 / 8.6e-07; sensitivity 3.9e-02 / 7.9e-02 / 1.2e-01
     gxyz, open (17, 24) (5, 0.6, 44): 100 %, 0.0e+00, 2284;  tq (17, 24) (5, 0.6, 45): 100 %, 0.0e+00, 1090
     cell (20, 24) (5, 0.6, 42): gxyz 100 %, 0.0e+00, 1567; gstrain 100 %, 0.0e+00, 1387;  training x rows 4.8e-02
+    coulomb fq, open (17, 24) (5, 0.6, 44): 100 %, 0.0e+00, 750
   nx = 3, T = 6
     forward (17, 0.35): noise 2.4e-07 / 3.3e-07 / 1.0e-06; sensitivity 3.7e-02 / 4.4e-02 / 2.4e-02
     gxyz, open (17, 24) (9, 0.35, 42): 90 %, 3.2e-03, 1236;  tq (17, 24) (9, 0.35, 42): 88 %, 3.4e-03, 794
     box (20, 24) (8, 0.6, 43): gxyz 100 %, 1.1e-04, 1767; gstrain 100 %, 1.3e-04, 1412;  training x rows 2.6e-02
+    coulomb fq, open (17, 24) (9, 0.35, 42): 84 %, 3.8e-03, 1110
   nx = 4, T = 7
     forward (17, 0.35): noise 4.4e-07 / 7.5e-07 / 8.2e-07; sensitivity 1.1e-01 / 2.1e-01 / 3.4e-01
     gxyz, open (17, 24) (5, 0.6, 40): 71 %, 5.0e-03, 560;  tq (17, 24) (8, 0.35, 45): 76 %, 1.7e-02, 1156
     cell (20, 24) (6, 0.6, 43): gxyz 100 %, 1.3e-06, 1123; gstrain 100 %, 5.0e-06, 3838;  training x rows 2.4e-02
+    coulomb fq, open (17, 24) (5, 0.6, 41): 75 %, 7.8e-03, 1634
   nx = 5, T = 4
     forward (17, 0.35): noise 3.4e-07 / 6.1e-07 / 8.0e-07; sensitivity 1.5e-01 / 2.7e-01 / 3.8e-01
     gxyz, open (17, 24) (7, 0.6, 40): 100 %, 1.6e-04, 552;  tq (17, 24) (7, 0.6, 40): 100 %, 1.1e-05, 437
     gxyz, open (33, 40) (7, 0.6, 40): 90 %, 2.8e-02, 609;  tq (33, 40) (9, 0.6, 42): 82 %, 5.9e-03, 1018
     box (20, 24) (5, 0.6, 40): gxyz 100 %, 9.3e-06, 1288; gstrain 100 %, 5.9e-06, 2017;  training x rows 1.1e-02
+    coulomb fq, open (17, 24) (7, 0.6, 40): 100 %, 8.5e-05, 397
   nx = 6, T = 8
     forward (17, 0.35): noise 6.0e-07 / 1.7e-06 / 1.4e-06; sensitivity 9.3e-02 / 2.1e-01 / 2.4e-01
     gxyz, open (17, 24) (6, 0.6, 43): 92 %, 7.0e-03, 1065;  tq (17, 24) (6, 0.6, 43): 88 %, 3.1e-03, 1051
     cell (20, 24) (5, 0.6, 42): gxyz 100 %, 1.6e-07, 1020; gstrain 100 %, 1.2e-07, 723;  training x rows 9.3e-03
+    coulomb fq, open (17, 24) (6, 0.6, 43): 84 %, 2.4e-02, 329
   nx = 7, T = 1
     forward (17, 0.35): noise 2.8e-07 / 2.9e-07 / 6.0e-07; sensitivity 9.3e-02 / 1.8e-01 / 2.4e-01
     gxyz, open (17, 24) (5, 0.6, 42): 100 %, 0.0e+00, 1014;  tq (17, 24) (5, 0.6, 42): 100 %, 0.0e+00, 1641
     box (20, 24) (5, 0.6, 40): gxyz 100 %, 0.0e+00, 299; gstrain 100 %, 0.0e+00, 482;  training x rows 5.9e-03
+    coulomb fq, open (17, 24) (5, 0.6, 42): 100 %, 0.0e+00, 957
   nx = 8, T = 6
     forward (17, 0.35): noise 6.0e-07 / 9.6e-07 / 1.6e-06; sensitivity 1.4e-01 / 2.0e-01 / 3.3e-01
     gxyz, open (17, 24) (7, 0.6, 42): 92 %, 1.7e-03, 715;  tq (17, 24) (8, 0.6, 45): 100 %, 2.9e-05, 779
     gxyz, open (33, 40) (6, 0.6, 44): 83 %, 7.3e-04, 299;  tq (33, 40) (6, 0.6, 44): 76 %, 2.4e-03, 624
     cell (20, 24) (5, 0.6, 41): gxyz 100 %, 9.4e-05, 1175; gstrain 100 %, 8.1e-05, 1498;  training x rows 4.4e-03
+    coulomb fq, open (17, 24) (7, 0.6, 42): 88 %, 5.4e-03, 1127
   nx = 9, T = 7
     forward (17, 0.35): noise 7.6e-07 / 1.1e-06 / 1.5e-06; sensitivity 8.1e-02 / 1.2e-01 / 2.0e-01
     gxyz, open (17, 24) (5, 0.6, 43): 100 %, 1.3e-04, 472;  tq (17, 24) (5, 0.6, 43): 88 %, 9.9e-04, 831
     box (20, 24) (7, 0.6, 42): gxyz 100 %, 8.0e-06, 1194; gstrain 100 %, 1.2e-05, 801;  training x rows 2.7e-03
+    coulomb fq, open (17, 24) (5, 0.6, 43): 88 %, 1.1e-03, 971
   nx = 10, T = 8
     forward (18, 0.3): noise 4.8e-07 / 1.5e-06 / 1.7e-06; sensitivity 2.0e-02 / 2.8e-02 / 4.5e-02
     gxyz, open (17, 24) (6, 0.6, 43): 96 %, 3.1e-04, 121;  tq (17, 24) (6, 0.6, 43): 94 %, 1.1e-03, 117
     cell (20, 24) (5, 0.6, 41): gxyz 100 %, 7.5e-08, 121; gstrain 100 %, 4.8e-08, 105;  training x rows 1.5e-03
+    coulomb fq, open (17, 24) (6, 0.6, 43): 96 %, 2.1e-03, 121
 
 Measured on an MI355X (worst over the ten shapes): forward |dq| 1.6e-6 on the five routes and 2.0e-6 on the tiled kernels at 150 atoms; make_model 6.7e-7, GNN_layer 3.7e-8 and
 EPN_layer 7.0e-7 (float32-oracle noise 2.3e-8 and 5.7e-7); gxyz 8.0e-7, gstrain 8.6e-7 and tq 3.8e-7 of their scale, every component
 inside its own bound by at least 9e-6 of absolute slack; training gradients 1.7e-5 per tensor and 1.3e-5 on the x rows alone (the
-float32 oracle's own noise); scratch within 0.02 % (forward mode) and 0.23 % (gradient call) of the formulas.  No shape failed: no
-kernel or host driver needed a change.
+float32 oracle's own noise); scratch within 0.02 % (forward mode) and 0.23 % (gradient call) of the formulas; the Coulomb call's
+phi 1.1e-7, ffix 1.9e-7 and E 3.3e-8 of their absolute sums, its q within 3.8e-6 and its fq within 1.3e-6 of its scale, every
+component inside its own bound by at least 1.3e-5 of absolute slack.  No shape failed: no kernel or host driver needed a change.
 """
 
 import numpy as np
@@ -73,6 +87,7 @@ import model_shapes as ms
 from conftest import random_weights
 from oracle import epnn_oracle as orc
 from oracle import epnn_oracle_train as ot
+from test_gpu_coulomb import _check_call
 from test_gpu_edge_constants import IN_KERNEL, ROUTES
 from test_gpu_grad_large import _batch, _check
 from test_gpu_jvp import _adjoint, _formula
@@ -244,6 +259,20 @@ def test_gradients_and_strain_in_a_cell(gpu_engine_factory, shape):
                 assert np.abs(qb - q_ref[:len(q)]).max() <= 2e-4
                 _components(gb, gxyz, kink_x, what + " gxyz with box=")
         assert np.abs(gs[2] - gs[1]).max() <= 4e-4 * scale + kink_s.max()
+
+
+# ---------------------------------------------------------------------------------------------------- the Coulomb call
+@shapes
+def test_coulomb(gpu_engine_factory, shape):
+    """coulomb_xyz at alpha = 0.3 on the 17-atom open molecule at N = 24: phi, ffix and E against coulomb64 on the device charges at
+    test_gpu_coulomb's BOUND, the bits of charges_vjp_xyz(g=phi) on the pair-list path, q within 2e-4 of the reference and fq =
+    -vjp64(g = phi_ref) by the per-component rule."""
+    w, mol, N, q_ref, phi_ref, fq_ref, kink, _, fig = ms.coulomb_case(shape)
+    eng = _engine(gpu_engine_factory, shape, w, grad_path=2)
+    q, phi, E, F, ffix, fq = _check_call(eng, mol, N, ms.COULOMB_ALPHA, f"{shape} coulomb")
+    print(f"{shape} coulomb: q {np.abs(q - q_ref).max():.3e}, phi {np.abs(phi - phi_ref).max():.3e} of {np.abs(phi_ref).max():.3e}")
+    assert np.abs(q - q_ref).max() <= 2e-4
+    _components(fq, fq_ref, kink, f"{shape} coulomb fq")
 
 
 # ---------------------------------------------------------------------------------------------------- forward mode

@@ -62,6 +62,18 @@ def test_open_gradient_cases_are_usable_and_the_references_agree(shape, size):
 
 
 @shapes
+def test_coulomb_cases_are_usable(shape):
+    """The Coulomb call's case meets the derivative conditions for fq = -vjp64(g = phi); its parts add up and fq is that gradient."""
+    from coulomb_ref import coulomb_forces64
+    w, mol, N, q, phi, fq, kink, _, fig = ms.coulomb_case(shape)
+    n = len(q)
+    assert np.abs(q).max() > 0.01 and np.abs(phi).max() > 0
+    assert np.array_equal(fq, -vjp64(mol[0], mol[1], mol[2], phi, w, N=N)[1])
+    full = coulomb_forces64(mol[0], mol[1], mol[2], w, N, ms.KE, ms.COULOMB_ALPHA)
+    assert np.array_equal(full[3], full[4] + full[5]) and np.array_equal(full[5], fq) and full[0].shape == (n,)
+
+
+@shapes
 def test_cell_gradient_cases_are_usable_and_the_references_agree(shape):
     """The box / cell case against strain64 meets the conditions; vjp64_large gives the same q, gxyz and gstrain."""
     w, mol, N, cell, g, q, gx, gs, kink_x, kink_s, _, figs = ms.periodic_case(shape)
