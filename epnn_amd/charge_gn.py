@@ -394,6 +394,15 @@ class EPNNModel(_Stack):
         the model's natom."""
         return self._eng().coulomb_xyz(offsets, xyz, x, Q, self.natom if N is None else N, ke=ke, alpha=alpha, parts=parts)
 
+    def coulomb_xyz_cell(self, offsets, xyz, x, Q, N=None, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                         parts=False, strain=False):
+        """coulomb_xyz in fully periodic cells, by an Ewald sum: (q (A,), phi (A,), E (B,) float64 per cell, F (A, 3)), with
+        strain=True also gstrain (B, 3, 3), the total dE/d eps; parts=True appends ffix and fq (and gstrain_fix, gstrain_q).  cell
+        (3, 3) or (B, 3, 3), or box for its diagonal cell; tol sets the Ewald parameters (Engine.ewald_params), ewald= gives them.
+        phi includes the split's self term and a charged cell's neutralising background.  N defaults to the model's natom."""
+        return self._eng().coulomb_xyz_cell(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke, alpha=alpha,
+                                            tol=tol, ewald=ewald, parts=parts, strain=strain)
+
     def charges_jvp_xyz_multi(self, offsets, xyz, x, Q, N=None, v=None, strain=None, dQ=None, box=None, cell=None):
         """charges_jvp_xyz along K directions in one pass: (q (A,), tq (K, A)), row k with the bits of the single call on the k-th
         slices.  v (K, A, 3), strain (K, 3, 3) or (K, B, 3, 3), dQ (K,) or (K, B); at least one, agreeing on K (1..16).  The

@@ -495,3 +495,4 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
 #include "epnn_api_train_large.hip.h"
 #include "epnn_api_jvp.hip.h"
 #include "epnn_api_coulomb.hip.h"
+#include "epnn_api_coulomb_cell.hip.h"

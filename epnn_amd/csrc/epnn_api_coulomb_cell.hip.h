@@ -1,0 +1,236 @@
+// epnn_coulomb_xyz_cell: epnn_coulomb_xyz in fully periodic cells, by an Ewald sum (kernels: epnn_ewald.hip.h), and epnn_ewald_params,
+// the host-only rule that chooses the sum's parameters.  The pair-list gradient call in GEO_CELL geometry with its strain rows and
+// its seed made on the device: set-up and checkpointed forward, the Ewald kernels on that forward's charges (phi = dE/dq into the
+// seed), the shared backward, one download.  A driver of its own: epnn_coulomb_xyz keeps its path, bits and scratch.
+// Part of the one translation unit epnn_api.hip.
+#pragma once
+#include "epnn_api_coulomb.hip.h"
+#include "epnn_ewald.hip.h"
+
+// (the library is built with -ffinite-math-only: a test of a value's own bits would fold away; they are read back from a volatile word)
+static bool ew_finite(double v) {
+    volatile uint64_t seen;
+    uint64_t bits;
+    memcpy(&bits, &v, 8);
+    seen = bits;
+    bits = seen;
+    return (bits & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+
+// What the rule and the entry's checks need of one cell [3][3], in float64: |a_k|, the perpendicular widths |det| / |a_k+1 x a_k+2|,
+// the smallest of them and the volume.  Refused in the style of check_cell: an entry that is not finite, an open axis, dependent rows.
+struct EwGeom { double len[3], w[3], wmin, vol; };
+static int ew_cell_geom(const char *what, int b, const float *cell, EwGeom &o) {
+    double a[3][3];
+    for (int k = 0; k < 3; ++k) {
+        for (int x = 0; x < 3; ++x) {
+            if (!ew_finite((double)cell[3 * k + x])) EPNN_FAIL("%s: cell[%d][%d][%d] is not finite (molecule %d, axis %d)", what, b, k, x, b, k);
+            a[k][x] = (double)cell[3 * k + x];
+        }
+        o.len[k] = sqrt(a[k][0] * a[k][0] + a[k][1] * a[k][1] + a[k][2] * a[k][2]);
+        if (!(o.len[k] > 0.0))
+            EPNN_FAIL("%s: cell[%d] (molecule %d): axis %d is open (a row of zeros); the Ewald sum is built for fully periodic cells (two- "
+                      "and one-dimensional sums are different mathematics)", what, b, b, k);
+    }
+    double cr[3][3];                                             // cr[k] = a_(k+1) x a_(k+2)
+    for (int k = 0; k < 3; ++k) {
+        const double *u = a[(k + 1) % 3], *v = a[(k + 2) % 3];
+        cr[k][0] = u[1] * v[2] - u[2] * v[1]; cr[k][1] = u[2] * v[0] - u[0] * v[2]; cr[k][2] = u[0] * v[1] - u[1] * v[0];
+    }
+    const double det = a[0][0] * cr[0][0] + a[0][1] * cr[0][1] + a[0][2] * cr[0][2];
+    if (!(fabs(det) > 1e-12 * o.len[0] * o.len[1] * o.len[2]))
+        EPNN_FAIL("%s: the rows of cell[%d] (molecule %d) are linearly dependent (axis 2 lies in the plane of axes 0 and 1)", what, b, b);
+    o.vol = fabs(det);
+    for (int k = 0; k < 3; ++k) {
+        o.w[k] = o.vol / sqrt(cr[k][0] * cr[k][0] + cr[k][1] * cr[k][1] + cr[k][2] * cr[k][2]);
+        o.wmin = k == 0 ? o.w[0] : std::min(o.wmin, o.w[k]);
+    }
+    return 0;
+}
+
+// The k box of M: its slots, refused above EW_SLOT_CAP (a cell of extreme aspect ratio is refused by name, not served slowly)
+static int ew_box_slots(const char *what, int b, const double *M, int &ns) {
+    const double slots = (2.0 * M[0] + 1.0) * (2.0 * M[1] + 1.0) * (M[2] + 1.0);
+    if (slots > (double)EW_SLOT_CAP)
+        EPNN_FAIL("%s: cell[%d] (molecule %d): the k box M = (%g, %g, %g) has %g slots, above the cap of %d (the cell's aspect ratio is "
+                  "too extreme for this sum, or tol too small)", what, b, b, M[0], M[1], M[2], slots, EW_SLOT_CAP);
+    ns = (int)slots;
+    return 0;
+}
+
+// The rule (include/epnn.h): s = sqrt(-ln tol), rc = w_min / 2, beta = s / rc, capped at alpha where alpha > 0 (there the real-space
+// term vanishes identically: rc is reported as 0), kc = 2 beta s, M_k = ceil(kc |a_k| / 2 pi).  out [6] = beta, rc, kc, M0, M1, M2.
+static int ew_rule(const char *what, int b, const float *cell, double alpha, double tol, double *out) {
+    EwGeom G;
+    if (ew_cell_geom(what, b, cell, G)) return 1;
+    const double s = sqrt(-log(tol));
+    double rc = 0.5 * G.wmin, beta = s / rc;
+    if (alpha > 0.0 && alpha <= beta) { beta = alpha; rc = 0.0; }
+    const double kc = 2.0 * beta * s;
+    out[0] = beta; out[1] = rc; out[2] = kc;
+    for (int k = 0; k < 3; ++k) out[3 + k] = ceil(kc * G.len[k] / 6.283185307179586);
+    int ns;
+    return ew_box_slots(what, b, out + 3, ns);
+}
+
+extern "C" int epnn_ewald_params(const float *cell, double alpha, double tol, double *out) {
+    const char *name = "epnn_ewald_params";
+    if (!cell || !out) EPNN_FAIL("%s: null argument", name);
+    if (!ew_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
+    if (!ew_finite(tol) || !(tol > 0.0 && tol < 1.0)) EPNN_FAIL("%s: tol must be finite and inside (0, 1)", name);
+    return ew_rule(name, 0, cell, alpha, tol, out);
+}
+
+// One checked row of the entry's `ewald` argument -> what the kernels take.  The entry runs at exactly these values.
+static int ew_cell_row(const char *what, int b, const float *cell, const double *row, double alpha, EwCell &e) {
+    EwGeom G;
+    if (ew_cell_geom(what, b, cell, G)) return 1;
+    for (int k = 0; k < 6; ++k)
+        if (!ew_finite(row[k])) EPNN_FAIL("%s: ewald[%d][%d] is not finite", what, b, k);
+    const double beta = row[0], rc = row[1], kc = row[2], *M = row + 3;
+    if (!(beta > 0.0)) EPNN_FAIL("%s: ewald[%d]: beta = %g must be positive", what, b, beta);
+    if (!(kc >= 0.0)) EPNN_FAIL("%s: ewald[%d]: kc = %g must not be negative", what, b, kc);
+    if (!(rc >= 0.0 && rc <= 0.5 * G.wmin))
+        EPNN_FAIL("%s: ewald[%d]: rc = %g must lie in [0, w_min / 2]: half the smallest perpendicular width of cell %d is %g, and beyond "
+                  "it a pair has more than one image in range", what, b, rc, b, 0.5 * G.wmin);
+    if (rc == 0.0 && !(alpha > 0.0 && beta == alpha))
+        EPNN_FAIL("%s: ewald[%d]: rc = 0 (no real-space part) takes beta == alpha > 0; beta = %g, alpha = %g", what, b, beta, alpha);
+    for (int k = 0; k < 3; ++k) {
+        const double need = ceil(kc * G.len[k] / 6.283185307179586 - 1e-9);
+        if (!(M[k] >= 0.0 && M[k] <= 1e6 && M[k] == floor(M[k]) && M[k] >= need))
+            EPNN_FAIL("%s: ewald[%d]: M%d = %g is not consistent with kc = %g: an integer of at least ceil(kc |a_%d| / 2 pi) = %g", what, b, k,
+                      M[k], kc, k, need);
+    }
+    if (ew_box_slots(what, b, M, e.ns)) return 1;
+    const double pi = 3.141592653589793;
+    e.kc2 = kc * kc;
+    e.c0 = 4.0 * pi / G.vol;
+    e.inv4b2 = 0.25 / (beta * beta);
+    e.self = 2.0 * beta / sqrt(pi);
+    e.bg = pi / G.vol * (1.0 / (beta * beta) - (alpha > 0.0 ? 1.0 / (alpha * alpha) : 0.0));
+    e.rc = (float)rc;
+    if ((double)e.rc > rc) e.rc = nextafterf(e.rc, 0.f);
+    e.beta = (float)beta;
+    e.M0 = (int)M[0]; e.M1 = (int)M[1]; e.M2 = (int)M[2];
+    e.soff = 0;
+    e.pad = 0;
+    return 0;
+}
+
+// The tasks of k_ew_atom, (first atom, atoms, cell, atoms of the cell), and of k_ew_sfac, (cell, first slot): 64 atoms or slots of
+// one cell each; the cells' first slots.  Returns the batch's slots.
+static size_t ew_build_tasks(int B, const int32_t *offsets, std::vector<EwCell> &ew, std::vector<int4> &atasks, std::vector<int2> &stasks) {
+    size_t slots = 0;
+    for (int b = 0; b < B; ++b) {
+        const int lo = offsets[b], hi = offsets[b + 1];
+        ew[b].soff = (int)std::min<size_t>(slots, 0x7fffffff);
+        slots += (size_t)ew[b].ns;
+        for (int a0 = lo; a0 < hi; a0 += EW_TILE) atasks.push_back(make_int4(a0, std::min(EW_TILE, hi - a0), b, hi - lo));
+        for (int s0 = 0; s0 < ew[b].ns; s0 += EW_TILE) stasks.push_back(make_int2(b, s0));
+    }
+    return slots;
+}
+
+static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                             const float *Q, const HostGeo &geo, std::vector<EwCell> &ew, double ke, double alpha, float *q_out, float *phi_out,
+                             double *e_out, float *f_out, float *gs_out, float *ffix_out, float *fq_out, float *gsfix_out, float *gsq_out) {
+    GradLarge *gl = grad_large_state(h);
+    if (grad_large_weights(h, gl)) return 1;
+    const int T = h->cfg.T, A = offsets[B];
+    std::vector<int4> ctasks, atasks;
+    std::vector<int2> stasks;
+    const size_t cpieces = (size_t)cl_build_tasks(B, offsets, ctasks), slots = ew_build_tasks(B, offsets, ew, atasks, stasks);
+    if (slots > ((size_t)1 << 27)) EPNN_FAIL("%s: the batch's k boxes have %zu slots, above 2^27: send fewer cells per call", name, slots);
+    bool sweep = false;
+    for (int b = 0; b < B; ++b) sweep = sweep || ew[b].rc > 0.f;
+    // one staged span: the three task tables and the cells' parameters, each at a multiple of 16 bytes
+    const size_t o_at = ctasks.size() * sizeof(int4), o_st = o_at + atasks.size() * sizeof(int4),
+                 o_ew = o_st + ((stasks.size() * sizeof(int2) + 15) & ~size_t(15)), blob_bytes = o_ew + (size_t)B * sizeof(EwCell);
+    std::vector<char> blob(blob_bytes, 0);
+    memcpy(blob.data(), ctasks.data(), ctasks.size() * sizeof(int4));
+    memcpy(blob.data() + o_at, atasks.data(), atasks.size() * sizeof(int4));
+    memcpy(blob.data() + o_st, stasks.data(), stasks.size() * sizeof(int2));
+    memcpy(blob.data() + o_ew, ew.data(), (size_t)B * sizeof(EwCell));
+    const GlSpan span{blob.data(), blob_bytes, false};
+    // [A] phi | [A][3] ffix | flag, then [B] E in float64 and [B][9] the fixed-charge strain: directly behind the backward's output
+    // block, one download for both; the sweep's partial rows, the atoms' shares, S and the slots' records
+    const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), o_gsf = o_E + (size_t)B * 8, co_bytes = o_gsf + (size_t)B * 36;
+    const size_t o_share = cpieces * (size_t)A * EW_PART * 8, o_S = (o_share + (size_t)A * EW_SHARE * 8 + 15) & ~size_t(15), o_rec = o_S + slots * 16;
+    const size_t more[2] = {co_bytes, o_rec + slots * 16};
+    GlGrad r;
+    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, &span, 1, more, 2, false, r)) return 1;
+    const GlCall &c = r.c;
+    char *co = c.dw + r.o_more[0], *sc = c.dw + r.o_more[1];
+    float *phi = reinterpret_cast<float *>(co), *ffix = phi + A, *gsf = reinterpret_cast<float *>(co + o_gsf);
+    int *hit = reinterpret_cast<int *>(phi + 4 * (size_t)A);
+    double *E = reinterpret_cast<double *>(co + o_E), *part = reinterpret_cast<double *>(sc), *share = reinterpret_cast<double *>(sc + o_share);
+    double2 *S = reinterpret_cast<double2 *>(sc + o_S);
+    float4 *rec = reinterpret_cast<float4 *>(sc + o_rec);
+    const float *q_dev = r.qck + (size_t)T * A;
+    const char *d_blob = reinterpret_cast<const char *>(c.d_extra[0]);
+    const int4 *d_ctasks = reinterpret_cast<const int4 *>(d_blob), *d_atasks = reinterpret_cast<const int4 *>(d_blob + o_at);
+    const int2 *d_stasks = reinterpret_cast<const int2 *>(d_blob + o_st);
+    const EwCell *d_ew = reinterpret_cast<const EwCell *>(d_blob + o_ew);
+    const EpnnCell *d_cells = c.geo.cells();
+    // ---- the Ewald sum on the forward's own charges: phi is the backward's seed
+    HIPCHK(hipMemsetAsync(hit, 0, 4, h->stream));
+    if (!sweep)                                                  // beta == alpha in every cell: the real-space term vanishes identically
+        HIPCHK(hipMemsetAsync(part, 0, o_share, h->stream));
+    else if (alpha > 0.0)
+        hipLaunchKernelGGL(k_ew_sweep<true>, dim3((unsigned)ctasks.size()), dim3(64), 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev,
+                           d_cells, d_ew, A, (float)alpha, part, hit);
+    else
+        hipLaunchKernelGGL(k_ew_sweep<false>, dim3((unsigned)ctasks.size()), dim3(64), 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev,
+                           d_cells, d_ew, A, 0.f, part, hit);
+    hipLaunchKernelGGL(k_ew_sfac, dim3((unsigned)stasks.size()), dim3(64), 0, h->stream, d_stasks, c.d_moff, c.d_xyz, q_dev, d_cells, d_ew, S, rec);
+    hipLaunchKernelGGL(k_ew_atom, dim3((unsigned)atasks.size()), dim3(64), 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew,
+                       (const double2 *)S, (const float4 *)rec, (const double *)part, ke, r.gq, phi, ffix, share);
+    hipLaunchKernelGGL(k_ew_energy, dim3((unsigned)B), dim3(64), 0, h->stream, c.d_moff, d_cells, d_ew, (const double2 *)S, (const double *)share,
+                       ke, E, gsf);
+    HIPCHK(hipGetLastError());
+    if (gl_grad_backward(h, gl, r, B, true)) return 1;
+    // ---- one download: q | gxyz | flag | the charges' strain rows | (the step to the next buffer) | phi | ffix | flag | E | the fixed-charge strain
+    const char *from = reinterpret_cast<const char *>(r.q_fin);
+    const size_t nbytes = (size_t)(co + co_bytes - from), at_co = (size_t)(co - from);
+    if (gl->pin_out.ensure(nbytes)) return 1;
+    char *back = gl->pin_out.as<char>();
+    HIPCHK(hipMemcpyAsync(back, from, nbytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const float *bq = reinterpret_cast<const float *>(back), *bgx = bq + A, *bgs = bq + 4 * (size_t)A + 1,
+                *bphi = reinterpret_cast<const float *>(back + at_co), *bffix = bphi + A, *bgsf = reinterpret_cast<const float *>(back + at_co + o_gsf);
+    const int flag = reinterpret_cast<const int *>(bq)[4 * (size_t)A], chit = reinterpret_cast<const int *>(bphi)[4 * (size_t)A];
+    if (flag & 2) EPNN_FAIL("%s: the pair list is not symmetric", name);
+    if (flag != 0 || chit != 0)
+        EPNN_FAIL("%s: two atoms of a cell or their periodic images coincide (distance 0: neither the Coulomb terms nor the edge features have a "
+                  "derivative there)", name);
+    memcpy(q_out, bq, (size_t)A * 4);
+    memcpy(phi_out, bphi, (size_t)A * 4);
+    memcpy(e_out, back + at_co + o_E, (size_t)B * 8);
+    for (size_t k = 0; k < 3 * (size_t)A; ++k) {
+        const float fq = -bgx[k];
+        f_out[k] = bffix[k] + fq;
+        if (fq_out) fq_out[k] = fq;
+    }
+    for (size_t k = 0; k < 9 * (size_t)B; ++k) gs_out[k] = bgsf[k] + bgs[k];
+    if (ffix_out) memcpy(ffix_out, bffix, (size_t)A * 12);
+    if (gsfix_out) memcpy(gsfix_out, bgsf, (size_t)B * 36);
+    if (gsq_out) memcpy(gsq_out, bgs, (size_t)B * 36);
+    return 0;
+}
+
+extern "C" int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                     const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
+                                     double *e_out, float *f_out, float *gstrain_out, float *ffix_out, float *fq_out,
+                                     float *gstrain_fix_out, float *gstrain_q_out) {
+    const char *name = "epnn_coulomb_xyz_cell";
+    if (!cell || !ewald || !phi_out || !e_out || !gstrain_out) EPNN_FAIL("%s: null argument", name);
+    if (!ew_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
+    if (!ew_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
+    GeoArg arg;
+    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, 1, q_out, f_out, arg)) return 1;
+    std::vector<EwCell> ew((size_t)B);
+    for (int b = 0; b < B; ++b)
+        if (ew_cell_row(name, b, cell + 9 * (size_t)b, ewald + 6 * (size_t)b, alpha, ew[b])) return 1;
+    return coulomb_cell_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ew, ke, alpha, q_out, phi_out, e_out, f_out, gstrain_out, ffix_out,
+                             fq_out, gstrain_fix_out, gstrain_q_out);
+}

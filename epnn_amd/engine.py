@@ -447,7 +447,7 @@ class Engine:
         erf(alpha D) / D for alpha > 0 (Gaussian charges of width sigma, alpha = 1 / (2 sigma)); ke is the unit constant
         (KE_EV_ANGSTROM, the default: eV, Angstrom, e; 332.0637: kcal/mol).  parts=True appends ffix (A, 3) and fq (A, 3),
         F = ffix + fq; fq is -gxyz of charges_vjp_xyz(g=phi) on "grad_path" 2, bit for bit, and q has that path's bits.  Open
-        systems only (no box or cell), no self-energy term, no bonded exclusions: alpha is the only short-range handle.  One
+        systems only (fully periodic cells: coulomb_xyz_cell), no self-energy term, no bonded exclusions: alpha is the only short-range handle.  One
         call costs about one gradient call of the pair-list path; it touches no training state and works without train_init."""
         offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz: array shapes do not match offsets", offsets, xyz, x, Q)
         q = np.empty((A,), dtype=np.float32)
@@ -460,6 +460,58 @@ class Engine:
                                         fptr(phi), E.ctypes.data_as(C.POINTER(C.c_double)), fptr(F), fptr(ffix) if parts else None,
                                         fptr(fq) if parts else None), self.lib)
         return (q, phi, E, F, ffix, fq) if parts else (q, phi, E, F)
+
+    def ewald_params(self, cell, alpha=0.0, tol=1e-6):
+        """The Ewald parameters coulomb_xyz_cell runs at for one cell (3, 3) (epnn_ewald_params, host only): float64 (6,) = beta,
+        rc, kc, M0, M1, M2 with s = sqrt(-ln tol), rc = w_min / 2, beta = s / rc capped at alpha (then rc = 0: no real-space
+        part), kc = 2 beta s, M_k = ceil(kc |a_k| / 2 pi).  Refuses open axes, tol outside (0, 1) and k boxes above 2^18 slots."""
+        cell = np.ascontiguousarray(cell, dtype=np.float32)
+        if cell.shape != (3, 3):
+            raise ValueError(f"ewald_params: cell must have shape (3, 3), got {cell.shape}")
+        out = np.empty((6,), dtype=np.float64)
+        check(self.lib.epnn_ewald_params(fptr(cell), float(alpha), float(tol), out.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
+        return out
+
+    def coulomb_xyz_cell(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None, parts=False,
+                         strain=False):
+        """coulomb_xyz in fully periodic cells, by an Ewald sum (epnn_coulomb_xyz_cell): flat batch -> (q (A,), phi (A,), E (B,)
+        float64 per cell, F (A, 3)); strain=True appends gstrain (B, 3, 3), the total dE/d eps under a homogeneous strain of
+        coordinates and cell (the convention of charges_vjp_xyz(strain=True)).  cell (3, 3) or (B, 3, 3), or box (3,) or (B, 3)
+        for its diagonal cell; every axis periodic.  phi includes the self term of the split and the neutralising background of
+        a charged cell (include/epnn.h has the sum).  ewald (6,) or (B, 6) float64: the parameters beta, rc, kc, M0, M1, M2 the
+        call runs at; None: ewald_params(cell, alpha, tol) per cell.  parts=True appends ffix and fq (F = ffix + fq) and, with
+        strain=True, gstrain_fix and gstrain_q behind them (gstrain = gstrain_fix + gstrain_q); fq and gstrain_q are -gxyz and gs
+        of charges_vjp_xyz(g=phi, cell=, strain=True) on "grad_path" 2, bit for bit.  Partially periodic cells, bonded exclusions
+        and PME are not built."""
+        _one_periodic_argument(box, cell)
+        if box is None and cell is None:
+            raise ValueError("coulomb_xyz_cell: give cell= or box= (open molecules: coulomb_xyz)")
+        offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz_cell: array shapes do not match offsets", offsets, xyz, x, Q)
+        _, cell = _geometry(box, cell, B, cells_only=True)
+        if ewald is None:
+            ewald = np.stack([self.ewald_params(cell[b], alpha, tol) for b in range(B)])
+        ewald = np.asarray(ewald, dtype=np.float64)
+        if ewald.shape == (6,):
+            ewald = np.tile(ewald, (B, 1))
+        if ewald.shape != (B, 6):
+            raise ValueError(f"coulomb_xyz_cell: ewald must have shape (6,) or ({B}, 6), got {ewald.shape}")
+        ewald = np.ascontiguousarray(ewald)
+        dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        q = np.empty((A,), dtype=np.float32)
+        phi = np.empty((A,), dtype=np.float32)
+        E = np.empty((B,), dtype=np.float64)
+        F = np.empty((A, 3), dtype=np.float32)
+        gs = np.empty((B, 3, 3), dtype=np.float32)
+        ffix, fq = (np.empty((A, 3), dtype=np.float32) if parts else None for _ in range(2))
+        gs_fix, gs_q = (np.empty((B, 3, 3), dtype=np.float32) if parts else None for _ in range(2))
+        opt = lambda a: None if a is None else fptr(a)
+        check(self.lib.epnn_coulomb_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), dptr(ewald), float(ke),
+                                             float(alpha), fptr(q), fptr(phi), dptr(E), fptr(F), fptr(gs), opt(ffix), opt(fq), opt(gs_fix),
+                                             opt(gs_q)), self.lib)
+        out = (q, phi, E, F) + ((gs,) if strain else ())
+        if parts:
+            out += (ffix, fq) + ((gs_fix, gs_q) if strain else ())
+        return out
 
     def get_gradients(self):
         g = np.empty((self.param_count(),), dtype=np.float32)

@@ -402,8 +402,8 @@ int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t 
  *     fq_i     = -sum_k phi_k dq_k/dr_i        = -gxyz_out of epnn_charges_vjp_xyz with g = phi
  *     f_i      = ffix_i + fq_i  (one float32 add per component)                          = -dE/dr_i, total
  * ke is the caller's unit constant (14.3996454784255 eV A / e^2, 332.0637 kcal A / mol e^2).  q is the model's output, so sum q = Q
- * holds by construction and no constraint term appears.  Open systems only: the entry takes no box or cell (periodic electrostatics
- * need an Ewald or PME sum whose real-space range is far beyond the model's cutoff).  No self-energy term (for alpha > 0 the
+ * holds by construction and no constraint term appears.  Open systems only: the entry takes no box or cell (fully periodic cells:
+ * epnn_coulomb_xyz_cell below, an Ewald sum; partially periodic cells are not built).  No self-energy term (for alpha > 0 the
  * Gaussians' self-energy -ke alpha / sqrt(pi) sum q_i^2 is left out; it depends on q alone), no bonded exclusions or scaling of
  * near neighbours: every pair of a molecule counts in full, and alpha is the only short-range handle.
  * Outputs (host): q_out[A], phi_out[A], e_out[B] in float64 (a float32 energy of a 100 000-atom system loses the digits its forces
@@ -434,6 +434,56 @@ int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t 
 int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                      double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out,
                      float *ffix_out, float *fq_out);
+/* ---- electrostatics of the predicted charges in fully periodic cells: epnn_coulomb_xyz by an Ewald sum (INTEGRATION.md,
+ * "Electrostatics in one call", the periodic section).  cell [B][3][3] as in epnn_forward_xyz_cell, every axis periodic.  ke and
+ * alpha as above; e_alpha(D) = 1 for alpha == 0 and erf(alpha D) for alpha > 0; beta the splitting parameter, V = |det H|,
+ * Q = sum_i q_i, d_ij the minimum-image displacement and D = |d_ij|; g(u) as above with g_0 = 1:
+ *     real         kappa_s(D) = [e_alpha(D) - erf(beta D)] / D for j != i and D <= rc, zero beyond; kappa_s' = -[g_alpha - g_beta] / D^2.
+ *                  With rc <= w_min / 2 (w_min the smallest perpendicular width) the image found by rounding the fractional
+ *                  difference is the only one in range and no atom meets an image of itself.
+ *     reciprocal   k = 2 pi (m0 g_0 + m1 g_1 + m2 g_2) != 0 with |k| <= kc;  c(k) = ke (4 pi / V) exp(-k^2 / 4 beta^2) / k^2;
+ *                  S(k) = sum_j q_j exp(i k r_j);  phi_i += sum_k c(k) Re[exp(-i k r_i) S(k)];  E_rec = 1/2 sum_k c(k) |S(k)|^2;
+ *                  ffix_i -= q_i sum_k c(k) k Im[exp(-i k r_i) S(k)]   (= -dE_rec/dr_i; the half space is summed, doubled)
+ *     self         phi_i -= ke (2 beta / sqrt(pi)) q_i          (the split's own term, there for alpha == 0 too: no beta is left)
+ *     background   phi_i -= ke pi Q / V (1 / beta^2 - [alpha > 0] / alpha^2): the neutralising background of a charged cell (the
+ *                  model conserves Q, which need not be 0); uniform, so it does not change fq (sum_i dq_i/dr = 0)
+ *     energy       E = 1/2 sum_i q_i phi_i per cell
+ *     strain at fixed charges (the convention of epnn_charges_vjp_xyz_cell's gstrain_out: homogeneous strain of coordinates and cell)
+ *                  real 1/2 ke sum_{i != j} q_i q_j kappa_s'(D) d_a d_b / D;  reciprocal 1/2 sum_k c(k) |S|^2 [-delta_ab + 2 k_a k_b
+ *                  (1 / k^2 + 1 / 4 beta^2)] over the whole sphere;  background -E_bg delta_ab, E_bg = -ke pi Q^2 / (2 V) (1 / beta^2 -
+ *                  [alpha > 0] / alpha^2);  the self term has none.
+ * epnn_ewald_params (host only, no handle, no device) holds the rule for one cell [3][3]: s = sqrt(-ln tol), rc = w_min / 2,
+ * beta = s / rc, and where alpha > 0 beta = min(beta, alpha) -- at beta == alpha the real-space term vanishes identically, rc is
+ * reported as 0 and the sweep is skipped; kc = 2 beta s, M_k = ceil(kc |a_k| / 2 pi).  out [6] = beta, rc, kc, M0, M1, M2.  What tol
+ * means: against the same sum at tol = 1e-14, phi agrees within tol ke beta sum_j |q_j|, E within tol 1/2 ke beta (sum_j |q_j|)^2,
+ * ffix within tol ke beta^2 sum_j |q_j| max_j |q_j| (measured 0.02 to 0.03 of these on a 20-atom sheared cell).  It refuses, by
+ * name: a cell with an open axis (two- and one-dimensional Ewald sums are different mathematics), dependent rows, an entry that is
+ * not finite, alpha negative or not finite, tol outside (0, 1), and a cell whose k box (2 M0 + 1)(2 M1 + 1)(M2 + 1) exceeds
+ * 2^18 slots (extreme aspect ratios are refused, not served slowly).
+ * epnn_coulomb_xyz_cell takes the numbers, ewald [B][6] (host, float64, a row per cell as epnn_ewald_params writes it), checks
+ * that beta > 0, 0 <= rc <= w_min / 2 (rc == 0 only with beta == alpha > 0), that every M_k is an integer of at least
+ * ceil(kc |a_k| / 2 pi) and that the k box is under the cap, and runs at exactly those values.
+ * Outputs (host): q_out[A], phi_out[A], e_out[B] float64 (per cell), f_out[A][3] the total forces, gstrain_out[B][3][3] the total
+ * strain derivative dE/d eps (the part at fixed charges plus the part through dq/d eps); ffix_out, fq_out, gstrain_fix_out and
+ * gstrain_q_out may each be NULL and the other outputs have the same bits either way.
+ * Bits: q_out, fq_out = -gxyz_out and gstrain_q_out = gstrain_out of epnn_charges_vjp_xyz_cell on "grad_path" 2 called with
+ * g = phi_out; f_out == ffix_out + fq_out and gstrain_out == gstrain_fix_out + gstrain_q_out in float32.
+ * Contract: that of epnn_coulomb_xyz (the pair-list path whatever "grad_path" says, no training state touched, the same refusals;
+ * the cell is checked as in epnn_forward_xyz_cell), and a cell's rows do not depend on the rest of the batch at the same N.
+ * Arithmetic: the real-space part is the open call's all-pairs sweep with the minimum image of each pair (float64 displacement
+ * through the cell, rounded once; no cell list, no image loop); S(k) per cell and k slot and the reciprocal sums per atom take the
+ * phase as 2 pi frac(m . s_j) from fractional coordinates reduced in float64, so unwrapped coordinates cost nothing.  Per-pair and
+ * per-(atom, k) terms are float32, every running sum float64, no float atomics.  phi, ffix, E and the fixed-charge strain are each
+ * within 2e-6 of the sum of their absolute real-space terms plus 34 * 2^-24 of the sum of their absolute reciprocal terms
+ * (tests/test_gpu_coulomb_cell.py counts the roundings; measured: 0.03 of that at worst).
+ * Device scratch on top of the gradient path's: A (20 + 80 cpieces + 56) + 44 B + 32 slots + the task tables and 72 B of
+ * parameters; slots = the batch's k slots, about 3600 for a cube at tol = 1e-6 whatever its size.  Nothing of size n nk or n^2.
+ * Still missing: partially periodic cells, bonded exclusions, PME for very large cells. */
+int epnn_ewald_params(const float *cell, double alpha, double tol, double *out);
+int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                          const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
+                          double *e_out, float *f_out, float *gstrain_out, float *ffix_out, float *fq_out,
+                          float *gstrain_fix_out, float *gstrain_q_out);
 /* ---- training on periodic and large systems. epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
  * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
  * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's

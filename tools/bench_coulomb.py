@@ -12,7 +12,12 @@ reports (epnn_last_stats()[2]) beside the formula of include/epnn.h, and checks 
 against -gxyz of the gradient call seeded with phi (bits), and sum_i f_i over the batch.
     python tools/bench_coulomb.py --trace [--systems ...]
 makes three calls of coulomb_xyz per system and nothing else: the run to put under a kernel trace, whose k_cl_* rows are the Coulomb
-kernels."""
+kernels.
+    python tools/bench_coulomb.py --cell [--systems qm9cell,cell10000,cell100000] [--rounds 5] [--alpha 0.0] [--tol 1e-6] [--trace]
+is the periodic call coulomb_xyz_cell beside charges_vjp_xyz(cell=, strain=True) of the same system (profiles/r17_coulomb_cell.txt):
+1024 QM9-sized cells of 6 A, a 10 000-atom and a 100 000-atom cubic cell (synth.periodic_box_system).  The same alternation and
+windows; printed besides: the k slots of the batch, and the checks q (bits), fq and gstrain_q against the gradient call seeded with
+phi (bits), sum_i f_i.  With --trace: three calls of coulomb_xyz_cell per system (the k_ew_* rows are the Ewald kernels)."""
 import json
 import os
 import sys
@@ -83,15 +88,78 @@ def load(system):
     raise SystemExit(f"unknown system {system}")
 
 
+def load_cell(system):
+    """(name, offsets, xyz, x, Q, N, cells (B, 3, 3))"""
+    if system == "qm9cell":
+        ns = np.diff(synth.qm9_like_batch(B=1024, seed=0, N=29)[0])
+        parts = [synth.periodic_box_system(int(n), seed=k, density=int(n) / 6.0001 ** 3) for k, n in enumerate(ns)]
+        offsets = np.zeros(len(ns) + 1, np.int32)
+        offsets[1:] = np.cumsum(ns)
+        cells = np.stack([np.diag(p[5][0]) for p in parts]).astype(np.float32)
+        return ("1024 QM9-sized cells of 6 A, N = 29", offsets, np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts]),
+                np.concatenate([p[3] for p in parts]).astype(np.float32), 29, cells)
+    if system.startswith("cell"):
+        offsets, xyz, x, Q, N, box = synth.periodic_box_system(int(system[4:]), seed=0)
+        return f"{int(system[4:])} atoms, cubic cell of {float(box[0][0]):.2f} A", offsets, xyz, x, Q, N, np.diag(box[0]).astype(np.float32)[None]
+    raise SystemExit(f"unknown system {system}")
+
+
+def main_cell(eng, T, systems, rounds, alpha, tol):
+    for system in systems:
+        name, offsets, xyz, x, Q, N, cells = load_cell(system)
+        A = int(offsets[-1])
+        rows = np.stack([eng.ewald_params(c, alpha, tol) for c in cells])
+        slots = int(((2 * rows[:, 3] + 1) * (2 * rows[:, 4] + 1) * (rows[:, 5] + 1)).sum())
+        if "--trace" in sys.argv:
+            for _ in range(3):
+                eng.coulomb_xyz_cell(offsets, xyz, x, Q, N, cell=cells, alpha=alpha, ewald=rows)
+            print(json.dumps({"workload": name, "atoms": A, "calls": 3, "alpha": alpha, "tol": tol, "k_slots": slots}), flush=True)
+            continue
+        g = np.random.default_rng(0).normal(size=A).astype(np.float32)
+        calls = {"coulomb_cell": lambda: eng.coulomb_xyz_cell(offsets, xyz, x, Q, N, cell=cells, alpha=alpha, ewald=rows, parts=True, strain=True),
+                 "gradient": lambda: eng.charges_vjp_xyz(offsets, xyz, x, Q, g, N, cell=cells, strain=True)}
+        for fn in calls.values():
+            fn()
+        times = {k: [] for k in calls}
+        outs = {}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t, outs[k] = window(fn)
+                times[k].append(t * 1e3)
+        q, phi, E, F, gs, ffix, fq, gs_fix, gs_q = outs["coulomb_cell"]
+        st = eng.last_stats() if calls["coulomb_cell"]() else None
+        seeded = eng.charges_vjp_xyz(offsets, xyz, x, Q, phi, N, cell=cells, strain=True)
+        sg = eng.last_stats()
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        line = {"workload": name, "atoms": A, "cells": len(cells), "near_pairs": int(st[0]), "rounds": rounds, "alpha": alpha, "tol": tol,
+                "k_slots": slots, "ewald_first_cell": [round(float(v), 4) for v in rows[0]]}
+        for k, t in times.items():
+            line[k + "_ms_median"] = round(med[k], 3)
+            line[k + "_ms_range"] = [round(min(t), 3), round(max(t), 3)]
+        line.update({"coulomb_cell_over_gradient": round(med["coulomb_cell"] / med["gradient"], 3), "coulomb_cell_scratch_bytes": int(st[2]),
+                     "gradient_scratch_bytes": int(sg[2]), "q_bits_equal_gradient_call": bool(np.array_equal(q, outs["gradient"][0])),
+                     "fq_bits_equal_minus_gxyz_of_phi": bool(np.array_equal(fq, -seeded[1])),
+                     "gstrain_q_bits_equal_gstrain_of_phi": bool(np.array_equal(gs_q, seeded[2])),
+                     "energy_sum": float(E.sum()), "max_abs_f": float(np.abs(F).max()), "max_abs_ffix": float(np.abs(ffix).max()),
+                     "max_abs_fq": float(np.abs(fq).max()), "max_abs_sum_f": float(np.abs(F.sum(0, dtype=np.float64)).max()),
+                     "max_abs_gstrain": float(np.abs(gs).max())})
+        print(json.dumps(line), flush=True)
+
+
 def main():
     arg = lambda name, default: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
-    systems = arg("--systems", "protein,cluster10000,qm9").split(",")
+    cell_mode = "--cell" in sys.argv
+    systems = arg("--systems", "qm9cell,cell10000,cell100000" if cell_mode else "protein,cluster10000,qm9").split(",")
     rounds, alpha = int(arg("--rounds", "5")), float(arg("--alpha", "0.0"))
     w = checkpoint.load_epnn_weights(os.path.join(ROOT, "models/decay_model_weights"))
     T = len(w["msg"])
     eng = Engine(nx=9, T=T)
     eng.set_weights(w)
     eng.set_option("grad_path", 2)
+    if cell_mode:
+        main_cell(eng, T, systems, rounds, alpha, float(arg("--tol", "1e-6")))
+        eng.close()
+        return
     for system in systems:
         name, offsets, xyz, x, Q, N = load(system)
         A = int(offsets[-1])
