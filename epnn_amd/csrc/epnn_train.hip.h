@@ -464,6 +464,8 @@ static int train_fwd_bwd(epnn_handle *h, int B, int N, const float *d_e, const f
                          bool size_only = false, const XyzGrad *xg = nullptr) {
     TrainState *ts = xg ? xg->ts : train_state(h);
     if (!ts->ready) EPNN_FAIL("training: call epnn_train_init first");
+    ts->host_out = false;          // loss terms | predictions stay on the device: the caller downloads them (a row-fused step before
+                                   // this one left the flag set, and the step returned that step's outputs)
     const int T = h->cfg.T, nx = h->cfg.nx, H = EPNN_EDIM, E = EPNN_EDIM, F = nx + H + 1, D = 2 * F + E;
     const int BN = B * N;
     const size_t R = (size_t)BN * N;
