@@ -390,7 +390,7 @@ class EPNNModel(_Stack):
         """Charges, electrostatic potential, Coulomb energy and total forces in one call: (q (A,), phi (A,), E (B,) float64,
         F (A, 3)), F = -dE/dxyz including the part through dq/dxyz; parts=True appends its two parts ffix and fq.  ke is the unit
         constant (default KE_EV_ANGSTROM), alpha = 0 the bare 1 / D, alpha > 0 erf(alpha D) / D.  Open systems only, no
-        self-energy, no bonded exclusions.  One call costs about one charges_vjp_xyz call of the pair-list path.  N defaults to
+        self-energy; bonded exclusions: coulomb_xyz_excl.  One call costs about one charges_vjp_xyz call of the pair-list path.  N defaults to
         the model's natom."""
         return self._eng().coulomb_xyz(offsets, xyz, x, Q, self.natom if N is None else N, ke=ke, alpha=alpha, parts=parts)
 
@@ -402,6 +402,19 @@ class EPNNModel(_Stack):
         phi includes the split's self term and a charged cell's neutralising background.  N defaults to the model's natom."""
         return self._eng().coulomb_xyz_cell(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke, alpha=alpha,
                                             tol=tol, ewald=ewald, parts=parts, strain=strain)
+
+    def coulomb_xyz_excl(self, offsets, xyz, x, Q, N=None, ke=KE_EV_ANGSTROM, alpha=0.0, parts=False, exclusions=None):
+        """coulomb_xyz with bonded exclusions and pair scaling: exclusions = (pairs (P, 2), scale) as engine.bonded_exclusions
+        returns it; a listed pair counts with weight scale instead of 1 (0 excludes).  None is coulomb_xyz itself."""
+        return self._eng().coulomb_xyz_excl(offsets, xyz, x, Q, self.natom if N is None else N, ke=ke, alpha=alpha, parts=parts,
+                                            exclusions=exclusions)
+
+    def coulomb_xyz_cell_excl(self, offsets, xyz, x, Q, N=None, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                              parts=False, strain=False, exclusions=None):
+        """coulomb_xyz_cell with bonded exclusions and pair scaling: the nearest image of every listed pair counts with weight scale.
+        None is coulomb_xyz_cell itself."""
+        return self._eng().coulomb_xyz_cell_excl(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke, alpha=alpha,
+                                                 tol=tol, ewald=ewald, parts=parts, strain=strain, exclusions=exclusions)
 
     def charges_jvp_xyz_multi(self, offsets, xyz, x, Q, N=None, v=None, strain=None, dQ=None, box=None, cell=None):
         """charges_jvp_xyz along K directions in one pass: (q (A,), tq (K, A)), row k with the bits of the single call on the k-th

@@ -32,9 +32,105 @@ static int cl_build_tasks(int B, const int32_t *offsets, std::vector<int4> &task
     return maxp;
 }
 
+// ---- bonded exclusions and pair scaling: the list of the two _excl entries, checked and turned into a CSR by atom.  One blob, staged
+// as one span: row_off [A + 1] | partner [2 P] | factor [2 P] (= s - 1 in float32); every pair is entered in both directions and every
+// row is sorted by partner, so the order of every sum is the CSR's and the caller's order cannot reach the bits.
+struct ExclCsr {
+    std::vector<char> blob;
+    int A = 0;
+    int64_t P = 0;
+    size_t o_partner() const { return ((size_t)A + 1) * 4; }
+    size_t o_factor() const { return o_partner() + 8 * (size_t)P; }
+    const int *row_off() const { return reinterpret_cast<const int *>(blob.data()); }
+    const int *partner() const { return reinterpret_cast<const int *>(blob.data() + o_partner()); }
+    const float *factor() const { return reinterpret_cast<const float *>(blob.data() + o_factor()); }
+};
+// bytes of the staged CSR and of the kernel's row per atom (include/epnn.h quotes both)
+static size_t excl_csr_bytes(int A, int64_t P) { return ((size_t)A + 1) * 4 + 16 * (size_t)P; }
+static size_t excl_xpart_bytes(int A, bool cell) { return (size_t)A * (cell ? 10 : CL_XPART) * 8; }      // (10: EW_PART, asserted in epnn_ewald.hip.h)
+
+// (the library is built with -ffinite-math-only: the factor's bits are read back from a volatile word, as ew_finite does)
+static bool excl_finite(float v) {
+    volatile uint32_t seen;
+    uint32_t bits;
+    memcpy(&bits, &v, 4);
+    seen = bits;
+    bits = seen;
+    return (bits & 0x7f800000u) != 0x7f800000u;
+}
+
+// Refused by name, each with the pair's position in the list: a bad count, a NULL list, an index outside [0, A), i == j, atoms of two
+// molecules, a factor that is not finite, a pair listed twice (in either order).  offsets are already checked.
+static int excl_build(const char *name, int B, const int32_t *offsets, int64_t npairs, const int32_t *ex_i, const int32_t *ex_j,
+                      const float *ex_scale, ExclCsr &out) {
+    const int A = offsets[B];
+    if (npairs < 0) EPNN_FAIL("%s: npairs = %lld is negative", name, (long long)npairs);
+    if (npairs > (int64_t)0x3fffffff) EPNN_FAIL("%s: npairs = %lld: 2 npairs must not exceed 2^31 - 1", name, (long long)npairs);
+    if (npairs > 0 && (!ex_i || !ex_j || !ex_scale)) EPNN_FAIL("%s: a NULL exclusion list with npairs = %lld", name, (long long)npairs);
+    std::vector<int> mol_of((size_t)A);
+    for (int b = 0; b < B; ++b)
+        for (int a = offsets[b]; a < offsets[b + 1]; ++a) mol_of[a] = b;
+    out.A = A;
+    out.P = npairs;
+    out.blob.assign(excl_csr_bytes(A, npairs), 0);
+    int *row_off = reinterpret_cast<int *>(out.blob.data());
+    int *partner = reinterpret_cast<int *>(out.blob.data() + out.o_partner());
+    float *factor = reinterpret_cast<float *>(out.blob.data() + out.o_factor());
+    for (int64_t p = 0; p < npairs; ++p) {
+        const int i = ex_i[p], j = ex_j[p];
+        if (i < 0 || i >= A || j < 0 || j >= A)
+            EPNN_FAIL("%s: exclusion pair %lld = (%d, %d): an atom index outside [0, %d)", name, (long long)p, i, j, A);
+        if (i == j) EPNN_FAIL("%s: exclusion pair %lld = (%d, %d): an atom paired with itself", name, (long long)p, i, j);
+        if (mol_of[i] != mol_of[j])
+            EPNN_FAIL("%s: exclusion pair %lld = (%d, %d): the atoms are in different molecules (%d and %d)", name, (long long)p, i, j, mol_of[i],
+                      mol_of[j]);
+        if (!excl_finite(ex_scale[p])) EPNN_FAIL("%s: exclusion pair %lld = (%d, %d): its factor is not finite", name, (long long)p, i, j);
+        ++row_off[i + 1];
+        ++row_off[j + 1];
+    }
+    for (int a = 0; a < A; ++a) row_off[a + 1] += row_off[a];
+    // Rows sorted by partner without a sort: the directed entries go into their rows in list order first (partner, position), then
+    // the atoms are walked in ascending order and every entry a -> j puts a into row j, so each row fills in ascending partner order.
+    std::vector<int> cur(row_off, row_off + A), first(2 * (size_t)npairs), pos(2 * (size_t)npairs), where(2 * (size_t)npairs);
+    for (int64_t p = 0; p < npairs; ++p) {
+        const int ki = cur[ex_i[p]]++, kj = cur[ex_j[p]]++;
+        first[ki] = ex_j[p]; pos[ki] = (int)p;
+        first[kj] = ex_i[p]; pos[kj] = (int)p;
+    }
+    std::copy(row_off, row_off + A, cur.begin());
+    for (int a = 0; a < A; ++a)
+        for (int k = row_off[a]; k < row_off[a + 1]; ++k) {
+            const int j = first[k], slot = cur[j]++;
+            if (slot > row_off[j] && partner[slot - 1] == a) {
+                const int64_t p1 = std::max(pos[k], where[slot - 1]), p0 = std::min(pos[k], where[slot - 1]);
+                EPNN_FAIL("%s: exclusion pair %lld = (%d, %d) is listed twice: pair %lld names the same two atoms", name, (long long)p1, ex_i[p1],
+                          ex_j[p1], (long long)p0);
+            }
+            partner[slot] = a;
+            where[slot] = pos[k];
+            factor[slot] = ex_scale[pos[k]] - 1.f;
+        }
+    return 0;
+}
+// the correction's launch: one lane per atom (k_cl_excl), on the stream, behind the sweep
+template <bool CELL>
+static void excl_launch(epnn_handle *h, const GlCall &c, const char *d_csr, const ExclCsr &ex, const float *q_dev, const EpnnCell *d_cells,
+                        double alpha, double *xpart, int *hit) {
+    const int A = ex.A;
+    const int *row_off = reinterpret_cast<const int *>(d_csr), *partner = reinterpret_cast<const int *>(d_csr + ex.o_partner());
+    const float *factor = reinterpret_cast<const float *>(d_csr + ex.o_factor());
+    const dim3 grid((unsigned)((A + 63) / 64));
+    if (alpha > 0.0)
+        hipLaunchKernelGGL((k_cl_excl<true, CELL>), grid, dim3(64), 0, h->stream, A, c.d_molof, c.d_xyz, q_dev, row_off, partner, factor, d_cells,
+                           (float)alpha, xpart, hit);
+    else
+        hipLaunchKernelGGL((k_cl_excl<false, CELL>), grid, dim3(64), 0, h->stream, A, c.d_molof, c.d_xyz, q_dev, row_off, partner, factor, d_cells,
+                           0.f, xpart, hit);
+}
+
 static int coulomb_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                         const float *Q, const HostGeo &geo, double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
-                        float *fq_out) {
+                        float *fq_out, const ExclCsr *ex = nullptr) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
     const int T = h->cfg.T, A = offsets[B];
@@ -44,9 +140,11 @@ static int coulomb_impl(epnn_handle *h, const char *name, int B, int N, const in
     // [A] phi | [A][3] ffix | flag, then [B] E in float64: directly behind the backward's output block, one download for both;
     // the sweep's partial rows [pieces][A][4] and the atoms' energy shares [A], float64
     const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), co_bytes = o_E + (size_t)B * 8;
-    const size_t more[2] = {co_bytes, (cpieces * 4 + 1) * (size_t)A * 8};
+    // (the _excl entry: the CSR is one more span beside the task table, the correction's rows [A][4] one more buffer behind the others)
+    const GlSpan spans[2] = {span_t, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false}};
+    const size_t more[3] = {co_bytes, (cpieces * 4 + 1) * (size_t)A * 8, ex ? excl_xpart_bytes(A, false) : 0};
     GlGrad r;
-    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, &span_t, 1, more, 2, false, r)) return 1;
+    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
     const GlCall &c = r.c;
     char *co = c.dw + r.o_more[0];
     float *phi = reinterpret_cast<float *>(co), *ffix = phi + A;
@@ -63,8 +161,14 @@ static int coulomb_impl(epnn_handle *h, const char *name, int B, int N, const in
     else
         hipLaunchKernelGGL(k_cl_sweep<false>, dim3((unsigned)tasks.size()), dim3(64), 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev,
                            A, 0.f, part, hit);
-    hipLaunchKernelGGL(k_cl_atom, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, (const double *)part, ke, r.gq, phi, ffix,
-                       share);
+    if (ex) {
+        double *xpart = reinterpret_cast<double *>(c.dw + r.o_more[2]);
+        excl_launch<false>(h, c, reinterpret_cast<const char *>(c.d_extra[1]), *ex, q_dev, nullptr, alpha, xpart, hit);
+        hipLaunchKernelGGL(k_cl_atom_x, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, (const double *)part,
+                           (const double *)xpart, ke, r.gq, phi, ffix, share);
+    } else
+        hipLaunchKernelGGL(k_cl_atom, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, (const double *)part, ke, r.gq, phi, ffix,
+                           share);
     hipLaunchKernelGGL(k_cl_energy, dim3((unsigned)B), dim3(64), 0, h->stream, (const double *)share, c.d_moff, E);
     HIPCHK(hipGetLastError());
     if (gl_grad_backward(h, gl, r, B, false)) return 1;
@@ -92,10 +196,12 @@ static int coulomb_impl(epnn_handle *h, const char *name, int B, int N, const in
     return 0;
 }
 
-extern "C" int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
-                                float *fq_out) {
-    const char *name = "epnn_coulomb_xyz";
+// what an _excl entry adds to its plain entry's arguments
+struct ExclArgs { int64_t npairs; const int32_t *i, *j; const float *scale; };
+
+static int coulomb_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                         double ke, double alpha, const ExclArgs *xa, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
+                         float *fq_out) {
     if (!phi_out || !e_out) EPNN_FAIL("%s: null argument", name);
     // (the library is built with -ffinite-math-only: std::isfinite would fold to true, and so would a test of an argument's own
     //  bits -- the tests below read them back from volatile words, of which the compiler assumes nothing)
@@ -111,5 +217,21 @@ extern "C" int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *off
         EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
     GeoArg arg;                                                  // (open molecules: the entry takes no cell)
     if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, nullptr, 1, q_out, f_out, arg)) return 1;
-    return coulomb_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
+    if (!xa) return coulomb_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
+    ExclCsr ex;
+    if (excl_build(name, B, offsets, xa->npairs, xa->i, xa->j, xa->scale, ex)) return 1;
+    return coulomb_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, q_out, phi_out, e_out, f_out, ffix_out, fq_out, &ex);
+}
+
+extern "C" int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
+                                float *fq_out) {
+    return coulomb_enter(h, "epnn_coulomb_xyz", B, N, offsets, xyz, x, Q, ke, alpha, nullptr, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
+}
+
+extern "C" int epnn_coulomb_xyz_excl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                     double ke, double alpha, int64_t npairs, const int32_t *ex_i, const int32_t *ex_j, const float *ex_scale,
+                                     float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out, float *fq_out) {
+    const ExclArgs xa{npairs, ex_i, ex_j, ex_scale};
+    return coulomb_enter(h, "epnn_coulomb_xyz_excl", B, N, offsets, xyz, x, Q, ke, alpha, &xa, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
 }

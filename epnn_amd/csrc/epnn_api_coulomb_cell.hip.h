@@ -130,10 +130,35 @@ static size_t ew_build_tasks(int B, const int32_t *offsets, std::vector<EwCell> 
     }
     return slots;
 }
+// The refusal behind the device's CL_FLAG_FAR: the first listed pair whose nearest image lies beyond half the smallest perpendicular
+// width of its cell, found again on the host (the image of epnn_mic_cell, the width as k_cl_excl takes it: 1 / max_k |g_k|).
+static int excl_name_far(const char *name, const int32_t *offsets, const float *xyz, const HostGeo &geo, const ExclArgs &xa) {
+    const EpnnCell *cells = static_cast<const EpnnCell *>(geo.rows);
+    for (int64_t p = 0; p < xa.npairs; ++p) {
+        const int i = xa.i[p], j = xa.j[p];
+        int b = 0;
+        while (offsets[b + 1] <= i) ++b;
+        const EpnnCell &c = cells[b];
+        double d[3], n[3], g2 = 0.0;
+        for (int k = 0; k < 3; ++k) d[k] = (double)xyz[3 * (size_t)i + k] - (double)xyz[3 * (size_t)j + k];
+        for (int k = 0; k < 3; ++k) {
+            n[k] = rint(c.g[3 * k] * d[0] + c.g[3 * k + 1] * d[1] + c.g[3 * k + 2] * d[2]);
+            g2 = std::max(g2, c.g[3 * k] * c.g[3 * k] + c.g[3 * k + 1] * c.g[3 * k + 1] + c.g[3 * k + 2] * c.g[3 * k + 2]);
+        }
+        for (int k = 0; k < 3; ++k) d[k] -= n[0] * (double)c.a[k] + n[1] * (double)c.a[3 + k] + n[2] * (double)c.a[6 + k];
+        const double D = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), half_w = 0.5 / sqrt(g2);
+        if ((float)D > (float)half_w)
+            EPNN_FAIL("%s: exclusion pair %lld = (%d, %d): its atoms are %g apart, beyond half the smallest perpendicular width of cell %d (%g): "
+                      "past it the rounding rule no longer returns the nearest image (bonded atoms are never that far apart)", name,
+                      (long long)p, i, j, D, b, half_w);
+    }
+    EPNN_FAIL("%s: an exclusion pair lies beyond half the smallest perpendicular width of its cell", name);
+}
 
 static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                              const float *Q, const HostGeo &geo, std::vector<EwCell> &ew, double ke, double alpha, float *q_out, float *phi_out,
-                             double *e_out, float *f_out, float *gs_out, float *ffix_out, float *fq_out, float *gsfix_out, float *gsq_out) {
+                             double *e_out, float *f_out, float *gs_out, float *ffix_out, float *fq_out, float *gsfix_out, float *gsq_out,
+                             const ExclCsr *ex = nullptr, const ExclArgs *xa = nullptr) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
     const int T = h->cfg.T, A = offsets[B];
@@ -156,9 +181,11 @@ static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, con
     // block, one download for both; the sweep's partial rows, the atoms' shares, S and the slots' records
     const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), o_gsf = o_E + (size_t)B * 8, co_bytes = o_gsf + (size_t)B * 36;
     const size_t o_share = cpieces * (size_t)A * EW_PART * 8, o_S = (o_share + (size_t)A * EW_SHARE * 8 + 15) & ~size_t(15), o_rec = o_S + slots * 16;
-    const size_t more[2] = {co_bytes, o_rec + slots * 16};
+    // (the _excl entry: the CSR is one more span beside the blob, the correction's rows [A][EW_PART] one more buffer behind the others)
+    const GlSpan spans[2] = {span, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false}};
+    const size_t more[3] = {co_bytes, o_rec + slots * 16, ex ? excl_xpart_bytes(A, true) : 0};
     GlGrad r;
-    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, &span, 1, more, 2, false, r)) return 1;
+    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
     const GlCall &c = r.c;
     char *co = c.dw + r.o_more[0], *sc = c.dw + r.o_more[1];
     float *phi = reinterpret_cast<float *>(co), *ffix = phi + A, *gsf = reinterpret_cast<float *>(co + o_gsf);
@@ -183,8 +210,14 @@ static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, con
         hipLaunchKernelGGL(k_ew_sweep<false>, dim3((unsigned)ctasks.size()), dim3(64), 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev,
                            d_cells, d_ew, A, 0.f, part, hit);
     hipLaunchKernelGGL(k_ew_sfac, dim3((unsigned)stasks.size()), dim3(64), 0, h->stream, d_stasks, c.d_moff, c.d_xyz, q_dev, d_cells, d_ew, S, rec);
-    hipLaunchKernelGGL(k_ew_atom, dim3((unsigned)atasks.size()), dim3(64), 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew,
-                       (const double2 *)S, (const float4 *)rec, (const double *)part, ke, r.gq, phi, ffix, share);
+    if (ex) {                                                    // (nothing of it depends on rc: it runs on a zeroed `part` too)
+        double *xpart = reinterpret_cast<double *>(c.dw + r.o_more[2]);
+        excl_launch<true>(h, c, reinterpret_cast<const char *>(c.d_extra[1]), *ex, q_dev, d_cells, alpha, xpart, hit);
+        hipLaunchKernelGGL(k_ew_atom_x, dim3((unsigned)atasks.size()), dim3(64), 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew,
+                           (const double2 *)S, (const float4 *)rec, (const double *)part, (const double *)xpart, ke, r.gq, phi, ffix, share);
+    } else
+        hipLaunchKernelGGL(k_ew_atom, dim3((unsigned)atasks.size()), dim3(64), 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew,
+                           (const double2 *)S, (const float4 *)rec, (const double *)part, ke, r.gq, phi, ffix, share);
     hipLaunchKernelGGL(k_ew_energy, dim3((unsigned)B), dim3(64), 0, h->stream, c.d_moff, d_cells, d_ew, (const double2 *)S, (const double *)share,
                        ke, E, gsf);
     HIPCHK(hipGetLastError());
@@ -200,6 +233,7 @@ static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, con
                 *bphi = reinterpret_cast<const float *>(back + at_co), *bffix = bphi + A, *bgsf = reinterpret_cast<const float *>(back + at_co + o_gsf);
     const int flag = reinterpret_cast<const int *>(bq)[4 * (size_t)A], chit = reinterpret_cast<const int *>(bphi)[4 * (size_t)A];
     if (flag & 2) EPNN_FAIL("%s: the pair list is not symmetric", name);
+    if (flag == 0 && chit == CL_FLAG_FAR && ex && xa) return excl_name_far(name, offsets, xyz, geo, *xa);
     if (flag != 0 || chit != 0)
         EPNN_FAIL("%s: two atoms of a cell or their periodic images coincide (distance 0: neither the Coulomb terms nor the edge features have a "
                   "derivative there)", name);
@@ -218,11 +252,10 @@ static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, con
     return 0;
 }
 
-extern "C" int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                     const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
-                                     double *e_out, float *f_out, float *gstrain_out, float *ffix_out, float *fq_out,
-                                     float *gstrain_fix_out, float *gstrain_q_out) {
-    const char *name = "epnn_coulomb_xyz_cell";
+static int coulomb_cell_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                              const float *Q, const float *cell, const double *ewald, double ke, double alpha, const ExclArgs *xa, float *q_out,
+                              float *phi_out, double *e_out, float *f_out, float *gstrain_out, float *ffix_out, float *fq_out,
+                              float *gstrain_fix_out, float *gstrain_q_out) {
     if (!cell || !ewald || !phi_out || !e_out || !gstrain_out) EPNN_FAIL("%s: null argument", name);
     if (!ew_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
     if (!ew_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
@@ -231,6 +264,28 @@ extern "C" int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t
     std::vector<EwCell> ew((size_t)B);
     for (int b = 0; b < B; ++b)
         if (ew_cell_row(name, b, cell + 9 * (size_t)b, ewald + 6 * (size_t)b, alpha, ew[b])) return 1;
+    if (!xa)
+        return coulomb_cell_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ew, ke, alpha, q_out, phi_out, e_out, f_out, gstrain_out, ffix_out,
+                                 fq_out, gstrain_fix_out, gstrain_q_out);
+    ExclCsr ex;
+    if (excl_build(name, B, offsets, xa->npairs, xa->i, xa->j, xa->scale, ex)) return 1;
     return coulomb_cell_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ew, ke, alpha, q_out, phi_out, e_out, f_out, gstrain_out, ffix_out,
-                             fq_out, gstrain_fix_out, gstrain_q_out);
+                             fq_out, gstrain_fix_out, gstrain_q_out, &ex, xa);
+}
+
+extern "C" int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                     const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
+                                     double *e_out, float *f_out, float *gstrain_out, float *ffix_out, float *fq_out,
+                                     float *gstrain_fix_out, float *gstrain_q_out) {
+    return coulomb_cell_enter(h, "epnn_coulomb_xyz_cell", B, N, offsets, xyz, x, Q, cell, ewald, ke, alpha, nullptr, q_out, phi_out, e_out, f_out,
+                              gstrain_out, ffix_out, fq_out, gstrain_fix_out, gstrain_q_out);
+}
+
+extern "C" int epnn_coulomb_xyz_cell_excl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                          const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
+                                          const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
+                                          float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out) {
+    const ExclArgs xa{npairs, ex_i, ex_j, ex_scale};
+    return coulomb_cell_enter(h, "epnn_coulomb_xyz_cell_excl", B, N, offsets, xyz, x, Q, cell, ewald, ke, alpha, &xa, q_out, phi_out, e_out,
+                              f_out, gstrain_out, ffix_out, fq_out, gstrain_fix_out, gstrain_q_out);
 }

@@ -23,7 +23,7 @@ static void xyz_grad_release(epnn_handle *h) {
 // gl_grad_backward (the backward from a seed already on the device, in r.gq).  Between the two an entry writes its seed.
 struct GlGrad {
     GlCall c;
-    size_t o_slotx, o_share, o_more[2];                          // o_more: the entry's own buffers, placed behind the shared ones
+    size_t o_slotx, o_share, o_more[3];                          // o_more: the entry's own buffers, placed behind the shared ones
     float *hck, *Sck, *qck, *dP, *dR, *Yb, *Yc, *dS, *partP, *partR, *slotP, *slotR, *slotq, *gE, *gh, *ghp;
     float *out, *gq, *q_fin, *gx, *gs;                           // out: [A] gq | [A] q | [A][3] gxyz | bad | [B][9] gstrain
     int *bad;

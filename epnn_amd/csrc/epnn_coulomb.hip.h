@@ -18,6 +18,7 @@
 // No atomics on floats; the only atomic is the OR into the coincident-atoms flag.
 #pragma once
 #include "epnn_host.h"
+#include "epnn_frontend.hip.h"
 
 #define CL_BLOCK 64               // atoms of a task: one per lane
 #define CL_TILE 64                // partners staged in LDS at a time: one per lane
@@ -104,19 +105,30 @@ __global__ __launch_bounds__(64) void k_cl_sweep(const int4 *tasks, const int *m
 }
 
 // every atom adds its pieces in piece order: phi [A] (float32, written twice: the backward's seed and the output), ffix [A][3],
-// and its share of the energy, 1/2 q_i phi_i, in float64
-__global__ __launch_bounds__(256) void k_cl_atom(int A, const int *moff, const int *mol_of, const float *q, const double *part, double ke,
-                                                 float *seed, float *phi, float *ffix, double *share) {
+// and its share of the energy, 1/2 q_i phi_i, in float64.  X: the listed pairs' row xpart [A][4] (k_cl_excl) is one more piece, added last.
+template <bool X>
+__device__ __forceinline__ void cl_atom_body(int A, const int *moff, const int *mol_of, const float *q, const double *part, const double *xpart,
+                                             double ke, float *seed, float *phi, float *ffix, double *share) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A) return;
     const int b = mol_of[i], np = cl_pieces(moff[b + 1] - moff[b]);
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < np; ++k)
         for (int c = 0; c < 4; ++c) s[c] += part[((size_t)k * A + i) * 4 + c];
+    if (X)
+        for (int c = 0; c < 4; ++c) s[c] += xpart[(size_t)i * 4 + c];
     const double p = ke * s[0], qi = (double)q[i];
     seed[i] = phi[i] = (float)p;
     for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
     share[i] = 0.5 * qi * p;
+}
+__global__ __launch_bounds__(256) void k_cl_atom(int A, const int *moff, const int *mol_of, const float *q, const double *part, double ke,
+                                                 float *seed, float *phi, float *ffix, double *share) {
+    cl_atom_body<false>(A, moff, mol_of, q, part, nullptr, ke, seed, phi, ffix, share);
+}
+__global__ __launch_bounds__(256) void k_cl_atom_x(int A, const int *moff, const int *mol_of, const float *q, const double *part,
+                                                   const double *xpart, double ke, float *seed, float *phi, float *ffix, double *share) {
+    cl_atom_body<true>(A, moff, mol_of, q, part, xpart, ke, seed, phi, ffix, share);
 }
 
 // E_b: a molecule's shares, lane by lane in atom order, then across the lanes (the order of k_g_strain_mol)
@@ -126,4 +138,85 @@ __global__ __launch_bounds__(64) void k_cl_energy(const double *share, const int
     for (int a = moff[b] + lane; a < moff[b + 1]; a += 64) v += share[a];
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
     if (lane == 0) e_out[b] = v;
+}
+
+// ---- bonded exclusions and pair scaling (epnn_coulomb_xyz_excl, epnn_coulomb_xyz_cell_excl): a listed pair counts with weight s instead
+// of 1, so the sweep's full term stays and (s - 1) times the same term is added.  The list arrives as a CSR by atom (the host's
+// excl_build): row_off [A + 1], partner [2 P] sorted within a row, factor [2 P] = s - 1 in float32, every pair in both directions.
+#define CL_XPART 4                // sums per atom of the open correction; the periodic one has EW_PART, with the virial row
+#define CL_FLAG_ZERO 1            // flag word, bit 0: two atoms at distance 0 (the sweeps set it too)
+#define CL_FLAG_FAR 2             // bit 1: a listed pair of a cell beyond half the smallest perpendicular width
+
+// The sweep's float32 pair term, restated (k_cl_sweep itself is not touched: its bits are the plain entries' bits): from the
+// squared length r2 of the rounded displacement, kap = kappa(D) and g3 = g(alpha D) / D^3; both 0 at r2 == 0.
+template <bool ERF>
+__device__ __forceinline__ void cl_pair_term(float r2, float alpha, float &kap, float &g3) {
+    const float rinv = r2 > 0.f ? rsqrtf(r2) : 0.f;
+    float g = 1.f;
+    kap = rinv;
+    if (ERF) {
+        const float u = alpha * (r2 * rinv), e = erff(u);
+        kap = e * rinv;
+        g = cl_g(u, e);
+    }
+    g3 = g * (rinv * rinv * rinv);
+}
+
+// One atom per lane, 64 atoms per wavefront; a lane walks its CSR row in partner order.  Displacement: the float64 difference of the
+// float32 coordinates, through epnn_mic_cell when CELL, rounded once.  Sums float64: xpart [A][4] = (sum f q_j kappa, sum f q_j g dx /
+// D^3, .. dy, .. dz), f the row's factor; CELL: xpart [A][10], the six virial sums f q_j g d_a d_b / D^3 (xx yy zz yz xz xy) behind
+// them, in the order of the periodic sweep's row.  Each word is written by exactly one lane; the only atomic is the OR into the flag word.
+// cells: the batch's EpnnCell records (CELL), from which every lane takes half the smallest width, 1 / (2 max_k |g_k|).
+template <bool ERF, bool CELL>
+__global__ __launch_bounds__(64) void k_cl_excl(int A, const int *mol_of, const float *xyz, const float *q, const int *row_off, const int *partner,
+                                                const float *factor, const EpnnCell *cells, float alpha, double *xpart, int *bad) {
+    constexpr int NS = CELL ? 10 : CL_XPART;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= A) return;
+    double g[9], a[9];
+    float half_w = 0.f;
+    if (CELL) {
+        const EpnnCell &c = cells[mol_of[i]];
+        double g2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { g[k] = c.g[k]; a[k] = (double)c.a[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g2 = fmax(g2, g[3 * k] * g[3 * k] + g[3 * k + 1] * g[3 * k + 1] + g[3 * k + 2] * g[3 * k + 2]);
+        half_w = (float)(0.5 / sqrt(g2));
+    }
+    const double xi = (double)xyz[3 * (size_t)i], yi = (double)xyz[3 * (size_t)i + 1], zi = (double)xyz[3 * (size_t)i + 2];
+    double sum[NS];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) sum[c] = 0.0;
+    int flag = 0;
+    for (int k = row_off[i], k1 = row_off[i + 1]; k < k1; ++k) {
+        const size_t j = (size_t)partner[k];
+        const float fac = factor[k], qj = q[j];
+        double ex = xi - (double)xyz[3 * j], ey = yi - (double)xyz[3 * j + 1], ez = zi - (double)xyz[3 * j + 2];
+        if (CELL) epnn_mic_cell(ex, ey, ez, g, a);
+        const float dx = (float)ex, dy = (float)ey, dz = (float)ez;
+        const float r2 = dx * dx + dy * dy + dz * dz;
+        if (r2 == 0.f) flag |= CL_FLAG_ZERO;
+        if (CELL && r2 > half_w * half_w) flag |= CL_FLAG_FAR;
+        float kap, g3;
+        cl_pair_term<ERF>(r2, alpha, kap, g3);
+        const float s = qj * g3;
+        const float fx = fac * (s * dx), fy = fac * (s * dy), fz = fac * (s * dz);
+        sum[0] += (double)(fac * (qj * kap));
+        sum[1] += (double)fx;
+        sum[2] += (double)fy;
+        sum[3] += (double)fz;
+        if (CELL) {
+            sum[4] += (double)(fx * dx);
+            sum[5] += (double)(fy * dy);
+            sum[6] += (double)(fz * dz);
+            sum[7] += (double)(fy * dz);
+            sum[8] += (double)(fx * dz);
+            sum[9] += (double)(fx * dy);
+        }
+    }
+    double *o = xpart + (size_t)i * NS;
+#pragma unroll
+    for (int c = 0; c < NS; ++c) o[c] = sum[c];
+    if (flag) atomicOr(bad, flag);
 }

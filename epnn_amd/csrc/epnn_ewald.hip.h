@@ -38,6 +38,7 @@ struct EwCell {
     int pad;
 };
 static_assert(sizeof(EwCell) == 72, "EwCell is staged as 18 words");
+static_assert(EW_PART == 10, "k_cl_excl<., true> writes the ten sums of k_ew_sweep's row");
 
 // Slot s of the cell's k box -> (m0, m1, m2), k and the doubled weight 2 c(k); 0 outside the half space or the sphere (and at k = 0)
 __device__ __forceinline__ double ew_slot(const EwCell &e, const double *g, int s, int &m0, int &m1, int &m2, double &kx, double &ky, double &kz) {
@@ -189,9 +190,11 @@ __global__ __launch_bounds__(64) void k_ew_sfac(const int2 *tasks, const int *mo
 // in LDS at a time, read at a wave-uniform address): the reciprocal part of phi and ffix.  Then every atom adds its real-space pieces
 // in piece order, the self and background terms, and writes phi [A] (twice: the backward's seed and the output), ffix [A][3] and its
 // shares [A][EW_SHARE] in float64: 1/2 q_i (phi_i - its reciprocal part) and -1/2 ke q_i times its virial row.
-__global__ __launch_bounds__(64) void k_ew_atom(const int4 *tasks, int A, const float *xyz, const float *q, const EpnnCell *cells, const EwCell *ew,
-                                                const double2 *S, const float4 *rec, const double *part, double ke, float *seed, float *phi,
-                                                float *ffix, double *share) {
+// X: the listed pairs' row xpart [A][EW_PART] (k_cl_excl) is one more piece, added behind the sweep's: its virial sums take the same 1/2.
+template <bool X>
+__device__ __forceinline__ void ew_atom_body(const int4 *tasks, int A, const float *xyz, const float *q, const EpnnCell *cells, const EwCell *ew,
+                                             const double2 *S, const float4 *rec, const double *part, const double *xpart, double ke, float *seed,
+                                             float *phi, float *ffix, double *share) {
     __shared__ double tm[3][EW_TILE];
     __shared__ float4 tr[EW_TILE];
     __shared__ float2 tS[EW_TILE];
@@ -249,6 +252,9 @@ __global__ __launch_bounds__(64) void k_ew_atom(const int4 *tasks, int A, const 
     for (int k = 0; k < np; ++k)
 #pragma unroll
         for (int c = 0; c < EW_PART; ++c) s[c] += part[((size_t)k * A + i) * EW_PART + c];
+    if (X)
+#pragma unroll
+        for (int c = 0; c < EW_PART; ++c) s[c] += xpart[(size_t)i * EW_PART + c];
     const double qi = (double)q[i], Qs = S[(size_t)e.soff + (size_t)e.M1 * (2 * e.M0 + 1) + e.M0].x;
     const double local = ke * ((s[0] - e.self * qi) - e.bg * Qs), p = local + ke * pr;
     seed[i] = phi[i] = (float)p;
@@ -259,6 +265,16 @@ __global__ __launch_bounds__(64) void k_ew_atom(const int4 *tasks, int A, const 
     o[0] = 0.5 * qi * local;
 #pragma unroll
     for (int c = 0; c < 6; ++c) o[1 + c] = -0.5 * ke * qi * s[4 + c];
+}
+__global__ __launch_bounds__(64) void k_ew_atom(const int4 *tasks, int A, const float *xyz, const float *q, const EpnnCell *cells, const EwCell *ew,
+                                                const double2 *S, const float4 *rec, const double *part, double ke, float *seed, float *phi,
+                                                float *ffix, double *share) {
+    ew_atom_body<false>(tasks, A, xyz, q, cells, ew, S, rec, part, nullptr, ke, seed, phi, ffix, share);
+}
+__global__ __launch_bounds__(64) void k_ew_atom_x(const int4 *tasks, int A, const float *xyz, const float *q, const EpnnCell *cells, const EwCell *ew,
+                                                  const double2 *S, const float4 *rec, const double *part, const double *xpart, double ke,
+                                                  float *seed, float *phi, float *ffix, double *share) {
+    ew_atom_body<true>(tasks, A, xyz, q, cells, ew, S, rec, part, xpart, ke, seed, phi, ffix, share);
 }
 
 // One wavefront per cell: E = sum of the atoms' shares + E_rec and the fixed-charge strain derivative [3][3] = the atoms' virial shares

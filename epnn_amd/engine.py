@@ -87,6 +87,66 @@ class DeviceArray:
         self.ptr = None
 
 
+
+def _exclusion_lists(where, exclusions):
+    """(pairs, scale) -> the three contiguous lists of the _excl entries: int32 (P,), int32 (P,), float32 (P,)."""
+    try:
+        pairs, scale = exclusions
+    except (TypeError, ValueError):
+        raise ValueError(f"{where}: exclusions must be (pairs, scale)") from None
+    pairs = np.asarray(pairs)
+    if pairs.size == 0:
+        pairs = np.zeros((0, 2), dtype=np.int64)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+        raise ValueError(f"{where}: exclusion pairs must be an integer array of shape (P, 2), got {pairs.dtype} {pairs.shape}")
+    P = pairs.shape[0]
+    if P and (pairs.min() < -2 ** 31 or pairs.max() >= 2 ** 31):
+        raise ValueError(f"{where}: an exclusion index does not fit 32 bits")
+    scale = np.asarray(scale, dtype=np.float32)
+    if scale.ndim == 0:
+        scale = np.full((P,), scale, dtype=np.float32)
+    if scale.shape != (P,):
+        raise ValueError(f"{where}: exclusion scale must be a scalar or have shape ({P},), got {scale.shape}")
+    return (np.ascontiguousarray(pairs[:, 0], dtype=np.int32), np.ascontiguousarray(pairs[:, 1], dtype=np.int32),
+            np.ascontiguousarray(scale))
+
+
+def bonded_exclusions(bonds, n_atoms, scale12=0.0, scale13=0.0, scale14=0.5):
+    """The exclusion list of a force field from a bond list: bonds (nb, 2) int, flat atom indices below n_atoms -> (pairs (P, 2) int32,
+    scale (P,) float32) for coulomb_xyz_excl and coulomb_xyz_cell_excl.  Every pair at graph distance 1, 2 or 3 once, i < j, sorted;
+    its factor is that of its shortest path (in a ring a pair that is both 1-3 and 1-4 counts as 1-3); pairs whose factor is 1 are
+    dropped.  Pure numpy, no GPU."""
+    n = int(n_atoms)
+    bonds = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)
+    if bonds.size and (bonds.min() < 0 or bonds.max() >= n):
+        raise ValueError(f"bonded_exclusions: a bond names an atom outside [0, {n})")
+    if (bonds[:, 0] == bonds[:, 1]).any():
+        raise ValueError("bonded_exclusions: a bond from an atom to itself")
+    both = np.unique(np.concatenate([bonds, bonds[:, ::-1]]), axis=0)               # directed, duplicates gone, sorted by (i, j)
+    key = lambda p: p[:, 0] * n + p[:, 1]
+    found, frontier, out = key(both), both, []
+    for depth, factor in enumerate((scale12, scale13, scale14)):
+        fwd = frontier[frontier[:, 0] < frontier[:, 1]]
+        out.append((fwd, np.full(len(fwd), factor, dtype=np.float32)))
+        if depth == 2 or not len(frontier):
+            break
+        # one bond further from every end j: (i, k) for the bonds (j, k), less what a shorter path reached already
+        start = np.searchsorted(both[:, 0], frontier[:, 1], "left")
+        cnt = np.searchsorted(both[:, 0], frontier[:, 1], "right") - start
+        src = np.repeat(np.arange(len(frontier)), cnt)
+        idx = np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(start, cnt)
+        nxt = np.unique(np.stack([frontier[src, 0], both[idx, 1]], 1), axis=0) if len(src) else np.zeros((0, 2), dtype=np.int64)
+        nxt = nxt[(nxt[:, 0] != nxt[:, 1]) & ~np.isin(key(nxt), found)]
+        found = np.concatenate([found, key(nxt)])
+        frontier = nxt
+    pairs = np.concatenate([p for p, _ in out]) if out else np.zeros((0, 2), dtype=np.int64)
+    scale = np.concatenate([f for _, f in out]) if out else np.zeros((0,), dtype=np.float32)
+    keep = scale != 1.0
+    pairs, scale = pairs[keep], scale[keep]
+    order = np.lexsort((pairs[:, 1], pairs[:, 0]))
+    return pairs[order].astype(np.int32), scale[order]
+
+
 class Engine:
     def __init__(self, nx=9, h_dim=48, e_dim=48, T=5, hidden=32, cutoff=3.0, eta=2.0, near_tol=1e-5, device=0, fused_only=False):
         """fused_only: epnn_create_fused -- nx up to 13, and with nx > 10 only forward_xyz* on molecules of at most 64 atoms."""
@@ -447,7 +507,7 @@ class Engine:
         erf(alpha D) / D for alpha > 0 (Gaussian charges of width sigma, alpha = 1 / (2 sigma)); ke is the unit constant
         (KE_EV_ANGSTROM, the default: eV, Angstrom, e; 332.0637: kcal/mol).  parts=True appends ffix (A, 3) and fq (A, 3),
         F = ffix + fq; fq is -gxyz of charges_vjp_xyz(g=phi) on "grad_path" 2, bit for bit, and q has that path's bits.  Open
-        systems only (fully periodic cells: coulomb_xyz_cell), no self-energy term, no bonded exclusions: alpha is the only short-range handle.  One
+        systems only (fully periodic cells: coulomb_xyz_cell), no self-energy term; bonded exclusions: coulomb_xyz_excl.  One
         call costs about one gradient call of the pair-list path; it touches no training state and works without train_init."""
         offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz: array shapes do not match offsets", offsets, xyz, x, Q)
         q = np.empty((A,), dtype=np.float32)
@@ -481,8 +541,8 @@ class Engine:
         a charged cell (include/epnn.h has the sum).  ewald (6,) or (B, 6) float64: the parameters beta, rc, kc, M0, M1, M2 the
         call runs at; None: ewald_params(cell, alpha, tol) per cell.  parts=True appends ffix and fq (F = ffix + fq) and, with
         strain=True, gstrain_fix and gstrain_q behind them (gstrain = gstrain_fix + gstrain_q); fq and gstrain_q are -gxyz and gs
-        of charges_vjp_xyz(g=phi, cell=, strain=True) on "grad_path" 2, bit for bit.  Partially periodic cells, bonded exclusions
-        and PME are not built."""
+        of charges_vjp_xyz(g=phi, cell=, strain=True) on "grad_path" 2, bit for bit.  Bonded exclusions: coulomb_xyz_cell_excl.
+        Partially periodic cells and PME are not built."""
         _one_periodic_argument(box, cell)
         if box is None and cell is None:
             raise ValueError("coulomb_xyz_cell: give cell= or box= (open molecules: coulomb_xyz)")
@@ -508,6 +568,69 @@ class Engine:
         check(self.lib.epnn_coulomb_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), dptr(ewald), float(ke),
                                              float(alpha), fptr(q), fptr(phi), dptr(E), fptr(F), fptr(gs), opt(ffix), opt(fq), opt(gs_fix),
                                              opt(gs_q)), self.lib)
+        out = (q, phi, E, F) + ((gs,) if strain else ())
+        if parts:
+            out += (ffix, fq) + ((gs_fix, gs_q) if strain else ())
+        return out
+
+    def coulomb_xyz_excl(self, offsets, xyz, x, Q, N, ke=KE_EV_ANGSTROM, alpha=0.0, parts=False, exclusions=None):
+        """coulomb_xyz with bonded exclusions and pair scaling (epnn_coulomb_xyz_excl).  exclusions=None is coulomb_xyz itself, the
+        plain entry; otherwise (pairs, scale): pairs an int array (P, 2) of flat atom indices, each unordered pair once, scale a
+        scalar or (P,).  A listed pair counts with weight scale instead of 1 in phi, E and ffix (0 excludes, 0.5 or 0.8333 scales),
+        and phi with these weights seeds fq.  bonded_exclusions(bonds, n_atoms) makes the list from a bond list.  The outputs do
+        not depend on the order of the list; refused by name: an index out of range, i == j, atoms of two molecules, a pair listed
+        twice, a factor that is not finite."""
+        if exclusions is None:
+            return self.coulomb_xyz(offsets, xyz, x, Q, N, ke=ke, alpha=alpha, parts=parts)
+        offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz_excl: array shapes do not match offsets", offsets, xyz, x, Q)
+        ei, ej, es = _exclusion_lists("coulomb_xyz_excl", exclusions)
+        q = np.empty((A,), dtype=np.float32)
+        phi = np.empty((A,), dtype=np.float32)
+        E = np.empty((B,), dtype=np.float64)
+        F = np.empty((A, 3), dtype=np.float32)
+        ffix = np.empty((A, 3), dtype=np.float32) if parts else None
+        fq = np.empty((A, 3), dtype=np.float32) if parts else None
+        opt = lambda a: None if a is None else fptr(a)
+        check(self.lib.epnn_coulomb_xyz_excl(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), float(ke), float(alpha), len(es),
+                                             iptr(ei), iptr(ej), fptr(es), fptr(q), fptr(phi), E.ctypes.data_as(C.POINTER(C.c_double)), fptr(F),
+                                             opt(ffix), opt(fq)), self.lib)
+        return (q, phi, E, F, ffix, fq) if parts else (q, phi, E, F)
+
+    def coulomb_xyz_cell_excl(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None, parts=False,
+                              strain=False, exclusions=None):
+        """coulomb_xyz_cell with bonded exclusions and pair scaling (epnn_coulomb_xyz_cell_excl).  exclusions=None is coulomb_xyz_cell
+        itself; otherwise (pairs, scale) as in coulomb_xyz_excl.  The Ewald sum runs over all pairs and images as before; the one
+        nearest image of every listed pair is corrected by (scale - 1) times its bare term, whatever beta, rc and kc are.  A listed
+        pair farther apart than half the smallest perpendicular width of its cell is refused by name."""
+        if exclusions is None:
+            return self.coulomb_xyz_cell(offsets, xyz, x, Q, N, cell=cell, box=box, ke=ke, alpha=alpha, tol=tol, ewald=ewald, parts=parts,
+                                         strain=strain)
+        _one_periodic_argument(box, cell)
+        if box is None and cell is None:
+            raise ValueError("coulomb_xyz_cell_excl: give cell= or box= (open molecules: coulomb_xyz_excl)")
+        offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz_cell_excl: array shapes do not match offsets", offsets, xyz, x, Q)
+        _, cell = _geometry(box, cell, B, cells_only=True)
+        if ewald is None:
+            ewald = np.stack([self.ewald_params(cell[b], alpha, tol) for b in range(B)])
+        ewald = np.asarray(ewald, dtype=np.float64)
+        if ewald.shape == (6,):
+            ewald = np.tile(ewald, (B, 1))
+        if ewald.shape != (B, 6):
+            raise ValueError(f"coulomb_xyz_cell_excl: ewald must have shape (6,) or ({B}, 6), got {ewald.shape}")
+        ewald = np.ascontiguousarray(ewald)
+        ei, ej, es = _exclusion_lists("coulomb_xyz_cell_excl", exclusions)
+        dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        q = np.empty((A,), dtype=np.float32)
+        phi = np.empty((A,), dtype=np.float32)
+        E = np.empty((B,), dtype=np.float64)
+        F = np.empty((A, 3), dtype=np.float32)
+        gs = np.empty((B, 3, 3), dtype=np.float32)
+        ffix, fq = (np.empty((A, 3), dtype=np.float32) if parts else None for _ in range(2))
+        gs_fix, gs_q = (np.empty((B, 3, 3), dtype=np.float32) if parts else None for _ in range(2))
+        opt = lambda a: None if a is None else fptr(a)
+        check(self.lib.epnn_coulomb_xyz_cell_excl(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), dptr(ewald), float(ke),
+                                                  float(alpha), len(es), iptr(ei), iptr(ej), fptr(es), fptr(q), fptr(phi), dptr(E), fptr(F),
+                                                  fptr(gs), opt(ffix), opt(fq), opt(gs_fix), opt(gs_q)), self.lib)
         out = (q, phi, E, F) + ((gs,) if strain else ())
         if parts:
             out += (ffix, fq) + ((gs_fix, gs_q) if strain else ())

@@ -404,8 +404,8 @@ int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t 
  * ke is the caller's unit constant (14.3996454784255 eV A / e^2, 332.0637 kcal A / mol e^2).  q is the model's output, so sum q = Q
  * holds by construction and no constraint term appears.  Open systems only: the entry takes no box or cell (fully periodic cells:
  * epnn_coulomb_xyz_cell below, an Ewald sum; partially periodic cells are not built).  No self-energy term (for alpha > 0 the
- * Gaussians' self-energy -ke alpha / sqrt(pi) sum q_i^2 is left out; it depends on q alone), no bonded exclusions or scaling of
- * near neighbours: every pair of a molecule counts in full, and alpha is the only short-range handle.
+ * Gaussians' self-energy -ke alpha / sqrt(pi) sum q_i^2 is left out; it depends on q alone).  Every pair of a molecule counts in full
+ * here; bonded exclusions and the scaling of near neighbours: epnn_coulomb_xyz_excl below.
  * Outputs (host): q_out[A], phi_out[A], e_out[B] in float64 (a float32 energy of a 100 000-atom system loses the digits its forces
  * live in), f_out[A][3]; ffix_out[A][3] and fq_out[A][3] may each be NULL, and the other outputs have the same bits either way.
  * Contract: that of epnn_charges_jvp_xyz_cell, word for word where it applies: the pair-list path whatever "grad_path" says; works
@@ -478,12 +478,52 @@ int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const
  * (tests/test_gpu_coulomb_cell.py counts the roundings; measured: 0.03 of that at worst).
  * Device scratch on top of the gradient path's: A (20 + 80 cpieces + 56) + 44 B + 32 slots + the task tables and 72 B of
  * parameters; slots = the batch's k slots, about 3600 for a cube at tol = 1e-6 whatever its size.  Nothing of size n nk or n^2.
- * Still missing: partially periodic cells, bonded exclusions, PME for very large cells. */
+ * Still missing: partially periodic cells, PME for very large cells (bonded exclusions: epnn_coulomb_xyz_cell_excl below). */
 int epnn_ewald_params(const float *cell, double alpha, double tol, double *out);
 int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                           const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
                           double *e_out, float *f_out, float *gstrain_out, float *ffix_out, float *fq_out,
                           float *gstrain_fix_out, float *gstrain_q_out);
+/* ---- bonded exclusions and pair scaling for the two calls above ("Electrostatics in one call": a water box with
+ * bonded_exclusions).  Every classical force field removes the 1-2 and 1-3 Coulomb terms and scales 1-4; a correction applied by
+ * the caller afterwards would leave fq and the charges' part of the strain wrong, because phi is the backward's seed on the device.
+ * The list: npairs unordered pairs (ex_i[p], ex_j[p]) of flat atom indices with a factor ex_scale[p] (host).  A listed pair interacts
+ * with weight s_p instead of 1: 0 excludes, 0.5 or 0.8333 scales, 1 changes nothing.  With w_ij = s_p for listed pairs and 1 otherwise:
+ *     open       phi_i  = ke sum_{j != i} w_ij q_j kappa(D_ij) = dE/dq_i (w is symmetric);   E_b = 1/2 sum_i q_i phi_i
+ *                ffix_i = -ke q_i sum_{j != i} w_ij q_j kappa'(D_ij) (r_i - r_j) / D_ij;      fq, f as above, with this phi as the seed
+ *     periodic   the Ewald sum of epnn_coulomb_xyz_cell over all pairs and images exactly as there, plus, for the one image d of each
+ *                listed pair that the cell's rounding rule returns (D = |d|), with the bare kappa_alpha = e_alpha(D) / D (no beta):
+ *                phi_i += ke (s - 1) q_j kappa_alpha(D);   ffix_i -= ke (s - 1) q_i q_j kappa_alpha'(D) d / D;
+ *                gstrain_fix += ke (s - 1) q_i q_j kappa_alpha'(D) d_a d_b / D, once per listed pair;   E = 1/2 sum q_i phi_i.
+ *                The correction is the same whatever beta, rc and kc are, and it is there when rc == 0 and the sweep is skipped.
+ * Contract: that of the entry each extends, word for word, plus: npairs == 0 is allowed (the three list pointers may then be NULL)
+ * and gives the bits of the plain entry on every output; so does a list whose factors are all 1 (the correction adds exact zeros to
+ * float64 sums); the outputs depend neither on the order of the list nor on which atom of a pair is named first (the host sorts the
+ * list into a CSR by atom: every pair in both directions, every row by partner index); a molecule's rows depend neither on the rest
+ * of the batch nor on the other molecules' pairs.  Refused by name, each message with the pair's position in the list, the handle
+ * stays usable: npairs < 0 or 2 npairs > 2^31 - 1; a NULL list with npairs > 0; an index outside [0, A); i == j; the two atoms in
+ * different molecules; a pair listed twice, in either order; a factor that is not finite; and, in the periodic entry after the device
+ * pass, a listed pair farther apart than half the smallest perpendicular width of its cell (beyond it the rounding rule no longer
+ * returns the nearest image; bonded atoms are never that far apart).
+ * Bits: q_out has the bits of the plain entry; fq_out and gstrain_q_out are bit for bit -gxyz_out and gstrain_out of
+ * epnn_charges_vjp_xyz[_cell] on "grad_path" 2 called with g = phi_out; f = ffix + fq and gstrain = gstrain_fix + gstrain_q in float32.
+ * Arithmetic: one kernel more, an atom per lane walking its CSR row in partner order; the pair term is the open sweep's float32 term
+ * (float64 displacement, through the cell's minimum image in the periodic entry, rounded once; one reciprocal square root; erff and
+ * g for alpha > 0) times the float32 factor s - 1, summed in float64 into one row per atom, which the atoms' kernel adds as one more
+ * piece behind the sweep's.  The plain entries keep their kernels, paths, bits and scratch.
+ * Accuracy: phi, ffix, E and the fixed-charge strain are each within 2e-6 of the sum of the absolute values of the terms actually
+ * added: the all-pairs (or real-space) terms AND the listed pairs' correction terms |(s - 1) term| -- an excluded pair's full term is
+ * added by the sweep and taken away by the correction, so both count in the yardstick -- plus 34 * 2^-24 of the absolute reciprocal
+ * terms in the periodic entry.  A correction term has the sweep's roundings and one multiply by the factor, about 11 * 2^-24.
+ * Device scratch (epnn_last_stats out[2]) on top of the plain entry's, with P = npairs: the staged CSR and the correction's rows,
+ *     open      (A + 1) 4 + 16 P + 32 A          periodic  (A + 1) 4 + 16 P + 80 A          (two buffers: plus up to 256 of rounding each) */
+int epnn_coulomb_xyz_excl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                          double ke, double alpha, int64_t npairs, const int32_t *ex_i, const int32_t *ex_j, const float *ex_scale,
+                          float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out, float *fq_out);
+int epnn_coulomb_xyz_cell_excl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                               const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
+                               const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
+                               float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out);
 /* ---- training on periodic and large systems. epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
  * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
  * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's

@@ -17,7 +17,14 @@ kernels.
 is the periodic call coulomb_xyz_cell beside charges_vjp_xyz(cell=, strain=True) of the same system (profiles/r17_coulomb_cell.txt):
 1024 QM9-sized cells of 6 A, a 10 000-atom and a 100 000-atom cubic cell (synth.periodic_box_system).  The same alternation and
 windows; printed besides: the k slots of the batch, and the checks q (bits), fq and gstrain_q against the gradient call seeded with
-phi (bits), sum_i f_i.  With --trace: three calls of coulomb_xyz_cell per system (the k_ew_* rows are the Ewald kernels)."""
+phi (bits), sum_i f_i.  With --trace: three calls of coulomb_xyz_cell per system (the k_ew_* rows are the Ewald kernels).
+    python tools/bench_coulomb.py --excl [--cell] [--systems ...] [--rounds 5] [--alpha 0.0] [--near 2.2] [--trace]
+is the call with bonded exclusions, coulomb_xyz_excl or coulomb_xyz_cell_excl, beside the plain call of the same batch
+(profiles/r18_coulomb_excl.txt).  The list: every pair of a molecule with (minimum-image) D < --near, factors cycling through 0, 0.5,
+0.8333 in sorted pair order, handed over shuffled with half of the rows swapped -- a few pairs per atom.  Printed per system: the two
+medians and their ratio, pairs per atom, the scratch the list adds beside the formula of include/epnn.h, and the checks q (bits
+against the plain call) and fq against -gxyz of the gradient call seeded with phi (bits).  With --trace: three calls of the _excl
+entry per system (the k_cl_excl row is the new kernel)."""
 import json
 import os
 import sys
@@ -104,6 +111,80 @@ def load_cell(system):
     raise SystemExit(f"unknown system {system}")
 
 
+def exclusion_list(offsets, xyz, cells, near):
+    """Every pair of a molecule nearer than `near` (minimum image in a cubic cell), factors cycling in sorted order; shuffled."""
+    from scipy.spatial import cKDTree
+    out = []
+    for b in range(len(offsets) - 1):
+        a0, a1 = int(offsets[b]), int(offsets[b + 1])
+        if a1 - a0 < 2:
+            continue
+        r = xyz[a0:a1].astype(np.float64)
+        if cells is None:
+            tree = cKDTree(r)
+        else:
+            L = float(cells[b][0, 0])
+            assert np.array_equal(cells[b], np.diag([cells[b][0, 0]] * 3)), "the list maker takes cubic cells"
+            tree = cKDTree(r - L * np.floor(r / L), boxsize=L)
+        p = tree.query_pairs(near, output_type="ndarray")
+        if len(p):
+            out.append(np.sort(p, 1) + a0)
+    pairs = np.concatenate(out) if out else np.zeros((0, 2), np.int64)
+    pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]
+    scale = np.float32([0.0, 0.5, 0.8333])[np.arange(len(pairs)) % 3]
+    rng = np.random.default_rng(11)
+    o = rng.permutation(len(pairs))
+    pairs, scale = pairs[o], scale[o]
+    swap = rng.permutation(len(pairs))[:len(pairs) // 2]
+    pairs[swap] = pairs[swap][:, ::-1]
+    return np.ascontiguousarray(pairs.astype(np.int32)), scale
+
+
+def main_excl(eng, systems, rounds, alpha, tol, near, cell_mode):
+    for system in systems:
+        if cell_mode:
+            name, offsets, xyz, x, Q, N, cells = load_cell(system)
+            rows = np.stack([eng.ewald_params(c, alpha, tol) for c in cells])
+            kw = dict(cell=cells, alpha=alpha, ewald=rows, parts=True, strain=True)
+            plain_fn, excl_fn = eng.coulomb_xyz_cell, eng.coulomb_xyz_cell_excl
+        else:
+            name, offsets, xyz, x, Q, N = load(system)
+            cells, kw = None, dict(alpha=alpha, parts=True)
+            plain_fn, excl_fn = eng.coulomb_xyz, eng.coulomb_xyz_excl
+        A = int(offsets[-1])
+        ex = exclusion_list(offsets, xyz, cells, near)
+        P = len(ex[0])
+        if "--trace" in sys.argv:
+            for _ in range(3):
+                excl_fn(offsets, xyz, x, Q, N, exclusions=ex, **kw)
+            print(json.dumps({"workload": name, "atoms": A, "calls": 3, "alpha": alpha, "listed_pairs": P}), flush=True)
+            continue
+        calls = {"plain": lambda: plain_fn(offsets, xyz, x, Q, N, **kw), "excl": lambda: excl_fn(offsets, xyz, x, Q, N, exclusions=ex, **kw)}
+        for fn in calls.values():
+            fn()
+        times = {k: [] for k in calls}
+        outs, stats = {}, {}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t, outs[k] = window(fn)
+                stats[k] = eng.last_stats()
+                times[k].append(t * 1e3)
+        phi, fq = outs["excl"][1], outs["excl"][6 if cell_mode else 5]
+        seeded = eng.charges_vjp_xyz(offsets, xyz, x, Q, phi, N, **({"cell": cells, "strain": True} if cell_mode else {}))
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        line = {"workload": name, "atoms": A, "listed_pairs": P, "pairs_per_atom": round(P / A, 2), "near": near, "rounds": rounds, "alpha": alpha}
+        for k, t in times.items():
+            line[k + "_ms_median"] = round(med[k], 3)
+            line[k + "_ms_range"] = [round(min(t), 3), round(max(t), 3)]
+        line.update({"excl_over_plain": round(med["excl"] / med["plain"], 4), "scratch_bytes_added": int(stats["excl"][2]) - int(stats["plain"][2]),
+                     "scratch_formula_added": (A + 1) * 4 + 16 * P + A * (80 if cell_mode else 32),
+                     "q_bits_equal_plain_call": bool(np.array_equal(outs["excl"][0], outs["plain"][0])),
+                     "fq_bits_equal_minus_gxyz_of_phi": bool(np.array_equal(fq, -seeded[1])),
+                     "max_abs_phi_plain": float(np.abs(outs["plain"][1]).max()), "max_abs_phi_excl": float(np.abs(phi).max()),
+                     "energy_sum_plain": float(outs["plain"][2].sum()), "energy_sum_excl": float(outs["excl"][2].sum())})
+        print(json.dumps(line), flush=True)
+
+
 def main_cell(eng, T, systems, rounds, alpha, tol):
     for system in systems:
         name, offsets, xyz, x, Q, N, cells = load_cell(system)
@@ -156,6 +237,10 @@ def main():
     eng = Engine(nx=9, T=T)
     eng.set_weights(w)
     eng.set_option("grad_path", 2)
+    if "--excl" in sys.argv:
+        main_excl(eng, systems, rounds, alpha, float(arg("--tol", "1e-6")), float(arg("--near", "2.2")), cell_mode)
+        eng.close()
+        return
     if cell_mode:
         main_cell(eng, T, systems, rounds, alpha, float(arg("--tol", "1e-6")))
         eng.close()
