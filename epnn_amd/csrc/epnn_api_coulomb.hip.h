@@ -1,6 +1,6 @@
-// epnn_coulomb_xyz: charges, electrostatic potential, Coulomb energy and total forces of a flat coordinate batch in one call
-// (kernels: epnn_coulomb.hip.h).  The pair-list gradient call (epnn_api_grad.hip.h) with its seed made on the device: set-up and
-// checkpointed forward, the Coulomb sweep on that forward's charges (phi = dE/dq into the seed), the shared backward, one download.
+// epnn_coulomb_xyz and epnn_coulomb_xyz_excl: charges, electrostatic potential, Coulomb energy and total forces of a flat coordinate
+// batch in one call (kernels: epnn_coulomb.hip.h).  Here: the sweep's task table, the exclusion list's validator and CSR, and the two
+// open entries; the driver they share with the periodic entries, coulomb_run, is defined in epnn_api_coulomb_cell.hip.h.
 // Part of the one translation unit epnn_api.hip.
 #pragma once
 #include "epnn_api_grad.hip.h"
@@ -49,16 +49,6 @@ struct ExclCsr {
 static size_t excl_csr_bytes(int A, int64_t P) { return ((size_t)A + 1) * 4 + 16 * (size_t)P; }
 static size_t excl_xpart_bytes(int A, bool cell) { return (size_t)A * (cell ? 10 : CL_XPART) * 8; }      // (10: EW_PART, asserted in epnn_ewald.hip.h)
 
-// (the library is built with -ffinite-math-only: the factor's bits are read back from a volatile word, as ew_finite does)
-static bool excl_finite(float v) {
-    volatile uint32_t seen;
-    uint32_t bits;
-    memcpy(&bits, &v, 4);
-    seen = bits;
-    bits = seen;
-    return (bits & 0x7f800000u) != 0x7f800000u;
-}
-
 // Refused by name, each with the pair's position in the list: a bad count, a NULL list, an index outside [0, A), i == j, atoms of two
 // molecules, a factor that is not finite, a pair listed twice (in either order).  offsets are already checked.
 static int excl_build(const char *name, int B, const int32_t *offsets, int64_t npairs, const int32_t *ex_i, const int32_t *ex_j,
@@ -84,7 +74,7 @@ static int excl_build(const char *name, int B, const int32_t *offsets, int64_t n
         if (mol_of[i] != mol_of[j])
             EPNN_FAIL("%s: exclusion pair %lld = (%d, %d): the atoms are in different molecules (%d and %d)", name, (long long)p, i, j, mol_of[i],
                       mol_of[j]);
-        if (!excl_finite(ex_scale[p])) EPNN_FAIL("%s: exclusion pair %lld = (%d, %d): its factor is not finite", name, (long long)p, i, j);
+        if (!epnn_finite(ex_scale[p])) EPNN_FAIL("%s: exclusion pair %lld = (%d, %d): its factor is not finite", name, (long long)p, i, j);
         ++row_off[i + 1];
         ++row_off[j + 1];
     }
@@ -112,126 +102,51 @@ static int excl_build(const char *name, int B, const int32_t *offsets, int64_t n
         }
     return 0;
 }
-// the correction's launch: one lane per atom (k_cl_excl), on the stream, behind the sweep
-template <bool CELL>
+// the correction's launch: one lane per atom (k_cl_excl), on the stream, behind the sweep; d_cells: the periodic entries' cells, or NULL
 static void excl_launch(epnn_handle *h, const GlCall &c, const char *d_csr, const ExclCsr &ex, const float *q_dev, const EpnnCell *d_cells,
                         double alpha, double *xpart, int *hit) {
     const int A = ex.A;
     const int *row_off = reinterpret_cast<const int *>(d_csr), *partner = reinterpret_cast<const int *>(d_csr + ex.o_partner());
     const float *factor = reinterpret_cast<const float *>(d_csr + ex.o_factor());
-    const dim3 grid((unsigned)((A + 63) / 64));
-    if (alpha > 0.0)
-        hipLaunchKernelGGL((k_cl_excl<true, CELL>), grid, dim3(64), 0, h->stream, A, c.d_molof, c.d_xyz, q_dev, row_off, partner, factor, d_cells,
-                           (float)alpha, xpart, hit);
-    else
-        hipLaunchKernelGGL((k_cl_excl<false, CELL>), grid, dim3(64), 0, h->stream, A, c.d_molof, c.d_xyz, q_dev, row_off, partner, factor, d_cells,
-                           0.f, xpart, hit);
+    auto *kern = d_cells ? (alpha > 0.0 ? k_cl_excl<true, true> : k_cl_excl<false, true>)
+                         : (alpha > 0.0 ? k_cl_excl<true, false> : k_cl_excl<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((A + 63) / 64)), dim3(64), 0, h->stream, A, c.d_molof, c.d_xyz, q_dev, row_off, partner, factor,
+                       d_cells, (float)alpha, xpart, hit);
 }
 
-static int coulomb_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                        const float *Q, const HostGeo &geo, double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
-                        float *fq_out, const ExclCsr *ex = nullptr) {
-    GradLarge *gl = grad_large_state(h);
-    if (grad_large_weights(h, gl)) return 1;
-    const int T = h->cfg.T, A = offsets[B];
-    std::vector<int4> tasks;
-    const size_t cpieces = (size_t)cl_build_tasks(B, offsets, tasks);
-    const GlSpan span_t{tasks.data(), tasks.size() * sizeof(int4), false};
-    // [A] phi | [A][3] ffix | flag, then [B] E in float64: directly behind the backward's output block, one download for both;
-    // the sweep's partial rows [pieces][A][4] and the atoms' energy shares [A], float64
-    const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), co_bytes = o_E + (size_t)B * 8;
-    // (the _excl entry: the CSR is one more span beside the task table, the correction's rows [A][4] one more buffer behind the others)
-    const GlSpan spans[2] = {span_t, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false}};
-    const size_t more[3] = {co_bytes, (cpieces * 4 + 1) * (size_t)A * 8, ex ? excl_xpart_bytes(A, false) : 0};
-    GlGrad r;
-    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
-    const GlCall &c = r.c;
-    char *co = c.dw + r.o_more[0];
-    float *phi = reinterpret_cast<float *>(co), *ffix = phi + A;
-    int *hit = reinterpret_cast<int *>(phi + 4 * (size_t)A);
-    double *E = reinterpret_cast<double *>(co + o_E), *part = reinterpret_cast<double *>(c.dw + r.o_more[1]),
-           *share = part + cpieces * 4 * (size_t)A;
-    const float *q_dev = r.qck + (size_t)T * A;
-    const int4 *d_ctasks = reinterpret_cast<const int4 *>(c.d_extra[0]);
-    // ---- the Coulomb sweep on the forward's own charges: phi is the backward's seed
-    HIPCHK(hipMemsetAsync(hit, 0, 4, h->stream));
-    if (alpha > 0.0)
-        hipLaunchKernelGGL(k_cl_sweep<true>, dim3((unsigned)tasks.size()), dim3(64), 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev,
-                           A, (float)alpha, part, hit);
-    else
-        hipLaunchKernelGGL(k_cl_sweep<false>, dim3((unsigned)tasks.size()), dim3(64), 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev,
-                           A, 0.f, part, hit);
-    if (ex) {
-        double *xpart = reinterpret_cast<double *>(c.dw + r.o_more[2]);
-        excl_launch<false>(h, c, reinterpret_cast<const char *>(c.d_extra[1]), *ex, q_dev, nullptr, alpha, xpart, hit);
-        hipLaunchKernelGGL(k_cl_atom_x, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, (const double *)part,
-                           (const double *)xpart, ke, r.gq, phi, ffix, share);
-    } else
-        hipLaunchKernelGGL(k_cl_atom, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, (const double *)part, ke, r.gq, phi, ffix,
-                           share);
-    hipLaunchKernelGGL(k_cl_energy, dim3((unsigned)B), dim3(64), 0, h->stream, (const double *)share, c.d_moff, E);
-    HIPCHK(hipGetLastError());
-    if (gl_grad_backward(h, gl, r, B, false)) return 1;
-    // ---- one download: q | gxyz | flag | (the unused strain rows and the step to the next buffer) | phi | ffix | flag | E
-    const char *from = reinterpret_cast<const char *>(r.q_fin);
-    const size_t nbytes = (size_t)(co + co_bytes - from), at_co = (size_t)(co - from);
-    if (gl->pin_out.ensure(nbytes)) return 1;
-    char *back = gl->pin_out.as<char>();
-    HIPCHK(hipMemcpyAsync(back, from, nbytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const float *bq = reinterpret_cast<const float *>(back), *bgx = bq + A, *bphi = reinterpret_cast<const float *>(back + at_co),
-                *bffix = bphi + A;
-    const int flag = reinterpret_cast<const int *>(bq)[4 * (size_t)A], chit = reinterpret_cast<const int *>(bphi)[4 * (size_t)A];
-    if (flag & 2) EPNN_FAIL("%s: the pair list is not symmetric", name);
-    if (flag != 0 || chit != 0) EPNN_FAIL("%s: two atoms of a molecule coincide (distance 0: neither the Coulomb terms nor the edge features have a derivative there)", name);
-    memcpy(q_out, bq, (size_t)A * 4);
-    memcpy(phi_out, bphi, (size_t)A * 4);
-    memcpy(e_out, back + at_co + o_E, (size_t)B * 8);
-    for (size_t k = 0; k < 3 * (size_t)A; ++k) {
-        const float fq = -bgx[k];
-        f_out[k] = bffix[k] + fq;
-        if (fq_out) fq_out[k] = fq;
-    }
-    if (ffix_out) memcpy(ffix_out, bffix, (size_t)A * 12);
-    return 0;
-}
-
-// what an _excl entry adds to its plain entry's arguments
+// what an _excl entry adds to its plain entry's arguments, and the outputs of the four entries (the strain rows: the periodic ones only)
 struct ExclArgs { int64_t npairs; const int32_t *i, *j; const float *scale; };
+struct CoulombOut { float *q, *phi; double *e; float *f, *ffix, *fq, *gs, *gs_fix, *gs_q; };
+
+// The one driver behind the four entries, defined in epnn_api_coulomb_cell.hip.h, where the periodic part is known; the open entries
+// hand it none, and then it stages no cell parameters, launches no Ewald kernel and allocates no strain rows.
+struct CoulombPeriodic;
+static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                       const HostGeo &geo, double ke, double alpha, CoulombPeriodic *per, const ExclCsr *ex, const CoulombOut &out);
 
 static int coulomb_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                         double ke, double alpha, const ExclArgs *xa, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
-                         float *fq_out) {
-    if (!phi_out || !e_out) EPNN_FAIL("%s: null argument", name);
-    // (the library is built with -ffinite-math-only: std::isfinite would fold to true, and so would a test of an argument's own
-    //  bits -- the tests below read them back from volatile words, of which the compiler assumes nothing)
-    volatile uint64_t seen[2];
-    uint64_t kbits, abits;
-    memcpy(&kbits, &ke, 8);
-    memcpy(&abits, &alpha, 8);
-    seen[0] = kbits; seen[1] = abits;
-    kbits = seen[0]; abits = seen[1];
-    const uint64_t expo = 0x7ff0000000000000ull;
-    if ((kbits & expo) == expo) EPNN_FAIL("%s: ke must be finite", name);
-    if ((abits & expo) == expo || ((abits >> 63) && (abits << 1)))
-        EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
+                         double ke, double alpha, const ExclArgs *xa, const CoulombOut &out) {
+    if (!out.phi || !out.e) EPNN_FAIL("%s: null argument", name);
+    if (!epnn_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
+    if (!epnn_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
     GeoArg arg;                                                  // (open molecules: the entry takes no cell)
-    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, nullptr, 1, q_out, f_out, arg)) return 1;
-    if (!xa) return coulomb_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
+    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, nullptr, 1, out.q, out.f, arg)) return 1;
     ExclCsr ex;
-    if (excl_build(name, B, offsets, xa->npairs, xa->i, xa->j, xa->scale, ex)) return 1;
-    return coulomb_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, q_out, phi_out, e_out, f_out, ffix_out, fq_out, &ex);
+    if (xa && excl_build(name, B, offsets, xa->npairs, xa->i, xa->j, xa->scale, ex)) return 1;
+    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, nullptr, xa ? &ex : nullptr, out);
 }
 
 extern "C" int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                 double ke, double alpha, float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out,
                                 float *fq_out) {
-    return coulomb_enter(h, "epnn_coulomb_xyz", B, N, offsets, xyz, x, Q, ke, alpha, nullptr, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
+    return coulomb_enter(h, "epnn_coulomb_xyz", B, N, offsets, xyz, x, Q, ke, alpha, nullptr,
+                         CoulombOut{q_out, phi_out, e_out, f_out, ffix_out, fq_out, nullptr, nullptr, nullptr});
 }
 
 extern "C" int epnn_coulomb_xyz_excl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                      double ke, double alpha, int64_t npairs, const int32_t *ex_i, const int32_t *ex_j, const float *ex_scale,
                                      float *q_out, float *phi_out, double *e_out, float *f_out, float *ffix_out, float *fq_out) {
     const ExclArgs xa{npairs, ex_i, ex_j, ex_scale};
-    return coulomb_enter(h, "epnn_coulomb_xyz_excl", B, N, offsets, xyz, x, Q, ke, alpha, &xa, q_out, phi_out, e_out, f_out, ffix_out, fq_out);
+    return coulomb_enter(h, "epnn_coulomb_xyz_excl", B, N, offsets, xyz, x, Q, ke, alpha, &xa,
+                         CoulombOut{q_out, phi_out, e_out, f_out, ffix_out, fq_out, nullptr, nullptr, nullptr});
 }

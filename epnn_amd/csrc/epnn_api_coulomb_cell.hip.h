@@ -1,21 +1,10 @@
-// epnn_coulomb_xyz_cell: epnn_coulomb_xyz in fully periodic cells, by an Ewald sum (kernels: epnn_ewald.hip.h), and epnn_ewald_params,
-// the host-only rule that chooses the sum's parameters.  The pair-list gradient call in GEO_CELL geometry with its strain rows and
-// its seed made on the device: set-up and checkpointed forward, the Ewald kernels on that forward's charges (phi = dE/dq into the
-// seed), the shared backward, one download.  A driver of its own: epnn_coulomb_xyz keeps its path, bits and scratch.
+// epnn_coulomb_xyz_cell and epnn_coulomb_xyz_cell_excl: epnn_coulomb_xyz in fully periodic cells, by an Ewald sum (kernels:
+// epnn_ewald.hip.h); epnn_ewald_params, the host-only rule that chooses the sum's parameters; and coulomb_run, the driver of all four
+// Coulomb entries, which needs both kernel files.  The open entries reach it without a periodic part and keep their path, bits and scratch.
 // Part of the one translation unit epnn_api.hip.
 #pragma once
 #include "epnn_api_coulomb.hip.h"
 #include "epnn_ewald.hip.h"
-
-// (the library is built with -ffinite-math-only: a test of a value's own bits would fold away; they are read back from a volatile word)
-static bool ew_finite(double v) {
-    volatile uint64_t seen;
-    uint64_t bits;
-    memcpy(&bits, &v, 8);
-    seen = bits;
-    bits = seen;
-    return (bits & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
 
 // What the rule and the entry's checks need of one cell [3][3], in float64: |a_k|, the perpendicular widths |det| / |a_k+1 x a_k+2|,
 // the smallest of them and the volume.  Refused in the style of check_cell: an entry that is not finite, an open axis, dependent rows.
@@ -24,7 +13,7 @@ static int ew_cell_geom(const char *what, int b, const float *cell, EwGeom &o) {
     double a[3][3];
     for (int k = 0; k < 3; ++k) {
         for (int x = 0; x < 3; ++x) {
-            if (!ew_finite((double)cell[3 * k + x])) EPNN_FAIL("%s: cell[%d][%d][%d] is not finite (molecule %d, axis %d)", what, b, k, x, b, k);
+            if (!epnn_finite(cell[3 * k + x])) EPNN_FAIL("%s: cell[%d][%d][%d] is not finite (molecule %d, axis %d)", what, b, k, x, b, k);
             a[k][x] = (double)cell[3 * k + x];
         }
         o.len[k] = sqrt(a[k][0] * a[k][0] + a[k][1] * a[k][1] + a[k][2] * a[k][2]);
@@ -76,8 +65,8 @@ static int ew_rule(const char *what, int b, const float *cell, double alpha, dou
 extern "C" int epnn_ewald_params(const float *cell, double alpha, double tol, double *out) {
     const char *name = "epnn_ewald_params";
     if (!cell || !out) EPNN_FAIL("%s: null argument", name);
-    if (!ew_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
-    if (!ew_finite(tol) || !(tol > 0.0 && tol < 1.0)) EPNN_FAIL("%s: tol must be finite and inside (0, 1)", name);
+    if (!epnn_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
+    if (!epnn_finite(tol) || !(tol > 0.0 && tol < 1.0)) EPNN_FAIL("%s: tol must be finite and inside (0, 1)", name);
     return ew_rule(name, 0, cell, alpha, tol, out);
 }
 
@@ -86,7 +75,7 @@ static int ew_cell_row(const char *what, int b, const float *cell, const double 
     EwGeom G;
     if (ew_cell_geom(what, b, cell, G)) return 1;
     for (int k = 0; k < 6; ++k)
-        if (!ew_finite(row[k])) EPNN_FAIL("%s: ewald[%d][%d] is not finite", what, b, k);
+        if (!epnn_finite(row[k])) EPNN_FAIL("%s: ewald[%d][%d] is not finite", what, b, k);
     const double beta = row[0], rc = row[1], kc = row[2], *M = row + 3;
     if (!(beta > 0.0)) EPNN_FAIL("%s: ewald[%d]: beta = %g must be positive", what, b, beta);
     if (!(kc >= 0.0)) EPNN_FAIL("%s: ewald[%d]: kc = %g must not be negative", what, b, kc);
@@ -155,35 +144,49 @@ static int excl_name_far(const char *name, const int32_t *offsets, const float *
     EPNN_FAIL("%s: an exclusion pair lies beyond half the smallest perpendicular width of its cell", name);
 }
 
-static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                             const float *Q, const HostGeo &geo, std::vector<EwCell> &ew, double ke, double alpha, float *q_out, float *phi_out,
-                             double *e_out, float *f_out, float *gs_out, float *ffix_out, float *fq_out, float *gsfix_out, float *gsq_out,
-                             const ExclCsr *ex = nullptr, const ExclArgs *xa = nullptr) {
+// what a periodic entry adds to the driver's arguments: the cells' checked parameters, and the caller's list for excl_name_far
+struct CoulombPeriodic {
+    std::vector<EwCell> ew;
+    const ExclArgs *xa;
+};
+
+// The driver of the four entries: the pair-list gradient call with its seed made on the device.  Set-up and checkpointed forward; on
+// that forward's charges the sweep (per: the Ewald sum), the listed pairs' correction (ex) and the energy, phi = dE/dq into the
+// seed; the shared backward; one download.
+static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                       const HostGeo &geo, double ke, double alpha, CoulombPeriodic *per, const ExclCsr *ex, const CoulombOut &out) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
     const int T = h->cfg.T, A = offsets[B];
     std::vector<int4> ctasks, atasks;
     std::vector<int2> stasks;
-    const size_t cpieces = (size_t)cl_build_tasks(B, offsets, ctasks), slots = ew_build_tasks(B, offsets, ew, atasks, stasks);
-    if (slots > ((size_t)1 << 27)) EPNN_FAIL("%s: the batch's k boxes have %zu slots, above 2^27: send fewer cells per call", name, slots);
-    bool sweep = false;
-    for (int b = 0; b < B; ++b) sweep = sweep || ew[b].rc > 0.f;
-    // one staged span: the three task tables and the cells' parameters, each at a multiple of 16 bytes
+    const size_t cpieces = (size_t)cl_build_tasks(B, offsets, ctasks);
+    size_t slots = 0;
+    bool sweep = !per;
+    if (per) {
+        slots = ew_build_tasks(B, offsets, per->ew, atasks, stasks);
+        if (slots > ((size_t)1 << 27)) EPNN_FAIL("%s: the batch's k boxes have %zu slots, above 2^27: send fewer cells per call", name, slots);
+        for (int b = 0; b < B; ++b) sweep = sweep || per->ew[b].rc > 0.f;
+    }
+    // one staged span: the sweep's task table and, per, the two Ewald task tables and the cells' parameters, each at a multiple of 16 bytes
     const size_t o_at = ctasks.size() * sizeof(int4), o_st = o_at + atasks.size() * sizeof(int4),
-                 o_ew = o_st + ((stasks.size() * sizeof(int2) + 15) & ~size_t(15)), blob_bytes = o_ew + (size_t)B * sizeof(EwCell);
+                 o_ew = o_st + ((stasks.size() * sizeof(int2) + 15) & ~size_t(15)), blob_bytes = o_ew + (per ? (size_t)B * sizeof(EwCell) : 0);
     std::vector<char> blob(blob_bytes, 0);
     memcpy(blob.data(), ctasks.data(), ctasks.size() * sizeof(int4));
-    memcpy(blob.data() + o_at, atasks.data(), atasks.size() * sizeof(int4));
-    memcpy(blob.data() + o_st, stasks.data(), stasks.size() * sizeof(int2));
-    memcpy(blob.data() + o_ew, ew.data(), (size_t)B * sizeof(EwCell));
-    const GlSpan span{blob.data(), blob_bytes, false};
-    // [A] phi | [A][3] ffix | flag, then [B] E in float64 and [B][9] the fixed-charge strain: directly behind the backward's output
-    // block, one download for both; the sweep's partial rows, the atoms' shares, S and the slots' records
-    const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), o_gsf = o_E + (size_t)B * 8, co_bytes = o_gsf + (size_t)B * 36;
-    const size_t o_share = cpieces * (size_t)A * EW_PART * 8, o_S = (o_share + (size_t)A * EW_SHARE * 8 + 15) & ~size_t(15), o_rec = o_S + slots * 16;
-    // (the _excl entry: the CSR is one more span beside the blob, the correction's rows [A][EW_PART] one more buffer behind the others)
-    const GlSpan spans[2] = {span, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false}};
-    const size_t more[3] = {co_bytes, o_rec + slots * 16, ex ? excl_xpart_bytes(A, true) : 0};
+    if (per) {
+        memcpy(blob.data() + o_at, atasks.data(), atasks.size() * sizeof(int4));
+        memcpy(blob.data() + o_st, stasks.data(), stasks.size() * sizeof(int2));
+        memcpy(blob.data() + o_ew, per->ew.data(), (size_t)B * sizeof(EwCell));
+    }
+    // [A] phi | [A][3] ffix | flag, then [B] E in float64 and, per, [B][9] the fixed-charge strain: directly behind the backward's output
+    // block, one download for both; the sweep's partial rows [pieces][A][4 or EW_PART] and the atoms' shares [A][1 or EW_SHARE] in
+    // float64, then, per, S and the slots' records
+    const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), o_gsf = o_E + (size_t)B * 8, co_bytes = o_gsf + (per ? (size_t)B * 36 : 0);
+    const size_t o_share = cpieces * (size_t)A * (per ? EW_PART : 4) * 8, share_end = o_share + (size_t)A * (per ? EW_SHARE : 1) * 8,
+                 o_S = (share_end + 15) & ~size_t(15), o_rec = o_S + slots * 16;
+    // (the _excl entries: the CSR is one more span beside the blob, the correction's rows [A][4 or EW_PART] one more buffer behind the others)
+    const GlSpan spans[2] = {GlSpan{blob.data(), blob_bytes, false}, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false}};
+    const size_t more[3] = {co_bytes, per ? o_rec + slots * 16 : share_end, ex ? excl_xpart_bytes(A, per != nullptr) : 0};
     GlGrad r;
     if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
     const GlCall &c = r.c;
@@ -191,38 +194,50 @@ static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, con
     float *phi = reinterpret_cast<float *>(co), *ffix = phi + A, *gsf = reinterpret_cast<float *>(co + o_gsf);
     int *hit = reinterpret_cast<int *>(phi + 4 * (size_t)A);
     double *E = reinterpret_cast<double *>(co + o_E), *part = reinterpret_cast<double *>(sc), *share = reinterpret_cast<double *>(sc + o_share);
+    double *xpart = ex ? reinterpret_cast<double *>(c.dw + r.o_more[2]) : nullptr;
     double2 *S = reinterpret_cast<double2 *>(sc + o_S);
     float4 *rec = reinterpret_cast<float4 *>(sc + o_rec);
     const float *q_dev = r.qck + (size_t)T * A;
-    const char *d_blob = reinterpret_cast<const char *>(c.d_extra[0]);
+    const char *d_blob = reinterpret_cast<const char *>(c.d_extra[0]), *d_csr = ex ? reinterpret_cast<const char *>(c.d_extra[1]) : nullptr;
     const int4 *d_ctasks = reinterpret_cast<const int4 *>(d_blob), *d_atasks = reinterpret_cast<const int4 *>(d_blob + o_at);
     const int2 *d_stasks = reinterpret_cast<const int2 *>(d_blob + o_st);
     const EwCell *d_ew = reinterpret_cast<const EwCell *>(d_blob + o_ew);
-    const EpnnCell *d_cells = c.geo.cells();
-    // ---- the Ewald sum on the forward's own charges: phi is the backward's seed
+    const EpnnCell *d_cells = per ? c.geo.cells() : nullptr;
+    const dim3 gsweep((unsigned)ctasks.size()), gatom((unsigned)atasks.size()), wave(64);
+    // ---- the sum on the forward's own charges: phi is the backward's seed
     HIPCHK(hipMemsetAsync(hit, 0, 4, h->stream));
     if (!sweep)                                                  // beta == alpha in every cell: the real-space term vanishes identically
         HIPCHK(hipMemsetAsync(part, 0, o_share, h->stream));
-    else if (alpha > 0.0)
-        hipLaunchKernelGGL(k_ew_sweep<true>, dim3((unsigned)ctasks.size()), dim3(64), 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev,
-                           d_cells, d_ew, A, (float)alpha, part, hit);
+    else if (per)
+        hipLaunchKernelGGL((alpha > 0.0 ? k_ew_sweep<true> : k_ew_sweep<false>), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz,
+                           q_dev, d_cells, d_ew, A, (float)alpha, part, hit);
     else
-        hipLaunchKernelGGL(k_ew_sweep<false>, dim3((unsigned)ctasks.size()), dim3(64), 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev,
-                           d_cells, d_ew, A, 0.f, part, hit);
-    hipLaunchKernelGGL(k_ew_sfac, dim3((unsigned)stasks.size()), dim3(64), 0, h->stream, d_stasks, c.d_moff, c.d_xyz, q_dev, d_cells, d_ew, S, rec);
-    if (ex) {                                                    // (nothing of it depends on rc: it runs on a zeroed `part` too)
-        double *xpart = reinterpret_cast<double *>(c.dw + r.o_more[2]);
-        excl_launch<true>(h, c, reinterpret_cast<const char *>(c.d_extra[1]), *ex, q_dev, d_cells, alpha, xpart, hit);
-        hipLaunchKernelGGL(k_ew_atom_x, dim3((unsigned)atasks.size()), dim3(64), 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew,
-                           (const double2 *)S, (const float4 *)rec, (const double *)part, (const double *)xpart, ke, r.gq, phi, ffix, share);
-    } else
-        hipLaunchKernelGGL(k_ew_atom, dim3((unsigned)atasks.size()), dim3(64), 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew,
-                           (const double2 *)S, (const float4 *)rec, (const double *)part, ke, r.gq, phi, ffix, share);
-    hipLaunchKernelGGL(k_ew_energy, dim3((unsigned)B), dim3(64), 0, h->stream, c.d_moff, d_cells, d_ew, (const double2 *)S, (const double *)share,
-                       ke, E, gsf);
+        hipLaunchKernelGGL((alpha > 0.0 ? k_cl_sweep<true> : k_cl_sweep<false>), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz,
+                           q_dev, A, (float)alpha, part, hit);
+    if (per) hipLaunchKernelGGL(k_ew_sfac, dim3((unsigned)stasks.size()), wave, 0, h->stream, d_stasks, c.d_moff, c.d_xyz, q_dev, d_cells, d_ew, S, rec);
+    if (ex) excl_launch(h, c, d_csr, *ex, q_dev, d_cells, alpha, xpart, hit);     // (nothing of it depends on rc: it runs on a zeroed `part` too)
+    if (per) {
+        if (ex)
+            hipLaunchKernelGGL(k_ew_atom_x, gatom, wave, 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew, (const double2 *)S,
+                               (const float4 *)rec, (const double *)part, (const double *)xpart, ke, r.gq, phi, ffix, share);
+        else
+            hipLaunchKernelGGL(k_ew_atom, gatom, wave, 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew, (const double2 *)S,
+                               (const float4 *)rec, (const double *)part, ke, r.gq, phi, ffix, share);
+        hipLaunchKernelGGL(k_ew_energy, dim3((unsigned)B), wave, 0, h->stream, c.d_moff, d_cells, d_ew, (const double2 *)S, (const double *)share,
+                           ke, E, gsf);
+    } else {
+        if (ex)
+            hipLaunchKernelGGL(k_cl_atom_x, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, (const double *)part,
+                               (const double *)xpart, ke, r.gq, phi, ffix, share);
+        else
+            hipLaunchKernelGGL(k_cl_atom, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, (const double *)part, ke, r.gq, phi,
+                               ffix, share);
+        hipLaunchKernelGGL(k_cl_energy, dim3((unsigned)B), wave, 0, h->stream, (const double *)share, c.d_moff, E);
+    }
     HIPCHK(hipGetLastError());
-    if (gl_grad_backward(h, gl, r, B, true)) return 1;
-    // ---- one download: q | gxyz | flag | the charges' strain rows | (the step to the next buffer) | phi | ffix | flag | E | the fixed-charge strain
+    if (gl_grad_backward(h, gl, r, B, per != nullptr)) return 1;
+    // ---- one download: q | gxyz | flag | the charges' strain rows (open: unused) | (the step to the next buffer) | phi | ffix | flag | E
+    // | per: the fixed-charge strain
     const char *from = reinterpret_cast<const char *>(r.q_fin);
     const size_t nbytes = (size_t)(co + co_bytes - from), at_co = (size_t)(co - from);
     if (gl->pin_out.ensure(nbytes)) return 1;
@@ -233,52 +248,50 @@ static int coulomb_cell_impl(epnn_handle *h, const char *name, int B, int N, con
                 *bphi = reinterpret_cast<const float *>(back + at_co), *bffix = bphi + A, *bgsf = reinterpret_cast<const float *>(back + at_co + o_gsf);
     const int flag = reinterpret_cast<const int *>(bq)[4 * (size_t)A], chit = reinterpret_cast<const int *>(bphi)[4 * (size_t)A];
     if (flag & 2) EPNN_FAIL("%s: the pair list is not symmetric", name);
-    if (flag == 0 && chit == CL_FLAG_FAR && ex && xa) return excl_name_far(name, offsets, xyz, geo, *xa);
+    if (per && flag == 0 && chit == CL_FLAG_FAR && ex && per->xa) return excl_name_far(name, offsets, xyz, geo, *per->xa);
     if (flag != 0 || chit != 0)
-        EPNN_FAIL("%s: two atoms of a cell or their periodic images coincide (distance 0: neither the Coulomb terms nor the edge features have a "
-                  "derivative there)", name);
-    memcpy(q_out, bq, (size_t)A * 4);
-    memcpy(phi_out, bphi, (size_t)A * 4);
-    memcpy(e_out, back + at_co + o_E, (size_t)B * 8);
+        EPNN_FAIL(per ? "%s: two atoms of a cell or their periodic images coincide (distance 0: neither the Coulomb terms nor the edge features "
+                        "have a derivative there)"
+                      : "%s: two atoms of a molecule coincide (distance 0: neither the Coulomb terms nor the edge features have a derivative there)",
+                  name);
+    memcpy(out.q, bq, (size_t)A * 4);
+    memcpy(out.phi, bphi, (size_t)A * 4);
+    memcpy(out.e, back + at_co + o_E, (size_t)B * 8);
     for (size_t k = 0; k < 3 * (size_t)A; ++k) {
         const float fq = -bgx[k];
-        f_out[k] = bffix[k] + fq;
-        if (fq_out) fq_out[k] = fq;
+        out.f[k] = bffix[k] + fq;
+        if (out.fq) out.fq[k] = fq;
     }
-    for (size_t k = 0; k < 9 * (size_t)B; ++k) gs_out[k] = bgsf[k] + bgs[k];
-    if (ffix_out) memcpy(ffix_out, bffix, (size_t)A * 12);
-    if (gsfix_out) memcpy(gsfix_out, bgsf, (size_t)B * 36);
-    if (gsq_out) memcpy(gsq_out, bgs, (size_t)B * 36);
+    if (out.ffix) memcpy(out.ffix, bffix, (size_t)A * 12);
+    if (!per) return 0;
+    for (size_t k = 0; k < 9 * (size_t)B; ++k) out.gs[k] = bgsf[k] + bgs[k];
+    if (out.gs_fix) memcpy(out.gs_fix, bgsf, (size_t)B * 36);
+    if (out.gs_q) memcpy(out.gs_q, bgs, (size_t)B * 36);
     return 0;
 }
 
 static int coulomb_cell_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                              const float *Q, const float *cell, const double *ewald, double ke, double alpha, const ExclArgs *xa, float *q_out,
-                              float *phi_out, double *e_out, float *f_out, float *gstrain_out, float *ffix_out, float *fq_out,
-                              float *gstrain_fix_out, float *gstrain_q_out) {
-    if (!cell || !ewald || !phi_out || !e_out || !gstrain_out) EPNN_FAIL("%s: null argument", name);
-    if (!ew_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
-    if (!ew_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
+                              const float *Q, const float *cell, const double *ewald, double ke, double alpha, const ExclArgs *xa,
+                              const CoulombOut &out) {
+    if (!cell || !ewald || !out.phi || !out.e || !out.gs) EPNN_FAIL("%s: null argument", name);
+    if (!epnn_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
+    if (!epnn_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
     GeoArg arg;
-    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, 1, q_out, f_out, arg)) return 1;
-    std::vector<EwCell> ew((size_t)B);
+    if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, cell, 1, out.q, out.f, arg)) return 1;
+    CoulombPeriodic per{std::vector<EwCell>((size_t)B), xa};
     for (int b = 0; b < B; ++b)
-        if (ew_cell_row(name, b, cell + 9 * (size_t)b, ewald + 6 * (size_t)b, alpha, ew[b])) return 1;
-    if (!xa)
-        return coulomb_cell_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ew, ke, alpha, q_out, phi_out, e_out, f_out, gstrain_out, ffix_out,
-                                 fq_out, gstrain_fix_out, gstrain_q_out);
+        if (ew_cell_row(name, b, cell + 9 * (size_t)b, ewald + 6 * (size_t)b, alpha, per.ew[b])) return 1;
     ExclCsr ex;
-    if (excl_build(name, B, offsets, xa->npairs, xa->i, xa->j, xa->scale, ex)) return 1;
-    return coulomb_cell_impl(h, name, B, N, offsets, xyz, x, Q, arg.geo, ew, ke, alpha, q_out, phi_out, e_out, f_out, gstrain_out, ffix_out,
-                             fq_out, gstrain_fix_out, gstrain_q_out, &ex, xa);
+    if (xa && excl_build(name, B, offsets, xa->npairs, xa->i, xa->j, xa->scale, ex)) return 1;
+    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, &per, xa ? &ex : nullptr, out);
 }
 
 extern "C" int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                      const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
                                      double *e_out, float *f_out, float *gstrain_out, float *ffix_out, float *fq_out,
                                      float *gstrain_fix_out, float *gstrain_q_out) {
-    return coulomb_cell_enter(h, "epnn_coulomb_xyz_cell", B, N, offsets, xyz, x, Q, cell, ewald, ke, alpha, nullptr, q_out, phi_out, e_out, f_out,
-                              gstrain_out, ffix_out, fq_out, gstrain_fix_out, gstrain_q_out);
+    return coulomb_cell_enter(h, "epnn_coulomb_xyz_cell", B, N, offsets, xyz, x, Q, cell, ewald, ke, alpha, nullptr,
+                              CoulombOut{q_out, phi_out, e_out, f_out, ffix_out, fq_out, gstrain_out, gstrain_fix_out, gstrain_q_out});
 }
 
 extern "C" int epnn_coulomb_xyz_cell_excl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
@@ -286,6 +299,7 @@ extern "C" int epnn_coulomb_xyz_cell_excl(epnn_handle *h, int B, int N, const in
                                           const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
                                           float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out) {
     const ExclArgs xa{npairs, ex_i, ex_j, ex_scale};
-    return coulomb_cell_enter(h, "epnn_coulomb_xyz_cell_excl", B, N, offsets, xyz, x, Q, cell, ewald, ke, alpha, &xa, q_out, phi_out, e_out,
-                              f_out, gstrain_out, ffix_out, fq_out, gstrain_fix_out, gstrain_q_out);
+    return coulomb_cell_enter(h, "epnn_coulomb_xyz_cell_excl", B, N, offsets, xyz, x, Q, cell, ewald, ke, alpha, &xa,
+                              CoulombOut{q_out, phi_out, e_out, f_out, ffix_out, fq_out, gstrain_out, gstrain_fix_out, gstrain_q_out});
 }
+

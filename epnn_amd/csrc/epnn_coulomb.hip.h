@@ -54,10 +54,32 @@ __device__ __forceinline__ float cl_g(float u, float erf_u) {
     return two_rpi * (u * w) * s;
 }
 
-// task = (first atom, atoms | piece << 8, first partner, end of the partners); atoms and partners are flat atom indices
+// The float32 pair term of the open sweep and of k_cl_excl, from the squared length r2 of the rounded displacement: kap = kappa(D),
+// g = g(alpha D) and r3 = 1 / D^3; kap and r3 are 0 at r2 == 0 and for a pair that does not count (use: k_cl_excl counts every one).
 template <bool ERF>
-__global__ __launch_bounds__(64) void k_cl_sweep(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q, int A,
-                                                 float alpha, double *part, int *bad) {
+__device__ __forceinline__ void cl_pair_term(bool use, float r2, float alpha, float &kap, float &g, float &r3) {
+    const float rinv = (use && r2 > 0.f) ? rsqrtf(r2) : 0.f;
+    g = 1.f;
+    kap = rinv;
+    if (ERF) {
+        const float u = alpha * (r2 * rinv), e = erff(u);
+        kap = e * rinv;
+        g = cl_g(u, e);
+    }
+    r3 = rinv * rinv * rinv;
+}
+// (the periodic sweep's pair term, with the same outputs: epnn_ewald.hip.h, beside ew_h)
+template <bool ERF>
+__device__ __forceinline__ void ew_pair_term(bool use, float r2, float alpha, float beta, float rc, float &kap, float &g, float &r3);
+
+// The sweep of both geometries.  task = (first atom, atoms | piece << 8, first partner, end of the partners); atoms and partners are flat
+// atom indices.  CELL: the displacement goes through the minimum image of the lane's own cell, the pair term is the split one inside
+// rc (EW: EwCell, of which the open file knows only that it has rc and beta) and six more sums follow the open sweep's four, the virial
+// row xx yy zz yz xz xy: part [pieces][A][NS].
+template <bool ERF, bool CELL, class EW>
+__device__ __forceinline__ void cl_sweep_body(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
+                                              const EpnnCell *cells, const EW *ew, int A, float alpha, double *part, int *bad) {
+    constexpr int NS = CELL ? 10 : 4;                            // (10: EW_PART, asserted in epnn_ewald.hip.h)
     __shared__ double tx[CL_TILE], ty[CL_TILE], tz[CL_TILE];
     __shared__ float tq[CL_TILE];
     const int4 tk = tasks[blockIdx.x];
@@ -65,8 +87,18 @@ __global__ __launch_bounds__(64) void k_cl_sweep(const int4 *tasks, const int *m
     const bool valid = lane < na;
     const int i = tk.x + (valid ? lane : 0);
     const int b = mol_of[i], lo = moff[b], hi = moff[b + 1];
+    double g[9], a[9];
+    float rc = 0.f, beta = 0.f;
+    if constexpr (CELL) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { g[k] = cells[b].g[k]; a[k] = (double)cells[b].a[k]; }
+        rc = ew[b].rc;
+        beta = ew[b].beta;
+    }
     const double xi = (double)xyz[3 * (size_t)i], yi = (double)xyz[3 * (size_t)i + 1], zi = (double)xyz[3 * (size_t)i + 2];
-    double sp = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    double sum[NS];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) sum[c] = 0.0;
     bool hit = false;
     for (int t0 = tk.z; t0 < tk.w; t0 += CL_TILE) {
         const int cnt = min(CL_TILE, tk.w - t0);
@@ -79,29 +111,42 @@ __global__ __launch_bounds__(64) void k_cl_sweep(const int4 *tasks, const int *m
         __syncthreads();
         for (int jj = 0; jj < cnt; ++jj) {
             const int j = t0 + jj;
-            const float dx = (float)(xi - tx[jj]), dy = (float)(yi - ty[jj]), dz = (float)(zi - tz[jj]), qj = tq[jj];
+            double ex = xi - tx[jj], ey = yi - ty[jj], ez = zi - tz[jj];
+            if (CELL) epnn_mic_cell(ex, ey, ez, g, a);
+            const float dx = (float)ex, dy = (float)ey, dz = (float)ez, qj = tq[jj];
             const float r2 = dx * dx + dy * dy + dz * dz;
             const bool use = valid && j != i && j >= lo && j < hi;        // the self term goes by index
             hit |= use && r2 == 0.f;
-            const float rinv = (use && r2 > 0.f) ? rsqrtf(r2) : 0.f;
-            float kap = rinv, g = 1.f;
-            if (ERF) {
-                const float u = alpha * (r2 * rinv), e = erff(u);
-                kap = e * rinv;
-                g = cl_g(u, e);
+            float kap, gg, r3;
+            if constexpr (CELL) ew_pair_term<ERF>(use, r2, alpha, beta, rc, kap, gg, r3);
+            else cl_pair_term<ERF>(use, r2, alpha, kap, gg, r3);
+            const float s = qj * gg * r3;
+            const float fx = s * dx, fy = s * dy, fz = s * dz;
+            sum[0] += (double)(qj * kap);
+            sum[1] += (double)fx;
+            sum[2] += (double)fy;
+            sum[3] += (double)fz;
+            if (CELL) {
+                sum[4] += (double)(fx * dx);
+                sum[5] += (double)(fy * dy);
+                sum[6] += (double)(fz * dz);
+                sum[7] += (double)(fy * dz);
+                sum[8] += (double)(fx * dz);
+                sum[9] += (double)(fx * dy);
             }
-            const float s = qj * g * (rinv * rinv * rinv);
-            sp += (double)(qj * kap);
-            sx += (double)(s * dx);
-            sy += (double)(s * dy);
-            sz += (double)(s * dz);
         }
     }
     if (valid) {
-        double *o = part + ((size_t)piece * A + i) * 4;
-        o[0] = sp; o[1] = sx; o[2] = sy; o[3] = sz;
+        double *o = part + ((size_t)piece * A + i) * NS;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) o[c] = sum[c];
     }
     if (hit) atomicOr(bad, 1);
+}
+template <bool ERF>
+__global__ __launch_bounds__(64) void k_cl_sweep(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q, int A,
+                                                 float alpha, double *part, int *bad) {
+    cl_sweep_body<ERF, false, void>(tasks, moff, mol_of, xyz, q, nullptr, nullptr, A, alpha, part, bad);
 }
 
 // every atom adds its pieces in piece order: phi [A] (float32, written twice: the backward's seed and the output), ffix [A][3],
@@ -147,21 +192,6 @@ __global__ __launch_bounds__(64) void k_cl_energy(const double *share, const int
 #define CL_FLAG_ZERO 1            // flag word, bit 0: two atoms at distance 0 (the sweeps set it too)
 #define CL_FLAG_FAR 2             // bit 1: a listed pair of a cell beyond half the smallest perpendicular width
 
-// The sweep's float32 pair term, restated (k_cl_sweep itself is not touched: its bits are the plain entries' bits): from the
-// squared length r2 of the rounded displacement, kap = kappa(D) and g3 = g(alpha D) / D^3; both 0 at r2 == 0.
-template <bool ERF>
-__device__ __forceinline__ void cl_pair_term(float r2, float alpha, float &kap, float &g3) {
-    const float rinv = r2 > 0.f ? rsqrtf(r2) : 0.f;
-    float g = 1.f;
-    kap = rinv;
-    if (ERF) {
-        const float u = alpha * (r2 * rinv), e = erff(u);
-        kap = e * rinv;
-        g = cl_g(u, e);
-    }
-    g3 = g * (rinv * rinv * rinv);
-}
-
 // One atom per lane, 64 atoms per wavefront; a lane walks its CSR row in partner order.  Displacement: the float64 difference of the
 // float32 coordinates, through epnn_mic_cell when CELL, rounded once.  Sums float64: xpart [A][4] = (sum f q_j kappa, sum f q_j g dx /
 // D^3, .. dy, .. dz), f the row's factor; CELL: xpart [A][10], the six virial sums f q_j g d_a d_b / D^3 (xx yy zz yz xz xy) behind
@@ -198,9 +228,9 @@ __global__ __launch_bounds__(64) void k_cl_excl(int A, const int *mol_of, const 
         const float r2 = dx * dx + dy * dy + dz * dz;
         if (r2 == 0.f) flag |= CL_FLAG_ZERO;
         if (CELL && r2 > half_w * half_w) flag |= CL_FLAG_FAR;
-        float kap, g3;
-        cl_pair_term<ERF>(r2, alpha, kap, g3);
-        const float s = qj * g3;
+        float kap, gg, r3;
+        cl_pair_term<ERF>(true, r2, alpha, kap, gg, r3);
+        const float s = qj * (gg * r3);                                   // (the sweep multiplies from the left: (q_j g) / D^3)
         const float fx = fac * (s * dx), fy = fac * (s * dy), fz = fac * (s * dz);
         sum[0] += (double)(fac * (qj * kap));
         sum[1] += (double)fx;

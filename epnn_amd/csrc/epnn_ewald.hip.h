@@ -38,7 +38,7 @@ struct EwCell {
     int pad;
 };
 static_assert(sizeof(EwCell) == 72, "EwCell is staged as 18 words");
-static_assert(EW_PART == 10, "k_cl_excl<., true> writes the ten sums of k_ew_sweep's row");
+static_assert(EW_PART == 10, "cl_sweep_body<., true> and k_cl_excl<., true> write the ten sums of k_ew_sweep's row");
 
 // Slot s of the cell's k box -> (m0, m1, m2), k and the doubled weight 2 c(k); 0 outside the half space or the sphere (and at k = 0)
 __device__ __forceinline__ double ew_slot(const EwCell &e, const double *g, int s, int &m0, int &m1, int &m2, double &kx, double &ky, double &kz) {
@@ -59,77 +59,33 @@ __device__ __forceinline__ double ew_slot(const EwCell &e, const double *g, int 
 // h(u) = erfc(u) + 2 / sqrt(pi) u exp(-u^2) = 1 - g(u): no cancellation at any u
 __device__ __forceinline__ float ew_h(float u) { return erfcf(u) + 1.1283791670955126f * u * expf(-u * u); }
 
-// task as in k_cl_sweep.  part [pieces][A][EW_PART] = (sum q_j kappa_s D, sum q_j gs dx / D^3, .. dy, .. dz, then sum q_j gs d_a d_b / D^3
-// for ab = xx yy zz yz xz xy), gs = g_alpha - g_beta = -D^2 kappa_s'.  The two differences cancel where alpha D and beta D are
-// both large (erf -> 1, g -> 1): there they are taken between the complements erfc and h = 1 - g.
+// The split pair term of the periodic sweep, cl_pair_term's outputs: kap = kappa_s(D) = de / D, g = gs = g_alpha - g_beta = -D^2 kappa_s'
+// and r3 = 1 / D^3, kap and r3 0 at r2 == 0, beyond rc and without use.  The two differences cancel where alpha D and beta D are both large
+// (erf -> 1, g -> 1): there they are taken between the complements erfc and h = 1 - g.
+template <bool ERF>
+__device__ __forceinline__ void ew_pair_term(bool use, float r2, float alpha, float beta, float rc, float &kap, float &g, float &r3) {
+    const float rinv0 = r2 > 0.f ? rsqrtf(r2) : 0.f, D = r2 * rinv0;
+    const float rinv = (use && r2 > 0.f && D <= rc) ? rinv0 : 0.f;
+    const float ub = beta * D;
+    float de;
+    if (ERF) {
+        const float ua = alpha * D, um = fminf(ua, ub);
+        de = um >= 0.5f ? erfcf(ub) - erfcf(ua) : erff(ua) - erff(ub);
+        g = um >= 1.f ? ew_h(ub) - ew_h(ua) : cl_g(ua, erff(ua)) - cl_g(ub, erff(ub));
+    } else {
+        de = erfcf(ub);
+        g = ew_h(ub);
+    }
+    kap = de * rinv;
+    r3 = rinv * rinv * rinv;
+}
+
+// task as in k_cl_sweep: cl_sweep_body in this file's geometry.  part [pieces][A][EW_PART] = (sum q_j kappa_s, sum q_j gs dx / D^3, .. dy,
+// .. dz, then sum q_j gs d_a d_b / D^3 for ab = xx yy zz yz xz xy).
 template <bool ERF>
 __global__ __launch_bounds__(64) void k_ew_sweep(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
                                                  const EpnnCell *cells, const EwCell *ew, int A, float alpha, double *part, int *bad) {
-    __shared__ double tx[CL_TILE], ty[CL_TILE], tz[CL_TILE];
-    __shared__ float tq[CL_TILE];
-    const int4 tk = tasks[blockIdx.x];
-    const int lane = threadIdx.x, na = tk.y & 255, piece = tk.y >> 8;
-    const bool valid = lane < na;
-    const int i = tk.x + (valid ? lane : 0);
-    const int b = mol_of[i], lo = moff[b], hi = moff[b + 1];
-    double g[9], a[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { g[k] = cells[b].g[k]; a[k] = (double)cells[b].a[k]; }
-    const float rc = ew[b].rc, beta = ew[b].beta;
-    const double xi = (double)xyz[3 * (size_t)i], yi = (double)xyz[3 * (size_t)i + 1], zi = (double)xyz[3 * (size_t)i + 2];
-    double sum[EW_PART];
-#pragma unroll
-    for (int c = 0; c < EW_PART; ++c) sum[c] = 0.0;
-    bool hit = false;
-    for (int t0 = tk.z; t0 < tk.w; t0 += CL_TILE) {
-        const int cnt = min(CL_TILE, tk.w - t0);
-        __syncthreads();
-        if (lane < cnt) {
-            const size_t j = (size_t)(t0 + lane);
-            tx[lane] = (double)xyz[3 * j]; ty[lane] = (double)xyz[3 * j + 1]; tz[lane] = (double)xyz[3 * j + 2];
-            tq[lane] = q[j];
-        }
-        __syncthreads();
-        for (int jj = 0; jj < cnt; ++jj) {
-            const int j = t0 + jj;
-            double ex = xi - tx[jj], ey = yi - ty[jj], ez = zi - tz[jj];
-            epnn_mic_cell(ex, ey, ez, g, a);
-            const float dx = (float)ex, dy = (float)ey, dz = (float)ez, qj = tq[jj];
-            const float r2 = dx * dx + dy * dy + dz * dz;
-            const bool use = valid && j != i && j >= lo && j < hi;        // the self term goes by index
-            hit |= use && r2 == 0.f;
-            const float rinv0 = r2 > 0.f ? rsqrtf(r2) : 0.f, D = r2 * rinv0;
-            const float rinv = (use && r2 > 0.f && D <= rc) ? rinv0 : 0.f;
-            const float ub = beta * D;
-            float de, gs;
-            if (ERF) {
-                const float ua = alpha * D, um = fminf(ua, ub);
-                de = um >= 0.5f ? erfcf(ub) - erfcf(ua) : erff(ua) - erff(ub);
-                gs = um >= 1.f ? ew_h(ub) - ew_h(ua) : cl_g(ua, erff(ua)) - cl_g(ub, erff(ub));
-            } else {
-                de = erfcf(ub);
-                gs = ew_h(ub);
-            }
-            const float s = qj * gs * (rinv * rinv * rinv);
-            const float fx = s * dx, fy = s * dy, fz = s * dz;
-            sum[0] += (double)(qj * (de * rinv));
-            sum[1] += (double)fx;
-            sum[2] += (double)fy;
-            sum[3] += (double)fz;
-            sum[4] += (double)(fx * dx);
-            sum[5] += (double)(fy * dy);
-            sum[6] += (double)(fz * dz);
-            sum[7] += (double)(fy * dz);
-            sum[8] += (double)(fx * dz);
-            sum[9] += (double)(fx * dy);
-        }
-    }
-    if (valid) {
-        double *o = part + ((size_t)piece * A + i) * EW_PART;
-#pragma unroll
-        for (int c = 0; c < EW_PART; ++c) o[c] = sum[c];
-    }
-    if (hit) atomicOr(bad, 1);
+    cl_sweep_body<ERF, true>(tasks, moff, mol_of, xyz, q, cells, ew, A, alpha, part, bad);
 }
 
 // task = (cell, first slot): S(k) of 64 slots of the cell's k box, a slot per lane, over the cell's atoms in index order.  The

@@ -29,6 +29,25 @@ extern thread_local std::string g_epnn_err;
         if (_e != hipSuccess) EPNN_FAIL("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
+// Is an argument finite?  The library is built with -ffinite-math-only: std::isfinite would fold to true, and so would a test of the
+// value's own bits -- they are read back from a volatile word, of which the compiler assumes nothing.
+static inline bool epnn_finite(double v) {
+    volatile uint64_t seen;
+    uint64_t bits;
+    memcpy(&bits, &v, 8);
+    seen = bits;
+    bits = seen;
+    return (bits & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+static inline bool epnn_finite(float v) {
+    volatile uint32_t seen;
+    uint32_t bits;
+    memcpy(&bits, &v, 4);
+    seen = bits;
+    bits = seen;
+    return (bits & 0x7f800000u) != 0x7f800000u;
+}
+
 // growable device buffer
 struct DevBuf {
     void *p = nullptr;

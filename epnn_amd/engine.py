@@ -509,17 +509,7 @@ class Engine:
         F = ffix + fq; fq is -gxyz of charges_vjp_xyz(g=phi) on "grad_path" 2, bit for bit, and q has that path's bits.  Open
         systems only (fully periodic cells: coulomb_xyz_cell), no self-energy term; bonded exclusions: coulomb_xyz_excl.  One
         call costs about one gradient call of the pair-list path; it touches no training state and works without train_init."""
-        offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz: array shapes do not match offsets", offsets, xyz, x, Q)
-        q = np.empty((A,), dtype=np.float32)
-        phi = np.empty((A,), dtype=np.float32)
-        E = np.empty((B,), dtype=np.float64)
-        F = np.empty((A, 3), dtype=np.float32)
-        ffix = np.empty((A, 3), dtype=np.float32) if parts else None
-        fq = np.empty((A, 3), dtype=np.float32) if parts else None
-        check(self.lib.epnn_coulomb_xyz(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), float(ke), float(alpha), fptr(q),
-                                        fptr(phi), E.ctypes.data_as(C.POINTER(C.c_double)), fptr(F), fptr(ffix) if parts else None,
-                                        fptr(fq) if parts else None), self.lib)
-        return (q, phi, E, F, ffix, fq) if parts else (q, phi, E, F)
+        return self._coulomb("coulomb_xyz", offsets, xyz, x, Q, N, ke, alpha, parts)
 
     def ewald_params(self, cell, alpha=0.0, tol=1e-6):
         """The Ewald parameters coulomb_xyz_cell runs at for one cell (3, 3) (epnn_ewald_params, host only): float64 (6,) = beta,
@@ -543,35 +533,7 @@ class Engine:
         strain=True, gstrain_fix and gstrain_q behind them (gstrain = gstrain_fix + gstrain_q); fq and gstrain_q are -gxyz and gs
         of charges_vjp_xyz(g=phi, cell=, strain=True) on "grad_path" 2, bit for bit.  Bonded exclusions: coulomb_xyz_cell_excl.
         Partially periodic cells and PME are not built."""
-        _one_periodic_argument(box, cell)
-        if box is None and cell is None:
-            raise ValueError("coulomb_xyz_cell: give cell= or box= (open molecules: coulomb_xyz)")
-        offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz_cell: array shapes do not match offsets", offsets, xyz, x, Q)
-        _, cell = _geometry(box, cell, B, cells_only=True)
-        if ewald is None:
-            ewald = np.stack([self.ewald_params(cell[b], alpha, tol) for b in range(B)])
-        ewald = np.asarray(ewald, dtype=np.float64)
-        if ewald.shape == (6,):
-            ewald = np.tile(ewald, (B, 1))
-        if ewald.shape != (B, 6):
-            raise ValueError(f"coulomb_xyz_cell: ewald must have shape (6,) or ({B}, 6), got {ewald.shape}")
-        ewald = np.ascontiguousarray(ewald)
-        dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        q = np.empty((A,), dtype=np.float32)
-        phi = np.empty((A,), dtype=np.float32)
-        E = np.empty((B,), dtype=np.float64)
-        F = np.empty((A, 3), dtype=np.float32)
-        gs = np.empty((B, 3, 3), dtype=np.float32)
-        ffix, fq = (np.empty((A, 3), dtype=np.float32) if parts else None for _ in range(2))
-        gs_fix, gs_q = (np.empty((B, 3, 3), dtype=np.float32) if parts else None for _ in range(2))
-        opt = lambda a: None if a is None else fptr(a)
-        check(self.lib.epnn_coulomb_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), dptr(ewald), float(ke),
-                                             float(alpha), fptr(q), fptr(phi), dptr(E), fptr(F), fptr(gs), opt(ffix), opt(fq), opt(gs_fix),
-                                             opt(gs_q)), self.lib)
-        out = (q, phi, E, F) + ((gs,) if strain else ())
-        if parts:
-            out += (ffix, fq) + ((gs_fix, gs_q) if strain else ())
-        return out
+        return self._coulomb("coulomb_xyz_cell", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, strain))
 
     def coulomb_xyz_excl(self, offsets, xyz, x, Q, N, ke=KE_EV_ANGSTROM, alpha=0.0, parts=False, exclusions=None):
         """coulomb_xyz with bonded exclusions and pair scaling (epnn_coulomb_xyz_excl).  exclusions=None is coulomb_xyz itself, the
@@ -580,21 +542,7 @@ class Engine:
         and phi with these weights seeds fq.  bonded_exclusions(bonds, n_atoms) makes the list from a bond list.  The outputs do
         not depend on the order of the list; refused by name: an index out of range, i == j, atoms of two molecules, a pair listed
         twice, a factor that is not finite."""
-        if exclusions is None:
-            return self.coulomb_xyz(offsets, xyz, x, Q, N, ke=ke, alpha=alpha, parts=parts)
-        offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz_excl: array shapes do not match offsets", offsets, xyz, x, Q)
-        ei, ej, es = _exclusion_lists("coulomb_xyz_excl", exclusions)
-        q = np.empty((A,), dtype=np.float32)
-        phi = np.empty((A,), dtype=np.float32)
-        E = np.empty((B,), dtype=np.float64)
-        F = np.empty((A, 3), dtype=np.float32)
-        ffix = np.empty((A, 3), dtype=np.float32) if parts else None
-        fq = np.empty((A, 3), dtype=np.float32) if parts else None
-        opt = lambda a: None if a is None else fptr(a)
-        check(self.lib.epnn_coulomb_xyz_excl(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), float(ke), float(alpha), len(es),
-                                             iptr(ei), iptr(ej), fptr(es), fptr(q), fptr(phi), E.ctypes.data_as(C.POINTER(C.c_double)), fptr(F),
-                                             opt(ffix), opt(fq)), self.lib)
-        return (q, phi, E, F, ffix, fq) if parts else (q, phi, E, F)
+        return self._coulomb("coulomb_xyz_excl", offsets, xyz, x, Q, N, ke, alpha, parts, exclusions=exclusions)
 
     def coulomb_xyz_cell_excl(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None, parts=False,
                               strain=False, exclusions=None):
@@ -602,35 +550,49 @@ class Engine:
         itself; otherwise (pairs, scale) as in coulomb_xyz_excl.  The Ewald sum runs over all pairs and images as before; the one
         nearest image of every listed pair is corrected by (scale - 1) times its bare term, whatever beta, rc and kc are.  A listed
         pair farther apart than half the smallest perpendicular width of its cell is refused by name."""
+        return self._coulomb("coulomb_xyz_cell_excl", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, strain),
+                             exclusions=exclusions)
+
+    def _coulomb(self, where, offsets, xyz, x, Q, N, ke, alpha, parts, periodic=None, exclusions=None):
+        """The four coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
+        molecules, exclusions = (pairs, scale) or None for the plain C entry (an _excl method without a list is its plain method)."""
         if exclusions is None:
-            return self.coulomb_xyz_cell(offsets, xyz, x, Q, N, cell=cell, box=box, ke=ke, alpha=alpha, tol=tol, ewald=ewald, parts=parts,
-                                         strain=strain)
-        _one_periodic_argument(box, cell)
-        if box is None and cell is None:
-            raise ValueError("coulomb_xyz_cell_excl: give cell= or box= (open molecules: coulomb_xyz_excl)")
-        offsets, xyz, x, Q, _, B, A = self._flat_batch("coulomb_xyz_cell_excl: array shapes do not match offsets", offsets, xyz, x, Q)
-        _, cell = _geometry(box, cell, B, cells_only=True)
-        if ewald is None:
-            ewald = np.stack([self.ewald_params(cell[b], alpha, tol) for b in range(B)])
-        ewald = np.asarray(ewald, dtype=np.float64)
-        if ewald.shape == (6,):
-            ewald = np.tile(ewald, (B, 1))
-        if ewald.shape != (B, 6):
-            raise ValueError(f"coulomb_xyz_cell_excl: ewald must have shape (6,) or ({B}, 6), got {ewald.shape}")
-        ewald = np.ascontiguousarray(ewald)
-        ei, ej, es = _exclusion_lists("coulomb_xyz_cell_excl", exclusions)
+            where = where.replace("_excl", "")
+        strain = False
+        if periodic is not None:
+            cell, box, tol, ewald, strain = periodic
+            _one_periodic_argument(box, cell)
+            if box is None and cell is None:
+                raise ValueError(f"{where}: give cell= or box= (open molecules: {where.replace('_cell', '')})")
+        offsets, xyz, x, Q, _, B, A = self._flat_batch(where + ": array shapes do not match offsets", offsets, xyz, x, Q)
         dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        opt = lambda a: None if a is None else fptr(a)
+        args = [float(ke), float(alpha)]
+        if periodic is not None:
+            _, cell = _geometry(box, cell, B, cells_only=True)
+            if ewald is None:
+                ewald = np.stack([self.ewald_params(cell[b], alpha, tol) for b in range(B)])
+            ewald = np.asarray(ewald, dtype=np.float64)
+            if ewald.shape == (6,):
+                ewald = np.tile(ewald, (B, 1))
+            if ewald.shape != (B, 6):
+                raise ValueError(f"{where}: ewald must have shape (6,) or ({B}, 6), got {ewald.shape}")
+            ewald = np.ascontiguousarray(ewald)
+            args = [fptr(cell), dptr(ewald)] + args
+        if exclusions is not None:
+            ei, ej, es = _exclusion_lists(where, exclusions)
+            args += [len(es), iptr(ei), iptr(ej), fptr(es)]
         q = np.empty((A,), dtype=np.float32)
         phi = np.empty((A,), dtype=np.float32)
         E = np.empty((B,), dtype=np.float64)
         F = np.empty((A, 3), dtype=np.float32)
-        gs = np.empty((B, 3, 3), dtype=np.float32)
         ffix, fq = (np.empty((A, 3), dtype=np.float32) if parts else None for _ in range(2))
-        gs_fix, gs_q = (np.empty((B, 3, 3), dtype=np.float32) if parts else None for _ in range(2))
-        opt = lambda a: None if a is None else fptr(a)
-        check(self.lib.epnn_coulomb_xyz_cell_excl(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), fptr(cell), dptr(ewald), float(ke),
-                                                  float(alpha), len(es), iptr(ei), iptr(ej), fptr(es), fptr(q), fptr(phi), dptr(E), fptr(F),
-                                                  fptr(gs), opt(ffix), opt(fq), opt(gs_fix), opt(gs_q)), self.lib)
+        outs = [fptr(q), fptr(phi), dptr(E), fptr(F), opt(ffix), opt(fq)]
+        if periodic is not None:
+            gs = np.empty((B, 3, 3), dtype=np.float32)
+            gs_fix, gs_q = (np.empty((B, 3, 3), dtype=np.float32) if parts else None for _ in range(2))
+            outs = outs[:4] + [fptr(gs)] + outs[4:] + [opt(gs_fix), opt(gs_q)]
+        check(getattr(self.lib, "epnn_" + where)(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), *args, *outs), self.lib)
         out = (q, phi, E, F) + ((gs,) if strain else ())
         if parts:
             out += (ffix, fq) + ((gs_fix, gs_q) if strain else ())
