@@ -126,13 +126,10 @@ static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, boo
 // The listed pairs' edge gradients gE -> their coordinate slots, in the call's geometry.  (Behind its caller: kernels are emitted in the
 // order the host code first names them, and a build's device listing is compared with its parent's.)
 static void launch_gl_pair_xyz(epnn_handle *h, const GlCall &c, const float *gE, double *slotx, int *bad) {
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((c.np + 255) / 256)), dim3(256), 0, h->stream, c.L, c.np, c.d_molof, c.d_xyz, c.geo.words(),
-                           gE, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), slotx, bad);
-    };
-    if (c.geo.kind == GEO_CELL) launch(k_gl_pair_xyz<GEO_CELL>);
-    else if (c.geo.kind == GEO_BOX) launch(k_gl_pair_xyz<GEO_BOX>);
-    else launch(k_gl_pair_xyz<GEO_OPEN>);
+    geo_dispatch(c.geo.kind, [&](auto kind) {
+        hipLaunchKernelGGL(k_gl_pair_xyz<decltype(kind)::value>, dim3((unsigned)((c.np + 255) / 256)), dim3(256), 0, h->stream, c.L, c.np,
+                           c.d_molof, c.d_xyz, c.geo.words(), gE, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), slotx, bad);
+    });
 }
 
 static int charges_vjp_large_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
@@ -165,17 +162,14 @@ static int charges_vjp_large_impl(epnn_handle *h, const char *name, int B, int N
 // the edge gradients gE [B][N][N][48] -> gxyz, a wavefront per atom, in the call's geometry; share: with cells, the atoms' strain shares, or null
 static void launch_g_xyz(epnn_handle *h, int A, const float *d_xyz, const int *d_moff, int B, int N, const float *gE, float *gxyz, int *bad,
                          const DevGeo &geo, double *share) {
-    auto launch = [&](auto kernel, auto... rows) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)A), dim3(64), 0, h->stream, d_xyz, d_moff, B, N, gE, (double)h->cfg.cutoff, (double)h->cfg.eta,
-                           h->d_mu.as<double>(), gxyz, bad, rows...);
-    };
-    if (geo.kind == GEO_CELL) launch(k_g_xyz_cell, geo.cells(), share);
-    else if (geo.kind == GEO_BOX) launch(k_g_xyz_pbc, geo.box());
-    else launch(k_g_xyz);
+    geo_dispatch(geo.kind, [&](auto kind) {
+        hipLaunchKernelGGL(k_g_xyz<decltype(kind)::value>, dim3((unsigned)A), dim3(64), 0, h->stream, d_xyz, d_moff, B, N, gE,
+                           (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), gxyz, bad, geo.words(), share);
+    });
 }
 
 // name: the entry's; geo: the batch's geometry, its rows on the host (staged with the other inputs); gstrain_out [B][3][3]:
-// with cells, the strain derivative (k_g_xyz_cell / k_g_strain_mol), or null.
+// with cells, the strain derivative (k_g_xyz<GEO_CELL> / k_g_strain_mol), or null.
 static int charges_vjp_xyz_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                 const float *g, float *q_out, float *gxyz_out, const HostGeo &geo, float *gstrain_out) {
     for (int b = 0; b < B; ++b)

@@ -25,15 +25,15 @@ static void jvm_bucket(int K, Launch &&launch) {
     else launch(std::integral_constant<int, 16>{});
 }
 
-// The listed pairs' edge tangents te in the call's geometry: open molecules or cells, as the entries take (charges_jvp_multi_impl refuses box rows)
+// The listed pairs' edge tangents te in the call's geometry: open molecules or cells (charges_jvp_multi_impl refuses box rows: no box instance)
 template <int KM>
 static void launch_jvm_edge(epnn_handle *h, const GlCall &c, int K, int B, const float *d_v, const float *d_E, float *te, int *bad) {
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((c.np + 255) / 256)), dim3(256), 0, h->stream, c.L, c.np, c.d_molof, c.d_xyz, c.geo.words(), K,
-                           c.G.A, B, d_v, d_E, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), te, c.P1 * GL_E, bad);
-    };
-    if (c.geo.kind == GEO_CELL) launch(k_jvm_edge<GEO_CELL, KM>);
-    else launch(k_jvm_edge<GEO_OPEN, KM>);
+    geo_dispatch(c.geo.kind, [&](auto kind) {
+        if constexpr (decltype(kind)::value != GEO_BOX)
+            hipLaunchKernelGGL((k_jvm_edge<decltype(kind)::value, KM>), dim3((unsigned)((c.np + 255) / 256)), dim3(256), 0, h->stream, c.L, c.np,
+                               c.d_molof, c.d_xyz, c.geo.words(), K, c.G.A, B, d_v, d_E, (double)h->cfg.cutoff, (double)h->cfg.eta,
+                               h->d_mu.as<double>(), te, c.P1 * GL_E, bad);
+    });
 }
 
 // K tangents beside the one primal; the single-tangent entry is K = 1.  The call shares the pair-list gradient path's state

@@ -1,22 +1,20 @@
 // train_step (charge_gn.py:393-402): entry points, hipGraph replay, the RCCL communicator and its collectives; debug exports.
 // Part of the one translation unit epnn_api.hip.
 #pragma once
+#include "epnn_pair_geo.hip.h"
 
 // ------------------------------------------------------------------------------------------------ training
 // dense (B,N,N,.) make_model inputs from a flat coordinate batch: what gen_padded_init_state builds on the host
 // the body: `in(k)` reads word k of the staged block  offsets | xyz | x | Q | y  (word offsets o_*), wherever that block is
-// PBC 1: minimum-image distances in the cells box [B][3] at word o_box of the block (epnn_charges_vjp_xyz_pbc); PBC 2: in the
-// general cells `cells` [B] (epnn_charges_vjp_xyz_cell)
-template <int PBC = 0, typename IN>
+// GEO (GeoKind): the image of every displacement in the rows `geo` in device memory, box rows [B][3] or EpnnCell records [B]; open: none
+template <int GEO = 0, typename IN>
 __device__ __forceinline__ void t_pad_inputs_body(IN &&in, int o_xyz, int o_x, int o_Q, int o_y, int B, int N, int nx, int E, double cutoff,
                                                   double eta, const double *mu, float *e, float *mask, float *xs, float *hs, float *qs,
-                                                  float *ys, int *real_out, int *moff_out, int o_box = 0,
-                                                  const EpnnCell *cells = nullptr) {
+                                                  float *ys, int *real_out, int *moff_out, const float *geo = nullptr) {
     // a thread per (pair, four channels): one thread per pair was 48 double-precision exp in a row on 7 workgroups (13 us of a
     // 0.27 ms one-molecule step); the distance and the cutoff are recomputed by the 12 threads of a pair
     const size_t pairs = (size_t)B * N * N;
     const int G = (E + 3) / 4;
-    const double pi_d = 3.141592653589793;
     if (moff_out && blockIdx.x == 0 && (int)threadIdx.x <= B) moff_out[threadIdx.x] = __float_as_int(in((int)threadIdx.x));
     for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < pairs * G; it += (size_t)gridDim.x * 256) {
         const size_t r = it / G;
@@ -27,32 +25,21 @@ __device__ __forceinline__ void t_pad_inputs_body(IN &&in, int o_xyz, int o_x, i
         if (cg == 0) mask[r] = real ? 1.f : 0.f;
         double D = 0, Cc = 0;
         if (real) {
-            // distance exactly as scipy.spatial.distance_matrix on float32 coordinates promoted to float64 (epnn_dist)
+            // distance exactly as scipy.spatial.distance_matrix on float32 coordinates promoted to float64 (pair_dist)
             const int pi_ = o_xyz + 3 * (a0 + i), pj_ = o_xyz + 3 * (a0 + j);
             double dx = (double)in(pj_) - (double)in(pi_), dy = (double)in(pj_ + 1) - (double)in(pi_ + 1),
                    dz = (double)in(pj_ + 2) - (double)in(pi_ + 2);
-            if (PBC == 2) {
-                const EpnnCell &c = cells[b];
-                double g[9], av[9];
-#pragma unroll
-                for (int k = 0; k < 9; ++k) { g[k] = c.g[k]; av[k] = (double)c.a[k]; }
-                epnn_mic_cell(dx, dy, dz, g, av);
-            }
-            if (PBC == 1) {
-                dx = epnn_mic(dx, (double)in(o_box + 3 * b));
-                dy = epnn_mic(dy, (double)in(o_box + 3 * b + 1));
-                dz = epnn_mic(dz, (double)in(o_box + 3 * b + 2));
-            }
-            D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
-            Cc = (cos(pi_d * (D - 0.0) / cutoff) + 1.0) / 2.0;
+            PairGeo<GEO> pg;
+            pg.load_lane(geo, b);                     // (a workgroup's threads span molecules)
+            pg.image(dx, dy, dz);
+            D = pair_dist(dx, dy, dz);
+            Cc = edge_cut(D, cutoff);
             if (D >= cutoff) Cc = 0.0;
             if (D <= 0.0) Cc = 1.0;
             if (i == j) Cc = 0.0;
         }
-        for (int ch = 4 * cg; ch < min(E, 4 * cg + 4); ++ch) {
-            const double d = D - mu[ch];
-            e[r * E + ch] = real ? (float)(Cc * exp(-eta * (d * d))) : 0.f;
-        }
+        for (int ch = 4 * cg; ch < min(E, 4 * cg + 4); ++ch)
+            e[r * E + ch] = real ? (float)(Cc * edge_gauss(D - mu[ch], eta)) : 0.f;
         if (j == 0 && cg == 0) {
             const size_t at = (size_t)b * N + i;
             for (int f = 0; f < nx; ++f) xs[at * nx + f] = i < n ? in(o_x + (a0 + i) * nx + f) : 0.f;
@@ -63,25 +50,17 @@ __device__ __forceinline__ void t_pad_inputs_body(IN &&in, int o_xyz, int o_x, i
         }
     }
 }
-// the staged block in device memory (uploaded before the launch)
+// the staged block in device memory (uploaded before the launch); geo: the geometry's rows in it (8-byte aligned for cells), or null
+template <int GEO>
 __global__ __launch_bounds__(256) void k_t_pad_inputs(const float *blk, int o_xyz, int o_x, int o_Q, int o_y, int B, int N, int nx, int E,
                                                       double cutoff, double eta, const double *mu, float *e, float *mask, float *xs,
-                                                      float *hs, float *qs, float *ys, int *real_out) {
-    t_pad_inputs_body([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys, real_out, nullptr);
+                                                      float *hs, float *qs, float *ys, int *real_out, const float *geo) {
+    t_pad_inputs_body<GEO>([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys,
+                           real_out, nullptr, geo);
 }
-__global__ __launch_bounds__(256) void k_t_pad_inputs_pbc(const float *blk, int o_xyz, int o_x, int o_Q, int o_y, int o_box, int B, int N,
-                                                          int nx, int E, double cutoff, double eta, const double *mu, float *e, float *mask,
-                                                          float *xs, float *hs, float *qs, float *ys, int *real_out) {
-    t_pad_inputs_body<1>([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys,
-                         real_out, nullptr, o_box);
-}
-// o_cell: the word (a multiple of 2) at which the EpnnCell records of the B molecules start
-__global__ __launch_bounds__(256) void k_t_pad_inputs_cell(const float *blk, int o_xyz, int o_x, int o_Q, int o_y, int o_cell, int B, int N,
-                                                           int nx, int E, double cutoff, double eta, const double *mu, float *e, float *mask,
-                                                           float *xs, float *hs, float *qs, float *ys, int *real_out) {
-    t_pad_inputs_body<2>([&](int k) { return blk[k]; }, o_xyz, o_x, o_Q, o_y, B, N, nx, E, cutoff, eta, mu, e, mask, xs, hs, qs, ys,
-                         real_out, nullptr, 0, reinterpret_cast<const EpnnCell *>(blk + o_cell));
-}
+template __global__ decltype(k_t_pad_inputs<0>) k_t_pad_inputs<0>;          // (here, in this order: the device listing keeps their place, see k_g_xyz)
+template __global__ decltype(k_t_pad_inputs<1>) k_t_pad_inputs<1>;
+template __global__ decltype(k_t_pad_inputs<2>) k_t_pad_inputs<2>;
 // ... or riding in the kernel's own argument block (up to 3.6 KB: one molecule of up to ~69 atoms): no upload, i.e. no copy kernel
 // and no launch boundary in front of the step (5 us of a 0.22 ms one-molecule step); the offsets are left in device memory for the
 // step's kernels (moff_out)
@@ -429,17 +408,15 @@ static int dense_in_ensure(epnn_handle *h, const DenseIn &L) {
            h->sd_mask.ensure(L.pairs * 4) || h->dn_xs.ensure(L.slots * h->cfg.nx * 4) || h->dn_hs.ensure(L.slots * EPNN_EDIM * 4) ||
            h->dn_qs.ensure(L.slots * 4) || h->sd_out.ensure(L.slots * 4) || h->tr_realbuf.ensure(L.slots * 4);
 }
-// the padding kernel on the uploaded block: the entry point of the geometry's kind (a periodic one takes the word its rows start at)
-static void launch_pad_inputs(epnn_handle *h, const DenseIn &L, int B, int N, GeoKind kind) {
-    auto launch = [&](auto kernel, auto... w_geo) {
-        hipLaunchKernelGGL(kernel, dim3(L.pgrid), dim3(256), 0, h->stream, h->s_train.as<float>(), (int)(L.o_xyz / 4), (int)(L.o_x / 4),
-                           (int)(L.o_Q / 4), (int)(L.o_y / 4), w_geo..., B, N, h->cfg.nx, h->cfg.e_dim, (double)h->cfg.cutoff, (double)h->cfg.eta,
-                           h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(), h->dn_xs.as<float>(), h->dn_hs.as<float>(),
-                           h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>());
-    };
-    if (kind == GEO_CELL) launch(k_t_pad_inputs_cell, (int)(L.o_geo / 4));
-    else if (kind == GEO_BOX) launch(k_t_pad_inputs_pbc, (int)(L.o_geo / 4));
-    else launch(k_t_pad_inputs);
+// the padding kernel on the uploaded block, in the geometry whose rows were uploaded with it
+static void launch_pad_inputs(epnn_handle *h, const DenseIn &L, int B, int N, const DevGeo &geo) {
+    geo_dispatch(geo.kind, [&](auto kind) {
+        hipLaunchKernelGGL(k_t_pad_inputs<decltype(kind)::value>, dim3(L.pgrid), dim3(256), 0, h->stream, h->s_train.as<float>(),
+                           (int)(L.o_xyz / 4), (int)(L.o_x / 4), (int)(L.o_Q / 4), (int)(L.o_y / 4), B, N, h->cfg.nx, h->cfg.e_dim,
+                           (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), h->sd_e.as<float>(), h->sd_mask.as<float>(),
+                           h->dn_xs.as<float>(), h->dn_hs.as<float>(), h->dn_qs.as<float>(), h->sd_out.as<float>(), h->tr_realbuf.as<int>(),
+                           geo.words());
+    });
 }
 // The copies into page-locked memory (labels(slot) writes the A words of the label section: what it holds is the caller's), the
 // upload and the padding launch, after dense_in_ensure.  (The previous call on these buffers ended with a stream synchronisation.)
@@ -455,7 +432,7 @@ static int dense_in_stage(epnn_handle *h, const DenseIn &L, int B, int N, const 
     labels(reinterpret_cast<float *>(stage + L.o_y));
     if (geo.periodic()) memcpy(stage + L.o_geo, geo.rows, geo.bytes(B));
     HIPCHK(hipMemcpyAsync(h->s_train.p, stage, L.in_bytes, hipMemcpyHostToDevice, h->stream));
-    launch_pad_inputs(h, L, B, N, geo.kind);
+    launch_pad_inputs(h, L, B, N, geo_on_device(geo, h->s_train.as<char>() + L.o_geo));
     return 0;
 }
 

@@ -18,7 +18,7 @@
 // No atomics on floats; the only atomic is the OR into the coincident-atoms flag.
 #pragma once
 #include "epnn_host.h"
-#include "epnn_frontend.hip.h"
+#include "epnn_pair_geo.hip.h"
 
 #define CL_BLOCK 64               // atoms of a task: one per lane
 #define CL_TILE 64                // partners staged in LDS at a time: one per lane
@@ -87,11 +87,10 @@ __device__ __forceinline__ void cl_sweep_body(const int4 *tasks, const int *moff
     const bool valid = lane < na;
     const int i = tk.x + (valid ? lane : 0);
     const int b = mol_of[i], lo = moff[b], hi = moff[b + 1];
-    double g[9], a[9];
+    PairGeo<CELL ? 2 : 0> pg;
+    pg.load_lane(cells, b);                                      // (packed molecules: b differs between the lanes)
     float rc = 0.f, beta = 0.f;
     if constexpr (CELL) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { g[k] = cells[b].g[k]; a[k] = (double)cells[b].a[k]; }
         rc = ew[b].rc;
         beta = ew[b].beta;
     }
@@ -112,7 +111,7 @@ __device__ __forceinline__ void cl_sweep_body(const int4 *tasks, const int *moff
         for (int jj = 0; jj < cnt; ++jj) {
             const int j = t0 + jj;
             double ex = xi - tx[jj], ey = yi - ty[jj], ez = zi - tz[jj];
-            if (CELL) epnn_mic_cell(ex, ey, ez, g, a);
+            pg.image(ex, ey, ez);
             const float dx = (float)ex, dy = (float)ey, dz = (float)ez, qj = tq[jj];
             const float r2 = dx * dx + dy * dy + dz * dz;
             const bool use = valid && j != i && j >= lo && j < hi;        // the self term goes by index
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(64) void k_cl_energy(const double *share, const int
 #define CL_FLAG_FAR 2             // bit 1: a listed pair of a cell beyond half the smallest perpendicular width
 
 // One atom per lane, 64 atoms per wavefront; a lane walks its CSR row in partner order.  Displacement: the float64 difference of the
-// float32 coordinates, through epnn_mic_cell when CELL, rounded once.  Sums float64: xpart [A][4] = (sum f q_j kappa, sum f q_j g dx /
+// float32 coordinates, through the cell's image (PairGeo) when CELL, rounded once.  Sums float64: xpart [A][4] = (sum f q_j kappa, sum f q_j g dx /
 // D^3, .. dy, .. dz), f the row's factor; CELL: xpart [A][10], the six virial sums f q_j g d_a d_b / D^3 (xx yy zz yz xz xy) behind
 // them, in the order of the periodic sweep's row.  Each word is written by exactly one lane; the only atomic is the OR into the flag word.
 // cells: the batch's EpnnCell records (CELL), from which every lane takes half the smallest width, 1 / (2 max_k |g_k|).
@@ -203,15 +202,13 @@ __global__ __launch_bounds__(64) void k_cl_excl(int A, const int *mol_of, const 
     constexpr int NS = CELL ? 10 : CL_XPART;
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= A) return;
-    double g[9], a[9];
+    PairGeo<CELL ? 2 : 0> pg;
     float half_w = 0.f;
-    if (CELL) {
-        const EpnnCell &c = cells[mol_of[i]];
+    if constexpr (CELL) {
+        pg.load_lane(cells, mol_of[i]);
         double g2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) { g[k] = c.g[k]; a[k] = (double)c.a[k]; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) g2 = fmax(g2, g[3 * k] * g[3 * k] + g[3 * k + 1] * g[3 * k + 1] + g[3 * k + 2] * g[3 * k + 2]);
+        for (int k = 0; k < 9; k += 3) g2 = fmax(g2, pg.g[k] * pg.g[k] + pg.g[k + 1] * pg.g[k + 1] + pg.g[k + 2] * pg.g[k + 2]);
         half_w = (float)(0.5 / sqrt(g2));
     }
     const double xi = (double)xyz[3 * (size_t)i], yi = (double)xyz[3 * (size_t)i + 1], zi = (double)xyz[3 * (size_t)i + 2];
@@ -223,7 +220,7 @@ __global__ __launch_bounds__(64) void k_cl_excl(int A, const int *mol_of, const 
         const size_t j = (size_t)partner[k];
         const float fac = factor[k], qj = q[j];
         double ex = xi - (double)xyz[3 * j], ey = yi - (double)xyz[3 * j + 1], ez = zi - (double)xyz[3 * j + 2];
-        if (CELL) epnn_mic_cell(ex, ey, ez, g, a);
+        pg.image(ex, ey, ez);
         const float dx = (float)ex, dy = (float)ey, dz = (float)ez;
         const float r2 = dx * dx + dy * dy + dz * dz;
         if (r2 == 0.f) flag |= CL_FLAG_ZERO;

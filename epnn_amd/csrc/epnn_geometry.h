@@ -107,7 +107,7 @@ struct GeoRows {
     const char *raw() const { return static_cast<const char *>(rows); }          // the rows as bytes, for copies
     const float *box() const { return static_cast<const float *>(rows); }
     const EpnnCell *cells() const { return static_cast<const EpnnCell *>(rows); }
-    const float *words() const { return static_cast<const float *>(rows); }      // either kind's rows as k_gl_pair_xyz and k_jvm_edge take them
+    const float *words() const { return static_cast<const float *>(rows); }      // either kind's rows as the GeoKind-templated kernels take them
 };
 using HostGeo = GeoRows<false>;
 using DevGeo = GeoRows<true>;
@@ -125,6 +125,14 @@ struct GeoArg {
 }
 // the same geometry with its rows at `d_rows` on the device (open molecules have none)
 static inline DevGeo geo_on_device(const HostGeo &g, const void *d_rows) { return DevGeo{g.kind, g.periodic() ? d_rows : nullptr}; }
+
+// A runtime kind as a compile-time constant, f(std::integral_constant<int, kind>): for the kernels templated on the GeoKind (rows: words())
+template <class F>
+static inline void geo_dispatch(GeoKind kind, F &&f) {
+    if (kind == GEO_CELL) f(std::integral_constant<int, GEO_CELL>{});
+    else if (kind == GEO_BOX) f(std::integral_constant<int, GEO_BOX>{});
+    else f(std::integral_constant<int, GEO_OPEN>{});
+}
 
 // ---- the front-end's kernel families, each launched at the entry point of the geometry's kind.  The two passes of the pair list
 // (a workgroup per four atoms): the rows' counts with their prefix sums, then the pairs' records with their incidence links

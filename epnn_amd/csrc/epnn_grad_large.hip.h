@@ -30,7 +30,7 @@
 // epnn_forward_xyz to float32 accumulation (2e-4 in the tests), not bit for bit, like the dense path's.
 #pragma once
 #include "epnn_host.h"
-#include "epnn_frontend.hip.h"
+#include "epnn_pair_geo.hip.h"
 
 #define GL_H 32                   // hidden width of every MLP, and of the summed messages
 #define GL_E 48                   // channels of h and e
@@ -508,8 +508,8 @@ __global__ __launch_bounds__(64) void k_gl_epn_atom_bwd(GlPair M, GlGeom G, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------- edges -> coordinates
-// One thread per listed pair: the displacement d = image of r_j - r_i and D in float64 exactly as the front-end measures them (GEO 0
-// open, 1 box rows [B][3], 2 EpnnCell records [B]), gD = sum_k gE_k de_k/dD, w = gD / D; the first atom's slot gets -w d, the
+// One thread per listed pair: the displacement d = image of r_j - r_i and D in float64 as the front-end measures them (PairGeo<GEO>,
+// pair_dist: GEO 0 open, 1 box rows [B][3], 2 EpnnCell records [B]), gD = sum_k gE_k de_k/dD, w = gD / D; the first atom's slot gets -w d, the
 // second's +w d (d D / d r_i = (r_i - r_j) / D), and with strain each gets half of w d_a d_c (xx, yy, zz, yz, xz, xy).
 // slotx [slots][9] float64.  bad: bit 0 = two atoms or images coincide, bit 1 = a pair without both slots (atomicOr: the word does
 // not depend on which thread comes last).
@@ -521,25 +521,18 @@ __global__ __launch_bounds__(256) void k_gl_pair_xyz(GlPairs L, int npairs, cons
     const int i = L.pi[p], j = L.pj[p], b = mol_of[i];
     double dx = (double)xyz[3 * j] - (double)xyz[3 * i], dy = (double)xyz[3 * j + 1] - (double)xyz[3 * i + 1],
            dz = (double)xyz[3 * j + 2] - (double)xyz[3 * i + 2];
-    if (GEO == 1) {
-        dx = epnn_mic(dx, (double)geo[3 * b]); dy = epnn_mic(dy, (double)geo[3 * b + 1]); dz = epnn_mic(dz, (double)geo[3 * b + 2]);
-    }
-    if (GEO == 2) {
-        const EpnnCell &c = reinterpret_cast<const EpnnCell *>(geo)[b];
-        double a[9];
-        for (int k = 0; k < 9; ++k) a[k] = (double)c.a[k];
-        epnn_mic_cell(dx, dy, dz, c.g, a);
-    }
-    const double D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
+    PairGeo<GEO> pg;
+    pg.load_lane(geo, b);
+    pg.image(dx, dy, dz);
+    const double D = pair_dist(dx, dy, dz);
     double w = 0.0;
     if (!(D > 0.0)) atomicOr(bad, 1);
     else if (D < cutoff) {
-        const double pi_d = 3.141592653589793;
-        const double C = (cos(pi_d * D / cutoff) + 1.0) / 2.0, dC = -0.5 * (pi_d / cutoff) * sin(pi_d * D / cutoff);
+        const double C = edge_cut(D, cutoff), dC = edge_dcut(D, cutoff);
         double gD = 0.0;
         for (int k = 0; k < GL_E; ++k) {
-            const double u = D - mu[k], ex = exp(-eta * (u * u));
-            gD += (double)gE[(size_t)p * GL_E + k] * (dC - 2.0 * eta * u * C) * ex;
+            const double u = D - mu[k];
+            gD += (double)gE[(size_t)p * GL_E + k] * edge_slope(C, dC, u, eta) * edge_gauss(u, eta);
         }
         w = gD / D;
     }

@@ -13,7 +13,7 @@
 // depend on the other molecules of a batch.
 #pragma once
 #include "epnn_host.h"
-#include "epnn_frontend.hip.h"
+#include "epnn_pair_geo.hip.h"
 #include "epnn_train_fused.hip.h"
 
 struct TrainState;
@@ -82,19 +82,18 @@ __global__ __launch_bounds__(256) void k_g_edge_dz1(const float *dz1, const floa
 }
 
 // Edge-featurisation backward: one wavefront per real atom (a = moff[b] + i).  Lane j (and j + 64, ...) forms the pair (i, j):
-// D from the float32 coordinates in double exactly as k_t_pad_inputs does, gD_ij + gD_ji over the 48 channels, and its
-// contribution (gD_ij + gD_ji) (r_i - r_j) / D; the lanes' sums are combined by a fixed butterfly.  bad: set when two atoms of a
-// molecule coincide (D = 0: the distance has no derivative there).  PBC: minimum-image displacements in the cells box [B][3]
-// (their derivative is that of the unwrapped displacement: the image shift is a constant).  PBC 2: in the general cells that box
-// points to (EpnnCell [B]).
-// Strain derivative (PBC 2, strain != null): under r -> (1 + eps) r, a_k -> (1 + eps) a_k every image displacement d' becomes
+// the image and D as every path measures them (epnn_pair_geo.hip.h), gD_ij + gD_ji over the 48 channels, and its contribution
+// (gD_ij + gD_ji) (r_i - r_j) / D; the lanes' sums are combined by a fixed butterfly.  bad: set when two atoms of a molecule
+// coincide (D = 0: the distance has no derivative there).  GEO (GeoKind) 1: minimum-image displacements in the box rows geo [B][3]
+// (their derivative is that of the unwrapped displacement: the image shift is a constant); 2: in the EpnnCell records geo [B].
+// Strain derivative (GEO 2, strain != null): under r -> (1 + eps) r, a_k -> (1 + eps) a_k every image displacement d' becomes
 // (1 + eps) d', so dD/d eps_ac = d'_a d'_c / D and, with F = sum_i g_i q_i,
 //     dF/d eps_ac = sum over pairs i < j with D < cutoff of (gD_ij + gD_ji) d'_a d'_c / D.
 // This wavefront sees each of its atom's pairs, the partner's wavefront sees them again: the atom's share is half the sum over its
 // partners, kept in float64 as strain[a][xx, yy, zz, yz, xz, xy]; k_g_strain_mol adds a molecule's atoms up.
-template <int PBC>
-__device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff, double eta,
-                                           const double *mu, float *gxyz, int *bad, const float *box, double *strain = nullptr) {
+template <int GEO>
+__global__ __launch_bounds__(64) void k_g_xyz(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff, double eta,
+                                              const double *mu, float *gxyz, int *bad, const float *geo, double *strain) {
     const int a = blockIdx.x, lane = threadIdx.x;
     int lo = 0, hi = B;                               // molecule b: moff[b] <= a < moff[b + 1]
     while (hi - lo > 1) {
@@ -102,35 +101,31 @@ __device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, in
         if (moff[mid] <= a) lo = mid; else hi = mid;
     }
     const int b = lo, a0 = moff[b], n = moff[b + 1] - a0, i = a - a0;
-    const double pi_d = 3.141592653589793;
     const double xi = xyz[3 * a], yi = xyz[3 * a + 1], zi = xyz[3 * a + 2];
-    double Lx = 0.0, Ly = 0.0, Lz = 0.0;
-    if (PBC == 1) { Lx = (double)box[3 * b]; Ly = (double)box[3 * b + 1]; Lz = (double)box[3 * b + 2]; }
-    EpnnCellD cr;
-    if (PBC == 2) cr.load(reinterpret_cast<const EpnnCell *>(box), b);
+    PairGeo<GEO> pg;
+    pg.load_uniform(geo, b);
     double s[3] = {0.0, 0.0, 0.0};
     double W[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int j = lane; j < n; j += 64) {
         if (j == i) continue;
         const int aj = a0 + j;
         double dx = (double)xyz[3 * aj] - xi, dy = (double)xyz[3 * aj + 1] - yi, dz = (double)xyz[3 * aj + 2] - zi;
-        if (PBC == 1) { dx = epnn_mic(dx, Lx); dy = epnn_mic(dy, Ly); dz = epnn_mic(dz, Lz); }
-        if (PBC == 2) epnn_mic_cell(dx, dy, dz, cr.g, cr.a);
-        const double D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
+        pg.image(dx, dy, dz);
+        const double D = pair_dist(dx, dy, dz);
         if (!(D > 0.0)) { *bad = 1; continue; }
         if (D >= cutoff) continue;                    // C = 0 and C' = 0 beyond the cutoff
-        const double C = (cos(pi_d * D / cutoff) + 1.0) / 2.0, dC = -0.5 * (pi_d / cutoff) * sin(pi_d * D / cutoff);
+        const double C = edge_cut(D, cutoff), dC = edge_dcut(D, cutoff);
         const float *gij = gE + (((size_t)b * N + i) * N + j) * 48, *gji = gE + (((size_t)b * N + j) * N + i) * 48;
         double gD = 0.0;
         for (int k = 0; k < 48; ++k) {
-            const double u = D - mu[k], ex = exp(-eta * (u * u));
-            gD += ((double)gij[k] + (double)gji[k]) * (dC - 2.0 * eta * u * C) * ex;
+            const double u = D - mu[k];
+            gD += ((double)gij[k] + (double)gji[k]) * edge_slope(C, dC, u, eta) * edge_gauss(u, eta);
         }
         const double w = gD / D;                      // d D_ij / d r_i = (r_i - r_j) / D
         s[0] -= w * dx;
         s[1] -= w * dy;
         s[2] -= w * dz;
-        if (PBC == 2 && strain) {
+        if (GEO == 2 && strain) {
             const double hw = 0.5 * w;
             W[0] += hw * dx * dx; W[1] += hw * dy * dy; W[2] += hw * dz * dz;
             W[3] += hw * dy * dz; W[4] += hw * dx * dz; W[5] += hw * dx * dy;
@@ -143,7 +138,7 @@ __device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, in
         s[c] = v;
     }
     if (lane < 3) gxyz[3 * a + lane] = (float)(lane == 0 ? s[0] : (lane == 1 ? s[1] : s[2]));
-    if (PBC == 2 && strain) {
+    if (GEO == 2 && strain) {
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
             double v = W[c];
@@ -152,20 +147,10 @@ __device__ __forceinline__ void g_xyz_body(const float *xyz, const int *moff, in
         }
     }
 }
-__global__ __launch_bounds__(64) void k_g_xyz(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
-                                              double eta, const double *mu, float *gxyz, int *bad) {
-    g_xyz_body<0>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, nullptr);
-}
-__global__ __launch_bounds__(64) void k_g_xyz_pbc(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
-                                                  double eta, const double *mu, float *gxyz, int *bad, const float *box) {
-    g_xyz_body<1>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, box);
-}
-__global__ __launch_bounds__(64) void k_g_xyz_cell(const float *xyz, const int *moff, int B, int N, const float *gE, double cutoff,
-                                                   double eta, const double *mu, float *gxyz, int *bad, const EpnnCell *cells,
-                                                   double *strain) {
-    g_xyz_body<2>(xyz, moff, B, N, gE, cutoff, eta, mu, gxyz, bad, reinterpret_cast<const float *>(cells), strain);
-}
-// The per-atom strain shares of k_g_xyz_cell summed per molecule, one wavefront each: lane l adds atoms l, l + 64, ... of the
+template __global__ decltype(k_g_xyz<0>) k_g_xyz<0>;              // (here, in this order: the device listing keeps the kernels' places)
+template __global__ decltype(k_g_xyz<1>) k_g_xyz<1>;
+template __global__ decltype(k_g_xyz<2>) k_g_xyz<2>;
+// The per-atom strain shares of k_g_xyz<2> summed per molecule, one wavefront each: lane l adds atoms l, l + 64, ... of the
 // molecule in ascending order, a fixed butterfly combines the lanes (no atomics: bit-reproducible, and a molecule's result does not
 // depend on the rest of the batch).  out [B][3][3] float32, the full symmetric matrix.
 __global__ __launch_bounds__(64) void k_g_strain_mol(const double *strain, const int *moff, float *out) {

@@ -53,7 +53,7 @@ __device__ __forceinline__ void jvm_dotT(const float *W, int stride, int col, co
 }
 
 // ---------------------------------------------------------------------------------------------------------- edge tangents
-// One thread per listed pair, the displacement d' and D in float64 exactly as k_gl_pair_xyz (and the front-end) measure them; d', D
+// One thread per listed pair, the displacement d' and D in float64 from PairGeo<GEO> and pair_dist, as k_gl_pair_xyz takes them; d', D
 // and de/dD once, tD and te per tangent (tD in LDS, a thread's column; in a register at KM = 1).  v [K][A][3] or null,
 // E [K][B][3][3] or null, te [K][P1][48] float32 (te_stride = P1 * 48).  bad: bit 0 = two atoms or images coincide, bit 1 = a pair
 // without both incidence slots.
@@ -73,16 +73,10 @@ __global__ __launch_bounds__(256) void k_jvm_edge(GlPairs L, int npairs, const i
     const int i = L.pi[p], j = L.pj[p], b = mol_of[i];
     double dx = (double)xyz[3 * j] - (double)xyz[3 * i], dy = (double)xyz[3 * j + 1] - (double)xyz[3 * i + 1],
            dz = (double)xyz[3 * j + 2] - (double)xyz[3 * i + 2];
-    if (GEO == 1) {
-        dx = epnn_mic(dx, (double)geo[3 * b]); dy = epnn_mic(dy, (double)geo[3 * b + 1]); dz = epnn_mic(dz, (double)geo[3 * b + 2]);
-    }
-    if (GEO == 2) {
-        const EpnnCell &c = reinterpret_cast<const EpnnCell *>(geo)[b];
-        double a[9];
-        for (int k = 0; k < 9; ++k) a[k] = (double)c.a[k];
-        epnn_mic_cell(dx, dy, dz, c.g, a);
-    }
-    const double D = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
+    PairGeo<GEO> pg;
+    pg.load_lane(geo, b);
+    pg.image(dx, dy, dz);
+    const double D = pair_dist(dx, dy, dz);
     if (L.dest_i[p] < 0 || L.dest_j[p] < 0) atomicOr(bad, 2);
     float *row = te + (size_t)p * GL_E;
     if (!(D > 0.0)) atomicOr(bad, 1);
@@ -106,11 +100,10 @@ __global__ __launch_bounds__(256) void k_jvm_edge(GlPairs L, int npairs, const i
         }
         tD(t) = num / D;
     }
-    const double pi_d = 3.141592653589793;
-    const double C = (cos(pi_d * D / cutoff) + 1.0) / 2.0, dC = -0.5 * (pi_d / cutoff) * sin(pi_d * D / cutoff);
+    const double C = edge_cut(D, cutoff), dC = edge_dcut(D, cutoff);
     for (int k = 0; k < GL_E; ++k) {
-        const double u = D - mu[k], ex = exp(-eta * (u * u));
-        const double de = (dC - 2.0 * eta * u * C) * ex;
+        const double u = D - mu[k];
+        const double de = edge_slope(C, dC, u, eta) * edge_gauss(u, eta);
         for (int t = 0; t < K; ++t) row[t * te_stride + k] = (float)(de * tD(t));
     }
 }
