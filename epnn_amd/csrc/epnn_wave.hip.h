@@ -162,26 +162,29 @@ typedef __bf16 w16_bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f32x4 w16_mfma_bf(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(w16_bf16x8, a), __builtin_bit_cast(w16_bf16x8, b), c, 0, 0, 0);
 }
-// The remainders of a split on the MATRIX pipe (tools/micro/bf16x6.hip: exact, the pipe adds C unrounded).  With four values packed
-// as the B operand of v_mfma_f32_16x16x16_bf16 (lane 16 q + m: column m, K slots 4 q + s = its values v[s]) and the values themselves
-// as the accumulator (rows 4 q + r = v[r]), D = C + A B with A = -I (lane 16 qa + ma holds -1 in slot ma % 4 when qa = ma / 4) is
-// "x - piece" in place: 2 MFMAs per 8 values and level instead of 8 v_and + 8 v_sub -- 12 vector instructions per split instead
-// of 44, the SAME pieces bit for bit (round 5: bench 321 -> 327 M atoms/s; protein 0.382 -> 0.372 ms with the tiled sweep's own
-// arrangement, epnn_large.hip.h).  The K = 16 instruction's operand is two registers (a row block's four values are two dwords of
-// the packed piece), the same for both row blocks.  (It was taken for half the pipe time of the K = 32 one; the counters say it
-// keeps the pipe busy just as long, 16 cycles: profiles/r18_k16_pairs.txt section 2.)
+// The remainders of a split on the MATRIX pipe (tools/micro/bf16x6.hip: exact, the pipe adds C unrounded).
+// v_mfma_f32_4x4x4_16b_bf16 is sixteen independent 4x4x4 products: lane 4 b + i holds row i of block b's A, column i of its B (the
+// four K slots as two dwords of bf16 pairs, even slot low) and column i of its C / D (rows 0..3 in four registers).  With A = -I in
+// every block (lane 4 b + i: -1 in K slot i), a lane's four values as its accumulator and their packed upper halves as its B
+// operand, D[r] = C[r] - B[r] is "x - piece" in place and INSIDE the lane: nothing has to agree between the accumulator's layout
+// and the B operand's, whatever rows and columns the four values stand for.  2 MFMAs per 8 values and level instead of 8 v_and +
+// 8 v_sub -- 12 vector instructions per split instead of 44, the SAME pieces bit for bit (round 5: bench 321 -> 327 M atoms/s;
+// protein 0.382 -> 0.372 ms with the tiled sweep's own arrangement, epnn_large.hip.h).  The operand is two registers (four values
+// are two dwords of the packed piece), the same -I for every use.  (Until round 21 this was v_mfma_f32_16x16x16_bf16 with A = -I
+// over the whole 16x16 tile, which holds the pipe as long as a 16x16x32: what the 4x4x4 form costs beside it is measured in
+// profiles/r21_rem4x4.txt; the K = 16 form lives on in the micro tool, as the thing compared against.)
 typedef short w16_s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned w16_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ w16_u32x2 w16_ident() {
-    const int lane = threadIdx.x & 63, qa = lane >> 4, ma = lane & 15;
+    const int i = threadIdx.x & 3;
     w16_u32x2 I;
 #pragma unroll
-    for (int d = 0; d < 2; ++d) I[d] = (qa == (ma >> 2) && d == ((ma & 3) >> 1)) ? (0xbf80u << (16 * (ma & 1))) : 0u;
+    for (int d = 0; d < 2; ++d) I[d] = (d == (i >> 1)) ? (0xbf80u << (16 * (i & 1))) : 0u;
     return I;
 }
-// x - piece for one row block: p_lo | p_hi = the two dwords of the packed piece that hold the block's four values
+// x - piece for four values of a lane: p_lo | p_hi = the two dwords of the packed piece that hold them
 __device__ __forceinline__ f32x4 w16_rem(w16_u32x2 I, unsigned p_lo, unsigned p_hi, f32x4 x) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(w16_s16x4, I), __builtin_bit_cast(w16_s16x4, w16_u32x2{p_lo, p_hi}), x, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(w16_s16x4, I), __builtin_bit_cast(w16_s16x4, w16_u32x2{p_lo, p_hi}), x, 0, 0, 0);
 }
 __device__ __forceinline__ u32x4 w16_pack_hi(const f32x4 &lo, const f32x4 &hi) {      // v_perm_b32: the upper halves of two floats side by side
     u32x4 p;
@@ -243,7 +246,7 @@ __device__ __forceinline__ void w16_mm_bf(const u32x4 (&w)[2][3], u32x4 z1, u32x
             (dst)[rb_][pc_] = reinterpret_cast<const u32x4 *>(wp + (size_t)(unsigned)(off))[(rb_ * 3 + pc_) * 64 + lane];
 // ---- the same at K = 16: operands of up to 16 values -- the pair coordinates of a G product and the xq block
 // (node mask, one, charge, x: wave_xq_slot).  Lane 16 q + m holds row / column m and the K slots 4 q .. 4 q + 3 as two dwords of
-// bf16 pairs; the split of a lane's four values is one remainder MFMA (v_mfma_f32_16x16x16_bf16) per level.
+// bf16 pairs; the split of a lane's four values is one remainder MFMA (w16_rem) per level.
 // The six partial products are issued as THREE v_mfma_f32_16x16x32_bf16: two K = 16 operands side by side in four consecutive
 // registers are one K = 32 operand (lane 16 q + m: K slots 8 q .. 8 q + 3 from the first, 8 q + 4 .. 8 q + 7 from the second), so
 //     (w1|w2) . (z3|z1) = w1 z3 + w2 z1,    (w3|w1) . (z1|z2) = w3 z1 + w1 z2,    (w1|w2) . (z1|z2) = w1 z1 + w2 z2

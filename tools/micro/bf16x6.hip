@@ -3,8 +3,10 @@
 // (v_mfma_f32_16x16x32_bf16, 16 cycles each on gfx950 against 8 x 32 cycles of v_mfma_f32_16x16x4_f32 for the same K = 32).
 // Checks the operand layout (lane 16q + m: row / column m, K slots 8q .. 8q + 7 as four dwords of bf16 pairs) and the accuracy
 // against float64 and against the f32 MFMA, then times both forms with the split's VALU work included.
-//   hipcc --offload-arch=gfx950 -O3 -o bf16x6 bf16x6.hip && ./bf16x6            (./bf16x6 k16pairs: only the K = 16 pairing)
+//   hipcc --offload-arch=gfx950 -O3 -o bf16x6 bf16x6.hip && ./bf16x6            (./bf16x6 k16pairs: only the K = 16 pairing;
+//   ./bf16x6 rem4x4: the remainders on v_mfma_f32_4x4x4_16b_bf16 -- exactness, operand layout and cost beside the K = 16 form)
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -82,6 +84,7 @@ __device__ __forceinline__ void split3m(const float (&v)[8], const u32x4 (&A)[2]
 // four values are two dwords of the packed piece, the -I operand is the same for both row blocks)
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x2 pack_hi2(const f32x4 &v);
 __device__ __forceinline__ f32x4 mm16(u32x2 a, u32x2 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
 }
@@ -96,8 +99,29 @@ __device__ __forceinline__ void split3k(const float (&v)[8], u32x4 &p1, u32x4 &p
     x0 = mm16(I, u32x2{p2[0], p2[1]}, x0); x1 = mm16(I, u32x2{p2[2], p2[3]}, x1);
     p3 = pack_hi(x0, x1);
 }
+// Fifth form (what the kernels issue, w16_ident / w16_rem in epnn_wave.hip.h): the same remainders with v_mfma_f32_4x4x4_16b_bf16,
+// sixteen independent 4x4x4 blocks.  Lane 4 b + i holds row i of block b's A, column i of its B (four K slots, two dwords) and column
+// i of its C / D (rows 0..3): with A = -I per block (-1 in K slot i) D[r] = C[r] - B[r] inside the lane, whatever the lane's values mean.
+__device__ __forceinline__ u32x2 ident4() {
+    const int i = threadIdx.x & 3;
+    u32x2 I;
+    for (int d = 0; d < 2; ++d) I[d] = (d == (i >> 1)) ? (0xbf80u << (16 * (i & 1))) : 0u;
+    return I;
+}
+__device__ __forceinline__ f32x4 mm4(u32x2 a, u32x2 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ void split3q(const float (&v)[8], u32x4 &p1, u32x4 &p2, u32x4 &p3) {
+    const u32x2 I = ident4();
+    f32x4 x0 = {v[0], v[1], v[2], v[3]}, x1 = {v[4], v[5], v[6], v[7]};
+    p1 = pack_hi(x0, x1);
+    x0 = mm4(I, u32x2{p1[0], p1[1]}, x0); x1 = mm4(I, u32x2{p1[2], p1[3]}, x1);
+    p2 = pack_hi(x0, x1);
+    x0 = mm4(I, u32x2{p2[0], p2[1]}, x0); x1 = mm4(I, u32x2{p2[2], p2[3]}, x1);
+    p3 = pack_hi(x0, x1);
+}
 template <int SPLIT> __device__ __forceinline__ void split_any(const float (&v)[8], const u32x4 (&A)[2], u32x4 &p1, u32x4 &p2, u32x4 &p3) {
-    if (SPLIT == 3) split3k(v, p1, p2, p3); else if (SPLIT == 2) split3m(v, A, p1, p2, p3); else if (SPLIT) split3r(v, p1, p2, p3); else split3(v, p1, p2, p3);
+    if (SPLIT == 4) split3q(v, p1, p2, p3); else if (SPLIT == 3) split3k(v, p1, p2, p3); else if (SPLIT == 2) split3m(v, A, p1, p2, p3); else if (SPLIT) split3r(v, p1, p2, p3); else split3(v, p1, p2, p3);
 }
 // exactness of a split: every lane splits 8 values, the host adds the pieces in float64
 template <int SPLIT> __global__ void k_exact(const float *x, unsigned *pieces) {
@@ -133,9 +157,9 @@ template <int SPLIT> __global__ void k_check(const float *W, const float *Z, flo
 }
 // timing: `tiles` dependent-free tiles per wave; MODE 0 = f32 MFMA (16 per tile: 2 row blocks x 8), 1 = bf16x6 incl. the split of z
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int MODE, int EXTRA = 0, int SPLIT = 0>
-__global__ __launch_bounds__(64, 2) void k_time(const float *src, float *dst, int tiles) {
-    const int lane = threadIdx.x;
+template <int MODE, int EXTRA, int SPLIT>
+__device__ __forceinline__ void time_body(const float *src, float *dst, int tiles) {
+    const int lane = threadIdx.x & 63;
     float z[8], w32[2][8];
     u32x4 wb[2][3], A[2];
     ident_operand(A);
@@ -193,7 +217,55 @@ __global__ __launch_bounds__(64, 2) void k_time(const float *src, float *dst, in
         }
         S[0] += d[0]; S[1] += d[1];
     }
-    for (int r = 0; r < 4; ++r) dst[(blockIdx.x * 64 + lane) * 8 + r] = S[0][r], dst[(blockIdx.x * 64 + lane) * 8 + 4 + r] = S[1][r];
+    const size_t o = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
+    for (int r = 0; r < 4; ++r) dst[o + r] = S[0][r], dst[o + 4 + r] = S[1][r];
+}
+template <int MODE, int EXTRA = 0, int SPLIT = 0>
+__global__ __launch_bounds__(64, 2) void k_time(const float *src, float *dst, int tiles) { time_body<MODE, EXTRA, SPLIT>(src, dst, tiles); }
+// The same tile in workgroups of 256 or 512 threads -- a workgroup's wavefronts go round the CU's four SIMDs, so that is one or two
+// wavefronts per SIMD by construction, with few enough workgroups that each has a CU to itself -- and timed by the wavefront's own
+// clock: cyc[wavefront] = { s_memtime ticks, s_memrealtime ticks (100 MHz) } around the tile loop.
+template <int SPLIT>
+__global__ __launch_bounds__(512) void k_time_wg(const float *src, float *dst, int tiles, unsigned long long *cyc) {
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+    time_body<1, 0, SPLIT>(src, dst, tiles);
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if ((threadIdx.x & 63) == 0) { cyc[2 * w] = t1 - t0; cyc[2 * w + 1] = r1 - r0; }
+}
+// Layout probe of the 4x4x4 remainder: every lane holds four values (all zeros but in one lane of the launch), y = x - piece(x).
+__global__ void k_probe4(const float *x, float *y) {
+    const int lane = threadIdx.x;
+    f32x4 v = {x[lane * 4], x[lane * 4 + 1], x[lane * 4 + 2], x[lane * 4 + 3]};
+    v = mm4(ident4(), pack_hi2(v), v);
+    for (int r = 0; r < 4; ++r) y[lane * 4 + r] = v[r];
+}
+// Back-to-back MFMAs of one kind, n x 32 per wavefront: INDEP 1 = eight accumulators in turn (no instruction waits for the one before
+// it: the interval is what the pipe is held for), 0 = one accumulator (the instruction's latency).  KIND 0: 4x4x4, 1: 16x16x16, 2: 16x16x32.
+template <int KIND, int INDEP>
+__global__ __launch_bounds__(512) void k_rate(const float *src, float *dst, int n, unsigned long long *cyc) {
+    const int lane = threadIdx.x & 63;
+    const u32x4 a = {__float_as_uint(src[lane]) & 0xffff0000u, 0x3f803f80u, __float_as_uint(src[64 + lane]) >> 16, 0xbf800000u};
+    const u32x4 b = {__float_as_uint(src[128 + lane]) >> 16, 0x3f800000u, __float_as_uint(src[192 + lane]) & 0xffff0000u, 0x3f80bf80u};
+    f32x4 acc[8];
+    for (int k = 0; k < 8; ++k) acc[k] = f32x4{src[256 + lane], (float)k, 0.f, 1.f};
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+    for (int t = 0; t < n; ++t) {
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+            f32x4 &c = acc[INDEP ? k & 7 : 0];
+            if (KIND == 0) c = mm4(u32x2{a[0], a[1]}, u32x2{b[0], b[1]}, c);
+            else if (KIND == 1) c = mm16(u32x2{a[0], a[1]}, u32x2{b[0], b[1]}, c);
+            else c = mm(a, b, c);
+        }
+    }
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    f32x4 s = acc[0];
+    for (int k = 1; k < 8; ++k) s += acc[k];
+    const size_t o = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    for (int r = 0; r < 4; ++r) dst[o + r] = s[r];
+    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (lane == 0) { cyc[2 * w] = t1 - t0; cyc[2 * w + 1] = r1 - r0; }
 }
 // The K = 16 products of the fused kernels (w16_mm_bfk16, epnn_wave.hip.h): C[16x16] = W[16x16] * Z[16x16], six partial products.
 // Six-instruction form (what the kernels issued before): six v_mfma_f32_16x16x16_bf16.  Paired form, instruction for instruction
@@ -319,12 +391,157 @@ static int check_k16_pairs() {
     hipFree(dW); hipFree(dZ); hipFree(d6); hipFree(d3); hipFree(d32); hipFree(ds); hipFree(dp);
     return 0;
 }
-int main(int argc, char **argv) {
-    if (argc > 1 && !strcmp(argv[1], "k16pairs")) return check_k16_pairs();      // only the K = 16 pairing (tests/test_gpu_k16_pairs.py)
-    std::vector<float> W(16 * 32), Z(32 * 16), C6(256), C32(256);
+// the inputs of the default run, in the order it draws them: srand(1), the product's operands, then the split's 2^22 values
+static void product_operands(std::vector<float> &W, std::vector<float> &Z) {
     srand(1);
     for (auto &v : W) v = (rand() / (float)RAND_MAX - 0.5f) * 2.f;
     for (auto &v : Z) v = (rand() / (float)RAND_MAX) * 3.f * ((rand() & 3) ? 1.f : 0.f);       // relu-like: a quarter zeros
+}
+// uniform, tiny, huge, negative, powers of two, bf16 numbers, zeros
+static void split_values(std::vector<float> &xv) {
+    for (size_t i = 0; i < xv.size(); ++i) {
+        const int kind = i & 7;
+        unsigned bits = ((unsigned)rand() << 16) ^ (unsigned)rand() ^ ((unsigned)rand() << 31);
+        float f;
+        if (kind < 3) { bits = (bits & 0x807fffffu) | ((unsigned)(100 + rand() % 56) << 23); memcpy(&f, &bits, 4); }       // 2^-27 .. 2^28
+        else if (kind == 3) { bits = (bits & 0x807fffffu) | ((unsigned)(1 + rand() % 253) << 23); memcpy(&f, &bits, 4); }   // any normal exponent
+        else if (kind == 4) { bits &= 0xffff0000u; bits = (bits & 0x807fffffu) | ((unsigned)(110 + rand() % 30) << 23); memcpy(&f, &bits, 4); }
+        else if (kind == 5) { bits |= 0x00007fffu; bits = (bits & 0x807fffffu) | ((unsigned)(110 + rand() % 30) << 23); memcpy(&f, &bits, 4); }   // ties / all ones below
+        else if (kind == 6) f = ldexpf(1.f, rand() % 60 - 30) * ((rand() & 1) ? -1.f : 1.f);
+        else f = (rand() & 1) ? 0.f : (rand() / (float)RAND_MAX) * 3.f;
+        xv[i] = f;
+    }
+}
+// values of xv that the three pieces in pc ([lane][piece][4 dwords], 8 values per lane) do not add up to in float64
+static long not_reproduced(const std::vector<unsigned> &pc, const std::vector<float> &xv, double &worst, bool show) {
+    long bad = 0; int shown = 0;
+    worst = 0;
+    for (size_t t = 0; t < xv.size() / 8; ++t)
+        for (int s = 0; s < 8; ++s) {
+            double sum = 0;
+            for (int k = 0; k < 3; ++k) {
+                const unsigned w = pc[(t * 3 + k) * 4 + s / 2];
+                const unsigned b = (s & 1) ? (w & 0xffff0000u) : (w << 16);
+                float piece; memcpy(&piece, &b, 4);
+                sum += (double)piece;
+            }
+            const double x = xv[t * 8 + s];
+            if (sum != x) {
+                ++bad; worst = fmax(worst, fabs(sum - x) / fabs(x));
+                if (show && shown++ < 4) printf("   x = %.9g (%a): pieces add up to %.9g\n", x, x, sum);
+            }
+        }
+    return bad;
+}
+static double median(std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; }
+// ./bf16x6 rem4x4: the split's remainders on v_mfma_f32_4x4x4_16b_bf16 (tests/test_gpu_rem4x4.py reads the first two parts)
+static int check_rem4x4() {
+    int fails = 0;
+    {   // 1. exactness, on the default run's 2^22 values
+        const int nv = 1 << 22;
+        std::vector<float> W(16 * 32), Z(32 * 16), xv(nv);
+        product_operands(W, Z);
+        split_values(xv);
+        float *dx; unsigned *dp;
+        hipMalloc(&dx, (size_t)nv * 4); hipMalloc(&dp, (size_t)nv / 8 * 12 * 4);
+        hipMemcpy(dx, xv.data(), (size_t)nv * 4, hipMemcpyHostToDevice);
+        std::vector<unsigned> pc0((size_t)nv / 8 * 12), pc4(pc0.size());
+        hipLaunchKernelGGL(k_exact<0>, dim3(nv / 512), dim3(64), 0, 0, dx, dp);
+        if (hipMemcpy(pc0.data(), dp, pc0.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { printf("rem4x4: a kernel failed\n"); return 1; }
+        hipLaunchKernelGGL(k_exact<4>, dim3(nv / 512), dim3(64), 0, 0, dx, dp);
+        if (hipMemcpy(pc4.data(), dp, pc4.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { printf("rem4x4: a kernel failed\n"); return 1; }
+        long diff = 0;
+        for (size_t i = 0; i < pc0.size(); ++i) diff += pc4[i] != pc0[i];
+        double w0, w4;
+        const long bad0 = not_reproduced(pc0, xv, w0, false), bad4 = not_reproduced(pc4, xv, w4, false);
+        printf("rem4x4 exactness: %ld of %zu piece words differ from the v_and / v_sub form's\n", diff, pc0.size());
+        printf("rem4x4 exactness: %ld of %d values not reproduced by x1 + x2 + x3 (4x4x4 remainders), %ld (truncated form)\n", bad4, nv, bad0);
+        fails += diff != 0 || bad4 != bad0;
+        hipFree(dx); hipFree(dp);
+    }
+    {   // 2. layout: one lane of the wavefront holds values, the others zeros
+        float *dx, *dy;
+        hipMalloc(&dx, 1024); hipMalloc(&dy, 1024);
+        const int lanes[6] = {0, 5, 18, 27, 46, 63};
+        const float vals[4] = {1.2345678f, -0.0078112348f, 517.00391f, 3.0000002f};      // four different values, pieces in all three places
+        for (int k = 0; k < 6; ++k) {
+            const int L = lanes[k];
+            std::vector<float> x(256, 0.f), y(256, -1.f);
+            for (int r = 0; r < 4; ++r) x[L * 4 + r] = vals[r] * (1.f + 0.125f * k);
+            hipMemcpy(dx, x.data(), 1024, hipMemcpyHostToDevice);
+            hipLaunchKernelGGL(k_probe4, dim3(1), dim3(64), 0, 0, dx, dy);
+            if (hipMemcpy(y.data(), dy, 1024, hipMemcpyDeviceToHost) != hipSuccess) { printf("rem4x4: a kernel failed\n"); return 1; }
+            int others = 0, own = 0;
+            for (int l = 0; l < 64; ++l)
+                for (int r = 0; r < 4; ++r) {
+                    float want = x[l * 4 + r];
+                    if (l == L) { unsigned b; memcpy(&b, &want, 4); b &= 0xffff0000u; float top; memcpy(&top, &b, 4); want -= top; }
+                    const bool bad = memcmp(&y[l * 4 + r], &want, 4) != 0;
+                    if (l == L) own += bad; else others += bad;
+                }
+            printf("rem4x4 layout: values in lane %2d (block %2d, column %d) only: %d of its 4 results are not x[r] - piece[r], %d of the other 252 results changed: %s\n",
+                   L, L / 4, L % 4, own, others, own || others ? "FAILED" : "ok");
+            fails += own || others;
+        }
+        hipFree(dx); hipFree(dy);
+    }
+    {   // 3. cost, by the wavefronts' own clocks: 16 workgroups (a CU each) of one or two wavefronts per SIMD
+        const int groups = 16;
+        float *src, *dst; unsigned long long *cyc;
+        hipMalloc(&src, 1536 * 4); hipMalloc(&dst, (size_t)groups * 512 * 8 * 4); hipMalloc(&cyc, (size_t)groups * 8 * 16);
+        std::vector<float> s(1536);
+        for (auto &v : s) v = rand() / (float)RAND_MAX - 0.3f;
+        hipMemcpy(src, s.data(), 1536 * 4, hipMemcpyHostToDevice);
+        std::vector<unsigned long long> h((size_t)groups * 8 * 2);
+        auto clocks = [&](int waves, double per, double &ticks, double &ghz) {       // median over wavefronts of ticks / per
+            if (hipMemcpy(h.data(), cyc, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return false;
+            std::vector<double> t, g;
+            for (int w = 0; w < waves; ++w) { t.push_back((double)h[2 * w] / per); g.push_back((double)h[2 * w] / (double)h[2 * w + 1] * 0.1); }
+            ticks = median(t); ghz = median(g);
+            return true;
+        };
+        const char *kinds[3] = {"v_mfma_f32_4x4x4_16b_bf16", "v_mfma_f32_16x16x16_bf16 ", "v_mfma_f32_16x16x32_bf16 "};
+        const int n = 4000;
+        for (int kind = 0; kind < 3; ++kind) {
+            double t[2], g[2];
+            for (int indep = 1; indep >= 0; --indep) {
+                for (int rep = 0; rep < 2; ++rep) {          // (the second launch counts)
+                    if (kind == 0 && indep) hipLaunchKernelGGL((k_rate<0, 1>), dim3(groups), dim3(256), 0, 0, src, dst, n, cyc);
+                    else if (kind == 0) hipLaunchKernelGGL((k_rate<0, 0>), dim3(groups), dim3(256), 0, 0, src, dst, n, cyc);
+                    else if (kind == 1 && indep) hipLaunchKernelGGL((k_rate<1, 1>), dim3(groups), dim3(256), 0, 0, src, dst, n, cyc);
+                    else if (kind == 1) hipLaunchKernelGGL((k_rate<1, 0>), dim3(groups), dim3(256), 0, 0, src, dst, n, cyc);
+                    else if (indep) hipLaunchKernelGGL((k_rate<2, 1>), dim3(groups), dim3(256), 0, 0, src, dst, n, cyc);
+                    else hipLaunchKernelGGL((k_rate<2, 0>), dim3(groups), dim3(256), 0, 0, src, dst, n, cyc);
+                    if (!clocks(groups * 4, n * 32.0, t[indep], g[indep])) { printf("rem4x4: a kernel failed\n"); return 1; }
+                }
+            }
+            printf("rem4x4 cost: %s back to back, one wavefront per SIMD: %.2f cycles per instruction on eight accumulators in turn, %.2f on one accumulator (clock %.3f GHz)\n",
+                   kinds[kind], t[1], t[0], g[1]);
+        }
+        const char *splits[3] = {"v_and / v_sub            ", "v_mfma_f32_16x16x16_bf16 ", "v_mfma_f32_4x4x4_16b_bf16"};
+        const int tiles = 4000;
+        for (int sp = 0; sp < 3; ++sp) {
+            double t[2], g[2];
+            for (int two = 0; two < 2; ++two)
+                for (int rep = 0; rep < 2; ++rep) {
+                    const dim3 wg(two ? 512 : 256);
+                    if (sp == 0) hipLaunchKernelGGL(k_time_wg<0>, dim3(groups), wg, 0, 0, src, dst, tiles, cyc);
+                    else if (sp == 1) hipLaunchKernelGGL(k_time_wg<3>, dim3(groups), wg, 0, 0, src, dst, tiles, cyc);
+                    else hipLaunchKernelGGL(k_time_wg<4>, dim3(groups), wg, 0, 0, src, dst, tiles, cyc);
+                    if (!clocks(groups * (two ? 8 : 4), tiles, t[two], g[two])) { printf("rem4x4: a kernel failed\n"); return 1; }
+                }
+            printf("rem4x4 cost: tile (split + 12 MFMAs), remainders by %s: %.1f cycles per tile with one wavefront per SIMD, %.1f per tile and wavefront pair with two (%.1f per wavefront; clock %.3f GHz)\n",
+                   splits[sp], t[0], t[1], t[1] / 2, g[1]);
+        }
+        hipFree(src); hipFree(dst); hipFree(cyc);
+    }
+    return fails ? 1 : 0;
+}
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "k16pairs")) return check_k16_pairs();      // only the K = 16 pairing (tests/test_gpu_k16_pairs.py)
+    if (argc > 1 && !strcmp(argv[1], "rem4x4")) return check_rem4x4();           // only the 4x4x4 remainders (tests/test_gpu_rem4x4.py)
+    std::vector<float> W(16 * 32), Z(32 * 16), C6(256), C32(256);
+    product_operands(W, Z);
     float *dW, *dZ, *d6, *d32;
     hipMalloc(&dW, 2048); hipMalloc(&dZ, 2048); hipMalloc(&d6, 1024); hipMalloc(&d32, 1024);
     hipMemcpy(dW, W.data(), 2048, hipMemcpyHostToDevice); hipMemcpy(dZ, Z.data(), 2048, hipMemcpyHostToDevice);
@@ -345,18 +562,7 @@ int main(int argc, char **argv) {
     {   // exactness of both splits on 2^22 values: uniform, tiny, huge, negative, powers of two, bf16 numbers, zeros
         const int nv = 1 << 22;
         std::vector<float> xv(nv);
-        for (int i = 0; i < nv; ++i) {
-            const int kind = i & 7;
-            unsigned bits = ((unsigned)rand() << 16) ^ (unsigned)rand() ^ ((unsigned)rand() << 31);
-            float f;
-            if (kind < 3) { bits = (bits & 0x807fffffu) | ((unsigned)(100 + rand() % 56) << 23); memcpy(&f, &bits, 4); }       // 2^-27 .. 2^28
-            else if (kind == 3) { bits = (bits & 0x807fffffu) | ((unsigned)(1 + rand() % 253) << 23); memcpy(&f, &bits, 4); }   // any normal exponent
-            else if (kind == 4) { bits &= 0xffff0000u; bits = (bits & 0x807fffffu) | ((unsigned)(110 + rand() % 30) << 23); memcpy(&f, &bits, 4); }
-            else if (kind == 5) { bits |= 0x00007fffu; bits = (bits & 0x807fffffu) | ((unsigned)(110 + rand() % 30) << 23); memcpy(&f, &bits, 4); }   // ties / all ones below
-            else if (kind == 6) f = ldexpf(1.f, rand() % 60 - 30) * ((rand() & 1) ? -1.f : 1.f);
-            else f = (rand() & 1) ? 0.f : (rand() / (float)RAND_MAX) * 3.f;
-            xv[i] = f;
-        }
+        split_values(xv);
         float *dx; unsigned *dp;
         hipMalloc(&dx, (size_t)nv * 4); hipMalloc(&dp, (size_t)nv / 8 * 12 * 4);
         hipMemcpy(dx, xv.data(), (size_t)nv * 4, hipMemcpyHostToDevice);
@@ -367,22 +573,8 @@ int main(int argc, char **argv) {
             else if (sp) hipLaunchKernelGGL(k_exact<1>, dim3(nv / 512), dim3(64), 0, 0, dx, dp);
             else hipLaunchKernelGGL(k_exact<0>, dim3(nv / 512), dim3(64), 0, 0, dx, dp);
             hipMemcpy(pc.data(), dp, pc.size() * 4, hipMemcpyDeviceToHost);
-            long bad = 0; double worst = 0; int shown = 0;
-            for (int t = 0; t < nv / 8; ++t)
-                for (int s = 0; s < 8; ++s) {
-                    double sum = 0;
-                    for (int k = 0; k < 3; ++k) {
-                        const unsigned w = pc[((size_t)t * 3 + k) * 4 + s / 2];
-                        const unsigned b = (s & 1) ? (w & 0xffff0000u) : (w << 16);
-                        float piece; memcpy(&piece, &b, 4);
-                        sum += (double)piece;
-                    }
-                    const double x = xv[(size_t)t * 8 + s];
-                    if (sum != x) {
-                        ++bad; worst = fmax(worst, fabs(sum - x) / fabs(x));
-                        if (shown++ < 4) printf("   x = %.9g (%a): pieces add up to %.9g\n", x, x, sum);
-                    }
-                }
+            double worst;
+            const long bad = not_reproduced(pc, xv, worst, true);
             if (sp == 0) pc0 = pc;
             if (sp >= 2) {
                 long diff = 0;
