@@ -205,18 +205,20 @@ def _cell_grad_ref(cell, outer=False):
         xgr.edges64, xgr.orc = saved
 
 
-def vjp64_cell(xyz, x, Q, g, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5):
-    """(q (N,), gxyz (n, 3)) of one molecule in the cell (3,3): xgr.vjp64 on the cell's edges."""
+def vjp64_cell(xyz, x, Q, g, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5, dtype=np.float64):
+    """(q (N,), gxyz (n, 3)) of one molecule in the cell (3,3): xgr.vjp64 on the cell's edges (dtype: its float32 model)."""
     with _cell_grad_ref(cell):
-        return xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol)
+        return xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol, dtype=dtype)
 
 
-def strain64(xyz, x, Q, g, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5):
+def strain64(xyz, x, Q, g, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5, dtype=np.float64):
     """(q (N,), gxyz (n, 3), gstrain (3, 3)): gstrain[a][c] = d(sum_i g_i q_i)/d eps_ac under r -> (1 + eps) r, a_k -> (1 + eps) a_k,
-    = sum over pairs i < j with D < cutoff of (dF/dD_ij) d'_a d'_c / D_ij.  xgr sums over ordered pairs: half of it."""
+    = sum over pairs i < j with D < cutoff of (dF/dD_ij) d'_a d'_c / D_ij.  xgr sums over ordered pairs: half of it.  dtype:
+    xgr.vjp64's float32 model; the strain sum stays in float64 and is rounded to float32 at its end."""
     with _cell_grad_ref(cell, outer=True):
-        q, ext = xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol)
-    return q, ext[:, :3], 0.5 * ext[:, 3:].sum(0).reshape(3, 3)
+        q, ext = xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol, dtype=dtype)
+    gs = 0.5 * ext[:, 3:].sum(0).reshape(3, 3)
+    return q, ext[:, :3], gs if np.dtype(dtype) == np.float64 else gs.astype(np.float32).astype(np.float64)
 
 
 def forward64_cell(xyz, x, Q, cell, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):

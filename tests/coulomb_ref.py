@@ -123,12 +123,20 @@ def coulomb_energy64(xyz, q, ke, alpha, block=256):
     return E, sE
 
 
-def coulomb_forces64(xyz, x, Q, weights, N, ke, alpha, kink_shift=0, **ref_kw):
+def coulomb_forces64(xyz, x, Q, weights, N, ke, alpha, kink_shift=0, dtype=np.float64, **ref_kw):
     """(q (n,), phi (n,), E, f (n, 3), ffix (n, 3), fq (n, 3)) of one molecule padded to N: q from forward64, phi, E and ffix from
     coulomb64 on them, fq = -vjp64(g = phi) with the reference's ReLU-kink bracket, f = ffix + fq the total force.  ref_kw: the
-    references' own keywords (h_dim, cutoff, eta, near_tol: edge_constants.ref_kwargs)."""
+    references' own keywords (h_dim, cutoff, eta, near_tol: edge_constants.ref_kwargs).  dtype=np.float32: the float32 model of
+    the charges' part -- q from vjp64's float32 model, phi from them in float64 and rounded to float32 (the seed the device's
+    backward sees), fq from the float32 model's backward; phi, E and ffix are coulomb64's on those charges."""
     n = np.asarray(x).shape[0]
-    q = forward64(xyz, x, Q, weights, N=N, **ref_kw)[:n]
+    if np.dtype(dtype) == np.float64:
+        q = forward64(xyz, x, Q, weights, N=N, **ref_kw)[:n]
+        phi, E, ffix = coulomb64(np.asarray(xyz, dtype=np.float32), q, ke, alpha)[:3]
+        fq = -vjp64(xyz, x, Q, phi, weights, N=N, kink_shift=kink_shift, **ref_kw)[1]
+        return q, phi, E, ffix + fq, ffix, fq
+    q = vjp64(xyz, x, Q, np.zeros(n), weights, N=N, dtype=dtype, **ref_kw)[0][:n].astype(np.float32).astype(np.float64)
     phi, E, ffix = coulomb64(np.asarray(xyz, dtype=np.float32), q, ke, alpha)[:3]
-    fq = -vjp64(xyz, x, Q, phi, weights, N=N, kink_shift=kink_shift, **ref_kw)[1]
+    phi = phi.astype(np.float32).astype(np.float64)
+    fq = -vjp64(xyz, x, Q, phi, weights, N=N, kink_shift=kink_shift, dtype=dtype, **ref_kw)[1]
     return q, phi, E, ffix + fq, ffix, fq

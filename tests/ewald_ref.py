@@ -119,12 +119,19 @@ def ewald64(xyz, q, cell, ke, alpha, beta, rc, kc, M):
                            s_strain=s_strain)
 
 
-def ewald_forces64(xyz, x, Q, cell, weights, N, ke, alpha, params, kink_shift=0.0, **ref_kw):
+def ewald_forces64(xyz, x, Q, cell, weights, N, ke, alpha, params, kink_shift=0.0, dtype=np.float64, **ref_kw):
     """(q (n,), phi (n,), E, f (n,3), gstrain (3,3), ffix, fq, gstrain_fix, gstrain_q) of one cell padded to N: q from
     cell_ref.forward64_cell, the fixed-charge parts from ewald64 on them at params = (beta, rc, kc, M0, M1, M2), fq = -gxyz and
-    gstrain_q = gstrain of cell_ref.strain64 at g = phi, as coulomb_ref.coulomb_forces64 does for open molecules."""
+    gstrain_q = gstrain of cell_ref.strain64 at g = phi, as coulomb_ref.coulomb_forces64 does for open molecules (dtype as there:
+    charges and the backward from the float32 model, its seed phi rounded to float32)."""
     n = np.asarray(x).shape[0]
-    q = cell_ref.forward64_cell(xyz, x, Q, cell, weights, N=N, **ref_kw)[:n]
+    f64 = np.dtype(dtype) == np.float64
+    if f64:
+        q = cell_ref.forward64_cell(xyz, x, Q, cell, weights, N=N, **ref_kw)[:n]
+    else:
+        q = cell_ref.strain64(xyz, x, Q, np.zeros(n), cell, weights, N=N, dtype=dtype, **ref_kw)[0][:n].astype(np.float32).astype(np.float64)
     e = ewald64(np.asarray(xyz, dtype=np.float32), q, np.asarray(cell, dtype=np.float32), ke, alpha, params[0], params[1], params[2], params[3:6])
-    _, gxyz, gsq = cell_ref.strain64(xyz, x, Q, e.phi, cell, weights, N=N, kink_shift=kink_shift, **ref_kw)
+    if not f64:
+        e.phi = e.phi.astype(np.float32).astype(np.float64)
+    _, gxyz, gsq = cell_ref.strain64(xyz, x, Q, e.phi, cell, weights, N=N, kink_shift=kink_shift, dtype=dtype, **ref_kw)
     return q, e.phi, e.E, e.ffix - gxyz, e.strain + gsq, e.ffix, -gxyz, e.strain, gsq

@@ -37,8 +37,11 @@ def near_flags(xyz, cell, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):
     return np.clip(e32, tol, np.float32(1e5)).max(-1) != tol
 
 
-def _cast(weights):
-    c = lambda m: [(np.asarray(W, np.float64), np.asarray(b, np.float64)) for W, b in m]
+_CUT_TE = None        # tests/grad_noise_ref.py: a function applied to the edge tangent te as the MLPs see it (a defect model)
+
+
+def _cast(weights, dtype=np.float64):
+    c = lambda m: [(np.asarray(W, dtype), np.asarray(b, dtype)) for W, b in m]
     return {"msg": [c(m) for m in weights["msg"]], "upd": c(weights["upd"]), "pas": [c(m) for m in weights["pas"]]}
 
 
@@ -46,29 +49,34 @@ def _mlp(X, tX, layers, s):
     for W, b in layers[:-1]:
         pre = X @ W + b
         tX = (tX @ W) * (pre > s)
-        X = np.maximum(pre, 0.0)
+        X = np.maximum(pre, 0)
     W, b = layers[-1]
     return X @ W + b, tX @ W
 
 
-def model_jvp(e, te, near, x, q0, tq0, weights, N, kink_shift=0.0):
-    """(q (n,), tq (n,)) from float64 edges e, te (n, n, c), near (n, n) bool, x (n, nx), q0 and tq0 (scalars: Q / n, dQ / n)."""
-    w = _cast(weights)
+def model_jvp(e, te, near, x, q0, tq0, weights, N, kink_shift=0.0, dtype=np.float64):
+    """(q (n,), tq (n,)) from float64 edges e, te (n, n, c), near (n, n) bool, x (n, nx), q0 and tq0 (scalars: Q / n, dQ / n).
+    dtype=np.float32: the float32 model of the device's tangent kernels -- weights, e and te as the MLPs see them, activations, the
+    tangents th and tq and every Dense product and sum in float32, the result rounded to float32; e and te themselves come from the
+    float64 geometry either way."""
+    w = _cast(weights, dtype)
     s = float(kink_shift)
     n, nx = x.shape
     nh = e.shape[-1]
-    E = np.zeros((n, N, nh))
-    tE = np.zeros((n, N, nh))
+    E = np.zeros((n, N, nh), dtype=dtype)
+    tE = np.zeros((n, N, nh), dtype=dtype)
     E[:, :n] = e
     tE[:, :n] = te
-    xs = np.zeros((N, nx))
+    if _CUT_TE is not None:
+        tE = _CUT_TE(tE)
+    xs = np.zeros((N, nx), dtype=dtype)
     xs[:n] = x
-    real = np.zeros((N, 1))
+    real = np.zeros((N, 1), dtype=dtype)
     real[:n] = 1.0
-    q = real * q0
-    tq = real * tq0
-    h = np.zeros((N, nh))
-    th = np.zeros((N, nh))
+    q = real * np.asarray(q0, dtype=dtype)
+    tq = real * np.asarray(tq0, dtype=dtype)
+    h = np.zeros((N, nh), dtype=dtype)
+    th = np.zeros((N, nh), dtype=dtype)
     T = len(w["msg"])
 
     def rows(a, b, ee):
@@ -83,10 +91,11 @@ def model_jvp(e, te, near, x, q0, tq0, weights, N, kink_shift=0.0):
         m, tm = _mlp(rows(a[:n], a, E), rows(ta[:n], ta, tE), w["msg"][t], s)       # every real atom with all N partners
         M, tM = m.reshape(n, N, -1).sum(1), tm.reshape(n, N, -1).sum(1)
         hn, thn = _mlp(np.concatenate([h[:n], M], 1), np.concatenate([th[:n], tM], 1), w["upd"], s)
-        h = np.zeros((N, nh))
-        th = np.zeros((N, nh))
+        h = np.zeros((N, nh), dtype=dtype)
+        th = np.zeros((N, nh), dtype=dtype)
         h[:n], th[:n] = hn, thn                                                     # (the node mask keeps padded rows at zero)
-    wgt = near.astype(np.float64)
+    wgt = near.astype(dtype)
+    half = np.asarray(0.5, dtype=dtype)
     en, ten = E[:, :n], tE[:, :n]
     for t in range(T):
         a = np.concatenate([xs, h, q], -1)[:n]
@@ -96,9 +105,9 @@ def model_jvp(e, te, near, x, q0, tq0, weights, N, kink_shift=0.0):
         # the rows [a_j | a_i | e_ij] are the transposed evaluation (e_ij == e_ji)
         q = q.copy()
         tq = tq.copy()
-        q[:n, 0] += (0.5 * (fN - fN.T) * wgt).sum(1)
-        tq[:n, 0] += (0.5 * (tfN - tfN.T) * wgt).sum(1)
-    return q[:n, 0], tq[:n, 0]
+        q[:n, 0] += (half * (fN - fN.T) * wgt).sum(1)
+        tq[:n, 0] += (half * (tfN - tfN.T) * wgt).sum(1)
+    return q[:n, 0].astype(np.float64), tq[:n, 0].astype(np.float64)
 
 
 def edge_tangents(r, a, v=None, strain=None, num=48, cutoff=3.0, eta=2.0):
@@ -115,9 +124,9 @@ def edge_tangents(r, a, v=None, strain=None, num=48, cutoff=3.0, eta=2.0):
 
 
 def jvp64(xyz, x, Q, weights, N=None, v=None, strain=None, dQ=None, box=None, cell=None, h_dim=48, cutoff=3.0, eta=2.0,
-          kink_shift=0.0, near_tol=1e-5):
+          kink_shift=0.0, near_tol=1e-5, dtype=np.float64):
     """(q (n,), tq (n,)) of one molecule padded to N: open, in the box (3,) or in the cell (3, 3); v (n, 3), strain (3, 3), dQ a
-    scalar, each or all None (= 0)."""
+    scalar, each or all None (= 0).  dtype: model_jvp's."""
     c = cell_of(box, cell)
     x = np.asarray(x, dtype=np.float32).astype(np.float64)
     n = x.shape[0]
@@ -126,7 +135,7 @@ def jvp64(xyz, x, Q, weights, N=None, v=None, strain=None, dQ=None, box=None, ce
     e, te = edge_tangents(r, cell_ref.duals(c)[0], v, strain, h_dim, cutoff, eta)
     q0 = np.float64(np.float32(np.float32(Q) / np.float32(n)))
     tq0 = 0.0 if dQ is None else float(dQ) / n
-    return model_jvp(e, te, near_flags(xyz, c, h_dim, cutoff, eta, near_tol), x, q0, tq0, weights, N, kink_shift)
+    return model_jvp(e, te, near_flags(xyz, c, h_dim, cutoff, eta, near_tol), x, q0, tq0, weights, N, kink_shift, dtype)
 
 
 def forward64_at(r, a, x, Q, near, weights, N, h_dim=48, cutoff=3.0, eta=2.0):

@@ -170,10 +170,10 @@ def _periodic_grad_ref(box):
         xgr.edges64, xgr.orc = saved
 
 
-def vjp64_pbc(xyz, x, Q, g, box, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5):
-    """(q (N,), gxyz (n, 3)) of one molecule in the cell box (3,): xgr.vjp64 on minimum-image edges."""
+def vjp64_pbc(xyz, x, Q, g, box, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, near_tol=1e-5, dtype=np.float64):
+    """(q (N,), gxyz (n, 3)) of one molecule in the cell box (3,): xgr.vjp64 on minimum-image edges (dtype: its float32 model)."""
     with _periodic_grad_ref(box):
-        return xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol)
+        return xgr.vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, kink_shift=kink_shift, near_tol=near_tol, dtype=dtype)
 
 
 def forward64_pbc(xyz, x, Q, box, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, near_tol=1e-5):

@@ -60,23 +60,33 @@ def forward64(xyz, x, Q, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, near_to
     return vjp64(xyz, x, Q, np.zeros(x.shape[0]), weights, N, h_dim, cutoff, eta, near_tol=near_tol)[0]
 
 
-def vjp64(xyz, x, Q, g, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, kink_where="all", near_tol=1e-5):
-    """(q (N,), gxyz (n, 3) = sum_i g[i] dq_i/dxyz) for one molecule padded to N."""
+_CUT_GE = None        # tests/grad_noise_ref.py: a function applied to the edge cotangent gE before its contraction (a defect model)
+
+
+def vjp64(xyz, x, Q, g, weights, N=None, h_dim=48, cutoff=3.0, eta=2.0, kink_shift=0.0, kink_where="all", near_tol=1e-5,
+          dtype=np.float64):
+    """(q (N,), gxyz (n, 3) = sum_i g[i] dq_i/dxyz) for one molecule padded to N.  dtype=np.float32: the float32 model of the
+    device's derivative kernels -- weights, the edge tensor as the MLPs see it, activations, tapes, gE and every Dense product and
+    sweep sum in float32; the geometry (image, D, de/dD, the contraction of gE with de/dD and the displacement) stays in float64
+    and the result is rounded to float32, where the device stores it.  near flags and masks are the same for both."""
     otr._KINK_SHIFT, otr._KINK_WHERE = float(kink_shift), kink_where
     try:
-        return _vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, near_tol)
+        return _vjp64(xyz, x, Q, g, weights, N, h_dim, cutoff, eta, near_tol, dtype)
     finally:
         otr._KINK_SHIFT, otr._KINK_WHERE = 0.0, "all"
 
 
-def _vjp64(xyz, x_at, Q, g, weights, N, h_dim, cutoff, eta, near_tol=1e-5):
+def _vjp64(xyz, x_at, Q, g, weights, N, h_dim, cutoff, eta, near_tol=1e-5, dtype=np.float64):
     n = x_at.shape[0]
     N = n if N is None else N
-    w = otr._cast(weights, np.float64)
+    w = otr._cast(weights, dtype)
     e, de, dvec, Dm, near32, x, q0, mask = _inputs(xyz, x_at, Q, N, h_dim, cutoff, eta, near_tol)
+    f64 = np.dtype(dtype) == np.float64
+    if not f64:
+        e, x, q0, mask = (t.astype(dtype) for t in (e, x, q0, mask))
     B = 1
     nm = np.clip(mask.sum(axis=1), 0, 1)[..., None]                         # (1,N,1)
-    h0 = np.zeros((1, N, h_dim))
+    h0 = np.zeros((1, N, h_dim), dtype=dtype)
     T = len(w["msg"])
     tape_g = []
     h = h0
@@ -92,7 +102,7 @@ def _vjp64(xyz, x_at, Q, g, weights, N, h_dim, cutoff, eta, near_tol=1e-5):
         tape_g.append((acts, uacts, F))
         h = hn.reshape(B, N, -1) * nm
     feats = h
-    wgt = mask * near32[None]
+    wgt = mask * near32[None].astype(dtype)
     q = q0
     tape_e = []
     for t in range(T):
@@ -102,23 +112,24 @@ def _vjp64(xyz, x_at, Q, g, weights, N, h_dim, cutoff, eta, near_tol=1e-5):
         aj = np.broadcast_to(a[:, None, :, :], (B, N, N, F))
         fN, actsN = otr._mlp_fwd(np.concatenate([ai, aj, e], -1).reshape(B * N * N, -1), w["pas"][t])
         fT, actsT = otr._mlp_fwd(np.concatenate([aj, ai, e], -1).reshape(B * N * N, -1), w["pas"][t])
-        anti = 0.5 * (fN.reshape(B, N, N) - fT.reshape(B, N, N)) * wgt
+        anti = np.asarray(0.5, dtype=dtype) * (fN.reshape(B, N, N) - fT.reshape(B, N, N)) * wgt
         q = q + anti.sum(2)[..., None]
         tape_e.append((actsN, actsT, F))
     pred = q[0, :, 0]
 
     # ------------------------------------------------------------------ backward, seeded with g
-    gq = np.zeros((B, N, 1))
+    gq = np.zeros((B, N, 1), dtype=dtype)
     gq[0, :n, 0] = g
-    gE = np.zeros((B, N, N, h_dim))
+    gE = np.zeros((B, N, N, h_dim), dtype=dtype)
+    half = np.asarray(0.5, dtype=dtype)
     gfeat = np.zeros_like(feats)
     nh = feats.shape[-1]
     nx = x.shape[-1]
     for t in range(T - 1, -1, -1):
         actsN, actsT, F = tape_e[t]
         ganti = np.broadcast_to(gq, (B, N, N)) * wgt
-        dXN, _ = otr._mlp_bwd((0.5 * ganti).reshape(-1, 1), actsN, w["pas"][t], "listed")
-        dXT, _ = otr._mlp_bwd((-0.5 * ganti).reshape(-1, 1), actsT, w["pas"][t], "swapped")
+        dXN, _ = otr._mlp_bwd((half * ganti).reshape(-1, 1), actsN, w["pas"][t], "listed")
+        dXT, _ = otr._mlp_bwd((-half * ganti).reshape(-1, 1), actsT, w["pas"][t], "swapped")
         dXN = dXN.reshape(B, N, N, -1)
         dXT = dXT.reshape(B, N, N, -1)
         ga = dXN[..., :F].sum(2) + dXN[..., F:2 * F].sum(1) + dXT[..., :F].sum(1) + dXT[..., F:2 * F].sum(2)
@@ -140,9 +151,14 @@ def _vjp64(xyz, x_at, Q, g, weights, N, h_dim, cutoff, eta, near_tol=1e-5):
         gE += dX[..., 2 * F:]
         gh = gh_prev + ga[..., nx:nx + nh]
     # ------------------------------------------------------------------ edge features -> coordinates
-    gD = (gE[0, :n, :n] * de).sum(-1)                                       # (n,n)
+    if _CUT_GE is not None:
+        gE = _CUT_GE(gE)
+    gD = (gE[0, :n, :n].astype(np.float64) * de).sum(-1)                    # (n,n), float64 geometry whatever dtype is
     G = gD + gD.T
     with np.errstate(divide="ignore", invalid="ignore"):
         Wm = np.where(Dm > 0, G / np.where(Dm > 0, Dm, 1.0), 0.0)
     gxyz = (Wm[:, :, None] * dvec).sum(1)                                   # sum_j G_ij (r_i - r_j) / D_ij
+    if not f64:                                                             # (columns past the third: cell_ref's strain terms, summed first)
+        pred = pred.astype(np.float64)
+        gxyz[:, :3] = gxyz[:, :3].astype(np.float32)
     return pred, gxyz
