@@ -469,7 +469,8 @@ class EPNNModel(_Stack):
 
     def predict_xyz_stream(self, batches, N=None, depth=8):
         """Charges of every (offsets, xyz, x, Q) batch of `batches`, in order, with `depth` batches in flight on the GPU
-        (engine.Pipeline.map: the loop of infer.py:62-76 at the throughput of the compact entry)."""
+        (engine.Pipeline.map: the loop of infer.py:62-76 at the throughput of the compact entry).  A batch's arrays are the
+        caller's again as soon as `batches` is asked for the next item: a loader may refill one set of buffers in place."""
         from .engine import Pipeline
         pipe = Pipeline(depth=depth, nx=self.n_elems, T=self.T, h_dim=self.h_dim, e_dim=self.h_dim, device=_DEVICE)
         try:

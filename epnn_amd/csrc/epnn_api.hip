@@ -440,6 +440,11 @@ extern "C" int epnn_last_stats(epnn_handle *h, int64_t *out4) {
 extern "C" double epnn_edge_basis_residual(epnn_handle *h) { return h ? h->edge_res : 1.0; }
 extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
     if (!h || !name) EPNN_FAIL("epnn_set_option: null argument");
+    // (a forward that may still owe a capacity regrow is finished under the options it was enqueued with: its redo builds a new plan)
+    if (h->pending.active) {
+        HIPCHK(hipSetDevice(h->device));
+        if (finish_forward(h)) return 1;
+    }
     if (!strcmp(name, "profile")) {
         HIPCHK(hipSetDevice(h->device));
         if (finish_forward(h)) return 1;

@@ -651,6 +651,14 @@ extern "C" int epnn_sync(epnn_handle *h) {
 // its arrays at once), uploads + kernel + download of the charges are queued, and the call returns without waiting for
 // the GPU.  end: waits and hands the charges over.  One forward per handle between begin and end; several handles
 // (engine.Pipeline) keep several batches in flight.
+// Another entry on the handle between the two halves (include/epnn.h at epnn_forward_xyz_begin): a second begin and the box /
+// cell host forwards are refused by name (they would take over pin_ctl's payload and pin_out); every other entry is served --
+// forward_xyz_dev, the dense entries, charges_vjp / charges_jvp, coulomb_xyz, train_step_xyz, set_weights, set_option, sync.
+// What keeps the begun forward whole under them: a forward of small molecules only owes nothing once it is queued (the stream
+// orders what follows, build_plan waits for ev_ctl before it writes the staging again); one with tiled molecules is `pending`
+// and every such entry finishes it first, regrow and redo included -- set_weights and set_option too, or the redo would pack
+// the new weights / plan with the new options --, while its inputs still lie in d_ctl behind the plan; and nothing but begin
+// writes pin_out.
 // geo: the forward's geometry, its rows [B] on the host (staged with the other inputs)
 static int forward_xyz_begin_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                   const HostGeo &geo) {

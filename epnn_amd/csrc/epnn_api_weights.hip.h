@@ -206,6 +206,12 @@ extern "C" int epnn_weight_shape(epnn_handle *h, int which, int t, int layer, in
 extern "C" int epnn_set_weights(epnn_handle *h, int which, int t, int layer, const float *kernel, const float *bias) {
     HostDense *d = find_layer(h, which, t, layer);
     if (!d || !kernel || !bias) EPNN_FAIL("epnn_set_weights: bad (which=%d, t=%d, layer=%d) or null pointer", which, t, layer);
+    // a forward that may still owe a capacity regrow is run again by whoever waits for it (finish_forward), and that enqueue packs
+    // the weights it finds: it is finished with the weights it was begun with
+    if (h->pending.active) {
+        HIPCHK(hipSetDevice(h->device));
+        if (finish_forward(h)) return 1;
+    }
     if (h->train) { if (train_sync_to_host(h)) return 1; train_state(h)->ready = false; }   // masters are stale now
     if (h->model_dim == EPNN_EDIM) {
         memcpy(d->W.data(), kernel, d->W.size() * sizeof(float));

@@ -276,7 +276,9 @@ class Engine:
         return offsets, xyz, x, Q, per_atom, B, A
 
     def forward_xyz_begin(self, offsets, xyz, x, Q, N):
-        """First half of forward_xyz: returns as soon as the work is queued (the arrays may be reused at once)."""
+        """First half of forward_xyz: returns as soon as the work is queued (the arrays may be reused at once).  Until
+        forward_xyz_end, this engine refuses another begin and forward_xyz; its other methods are served and leave the begun forward's
+        result alone, new weights and options counting from the next forward on (include/epnn.h at epnn_forward_xyz_begin)."""
         offsets, xyz, x, Q, _, B, A = self._flat_batch(_FORWARD_SHAPES, offsets, xyz, x, Q)
         check(self.lib.epnn_forward_xyz_begin(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q)), self.lib)
         self._begun = A
@@ -817,7 +819,16 @@ class Pipeline:
         entry points release the GIL and every lane is a handle of its own.  Measured on the bench batch (MI355X box, 16 cores):
         inline 184-186 M atoms/s, one worker 209-218 M, two or more no better than one (the first halves of different lanes
         do not overlap: the HIP runtime's copies and launches serialise).  Default 1 with more than one lane; 0 = everything on
-        the calling thread."""
+        the calling thread.
+        The arrays of a batch: `map` is done with them when it asks `batches` for the next item (or ends it), as
+        `forward_xyz_begin` is when it returns -- a loader may refill one set of buffers in place for every batch.  (With workers the
+        first half runs later, on another thread: the calling thread takes its own copy of the four arrays first.  That costs: on
+        tools/bench_e2e.py's map line, 15 passes per process, medians of 127-176 M atoms/s against 202-248 M for the map that did not
+        copy and returned wrong charges to such a loader; holding the loader back until each first half has returned instead gave
+        131-167 M: profiles/r22_pipeline_contract.txt.)
+        Errors: the first one in call order reaches the caller, as raised (a batch whose arrays do not convert, a failed first or
+        second half, the loader's own); whatever else is in flight is collected first, its errors dropped, so that every lane takes
+        the next call.  The same holds when the caller stops iterating."""
         if workers is None:
             workers = 1 if len(self.engines) > 1 else 0
         if workers <= 0:
@@ -826,26 +837,53 @@ class Pipeline:
         from concurrent.futures import ThreadPoolExecutor
         busy = []                                   # (engine, future of its forward_xyz_begin), oldest first
         pool = ThreadPoolExecutor(max_workers=int(workers))
+        taking = False                              # an error now is the loader's or the new batch's: behind all that is in flight
         try:
-            for offsets, xyz, x, Q in batches:
+            batches = iter(batches)
+            while True:
+                taking = True
+                try:
+                    offsets, xyz, x, Q = next(batches)
+                except StopIteration:
+                    break
+                # the worker reads the arrays after the loader has been asked for the next batch: its own copies
+                offsets = np.array(offsets, dtype=np.int32, order="C")
+                xyz, x, Q = (np.array(a, dtype=np.float32, order="C") for a in (xyz, x, Q))
+                taking = False
                 e = self.lane()
                 if busy and busy[0][0] is e:        # the lane's previous forward is collected before it takes the next
                     e0, f0 = busy.pop(0)
                     f0.result()
                     yield e0.forward_xyz_end()
                 busy.append((e, pool.submit(e.forward_xyz_begin, offsets, xyz, x, Q, N)))
+            taking = False
             while busy:
                 e0, f0 = busy.pop(0)
                 f0.result()
                 yield e0.forward_xyz_end()
-        finally:
-            for e0, f0 in busy:                     # abandoned half way (error, or the caller stopped iterating): collect what
-                try:                                # is in flight so that the engines can be used again
-                    f0.result()
-                    e0.forward_xyz_end()
-                except EpnnError:
-                    pass
+        except Exception:
+            first = self._collect(busy)
+            if taking and first is not None:
+                raise first
+            raise
+        finally:                                    # (the caller stopped iterating)
+            self._collect(busy)
             pool.shutdown(wait=True)
+
+    @staticmethod
+    def _collect(busy):
+        """Abandoned half way (error, or the caller stopped iterating): collect what is in flight, oldest first, so that the engines can
+        be used again -> the first error met.  A lane whose first half failed has begun nothing: no second half for it."""
+        first = None
+        while busy:
+            e0, f0 = busy.pop(0)
+            try:
+                f0.result()
+                e0.forward_xyz_end()
+            except Exception as err:
+                if first is None:
+                    first = err
+        return first
 
     def _map_inline(self, batches, N):
         busy = []                                   # engines with a begun forward, oldest first
@@ -854,15 +892,15 @@ class Pipeline:
                 e = self.lane()
                 if busy and busy[0] is e:
                     yield busy.pop(0).forward_xyz_end()
-                e.forward_xyz_begin(offsets, xyz, x, Q, N)
+                e.forward_xyz_begin(offsets, xyz, x, Q, N)     # (done with the arrays when it returns; a failed one has begun nothing)
                 busy.append(e)
             while busy:
                 yield busy.pop(0).forward_xyz_end()
         finally:
-            for e in busy:                          # abandoned half way (error, or the caller stopped iterating): collect
-                try:                                # what is in flight so that the engines can be used again
-                    e.forward_xyz_end()
-                except EpnnError:
+            while busy:                             # abandoned half way (error, or the caller stopped iterating): collect what is in
+                try:                                # flight so that the engines can be used again; the error under way is the one kept
+                    busy.pop(0).forward_xyz_end()
+                except Exception:
                     pass
 
     def sync(self):

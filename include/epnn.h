@@ -158,7 +158,17 @@ int epnn_forward_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const
 /* The same call in two halves (the loop of infer.py:62-76 with several batches in flight): _begin copies the host arrays
  * into page-locked staging owned by the handle (the caller may reuse them at once), queues uploads, kernels and the
  * download of the charges, and returns without waiting for the GPU; _end waits and writes q_out[A].  One forward per
- * handle between _begin and _end; use several handles to overlap batches (epnn_amd.engine.Pipeline.map). */
+ * handle between _begin and _end; use several handles to overlap batches (epnn_amd.engine.Pipeline.map).
+ * Memory: offsets, xyz, x and Q are read before _begin returns and never afterwards, a pair-list regrow inside _end included (it
+ * runs again from the staged copy); q_out is written by _end only.
+ * Other entries on the SAME handle between _begin and _end (tests/test_gpu_pipeline_contract.py):
+ *   refused by name, the begun forward untouched: epnn_forward_xyz_begin, epnn_forward_xyz_pbc, epnn_forward_xyz_cell (and
+ *     epnn_forward_xyz, which is _begin + _end);
+ *   served, with the outputs the same call gives on a fresh handle: epnn_forward_xyz_dev (and _pbc_dev / _cell_dev), the dense
+ *     entries (epnn_model_forward_dense ...), epnn_charges_vjp_xyz, epnn_charges_jvp_xyz, epnn_coulomb_xyz, epnn_train_step_xyz,
+ *     epnn_set_weights, epnn_set_option, epnn_sync.  Each of them first finishes what the begun forward still owes (the wait for a
+ *     forward of tiled molecules and its pair-list regrow), so _end returns the charges of the begun batch, computed with the
+ *     weights and options that held at _begin: new weights or options count from the next forward on. */
 int epnn_forward_xyz_begin(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                            const float *Q);
 int epnn_forward_xyz_end(epnn_handle *h, float *q_out);

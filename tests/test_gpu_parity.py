@@ -465,7 +465,8 @@ def test_fused_kernel_every_size_vs_oracle(gpu_engine_factory):
 def test_pipeline_map_equals_one_call_at_a_time(weights_decay):
     """Pipeline.map (epnn_forward_xyz_begin / _end on several handles, page-locked staging, plans uploaded without
     waiting) returns, in order, bit-for-bit what forward_xyz returns for each batch - also when a batch contains a
-    system for the tiled path (the deferred pair-list regrow runs inside _end)."""
+    system for the tiled path (its 698 pairs fit the list's first 1024: the regrow deferred into _end is reached in
+    tests/test_gpu_pipeline_contract.py)."""
     from epnn_amd import synth
     from epnn_amd.engine import Engine, Pipeline
     batches = [synth.qm9_like_batch(B=40 + 7 * s, seed=s) for s in range(7)]
