@@ -403,6 +403,14 @@ class EPNNModel(_Stack):
         return self._eng().coulomb_xyz_cell(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke, alpha=alpha,
                                             tol=tol, ewald=ewald, parts=parts, strain=strain)
 
+    def coulomb_xyz_slab(self, offsets, xyz, x, Q, N=None, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                         parts=False, exclusions=None):
+        """coulomb_xyz in slab cells (two periodic axes, one row of zeros), by the exact two-dimensional Ewald sum: (q (A,), phi (A,),
+        E (B,) float64 per cell, F (A, 3)), with parts=True also ffix and fq.  tol sets the parameters (Engine.ewald_slab_params),
+        ewald= gives them; exclusions = (pairs, scale) as in coulomb_xyz_excl.  A charged slab has no neutralising background."""
+        return self._eng().coulomb_xyz_slab(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke, alpha=alpha,
+                                            tol=tol, ewald=ewald, parts=parts, exclusions=exclusions)
+
     def coulomb_xyz_excl(self, offsets, xyz, x, Q, N=None, ke=KE_EV_ANGSTROM, alpha=0.0, parts=False, exclusions=None):
         """coulomb_xyz with bonded exclusions and pair scaling: exclusions = (pairs (P, 2), scale) as engine.bonded_exclusions
         returns it; a listed pair counts with weight scale instead of 1 (0 excludes).  None is coulomb_xyz itself."""

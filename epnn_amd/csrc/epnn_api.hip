@@ -501,3 +501,4 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
 #include "epnn_api_jvp.hip.h"
 #include "epnn_api_coulomb.hip.h"
 #include "epnn_api_coulomb_cell.hip.h"
+#include "epnn_api_coulomb_slab.hip.h"

@@ -555,11 +555,43 @@ class Engine:
         return self._coulomb("coulomb_xyz_cell_excl", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, strain),
                              exclusions=exclusions)
 
-    def _coulomb(self, where, offsets, xyz, x, Q, N, ke, alpha, parts, periodic=None, exclusions=None):
-        """The four coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
-        molecules, exclusions = (pairs, scale) or None for the plain C entry (an _excl method without a list is its plain method)."""
+    def ewald_slab_params(self, cell, alpha=0.0, tol=1e-6):
+        """The parameters coulomb_xyz_slab runs at for one slab cell (3, 3) with one row of zeros (epnn_ewald_slab_params, host only):
+        float64 (6,) = beta, rc, kc, M0, M1, M2 by the rule of ewald_params over the two periodic rows; M of the open row is 0.
+        Refuses three periodic rows (ewald_params), fewer than two, dependent rows, tol outside (0, 1) and k boxes above 2^16 slots."""
+        cell = np.ascontiguousarray(cell, dtype=np.float32)
+        if cell.shape != (3, 3):
+            raise ValueError(f"ewald_slab_params: cell must have shape (3, 3), got {cell.shape}")
+        out = np.empty((6,), dtype=np.float64)
+        check(self.lib.epnn_ewald_slab_params(fptr(cell), float(alpha), float(tol), out.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
+        return out
+
+    def coulomb_xyz_slab(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None, parts=False,
+                         exclusions=None):
+        """coulomb_xyz in slab cells, two periodic axes and one open one, by the exact two-dimensional Ewald sum
+        (epnn_coulomb_xyz_slab): flat batch -> (q (A,), phi (A,), E (B,) float64 per cell, F (A, 3)).  cell (3, 3) or (B, 3, 3) with
+        exactly one row of zeros, the open axis, or box (3,) or (B, 3) with exactly one zero.  phi includes the self term of the
+        split; a charged slab (the model conserves Q, which need not be 0) gets the finite part of a charged sheet's potential and no
+        neutralising background, which does not exist in two dimensions (include/epnn.h has the sum).  ewald (6,) or (B, 6) float64:
+        the parameters the call runs at; None: ewald_slab_params(cell, alpha, tol) per cell.  parts=True appends ffix and fq
+        (F = ffix + fq); fq is -gxyz of charges_vjp_xyz(g=phi, cell=) on "grad_path" 2, bit for bit.  exclusions = (pairs, scale) as
+        in coulomb_xyz_excl: the nearest image of every listed pair counts with weight scale; None: no list.  One periodic axis
+        (wires) and the strain derivative of the slab sum are not built."""
+        if box is not None and cell is None:
+            rows = np.asarray(box, dtype=np.float32)
+            if rows.shape[-1:] != (3,) or ((rows.reshape(-1, 3) == 0).sum(1) != 1).any():
+                raise ValueError("coulomb_xyz_slab: box must have exactly one zero, the open axis (none: coulomb_xyz_cell)")
+        return self._coulomb("coulomb_xyz_slab", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, False),
+                             exclusions=exclusions, slab=True)
+
+    def _coulomb(self, where, offsets, xyz, x, Q, N, ke, alpha, parts, periodic=None, exclusions=None, slab=False):
+        """The five coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
+        molecules, exclusions = (pairs, scale) or None for the plain C entry (an _excl method without a list is its plain method).
+        slab: the one slab entry, which always takes a list (None: an empty one), its own rule and no strain rows."""
         if exclusions is None:
             where = where.replace("_excl", "")
+            if slab:
+                exclusions = (np.zeros((0, 2), dtype=np.int32), 1.0)
         strain = False
         if periodic is not None:
             cell, box, tol, ewald, strain = periodic
@@ -573,7 +605,8 @@ class Engine:
         if periodic is not None:
             _, cell = _geometry(box, cell, B, cells_only=True)
             if ewald is None:
-                ewald = np.stack([self.ewald_params(cell[b], alpha, tol) for b in range(B)])
+                rule = self.ewald_slab_params if slab else self.ewald_params
+                ewald = np.stack([rule(cell[b], alpha, tol) for b in range(B)])
             ewald = np.asarray(ewald, dtype=np.float64)
             if ewald.shape == (6,):
                 ewald = np.tile(ewald, (B, 1))
@@ -590,7 +623,7 @@ class Engine:
         F = np.empty((A, 3), dtype=np.float32)
         ffix, fq = (np.empty((A, 3), dtype=np.float32) if parts else None for _ in range(2))
         outs = [fptr(q), fptr(phi), dptr(E), fptr(F), opt(ffix), opt(fq)]
-        if periodic is not None:
+        if periodic is not None and not slab:
             gs = np.empty((B, 3, 3), dtype=np.float32)
             gs_fix, gs_q = (np.empty((B, 3, 3), dtype=np.float32) if parts else None for _ in range(2))
             outs = outs[:4] + [fptr(gs)] + outs[4:] + [opt(gs_fix), opt(gs_q)]

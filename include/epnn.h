@@ -413,7 +413,7 @@ int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t 
  *     f_i      = ffix_i + fq_i  (one float32 add per component)                          = -dE/dr_i, total
  * ke is the caller's unit constant (14.3996454784255 eV A / e^2, 332.0637 kcal A / mol e^2).  q is the model's output, so sum q = Q
  * holds by construction and no constraint term appears.  Open systems only: the entry takes no box or cell (fully periodic cells:
- * epnn_coulomb_xyz_cell below, an Ewald sum; partially periodic cells are not built).  No self-energy term (for alpha > 0 the
+ * epnn_coulomb_xyz_cell below, an Ewald sum; slabs, two periodic axes: epnn_coulomb_xyz_slab below).  No self-energy term (for alpha > 0 the
  * Gaussians' self-energy -ke alpha / sqrt(pi) sum q_i^2 is left out; it depends on q alone).  Every pair of a molecule counts in full
  * here; bonded exclusions and the scaling of near neighbours: epnn_coulomb_xyz_excl below.
  * Outputs (host): q_out[A], phi_out[A], e_out[B] in float64 (a float32 energy of a 100 000-atom system loses the digits its forces
@@ -488,7 +488,8 @@ int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const
  * (tests/test_gpu_coulomb_cell.py counts the roundings; measured: 0.03 of that at worst).
  * Device scratch on top of the gradient path's: A (20 + 80 cpieces + 56) + 44 B + 32 slots + the task tables and 72 B of
  * parameters; slots = the batch's k slots, about 3600 for a cube at tol = 1e-6 whatever its size.  Nothing of size n nk or n^2.
- * Still missing: partially periodic cells, PME for very large cells (bonded exclusions: epnn_coulomb_xyz_cell_excl below). */
+ * Still missing: one periodic axis (wires); the strain derivative of the slab sum; PME (bonded exclusions: epnn_coulomb_xyz_cell_excl
+ * below; two periodic axes: epnn_coulomb_xyz_slab below). */
 int epnn_ewald_params(const float *cell, double alpha, double tol, double *out);
 int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                           const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
@@ -534,6 +535,74 @@ int epnn_coulomb_xyz_cell_excl(epnn_handle *h, int B, int N, const int32_t *offs
                                const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
                                const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
                                float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out);
+/* ---- electrostatics of the predicted charges in slab cells: epnn_coulomb_xyz for two periodic axes and one open axis (surfaces,
+ * membranes, electrodes, adsorbed layers), by the exact two-dimensional Ewald sum (Parry; Heyes, Barber and Clarke; de Leeuw and
+ * Perram; INTEGRATION.md, "Electrostatics in one call", the section "Slabs").  cell [B][3][3] as in epnn_forward_xyz_cell with
+ * exactly one row of zeros, the open axis, at any of the three places (the distance rule: "A row of three zeros is an open axis"
+ * above).  a, b the two periodic rows, A = |a x b|, nhat = (a x b) / A, g_a, g_b their dual vectors, d_ij = r_i - r_j,
+ * z_ij = nhat . d_ij; ke, alpha, e_alpha and g as in epnn_coulomb_xyz_cell; beta the splitting parameter:
+ *     real         kappa_s(D) = [e_alpha(D) - erf(beta D)] / D over the minimum image of every pair j != i with D <= rc, zero beyond
+ *                  (rc <= w_min / 2 over the two periodic widths; the image rule is the forward's; z is not wrapped)
+ *     reciprocal   k = 2 pi (m0 g_a + m1 g_b) != 0, |k| <= kc, k = |k|, u = k / (2 beta):
+ *                  F+(k, z) = e^{ k z} erfc(u + beta z),   F-(k, z) = e^{-k z} erfc(u - beta z)
+ *                  phi_i  += sum_k (pi / (A k)) sum_j q_j cos(k . d_ij) [F+ + F-](k, z_ij)       (j over ALL atoms of the cell, j == i too)
+ *                  ffix_i -= q_i sum_k (pi / (A k)) sum_j q_j { -k sin(k . d_ij) [F+ + F-] + nhat k cos(k . d_ij) [F+ - F-] }
+ *                  (d[F+ + F-]/dz = k [F+ - F-]: the Gaussian terms cancel exactly; the half plane m1 > 0, or m1 == 0 and m0 > 0, is
+ *                  summed with the weight doubled: the summand is even in k)
+ *     k = 0        phi_i  += -(2 sqrt(pi) / A) sum_j q_j [ exp(-beta^2 z_ij^2) / beta + sqrt(pi) z_ij erf(beta z_ij) ]    (j == i too)
+ *                  ffix_i -= q_i sum_j q_j nhat [ -(2 pi / A) erf(beta z_ij) ]
+ *     self         phi_i  -= (2 beta / sqrt(pi)) q_i                        (there for alpha == 0 and alpha > 0 alike)
+ *     energy       E = 1/2 sum_i q_i phi_i per cell;   f = ffix + fq,  fq_i = -sum_k phi_k dq_k/dr_i
+ * all times ke.  F+- are evaluated without overflow or cancellation: with ex = exp(-u^2 - beta^2 z^2), ex erfcx(u +- beta z) for an
+ * argument u +- beta z >= 0 and 2 exp(+-k z) - ex erfcx(|u +- beta z|) otherwise.
+ * A charged slab: the model conserves Q, which need not be 0, and the formulas are applied as written whatever Q.  No neutralising
+ * background exists in two dimensions (a uniform sheet's potential grows with |z|, it cannot be hidden in a constant): the k = 0 term
+ * is the finite part of a charged sheet's potential, and the infinite constant proportional to Q that is dropped does not depend on
+ * beta.  phi of a charged slab is therefore defined up to that constant, E up to Q times it; ffix, fq and f are not touched by it
+ * (sum_i dq_i/dr = 0).
+ * epnn_ewald_slab_params (host only, no handle, no device) holds the rule for one cell [3][3], that of epnn_ewald_params over the
+ * two periodic rows: s = sqrt(-ln tol), rc = w_min / 2, beta = s / rc, capped at alpha where alpha > 0 (then rc = 0: no real-space
+ * part), kc = 2 beta s, M_k = ceil(kc |a_k| / 2 pi) for the periodic rows and 0 for the open row.  out [6] = beta, rc, kc, M0, M1,
+ * M2.  tol means what it means there (the same three bounds; measured 0.005 to 0.013 of them on a 12-atom sheared slab, neutral or
+ * charged).  About 131 half-plane vectors at tol = 1e-6 in a near-square cell, whatever its size.  It refuses, by name: a cell with
+ * three periodic rows (use epnn_coulomb_xyz_cell), with one or none (not built), dependent rows, an entry that is not finite,
+ * alpha negative or not finite, tol outside (0, 1), and a k box (2 M0' + 1)(M1' + 1) above 2^16 slots, M0' and M1' the M of the two
+ * periodic rows (every k slot meets every pair: extreme aspect ratios are refused, not served slowly).
+ * epnn_coulomb_xyz_slab takes ewald [B][6] (host, float64, a row per cell as epnn_ewald_slab_params writes it), checks that
+ * beta > 0, 0 <= rc <= w_min / 2 (rc == 0 only with beta == alpha > 0), that the open row's M is 0, that the two others are
+ * integers of at least ceil(kc |a_k| / 2 pi), and the slot cap, and runs at exactly those values.
+ * Exclusions: the list (npairs, ex_i, ex_j, ex_scale) has the meaning, the checks and the refusals of epnn_coulomb_xyz_cell_excl:
+ * the one nearest image of a listed pair gets (s - 1) times its bare kappa_alpha term, whatever beta; a listed pair farther apart
+ * than half the smaller periodic width is refused by name after the device pass.  npairs == 0 is allowed (the three pointers may
+ * then be NULL): the slab call needs one entry, not two.  A list whose factors are all 1 gives the bits of the call without a list;
+ * the outputs depend neither on the order of the list nor on which atom of a pair is named first.
+ * Outputs (host): q_out[A], phi_out[A], e_out[B] float64 (per cell), f_out[A][3]; ffix_out and fq_out may each be NULL and the
+ * other outputs have the same bits either way.  No strain derivative (out of scope, as is one periodic axis).
+ * Contract: that of epnn_coulomb_xyz_cell, word for word where it applies: the pair-list path whatever "grad_path" says, no
+ * training state touched, waits for a "train_async" step, the same refusals by name (coincident atoms or images included, a
+ * periodic width below twice the cutoff, a molecule that does not fit N), the handle left usable; h_dim below 48 zero-padded; no
+ * float atomics and every sum in a fixed order; a cell's rows depend neither on the rest of the batch nor on the order of the list.
+ * Bits: q_out has the bits of epnn_charges_vjp_xyz_cell on "grad_path" 2 with the same cell; fq_out is bit for bit -gxyz_out of
+ * that entry called with g = phi_out; f_out == ffix_out + fq_out in float32.
+ * Arithmetic: the real-space part is epnn_coulomb_xyz_cell's sweep as it is.  The reciprocal and k = 0 part is one all-pairs sweep
+ * on the open sweep's tasks in which every pair meets every slot of its cell's half plane (listed by the host in float64, with
+ * exp(-u^2) folded into the weight).  Per pair z_ij, the two fractional differences and exp(-beta^2 z^2) are float64; per (pair,
+ * slot) the phase 2 pi frac(m0 f0 + m1 f1) and the two erfc arguments are taken in float64 and rounded once, and the exponent of
+ * 2 exp(+-k z) is split into two float32; everything else is float32 (sincosf, erfcxf, expf, erff, the products); the running sums
+ * are float64.  phi, ffix and E are each within 2e-6 of the sum of their absolute real-space terms (and of the listed pairs'
+ * correction terms), plus 41 * 2^-24 of their absolute reciprocal terms (pi / (A k)) [F+ + F-] |q_j|, for ffix k times that, plus
+ * 16 * 2^-24 of their absolute k = 0 terms (tests/test_gpu_coulomb_slab.py counts the roundings; measured: 0.036 of that at worst).
+ * Device scratch (epnn_last_stats out[2]): that of epnn_coulomb_xyz on the same batch (both formulas there) plus what the slab adds
+ * -- the real-space rows are [cpieces][A][10] instead of [cpieces][A][4], the reciprocal sweep's rows [cpieces][A][5], and staged
+ * with the inputs the cells' records (120 B), the two sweeps' parameters (72 B and 112 B) and the slots:
+ *     bytes = epnn_coulomb_xyz's + 88 A cpieces + 304 B + 56 slots                (the 72 B rounded up to a multiple of 16)
+ * cpieces and ctasks as at epnn_coulomb_xyz, slots = the batch's listed half-plane slots; with a list of P pairs, P > 0, also
+ * (A + 1) 4 + 16 P + 80 A (two buffers).  Time grows as n^2 times the slots: the exact method's price. */
+int epnn_ewald_slab_params(const float *cell, double alpha, double tol, double *out);
+int epnn_coulomb_xyz_slab(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                          const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
+                          const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
+                          float *ffix_out, float *fq_out);
 /* ---- training on periodic and large systems. epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
  * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
  * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's

@@ -24,7 +24,15 @@ is the call with bonded exclusions, coulomb_xyz_excl or coulomb_xyz_cell_excl, b
 0.8333 in sorted pair order, handed over shuffled with half of the rows swapped -- a few pairs per atom.  Printed per system: the two
 medians and their ratio, pairs per atom, the scratch the list adds beside the formula of include/epnn.h, and the checks q (bits
 against the plain call) and fq against -gxyz of the gradient call seeded with phi (bits).  With --trace: three calls of the _excl
-entry per system (the k_cl_excl row is the new kernel)."""
+entry per system (the k_cl_excl row is the new kernel).
+    python tools/bench_coulomb.py --slab [--systems qm9slab,slab2048,slab10000] [--rounds 5] [--alpha 0.0] [--tol 1e-6] [--trace]
+is the slab call coulomb_xyz_slab (two periodic axes, the exact two-dimensional Ewald sum; profiles/r19_coulomb_slab.txt) beside two
+figures of the same process: charges_vjp_xyz(cell=slab cell) of the same atoms, the tool's yardstick, and coulomb_xyz_cell of the same
+atoms in a cell whose third vector is nhat times three slab thicknesses and at least twice the cutoff, which is what a caller had to
+do before.  The workloads: 1024 QM9-sized 6.5 A square slabs 5 A thick, a 2048-atom and a 10 000-atom slab on a jittered lattice at
+the tool's cell density (0.1 per A^3, four layers).  Printed besides: the listed half-plane slots, the scratch beside the formula of
+include/epnn.h, and the checks q (bits) and fq against -gxyz of the gradient call seeded with phi (bits).  With --trace: three calls
+of coulomb_xyz_slab per system (the k_sl_* rows are the new kernels; k_ew_sweep is the real-space part)."""
 import json
 import os
 import sys
@@ -109,6 +117,105 @@ def load_cell(system):
         offsets, xyz, x, Q, N, box = synth.periodic_box_system(int(system[4:]), seed=0)
         return f"{int(system[4:])} atoms, cubic cell of {float(box[0][0]):.2f} A", offsets, xyz, x, Q, N, np.diag(box[0]).astype(np.float32)[None]
     raise SystemExit(f"unknown system {system}")
+
+
+def lattice_slab(nx, ny, layers, seed, density=0.1):
+    """nx x ny x layers atoms on a lattice of spacing density^(-1/3), each moved by up to 0.5 A per axis (no two closer than the
+    spacing less 1 A), in the rectangular slab cell of that lattice, open along z; the element mix of periodic_box_system."""
+    rng = np.random.default_rng(seed)
+    d = density ** (-1.0 / 3.0)
+    g = np.stack(np.meshgrid(np.arange(nx), np.arange(ny), np.arange(layers), indexing="ij"), -1).reshape(-1, 3) * d
+    xyz = (g + rng.uniform(-0.5, 0.5, g.shape)).astype(np.float32)
+    names = [e for e, _ in synth.PROTEIN_ELEMS]
+    ep = np.array([p for _, p in synth.PROTEIN_ELEMS])
+    x = synth.features(rng.choice(names, size=len(xyz), p=ep / ep.sum()))
+    cell = np.float32([[nx * d, 0, 0], [0, ny * d, 0], [0, 0, 0]])
+    return np.array([0, len(xyz)], np.int32), xyz, x, np.zeros(1, np.float32), len(xyz), cell[None], layers * d
+
+
+def load_slab(system):
+    """(name, offsets, xyz, x, Q, N, cells (B, 3, 3) with a zero third row, thickness)"""
+    if system == "qm9slab":
+        offsets, _, x, Q, N = synth.qm9_like_batch(B=1024, seed=0, N=29)
+        rng = np.random.default_rng(0)
+        L, thick, pts = 6.5, 5.0, []
+        for n in np.diff(offsets):
+            mol = np.zeros((0, 3))
+            while len(mol) < n:
+                p = rng.uniform(0, 1, 3) * [L, L, thick]
+                v = mol - p
+                v[:, :2] -= L * np.rint(v[:, :2] / L)
+                if not len(mol) or (v * v).sum(1).min() >= 0.81:
+                    mol = np.vstack([mol, p])
+            pts.append(mol)
+        cells = np.tile(np.diag(np.float32([L, L, 0])), (len(offsets) - 1, 1, 1))
+        return "1024 QM9-sized square slabs of 6.5 A, N = 29", offsets, np.concatenate(pts).astype(np.float32), x, Q, N, cells, thick
+    if system.startswith("slab"):
+        n = int(system[4:])
+        nx = {2048: 32, 10000: 50}.get(n)
+        if nx is None or n % (4 * nx):
+            raise SystemExit("slab systems: slab2048 (32 x 16 x 4) and slab10000 (50 x 50 x 4)")
+        o, xyz, x, Q, N, cells, thick = lattice_slab(nx, n // (4 * nx), 4, seed=0)
+        return (f"{n} atoms, slab of {float(cells[0][0, 0]):.2f} x {float(cells[0][1, 1]):.2f} A, {thick:.2f} A thick", o, xyz, x, Q, N, cells, thick)
+    raise SystemExit(f"unknown system {system}")
+
+
+def slab_slots(cells, rows):
+    """the listed slots of the batch: the half plane m1 > 0, or m1 == 0 and m0 > 0, inside kc (cells open along z)"""
+    total = 0
+    for c, r in zip(cells, rows):
+        m0, m1 = np.meshgrid(np.arange(-r[3], r[3] + 1), np.arange(0, r[4] + 1), indexing="ij")
+        k = 2 * np.pi * np.sqrt((m0 / float(c[0, 0])) ** 2 + (m1 / float(c[1, 1])) ** 2)
+        total += int(((k <= r[2]) & ((m1 > 0) | (m0 > 0))).sum())
+    return total
+
+
+def main_slab(eng, T, systems, rounds, alpha, tol, cutoff=3.0):
+    for system in systems:
+        name, offsets, xyz, x, Q, N, cells, thick = load_slab(system)
+        A = int(offsets[-1])
+        rows = np.stack([eng.ewald_slab_params(c, alpha, tol) for c in cells])
+        slots = slab_slots(cells, rows)
+        if "--trace" in sys.argv:
+            for _ in range(3):
+                eng.coulomb_xyz_slab(offsets, xyz, x, Q, N, cell=cells, alpha=alpha, ewald=rows)
+            print(json.dumps({"workload": name, "atoms": A, "calls": 3, "alpha": alpha, "tol": tol, "k_slots": slots}), flush=True)
+            continue
+        padded = cells.copy()
+        padded[:, 2, 2] = max(3.0 * thick, 2.0 * cutoff)
+        rows3 = np.stack([eng.ewald_params(c, alpha, tol) for c in padded])
+        g = np.random.default_rng(0).normal(size=A).astype(np.float32)
+        calls = {"coulomb_slab": lambda: eng.coulomb_xyz_slab(offsets, xyz, x, Q, N, cell=cells, alpha=alpha, ewald=rows, parts=True),
+                 "gradient": lambda: eng.charges_vjp_xyz(offsets, xyz, x, Q, g, N, cell=cells),
+                 "coulomb_cell_padded": lambda: eng.coulomb_xyz_cell(offsets, xyz, x, Q, N, cell=padded, alpha=alpha, ewald=rows3, parts=True)}
+        for fn in calls.values():
+            fn()
+        times = {k: [] for k in calls}
+        outs = {}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t, outs[k] = window(fn)
+                times[k].append(t * 1e3)
+        q, phi, E, F, ffix, fq = outs["coulomb_slab"]
+        st = eng.last_stats() if calls["coulomb_slab"]() else None
+        seeded = eng.charges_vjp_xyz(offsets, xyz, x, Q, phi, N, cell=cells)
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        ns = [int(n) for n in np.diff(offsets)]
+        line = {"workload": name, "atoms": A, "cells": len(cells), "near_pairs": int(st[0]), "rounds": rounds, "alpha": alpha, "tol": tol,
+                "k_slots": slots, "ewald_first_cell": [round(float(v), 4) for v in rows[0]], "padded_third_vector": float(padded[0, 2, 2]),
+                "padded_k_slots": int(((2 * rows3[:, 3] + 1) * (2 * rows3[:, 4] + 1) * (rows3[:, 5] + 1)).sum())}
+        for k, t in times.items():
+            line[k + "_ms_median"] = round(med[k], 3)
+            line[k + "_ms_range"] = [round(min(t), 3), round(max(t), 3)]
+        line.update({"slab_over_gradient": round(med["coulomb_slab"] / med["gradient"], 3),
+                     "slab_over_padded_cell": round(med["coulomb_slab"] / med["coulomb_cell_padded"], 3), "slab_scratch_bytes": int(st[2]),
+                     "slab_scratch_formula_bytes": scratch_formula(ns, int(st[0]), 9, T) + 88 * A * max(map(cl_pieces, ns)) + 304 * len(ns) + 56 * slots,
+                     "q_bits_equal_gradient_call": bool(np.array_equal(q, outs["gradient"][0])),
+                     "fq_bits_equal_minus_gxyz_of_phi": bool(np.array_equal(fq, -seeded[1])),
+                     "energy_sum": float(E.sum()), "energy_sum_padded_cell": float(outs["coulomb_cell_padded"][2].sum()),
+                     "max_abs_f": float(np.abs(F).max()), "max_abs_ffix": float(np.abs(ffix).max()), "max_abs_fq": float(np.abs(fq).max()),
+                     "max_abs_sum_f": float(np.abs(F.sum(0, dtype=np.float64)).max())})
+        print(json.dumps(line), flush=True)
 
 
 def exclusion_list(offsets, xyz, cells, near):
@@ -230,13 +337,19 @@ def main_cell(eng, T, systems, rounds, alpha, tol):
 def main():
     arg = lambda name, default: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
     cell_mode = "--cell" in sys.argv
-    systems = arg("--systems", "qm9cell,cell10000,cell100000" if cell_mode else "protein,cluster10000,qm9").split(",")
+    slab_mode = "--slab" in sys.argv
+    systems = arg("--systems", "qm9slab,slab2048,slab10000" if slab_mode else "qm9cell,cell10000,cell100000" if cell_mode
+                  else "protein,cluster10000,qm9").split(",")
     rounds, alpha = int(arg("--rounds", "5")), float(arg("--alpha", "0.0"))
     w = checkpoint.load_epnn_weights(os.path.join(ROOT, "models/decay_model_weights"))
     T = len(w["msg"])
     eng = Engine(nx=9, T=T)
     eng.set_weights(w)
     eng.set_option("grad_path", 2)
+    if slab_mode:
+        main_slab(eng, T, systems, rounds, alpha, float(arg("--tol", "1e-6")))
+        eng.close()
+        return
     if "--excl" in sys.argv:
         main_excl(eng, systems, rounds, alpha, float(arg("--tol", "1e-6")), float(arg("--near", "2.2")), cell_mode)
         eng.close()
