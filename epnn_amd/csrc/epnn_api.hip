@@ -471,6 +471,7 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
     // ---- developer switches (include/epnn_dev.h)
     else if (!strcmp(name, "wave_lds")) { h->wave_lds = value; }
     else if (!strcmp(name, "wave_front")) { h->opt_wave_front = value; h->plan.valid = false; }
+    else if (!strcmp(name, "relu_clamp")) { if (value != 0 && value != 1) EPNN_FAIL("epnn_set_option: relu_clamp must be 0 or 1"); h->opt_relu_clamp = value; }
     else if (!strcmp(name, "wave_prio")) { h->opt_wave_prio = value; }
     else if (!strcmp(name, "wave_order")) { h->opt_wave_order = value; h->plan.valid = false; }
     else if (!strcmp(name, "large_fused")) { h->opt_large_fused = value; }

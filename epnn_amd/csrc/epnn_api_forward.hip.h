@@ -317,7 +317,9 @@ static int launch_wave(epnn_handle *h, const PairSource &S) {
         if (S.d_xyz) hipLaunchKernelGGL((k_wave_forward<true, true, true, 4>), grid, dim3(64), (size_t)lds, h->stream, A, X);
         else if (S.run_epn) hipLaunchKernelGGL((k_wave_forward<true, true, false, 4>), grid, dim3(64), (size_t)lds, h->stream, A, X);
         else hipLaunchKernelGGL((k_wave_forward<true, false, false, 4>), grid, dim3(64), (size_t)lds, h->stream, A, X);
-    } else if (S.d_xyz) hipLaunchKernelGGL((k_wave_forward<true, true, true>), grid, dim3(64), (size_t)lds, h->stream, A, X);
+    } else if (S.d_xyz && EPNN_RELU_CLAMP_BUILT && h->opt_relu_clamp && h->wvidx_c_ok)      // the scaled packs go with the clamp form
+        hipLaunchKernelGGL((k_wave_forward<true, true, true, 2, true>), grid, dim3(64), (size_t)lds, h->stream, A, h->wvidx_c);
+    else if (S.d_xyz) hipLaunchKernelGGL((k_wave_forward<true, true, true>), grid, dim3(64), (size_t)lds, h->stream, A, X);
     else if (S.run_gnn && S.run_epn) hipLaunchKernelGGL((k_wave_forward<true, true, false>), grid, dim3(64), (size_t)lds, h->stream, A, X);
     else if (S.run_gnn) hipLaunchKernelGGL((k_wave_forward<true, false, false>), grid, dim3(64), (size_t)lds, h->stream, A, X);
     else hipLaunchKernelGGL((k_wave_forward<false, true, false>), grid, dim3(64), (size_t)lds, h->stream, A, X);
@@ -482,15 +484,27 @@ static hipError_t wait_stream(epnn_handle *h) {
     }
     return hipStreamSynchronize(h->stream);
 }
+// EPNN_ST_RELU_RANGE of a finished forward: counted (epnn_last_stats out[3]) and taken out of the word -- the kernel has dealt with it
+// itself (k_wave_forward: the steps concerned ran in the max form), there is nothing to grow and nothing to run again
+static int take_relu_range(epnn_handle *h, int *slot) {
+    if (slot[0] & EPNN_ST_RELU_RANGE) {
+        slot[0] &= ~EPNN_ST_RELU_RANGE;
+        h->stats[3] += 1;
+    }
+    return slot[0];
+}
 // wait for the stream; if the last forward overflowed a capacity, grow it and run again
 static int finish_forward(epnn_handle *h) {
     for (int attempt = 0; attempt < 8; ++attempt) {
         HIPCHK(wait_stream(h));
         if (!h->pending.active) {
-            if (h->last_front) h->stats[0] = h->h_status[1];       // written by the last wave of the last forward
+            if (h->last_front) {
+                h->stats[0] = h->h_status[1];       // written by the last wave of the last forward
+                (void)take_relu_range(h, h->h_status);
+            }
             return 0;
         }
-        const int st = h->h_status[0];
+        const int st = take_relu_range(h, h->h_status);
         h->stats[0] = h->h_status[1];
         if (st == 0) {
             h->pending.active = false;
@@ -567,8 +581,8 @@ static int forward_xyz_dev_impl(epnn_handle *h, int B, int N, const int32_t *off
     if (ahead) {
         // the forward before this one: its own event, its own slot
         HIPCHK(hipEventSynchronize(h->ev_done[old_slot]));
-        const int *os = h->h_status_base + 4 * old_slot;
-        if (os[0] != 0) {
+        int *os = h->h_status_base + 4 * old_slot;
+        if (take_relu_range(h, os) != 0) {
             // it overflowed a capacity (this one, enqueued behind it with the same capacities, gave up at its first kernel as well):
             // wait for everything, regrow, run the old one again until it fits, then this one
             HIPCHK(hipStreamSynchronize(h->stream));

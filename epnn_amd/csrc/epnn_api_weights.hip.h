@@ -397,9 +397,13 @@ static int pack_weights(epnn_handle *h) {
         const int HU = h->upd_wide ? 64 : 32, NRU = HU / 16, KU = HU / 4;
         const float *Wu1 = ud[0].W.data(), *Wu2 = ud[1].W.data(), *Wu3 = ud[2].W.data();
         const float *bu1 = ud[0].b.data(), *bu2 = ud[1].b.data(), *bu3 = ud[2].b.data();
+        // every pack below stores float32(value) * pk_scale: 1, or a power of two while the scaled packs of the fused kernel's
+        // clamp form are built (at the end of this block) -- the float32 matrix is scaled BEFORE it is split, so the pieces of a
+        // scaled pack are the unscaled pack's with shifted exponents
+        float pk_scale = 1.f;
         auto vec = [&](int len, auto &&fn) {
             const int off = alloc(len);
-            for (int k = 0; k < len; ++k) buf[off + k] = (float)fn(k);
+            for (int k = 0; k < len; ++k) buf[off + k] = (float)fn(k) * pk_scale;
             return off;
         };
         // [nrb][steps / 4][64][4]: lane (q,m) of (rb, step s) = fn(s, q, 16rb + m)  (input selector, output feature); a lane's
@@ -409,7 +413,7 @@ static int pack_weights(epnn_handle *h) {
             for (int rb = 0; rb < nrb; ++rb)
                 for (int s = 0; s < steps; ++s)
                     for (int l = 0; l < 64; ++l)
-                        buf[off + ((rb * (steps / 4) + s / 4) * 64 + l) * 4 + (s & 3)] = (float)fn(s, l >> 4, 16 * rb + (l & 15));
+                        buf[off + ((rb * (steps / 4) + s / 4) * 64 + l) * 4 + (s & 3)] = (float)fn(s, l >> 4, 16 * rb + (l & 15)) * pk_scale;
             return off;
         };
         auto accf = [](int s, int q) { return 16 * (s >> 2) + 4 * q + (s & 3); };       // "acc" K order
@@ -422,7 +426,7 @@ static int pack_weights(epnn_handle *h) {
                 for (int l = 0; l < 64; ++l) {
                     uint32_t pc[3][8];
                     for (int s = 0; s < 8; ++s) {
-                        float v = (float)fn(l >> 4, s, 16 * rb + (l & 15));
+                        float v = (float)fn(l >> 4, s, 16 * rb + (l & 15)) * pk_scale;
                         for (int k = 0; k < 3; ++k) {
                             uint32_t bits;
                             memcpy(&bits, &v, 4);
@@ -452,7 +456,7 @@ static int pack_weights(epnn_handle *h) {
                 for (int l = 0; l < 64; ++l) {
                     uint32_t pc[3][4];
                     for (int s = 0; s < 4; ++s) {
-                        float v = (float)fn(l >> 4, s, 16 * rb + (l & 15));
+                        float v = (float)fn(l >> 4, s, 16 * rb + (l & 15)) * pk_scale;
                         for (int k = 0; k < 3; ++k) {
                             uint32_t bits;
                             memcpy(&bits, &v, 4);
@@ -519,6 +523,14 @@ static int pack_weights(epnn_handle *h) {
             return o;
         };
         const bool have_basis = (int)h->edge_B.size() == EPNN_EDIM * EPNN_ER;
+        auto we16b_pack = [&](const float *W1) {
+            return frag_bf3k16([&](int q, int s, int m) -> double {
+                if (!have_basis) return 0.0;
+                double a = 0;
+                for (int ch = 0; ch < EPNN_EDIM; ++ch) a += h->edge_B[(size_t)ch * EPNN_ER + 4 * q + s] * (double)W1[(size_t)(2 * F + ch) * 32 + m];
+                return a;
+            });
+        };
         auto pair_common = [&](HostDense (&mm)[3], int &we, int &we16, int &we16b, int &w2, int &b2) {
             const float *W1 = mm[0].W.data(), *W2 = mm[1].W.data(), *bb2 = mm[1].b.data();
             we = frag(2, 12, [&](int s, int q, int m) { return (double)W1[(size_t)(2 * F + 12 * q + s) * 32 + m]; });
@@ -528,12 +540,7 @@ static int pack_weights(epnn_handle *h) {
                 for (int ch = 0; ch < EPNN_EDIM; ++ch) a += h->edge_B[(size_t)ch * EPNN_ER + 4 * q + s] * (double)W1[(size_t)(2 * F + ch) * 32 + m];
                 return a;
             });
-            we16b = frag_bf3k16([&](int q, int s, int m) -> double {                // the same, K slot s of lane group q = coefficient 4q + s
-                if (!have_basis) return 0.0;
-                double a = 0;
-                for (int ch = 0; ch < EPNN_EDIM; ++ch) a += h->edge_B[(size_t)ch * EPNN_ER + 4 * q + s] * (double)W1[(size_t)(2 * F + ch) * 32 + m];
-                return a;
-            });
+            we16b = we16b_pack(W1);                                                 // the same, K slot s of lane group q = coefficient 4q + s
             w2 = frag(2, 8, [&](int s, int q, int m) { return (double)W2[(size_t)accf(s, q) * 32 + m]; });
             b2 = vec(32, [&](int k) { return (double)bb2[k]; });
         };
@@ -556,15 +563,11 @@ static int pack_weights(epnn_handle *h) {
         const int off_pu1b = HU == 32 ? frag_bf3([&](int in, int out) { return pu1[(size_t)in * HU + out]; }) : 0;
         const int off_bu1 = vec(HU, [&](int k) { return (double)bu1[k]; });
         const int off_bu2 = vec(HU, [&](int k) { return (double)bu2[k]; });
-        for (int t = 0; t < T; ++t) {
-            WaveGnnPack &G = X.g[t];
-            pair_common(h->msg[t], G.we, G.we16, G.we16b, G.w2, G.b2);
-            {
-                const float *W2m = h->msg[t][1].W.data();
-                G.w2b = frag_bf3([&](int in, int out) { return (double)W2m[(size_t)in * 32 + out]; });
-            }
+        // the last message Dense folded into the first update Dense (float64):  fold = W3_t Wu1_M,  cb3 = Wu1_M^T b3_t
+        auto fold_u1 = [&](int t, std::vector<double> &fold, std::vector<double> &cb3) {
             const float *W3 = h->msg[t][2].W.data(), *b3 = h->msg[t][2].b.data();
-            std::vector<double> fold((size_t)32 * HU), cb3(HU);
+            fold.assign((size_t)32 * HU, 0.0);
+            cb3.assign(HU, 0.0);
             for (int k = 0; k < 32; ++k)
                 for (int m = 0; m < HU; ++m) {
                     double a = 0;
@@ -576,6 +579,16 @@ static int pack_weights(epnn_handle *h) {
                 for (int j = 0; j < 32; ++j) a += (double)b3[j] * (double)Wu1[(size_t)(EPNN_EDIM + j) * HU + m];
                 cb3[m] = a;
             }
+        };
+        for (int t = 0; t < T; ++t) {
+            WaveGnnPack &G = X.g[t];
+            pair_common(h->msg[t], G.we, G.we16, G.we16b, G.w2, G.b2);
+            {
+                const float *W2m = h->msg[t][1].W.data();
+                G.w2b = frag_bf3([&](int in, int out) { return (double)W2m[(size_t)in * 32 + out]; });
+            }
+            std::vector<double> fold, cb3;
+            fold_u1(t, fold, cb3);
             G.u1s = frag(NRU, 8, [&](int s, int q, int m) { return fold[(size_t)accf(s, q) * HU + m]; });
             G.u1sb = G.u2b = G.pu1b = G.pwihb = G.pwixb = G.pwjhb = G.pwjxb = 0;
             if (HU == 32) {
@@ -622,6 +635,77 @@ static int pack_weights(epnn_handle *h) {
             const FoldedOff fi = folded(W1, b1, 0), fj = folded(W1, nullptr, F);
             E.wif = fi.f32; E.wifhb = fi.hb; E.wifxb = fi.xb;
             E.wjf = fj.f32; E.wjfhb = fj.hb; E.wjfxb = fj.xb;
+        }
+        // ---- The same index with the pair MLPs' operands SCALED by s = 2^-EPNN_RELU_SHIFT: the packs of k_wave_forward's CLAMP form
+        //      (epnn_wave.hip.h, w16_clamp01).  Times s: everything that produces P, R and G of a pair MLP, and b2 -- so that its
+        //      pre-activations, first-layer outputs, second-layer outputs and their sum are s times the unscaled kernel's, exactly:
+        //      a power of two changes no mantissa, in float32 or in a bf16 piece.  Times 1 / s: the one linear map that takes the
+        //      pair MLP's summed output (u1s: W3 Wu1_M of the GNN steps; w3 of the EPN steps), which brings the unscaled bits back.
+        //      Everything else is shared with the unscaled index.
+        //      What s = 2^-32 leaves of float32's range.  Above: a step of a molecule keeps the clamp form while |P'|, |R'| <=
+        //      relu_lim ~ 1/2, i.e. while its unscaled rows stay below 2^31 ~ 2e9 (beyond that the kernel runs the step in the
+        //      max form, which is right at any magnitude: nothing can be silently wrong at this end).  Below: the kernels keep
+        //      float32 denormals (denorm mode 3 in their descriptors) but the bf16 matrix pipe may not, so the smallest piece of a
+        //      scaled operand, 2^-24 of it, should stay normal: unscaled magnitudes down to 2^-126 + 24 + 32 = 2^-70 ~ 8e-22 keep
+        //      every bit they had (unscaled: 2^-102), and a product with the 1 / s packs overflows only beyond 2^96.
+        //      |G'| is bounded here: the edge features lie in [0, 1] (charge_gn.py:148-161), so |G_m| <= sum_ch |We[ch][m]|; the
+        //      kernel's G comes through the 16-dimensional basis, the table and three-piece products, which move it by parts in
+        //      10^6 of that sum at most -- 1 % is allowed for.
+        h->wvidx_c = X;
+        h->wvidx_c_ok = false;
+        if (HU == 32 && have_basis) {
+            WaveIndex &C = h->wvidx_c;
+            const float sc = ldexpf(1.f, -EPNN_RELU_SHIFT), isc = ldexpf(1.f, EPNN_RELU_SHIFT);
+            double gmax = 0.0;
+            auto we_norm = [&](const float *W1) {
+                for (int m = 0; m < 32; ++m) {
+                    double a = 0;
+                    for (int ch = 0; ch < EPNN_EDIM; ++ch) a += fabs((double)W1[(size_t)(2 * F + ch) * 32 + m]);
+                    gmax = std::max(gmax, a);
+                }
+            };
+            auto b2_pack = [&](const HostDense &d) { return vec(32, [&](int k) { return (double)d.b[k]; }); };
+            std::vector<double> fold, cb3;
+            for (int t = 0; t < T; ++t) {
+                WaveGnnPack &G = C.g[t];
+                const float *W1 = h->msg[t][0].W.data();
+                we_norm(W1);
+                pk_scale = sc;
+                G.we16b = we16b_pack(W1);
+                G.b2 = b2_pack(h->msg[t][1]);
+                if (t + 1 < T) {
+                    const float *N1 = h->msg[t + 1][0].W.data(), *nb1 = h->msg[t + 1][0].b.data();
+                    const FoldedOff fi = folded(N1, nb1, 0), fj = folded(N1, nullptr, F);
+                    G.pwi = fi.f32; G.pwihb = fi.hb; G.pwixb = fi.xb;
+                    G.pwj = fj.f32; G.pwjhb = fj.hb; G.pwjxb = fj.xb;
+                }
+                fold_u1(t, fold, cb3);
+                pk_scale = isc;
+                G.u1s = frag(NRU, 8, [&](int s, int q, int m) { return fold[(size_t)accf(s, q) * HU + m]; });
+                G.u1sb = frag_bf3([&](int in, int out) { return fold[(size_t)in * HU + out]; });
+            }
+            pk_scale = sc;
+            C.wi0 = unfolded(h->msg[0][0].W.data(), h->msg[0][0].b.data(), 0);
+            C.wj0 = unfolded(h->msg[0][0].W.data(), nullptr, F);
+            C.wi0xb = xq_bf3k16(h->msg[0][0].W.data(), h->msg[0][0].b.data(), 0, nullptr);
+            C.wj0xb = xq_bf3k16(h->msg[0][0].W.data(), nullptr, F, nullptr);
+            for (int t = 0; t < T; ++t) {
+                WaveEpnPack &E = C.e[t];
+                const float *W1 = h->pas[t][0].W.data(), *b1 = h->pas[t][0].b.data();
+                we_norm(W1);
+                pk_scale = sc;
+                E.we16b = we16b_pack(W1);
+                E.b2 = b2_pack(h->pas[t][1]);
+                const FoldedOff fi = folded(W1, b1, 0), fj = folded(W1, nullptr, F);
+                E.wif = fi.f32; E.wifhb = fi.hb; E.wifxb = fi.xb;
+                E.wjf = fj.f32; E.wjfhb = fj.hb; E.wjfxb = fj.xb;
+                pk_scale = isc;
+                E.w3 = vec(32, [&](int k) { return (double)h->pas[t][2].W[k]; });
+            }
+            pk_scale = 1.f;
+            const double gb = 1.01 * gmax * (double)sc;                  // |G'| of any pair, any step
+            C.relu_lim = (float)(0.4999 * (1.0 - gb));                  // |P'|, |R'| <= relu_lim  =>  (P' + R') + G' <= 1
+            h->wvidx_c_ok = gb < 0.5;
         }
     }
     std::vector<float> gbuf;

@@ -116,7 +116,13 @@ struct WaveIndex {
     int u1h0;             // [2][12][64]     acc order over 48 features  Wu1_H
     int u3;               // [3][8][64]      acc order  Wu3 (48 outputs = 3 row blocks)
     int bu3;              // [48]
+    // The SCALED copy of this index (epnn_handle::wvidx_c, k_wave_forward's CLAMP form) only: |P'|, |R'| of a step may reach this
+    // before the wavefront leaves the clamp form for that step; the host has bounded |G'| by 1 - 2 relu_lim (pack_weights)
+    float relu_lim;
 };
+// s = 2^-EPNN_RELU_SHIFT scales the operands of the pair MLPs in k_wave_forward's CLAMP form (pack_weights says what the choice leaves
+// on either side of float32's range)
+#define EPNN_RELU_SHIFT 32
 
 // A Dense stack of any widths (MLP_layer with other `nodes` than [32, 32], charge_gn.py:30-45): rows x dims[0] -> relu dims[1] ->
 // ... -> dims[n] (the last Dense linear).  Kernels in Keras layout [in][out].  Used by epnn_mlp_forward_layers and by the update
@@ -141,6 +147,7 @@ __host__ __device__ static inline int epnn_aeo(int f) { return (f & 1) * 32 + (f
 // status bits written by kernels
 #define EPNN_ST_PAIR_OVERFLOW 1   // near-pair list capacity exceeded
 #define EPNN_ST_TYPE_OVERFLOW 2   // tiled path, first GNN step by atom types: a molecule has more distinct feature rows than the table holds
+#define EPNN_ST_RELU_RANGE 4      // fused kernel, clamp form: a wavefront ran a step in the max form (its scaled rows left the clamp's range); nothing to redo
 #define EPNN_TYPE_MAX 64          // distinct atom-feature rows per molecule the first GNN step groups by (more: the all-pairs sweep runs)
 
 #if defined(__HIPCC__)

@@ -171,6 +171,8 @@ struct epnn_handle {
     void *infer_fused = nullptr;      // InferFused (epnn_train.hip.h)
     WeightIndex widx{};
     WaveIndex wvidx{};
+    WaveIndex wvidx_c{};              // the same with the pair MLPs' operands scaled for k_wave_forward's CLAMP form (pack_weights)
+    bool wvidx_c_ok = false;          // ... and whether that form can run at all (32-unit update MLP, edge basis, |G'| bounded)
     std::vector<double> edge_B;       // [48][EPNN_ER] orthonormal basis of the edge-feature family (epnn_api.hip edge_basis)
     double edge_res = 1.0;            // its residual max |e - B B^T e| over D in [0, cutoff]
     DevBuf d_wpack;
@@ -219,6 +221,7 @@ struct epnn_handle {
     int opt_train_graph = 1;          // training: 1 replays the step's launch sequence (optimizer step included) as a hipGraph: 0.22 vs 0.245 ms
                                       // per one-molecule step once the kernels were short enough for the launch boundaries to show
                                       // (round 2: 0.47 vs 0.45); a new (B, N, buffer set) means a new capture
+    int opt_relu_clamp = 1;           // fused kernel of the compact entry: first ReLUs as the add's output clamp (0: v_max, unscaled packs)
     int opt_wave_front = 1;           // xyz entry, small molecules only: pair list built inside the wave kernel (no front-end kernels)
     int opt_wave2 = -1;               // compact entry, block-per-wavefront kernel (epnn_wave2.hip.h): molecules with at least this many
                                       // atoms (17..32) are split over two wavefronts, those of at most 16 run in pairs, the rest on

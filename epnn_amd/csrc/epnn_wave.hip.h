@@ -287,6 +287,22 @@ __device__ __forceinline__ void w16_mm_bfk16(const u32x4 (&w)[2][2], const W16K1
 __device__ __forceinline__ f32x4 w16_relu(f32x4 v) {
     return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
 }
+// ReLU of a SUM as the add's own output clamp: min(max(a + b, 0), 1) is one v_add_f32 with the clamp modifier where relu(a + b) is a
+// v_add_f32 and a v_max_f32 -- the same bits wherever a + b <= 1.  The kernel's CLAMP form therefore runs every pair MLP on
+// operands scaled by a power of two (pack_weights: relu(s x) = s relu(x) exactly, in float32 and in every bf16 piece) and checks,
+// per wavefront and step, that the scaled pre-activations stay below 1 (k_wave_forward: `relu_lim`).
+__device__ __forceinline__ f32x4 w16_clamp01(f32x4 v) {
+    return f32x4{fminf(fmaxf(v[0], 0.f), 1.f), fminf(fmaxf(v[1], 0.f), 1.f), fminf(fmaxf(v[2], 0.f), 1.f), fminf(fmaxf(v[3], 0.f), 1.f)};
+}
+// running max |v| over a lane's eight values of a row (v_max3_f32 with abs modifiers: one instruction per two values)
+__device__ __forceinline__ float w16_absmax(float m, const f32x4 (&a)[2]) {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        m = fmaxf(fmaxf(m, fabsf(a[rb][0])), fabsf(a[rb][1]));
+        m = fmaxf(fmaxf(m, fabsf(a[rb][2])), fabsf(a[rb][3]));
+    }
+    return m;
+}
 // sum over the four lanes q = 0..3 that share a column: two VALU lane swaps (gfx950 v_permlane16/32_swap), no LDS
 // round trip; every lane ends up with the same bits ((q0 + q1) + (q2 + q3))
 __device__ __forceinline__ float w16_sumq(float v) {
@@ -393,7 +409,17 @@ __device__ __forceinline__ void w16_feed(const f32x4 (&a)[NRB], float (&in)[4 * 
             W16_LDB16(gwb, offb);                                                                                         \
         } else { W16_LD(gw, off, 2, KE); }                                                                                \
     } while (0)
-template <bool GNN, bool EPN, bool FRONT, int NRU = 2>
+// CLAMP: the first ReLU of every pair MLP folded into the add in front of it (w16_clamp01).  X is then the handle's SCALED index
+// (pack_weights: everything that produces P, R, G and b2 times s = 2^-EPNN_RELU_SHIFT, the one linear map behind the pair MLP
+// times 1 / s), so that the results are the other form's bit for bit.  The form is taken by the instantiation the compact entry
+// launches for 32-unit update MLPs (both stacks, in-kernel front-end, everything on the bf16 pipe); -DEPNN_RELU_MAX and the
+// option "relu_clamp" 0 leave it out.
+#if defined(EPNN_RELU_MAX) || defined(EPNN_SWEEP_F32) || defined(EPNN_CHAIN_F32) || defined(EPNN_G_F32) || defined(EPNN_SPLIT_VALU)
+#define EPNN_RELU_CLAMP_BUILT 0
+#else
+#define EPNN_RELU_CLAMP_BUILT 1
+#endif
+template <bool GNN, bool EPN, bool FRONT, int NRU = 2, bool CLAMP = false>
 __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveArgs A, WaveIndex X) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x, q = lane >> 4, n16 = lane & 15;
@@ -769,6 +795,20 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
     // With both stacks in one launch the EPN takes h the way the GNN steps do, through nm*u2 of the last step and the
     // folded matrices (K = 32 + xq instead of 48 + xq, h itself is then needed only when the caller asks for it).
     constexpr bool FOLD = GNN && EPN;
+    // The clamp form of the pair MLPs' first ReLU.  It is right only where s ((P + R) + G) <= 1, so every wavefront checks its
+    // own operands, per step and where they are produced: |P'|, |R'| <= X.relu_lim for all its atoms, and the host has bounded
+    // |G'| by 1 - 2 relu_lim (pack_weights).  A step whose rows go beyond that runs the max form on the same scaled operands
+    // -- relu(s x) = s relu(x) holds at any magnitude, so the bits are still the unscaled kernel's -- and raises
+    // EPNN_ST_RELU_RANGE for the host to count; nothing is run again.
+    constexpr bool CL = CLAMP && CHB && FOLD && GB && EPNN_RELU_CLAMP_BUILT != 0;
+    float rmax = 0.f;                                       // max |P'|, |R'| of the step being prepared (this lane's values)
+    auto relu_range_ok = [&]() -> bool {                   // wave-uniform; starts the next step's maximum
+        const bool ok = __ballot(rmax > X.relu_lim) == 0ull;
+        rmax = 0.f;
+        if (!ok && lane == 0) { atomicOr(A.status, EPNN_ST_RELU_RANGE); __threadfence(); }
+        return ok;
+    };
+    bool clg = false;                                       // the coming sweep / EPN step may take the clamp form
     f32x4 B0[NRU], B1[NRU];                                 // nm*u2 of the two columns
 #pragma unroll
     for (int rb = 0; rb < NRU; ++rb) { B0[rb] = w16_splat(0.f); B1[rb] = w16_splat(0.f); }
@@ -834,6 +874,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             }
             if (cat0) { w16_st(Rl + n16 * EPNN_PST + fo, r0[0]); w16_st(Rl + n16 * EPNN_PST + 16 + fo, r0[1]); }
             if (own1) { w16_st(Rl + col1 * EPNN_PST + fo, r1[0]); w16_st(Rl + col1 * EPNN_PST + 16 + fo, r1[1]); }
+            if constexpr (CL) { rmax = w16_absmax(w16_absmax(w16_absmax(w16_absmax(rmax, P0), P1), r0), r1); clg = relu_range_ok(); }
         }
         wave_sync_all();
         WAVE_STAMP();   // step-0 G tiles + projections
@@ -855,8 +896,9 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 //      charge_gn.py:70), counted N - n times, and nothing (jp > n, weight 0).
                 //      Per tile and lane: the R row (a broadcast in block 0), the pair map's entry (read two tiles ahead)
                 //      and the G row it points to; one v_add per running address.
-                auto sweep = [&](auto over_tag) {
+                auto sweep = [&](auto over_tag, auto cl_tag) {
                     constexpr bool OVER = decltype(over_tag)::value;
+                    constexpr bool CLT = decltype(cl_tag)::value;     // the first ReLU as the add's clamp (see CL)
                     struct Ops { f32x4 r0, r1, g0, g1; };
                     auto load_rg = [&](Ops &o_, unsigned ra, unsigned ent) {
                         o_.r0 = w16_lds_ld4(ra);
@@ -883,7 +925,8 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                     auto tile = [&](const f32x2 (&Pc)[4], f32x4 (&Sc)[2], const Ops &o_, f32x4 (&dp)[2]) {
                         Sc[0] += w16_relu(dp[0]);
                         Sc[1] += w16_relu(dp[1]);
-                        const f32x4 za = w16_relu((w16_cat(Pc[0], Pc[1]) + o_.r0) + o_.g0), zb = w16_relu((w16_cat(Pc[2], Pc[3]) + o_.r1) + o_.g1);
+                        const f32x4 sa = (w16_cat(Pc[0], Pc[1]) + o_.r0) + o_.g0, sb = (w16_cat(Pc[2], Pc[3]) + o_.r1) + o_.g1;
+                        const f32x4 za = CLT ? w16_clamp01(sa) : w16_relu(sa), zb = CLT ? w16_clamp01(sb) : w16_relu(sb);
                         const float z[8] = {za[0], za[1], za[2], za[3], zb[0], zb[1], zb[2], zb[3]};
 #ifdef EPNN_SWEEP_F32
                         dp[0] = b2v[0];
@@ -998,8 +1041,14 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                     if (two) pass(std::true_type{});              // block 1 first, then block 0
                     pass(std::false_type{});
                 };
-                if (gover) sweep(std::true_type{});
-                else sweep(std::false_type{});
+                auto sweeps = [&](auto cl_tag) {
+                    if (gover) sweep(std::true_type{}, cl_tag);
+                    else sweep(std::false_type{}, cl_tag);
+                };
+                if constexpr (CL) {
+                    if (clg) sweeps(std::true_type{});
+                    else sweeps(std::false_type{});
+                } else sweeps(std::false_type{});
                 if (two && C1 > 1) {
                     // every copy of a block-1 atom holds the sum over its own partners: add the copies in a fixed order (all of
                     // them end up with the same bits).  The G rows of this step are dead: their LDS words are the scratch.
@@ -1112,6 +1161,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], P0);
                 if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], P1);
                 xq_mm(wx, P0, P1);
+                if constexpr (CL) rmax = w16_absmax(w16_absmax(rmax, P0), P1);
                 W16_LDB(wh, M.pwjhb);
                 W16_LDB16(wx, M.pwjxb);
                 f32x4 cu[2];
@@ -1120,6 +1170,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], r0);
                 if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], r1);
                 xq_mm(wx, r0, r1);
+                if constexpr (CL) rmax = w16_absmax(w16_absmax(rmax, r0), r1);
                 if (cat0) { w16_st(Rl + n16 * EPNN_PST + fo, r0[0]); w16_st(Rl + n16 * EPNN_PST + 16 + fo, r0[1]); }
                 if (own1) { w16_st(Rl + col1 * EPNN_PST + fo, r1[0]); w16_st(Rl + col1 * EPNN_PST + 16 + fo, r1[1]); }
                 W16_LDB(wh, M.pu1b);
@@ -1133,6 +1184,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 for (int rb = 0; rb < 2; ++rb) { U0[rb] = nm0 * cu[rb]; U1[rb] = nm1 * cu[rb]; }
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], U0);
                 if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], U1);
+                if constexpr (CL) clg = relu_range_ok();
                 wave_sync_all();
                 if (t < 2) WAVE_STAMP();   // projections
               }
@@ -1276,6 +1328,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], d0);
                 if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], d1);
                 xq_mm(wx, d0, d1);
+                if constexpr (CL) rmax = w16_absmax(w16_absmax(rmax, d0), d1);
                 W16_LDB(wh, M.wjfhb);
                 W16_LDB16(wx, M.wjfxb);
                 if (cat0) { w16_st(Pl + n16 * EPNN_PST + fo, d0[0]); w16_st(Pl + n16 * EPNN_PST + 16 + fo, d0[1]); }
@@ -1284,6 +1337,7 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 w16_mm_bf(wh, Bp0[0], Bp0[1], Bp0[2], d0);
                 if (two) w16_mm_bf(wh, Bp1[0], Bp1[1], Bp1[2], d1);
                 xq_mm(wx, d0, d1);
+                if constexpr (CL) { rmax = w16_absmax(w16_absmax(rmax, d0), d1); clg = relu_range_ok(); }
                 if (cat0) { w16_st(Rl + n16 * EPNN_PST + fo, d0[0]); w16_st(Rl + n16 * EPNN_PST + 16 + fo, d0[1]); }
                 if (own1) { w16_st(Rl + col1 * EPNN_PST + fo, d1[0]); w16_st(Rl + col1 * EPNN_PST + 16 + fo, d1[1]); }
             } else {
@@ -1327,7 +1381,8 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
             vec2(M.w3, w3);
             wave_sync_all();
             if (t < 2) WAVE_STAMP();   // EPN P, R
-            {
+            auto epn_pairs = [&](auto cl_tag) {
+                constexpr bool CLT = decltype(cl_tag)::value;         // the first ReLU as the add's clamp (see CL)
                 // one column per UNORDERED near pair, 16 pairs per column block.  Software pipeline: the pair record
                 // (indices in LDS, weights in HBM) is fetched two blocks ahead, the gathered P / R rows and the e row one block ahead
                 const int nblk = (np + 15) >> 4;
@@ -1360,8 +1415,10 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                 };
                 // the pair MLP behind G for the 16 pairs of a block, both directions: half the antisymmetric transfer (charge_gn.py:105-116)
                 auto pair_d = [&](const f32x4 (&g)[2], const auto &w_) -> float {
-                    const f32x4 ua = w16_relu((g[0] + w_.pi_[0]) + w_.rj_[0]), ub = w16_relu((g[1] + w_.pi_[1]) + w_.rj_[1]);
-                    const f32x4 va = w16_relu((g[0] + w_.pj_[0]) + w_.ri_[0]), vb = w16_relu((g[1] + w_.pj_[1]) + w_.ri_[1]);
+                    const f32x4 sua = (g[0] + w_.pi_[0]) + w_.rj_[0], sub = (g[1] + w_.pi_[1]) + w_.rj_[1];
+                    const f32x4 sva = (g[0] + w_.pj_[0]) + w_.ri_[0], svb = (g[1] + w_.pj_[1]) + w_.ri_[1];
+                    const f32x4 ua = CLT ? w16_clamp01(sua) : w16_relu(sua), ub = CLT ? w16_clamp01(sub) : w16_relu(sub);
+                    const f32x4 va = CLT ? w16_clamp01(sva) : w16_relu(sva), vb = CLT ? w16_clamp01(svb) : w16_relu(svb);
                     const float zu[8] = {ua[0], ua[1], ua[2], ua[3], ub[0], ub[1], ub[2], ub[3]};
                     const float zv[8] = {va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
                     f32x4 au[2] = {b2v[0], b2v[1]}, av[2] = {b2v[0], b2v[1]};
@@ -1477,7 +1534,11 @@ __global__ __launch_bounds__(64, EPNN_WAVES_PER_SIMD) void k_wave_forward(WaveAr
                     }
                     if (blk < nblk) block(blk, r0, w0);
                 }
-            }
+            };
+            if constexpr (CL) {
+                if (clg) epn_pairs(std::true_type{});
+                else epn_pairs(std::false_type{});
+            } else epn_pairs(std::false_type{});
             wave_sync_lds();
             if (t + 1 < Te) { GW_LD(FRONT ? X.e[t + 1].we16 : X.e[t + 1].we, X.e[t + 1].we16b); }     // on its way during the charge update
             WAVE_FENCE();

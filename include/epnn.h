@@ -20,7 +20,12 @@
  *     of the pair and update MLPs on the bf16 matrix pipe as six bf16 products of EXACT three-piece splits of both operands per product (what is
  *     left out is below 2^-24 of a product, the rounding of an f32 multiply-add); results agree with a
  *     float64 evaluation of the reference's algorithm to float32 rounding noise (1e-7 .. 1e-6 on the charges).  Every sum has a
- *     fixed order: results are bit-reproducible and independent of batch composition and of sharding.
+ *     fixed order: results are bit-reproducible and independent of batch composition and of sharding.  The fused kernel of the compact
+ *     entry runs its pair MLPs on operands scaled by 2^-32 (the first ReLU is then the output clamp of the add in front of it, and the
+ *     linear map behind the pair MLP is scaled by 2^32): a power of two changes no mantissa, so the charges are the unscaled
+ *     arithmetic's bit for bit while the pair MLPs' first-layer inputs stay between 2^-70 and 2^31 in magnitude; a molecule's step whose
+ *     rows are larger runs with the plain ReLU by itself (counted in epnn_last_stats out[3]), values smaller than that are float32
+ *     rounding noise of the sums they enter.
  */
 #ifndef EPNN_H
 #define EPNN_H
@@ -689,7 +694,8 @@ int epnn_set_option(epnn_handle *h, const char *name, int value);
 double epnn_edge_basis_residual(epnn_handle *h);
 /* counters of the most recent forward: out[0]=listed pairs (unordered, D < cutoff; the is_near test of charge_gn.py:90-94
  * enters as the pairs' weights), out[1]=molecules on the fused path,
- * out[2]=molecules on the tiled path, out[3]=pair-list regrows. */
+ * out[2]=molecules on the tiled path, out[3]=pair-list regrows, plus forwards in which a wavefront of the fused kernel left the clamp form
+ * of the first ReLU for a step (its scaled rows beyond the clamp's range: see "arithmetic" at the top; the results are the same bits). */
 int epnn_last_stats(epnn_handle *h, int64_t *out4);
 
 #ifdef __cplusplus

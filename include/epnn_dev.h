@@ -8,6 +8,10 @@
  *                       basis); 0: separate front-end kernels and 48-channel rows (results differ by float32 rounding)
  *   "wave_lds"          LDS bytes per wavefront of the fused kernels (default 20480; 16384..65536)
  *   "wave_prio"         fused kernel: molecules with at least this many atoms run at raised wave priority (default 18; 0 = off)
+ *   "relu_clamp"        1 (default): the fused kernel of the compact entry (molecules of up to 32 atoms, in-kernel front-end, 32-unit update
+ *                       MLP) takes the first ReLU of every pair MLP as the output clamp of the add in front of it, on operands scaled
+ *                       by 2^-32 (a step of a molecule whose scaled rows leave the clamp's range runs in the max form by itself and is
+ *                       counted in epnn_last_stats out[3]); 0: v_max_f32 on the unscaled operands
  *   "wave_order"        order of a launch's wavefronts: 0 largest molecule first (default), 1 largest / smallest interleaved, 2 smallest first
  *   "large_fused"       1 (default): the tiled path merges reduction, update MLP and next projections into one launch per GNN step;
  *                       0: one kernel per stage

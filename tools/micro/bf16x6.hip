@@ -157,7 +157,10 @@ template <int SPLIT> __global__ void k_check(const float *W, const float *Z, flo
 }
 // timing: `tiles` dependent-free tiles per wave; MODE 0 = f32 MFMA (16 per tile: 2 row blocks x 8), 1 = bf16x6 incl. the split of z
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int MODE, int EXTRA, int SPLIT>
+// RELU 1 / 2: the tile with the pair sweep's own element-wise work around the MFMAs -- z1 = relu((P + R) + G), S += relu(acc) -- and the
+// first ReLU as v_max_f32 (1) or as the output clamp of the add in front of it (2: min(max(a + b, 0), 1), one v_add_f32 ... clamp; the
+// operands here keep every sum below 1, so both forms give the same bits)
+template <int MODE, int EXTRA, int SPLIT, int RELU = 0>
 __device__ __forceinline__ void time_body(const float *src, float *dst, int tiles) {
     const int lane = threadIdx.x & 63;
     float z[8], w32[2][8];
@@ -169,7 +172,13 @@ __device__ __forceinline__ void time_body(const float *src, float *dst, int tile
     for (int t = 0; t < tiles; ++t) {
         float zz[8];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) zz[s] = fmaxf(z[s] + S[s >> 2][s & 3] * 1e-9f, 0.f);     // (a dependence on the last tile, like S += relu(acc))
+        for (int s = 0; s < 8; ++s) {
+            if (RELU == 0) zz[s] = fmaxf(z[s] + S[s >> 2][s & 3] * 1e-9f, 0.f);     // (a dependence on the last tile, like S += relu(acc))
+            else {
+                const float pre = (z[s] + S[s >> 2][s & 3] * 1e-9f) + 0.25f * w32[1][s];
+                zz[s] = RELU == 2 ? fminf(fmaxf(pre, 0.f), 1.f) : fmaxf(pre, 0.f);
+            }
+        }
         if (EXTRA == 1) {
 #pragma unroll
             for (int s = 0; s < 8; s += 2) {
@@ -215,7 +224,10 @@ __device__ __forceinline__ void time_body(const float *src, float *dst, int tile
                 d[rb] = mm(wb[rb][0], z2, d[rb]); d[rb] = mm(wb[rb][1], z1, d[rb]); d[rb] = mm(wb[rb][0], z1, d[rb]);
             }
         }
-        S[0] += d[0]; S[1] += d[1];
+        if (RELU == 0) { S[0] += d[0]; S[1] += d[1]; }
+        else
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { S[0][r] += fmaxf(d[0][r], 0.f); S[1][r] += fmaxf(d[1][r], 0.f); }
     }
     const size_t o = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
     for (int r = 0; r < 4; ++r) dst[o + r] = S[0][r], dst[o + 4 + r] = S[1][r];
@@ -225,10 +237,10 @@ __global__ __launch_bounds__(64, 2) void k_time(const float *src, float *dst, in
 // The same tile in workgroups of 256 or 512 threads -- a workgroup's wavefronts go round the CU's four SIMDs, so that is one or two
 // wavefronts per SIMD by construction, with few enough workgroups that each has a CU to itself -- and timed by the wavefront's own
 // clock: cyc[wavefront] = { s_memtime ticks, s_memrealtime ticks (100 MHz) } around the tile loop.
-template <int SPLIT>
+template <int SPLIT, int RELU = 0>
 __global__ __launch_bounds__(512) void k_time_wg(const float *src, float *dst, int tiles, unsigned long long *cyc) {
     const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-    time_body<1, 0, SPLIT>(src, dst, tiles);
+    time_body<1, 0, SPLIT, RELU>(src, dst, tiles);
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if ((threadIdx.x & 63) == 0) { cyc[2 * w] = t1 - t0; cyc[2 * w + 1] = r1 - r0; }
@@ -537,7 +549,43 @@ static int check_rem4x4() {
     }
     return fails ? 1 : 0;
 }
+// The pair sweep's tile (split with the 4x4x4 remainders + 12 MFMAs + its element-wise work) with the first ReLU as v_max_f32 and as
+// the add's output clamp: the wavefronts' own clocks at one and two wavefronts per SIMD, and the two forms' results compared in bits.
+static int check_clamp() {
+    const int groups = 16, tiles = 4000;
+    float *src, *dst; unsigned long long *cyc;
+    hipMalloc(&src, 1536 * 4); hipMalloc(&dst, (size_t)groups * 512 * 8 * 4); hipMalloc(&cyc, (size_t)groups * 8 * 16);
+    std::vector<float> s(1536);
+    srand(1);
+    for (auto &v : s) v = rand() / (float)RAND_MAX - 0.3f;
+    hipMemcpy(src, s.data(), 1536 * 4, hipMemcpyHostToDevice);
+    std::vector<unsigned long long> h((size_t)groups * 8 * 2);
+    std::vector<unsigned> out[2];
+    double t[2][2], ghz = 0;
+    for (int form = 0; form < 2; ++form)
+        for (int two = 0; two < 2; ++two)
+            for (int rep = 0; rep < 2; ++rep) {          // (the second launch counts)
+                const dim3 wg(two ? 512 : 256);
+                if (form == 0) hipLaunchKernelGGL((k_time_wg<4, 1>), dim3(groups), wg, 0, 0, src, dst, tiles, cyc);
+                else hipLaunchKernelGGL((k_time_wg<4, 2>), dim3(groups), wg, 0, 0, src, dst, tiles, cyc);
+                if (hipMemcpy(h.data(), cyc, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { printf("clamp: a kernel failed\n"); return 1; }
+                std::vector<double> tk, g;
+                for (int w = 0; w < groups * (two ? 8 : 4); ++w) { tk.push_back((double)h[2 * w] / tiles); g.push_back((double)h[2 * w] / (double)h[2 * w + 1] * 0.1); }
+                t[form][two] = median(tk); ghz = median(g);
+                if (two) { out[form].resize((size_t)groups * 512 * 8); hipMemcpy(out[form].data(), dst, out[form].size() * 4, hipMemcpyDeviceToHost); }
+            }
+    long diff = 0;
+    for (size_t i = 0; i < out[0].size(); ++i) diff += out[0][i] != out[1][i];
+    const char *forms[2] = {"v_add_f32 + v_max_f32 ", "v_add_f32 ... clamp    "};
+    for (int form = 0; form < 2; ++form)
+        printf("clamp: sweep tile, first ReLU as %s: %.1f cycles per tile with one wavefront per SIMD, %.1f per tile and wavefront pair with two (%.1f per wavefront; clock %.3f GHz)\n",
+               forms[form], t[form][0], t[form][1], t[form][1] / 2, ghz);
+    printf("clamp: %ld of %zu results differ in bits between the two forms\n", diff, out[0].size());
+    hipFree(src); hipFree(dst); hipFree(cyc);
+    return diff ? 1 : 0;
+}
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "clamp")) return check_clamp();             // only the sweep tile's two ReLU forms (profiles/r23_relu_clamp.txt)
     if (argc > 1 && !strcmp(argv[1], "k16pairs")) return check_k16_pairs();      // only the K = 16 pairing (tests/test_gpu_k16_pairs.py)
     if (argc > 1 && !strcmp(argv[1], "rem4x4")) return check_rem4x4();           // only the 4x4x4 remainders (tests/test_gpu_rem4x4.py)
     std::vector<float> W(16 * 32), Z(32 * 16), C6(256), C32(256);
