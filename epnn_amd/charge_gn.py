@@ -411,6 +411,13 @@ class EPNNModel(_Stack):
         return self._eng().coulomb_xyz_slab(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke, alpha=alpha,
                                             tol=tol, ewald=ewald, parts=parts, exclusions=exclusions)
 
+    def coulomb_xyz_slab_strain(self, offsets, xyz, x, Q, N=None, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                                parts=False, exclusions=None):
+        """coulomb_xyz_slab with the strain derivative of the slab sum: (q, phi, E, F, gstrain (B, 3, 3)), with parts=True also ffix, fq,
+        gstrain_fix and gstrain_q.  The other outputs have the bits of coulomb_xyz_slab.  N defaults to the model's natom."""
+        return self._eng().coulomb_xyz_slab_strain(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke,
+                                                   alpha=alpha, tol=tol, ewald=ewald, parts=parts, exclusions=exclusions)
+
     def coulomb_xyz_excl(self, offsets, xyz, x, Q, N=None, ke=KE_EV_ANGSTROM, alpha=0.0, parts=False, exclusions=None):
         """coulomb_xyz with bonded exclusions and pair scaling: exclusions = (pairs (P, 2), scale) as engine.bonded_exclusions
         returns it; a listed pair counts with weight scale instead of 1 (0 excludes).  None is coulomb_xyz itself."""

@@ -1,5 +1,6 @@
 // epnn_coulomb_xyz_slab: epnn_coulomb_xyz in slab cells (two periodic axes, one open one) by the exact two-dimensional Ewald sum
-// (kernels: epnn_ewald_slab.hip.h), and epnn_ewald_slab_params, the host-only rule that chooses the sum's parameters.  The driver is a
+// (kernels: epnn_ewald_slab.hip.h); epnn_coulomb_xyz_slab_strain, the same call with the sum's strain derivative, on the same driver;
+// and epnn_ewald_slab_params, the host-only rule that chooses the sum's parameters.  The driver is a
 // sibling of coulomb_run: it shares gl_grad_forward, the open sweep's task table, k_ew_sweep, the exclusion list's kernel, the backward
 // and the one download; the plain and periodic entries keep their driver.  Part of the one translation unit epnn_api.hip.
 #pragma once
@@ -127,7 +128,7 @@ static int sl_cell_row(const char *what, int b, const float *cell, const double 
             const double k = sqrt(kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2]);
             if (k > kc) continue;
             const double u = 0.5 * k / beta, w = 2.0 * pi / (G.area * k) * exp(-u * u);
-            slots.push_back(SlSlot{(double)m0, (double)m1, k, u, (float)w, (float)(w * k), (float)kv[0], (float)kv[1], (float)kv[2], 0.f});
+            slots.push_back(SlSlot{(double)m0, (double)m1, k, u, (float)w, (float)(w * k), (float)kv[0], (float)kv[1], (float)kv[2], (float)(1.0 / k)});
         }
     c.ns = (int)slots.size() - c.soff;
     return 0;
@@ -135,11 +136,13 @@ static int sl_cell_row(const char *what, int b, const float *cell, const double 
 
 // The slab call: the pair-list gradient call with its seed made on the device, as coulomb_run.  Set-up and checkpointed forward; on that
 // forward's charges the real-space sweep (k_ew_sweep), the reciprocal sweep (k_sl_sweep), the listed pairs' correction (ex) and the
-// energy, phi = dE/dq into the seed; the shared backward; one download.
+// energy, phi = dE/dq into the seed; the shared backward; one download.  strain (epnn_coulomb_xyz_slab_strain): the reciprocal sweep is
+// k_sl_sweep_strain with its wider rows, the atoms write their strain shares, one wavefront per cell adds them, the backward runs with
+// its strain flag and the download carries both strain rows; without it the plain entry's kernels, bits and scratch.
 static int coulomb_slab_run(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                             const float *Q, const HostGeo &geo, double ke, double alpha, const std::vector<EwCell> &ew,
                             const std::vector<SlCell> &sl, const std::vector<SlSlot> &slots, const ExclCsr *ex, const ExclArgs &xa,
-                            const CoulombOut &out) {
+                            bool strain, const CoulombOut &out) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
     const int T = h->cfg.T, A = offsets[B];
@@ -156,19 +159,21 @@ static int coulomb_slab_run(epnn_handle *h, const char *name, int B, int N, cons
     memcpy(blob.data() + o_sl, sl.data(), (size_t)B * sizeof(SlCell));
     if (!slots.empty()) memcpy(blob.data() + o_slot, slots.data(), slots.size() * sizeof(SlSlot));
     // [A] phi | [A][3] ffix | flag, then [B] E in float64: directly behind the backward's output block, one download for both; the two
-    // sweeps' partial rows [pieces][A][EW_PART] and [pieces][A][SL_PART] and the atoms' energy shares [A] in float64
-    const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), co_bytes = o_E + (size_t)B * 8;
-    const size_t o_rpart = cpieces * (size_t)A * EW_PART * 8, o_share = o_rpart + cpieces * (size_t)A * SL_PART * 8, sc_bytes = o_share + (size_t)A * 8;
+    // sweeps' partial rows [pieces][A][EW_PART] and [pieces][A][SL_PART] and the atoms' energy shares [A] in float64.  strain: [B][9]
+    // the fixed-charge strain behind E, rows of SL_PART_STRAIN, and the atoms' strain shares [A][SL_SHARE_W] behind the energy's
+    const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), o_gsf = o_E + (size_t)B * 8, co_bytes = o_gsf + (strain ? (size_t)B * 36 : 0);
+    const size_t o_rpart = cpieces * (size_t)A * EW_PART * 8, o_share = o_rpart + cpieces * (size_t)A * (strain ? SL_PART_STRAIN : SL_PART) * 8,
+                 o_wshare = o_share + (size_t)A * 8, sc_bytes = o_wshare + (strain ? (size_t)A * SL_SHARE_W * 8 : 0);
     const GlSpan spans[2] = {GlSpan{blob.data(), blob_bytes, false}, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false}};
     const size_t more[3] = {co_bytes, sc_bytes, ex ? excl_xpart_bytes(A, true) : 0};
     GlGrad r;
     if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
     const GlCall &c = r.c;
     char *co = c.dw + r.o_more[0], *sc = c.dw + r.o_more[1];
-    float *phi = reinterpret_cast<float *>(co), *ffix = phi + A;
+    float *phi = reinterpret_cast<float *>(co), *ffix = phi + A, *gsf = reinterpret_cast<float *>(co + o_gsf);
     int *hit = reinterpret_cast<int *>(phi + 4 * (size_t)A);
     double *E = reinterpret_cast<double *>(co + o_E), *part = reinterpret_cast<double *>(sc), *rpart = reinterpret_cast<double *>(sc + o_rpart),
-           *share = reinterpret_cast<double *>(sc + o_share);
+           *share = reinterpret_cast<double *>(sc + o_share), *wshare = reinterpret_cast<double *>(sc + o_wshare);
     double *xpart = ex ? reinterpret_cast<double *>(c.dw + r.o_more[2]) : nullptr;
     const float *q_dev = r.qck + (size_t)T * A;
     const char *d_blob = reinterpret_cast<const char *>(c.d_extra[0]), *d_csr = ex ? reinterpret_cast<const char *>(c.d_extra[1]) : nullptr;
@@ -185,18 +190,26 @@ static int coulomb_slab_run(epnn_handle *h, const char *name, int B, int N, cons
     else
         hipLaunchKernelGGL((alpha > 0.0 ? k_ew_sweep<true> : k_ew_sweep<false>), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz,
                            q_dev, d_cells, d_ew, A, (float)alpha, part, hit);
-    hipLaunchKernelGGL(k_sl_sweep, gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev, d_sl, d_slots, A, rpart);
-    if (ex) {
-        excl_launch(h, c, d_csr, *ex, q_dev, d_cells, alpha, xpart, hit);
-        hipLaunchKernelGGL(k_sl_atom_x, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
-                           (const double *)rpart, (const double *)xpart, ke, r.gq, phi, ffix, share);
-    } else
-        hipLaunchKernelGGL(k_sl_atom, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
-                           (const double *)rpart, ke, r.gq, phi, ffix, share);
-    hipLaunchKernelGGL(k_cl_energy, dim3((unsigned)B), wave, 0, h->stream, (const double *)share, c.d_moff, E);
+    hipLaunchKernelGGL((strain ? k_sl_sweep_strain : k_sl_sweep), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev, d_sl,
+                       d_slots, A, rpart);
+    if (ex) excl_launch(h, c, d_csr, *ex, q_dev, d_cells, alpha, xpart, hit);
+    if (strain) {
+        hipLaunchKernelGGL(k_sl_atom_strain, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
+                           (const double *)rpart, (const double *)xpart, ke, r.gq, phi, ffix, share, wshare);
+        hipLaunchKernelGGL(k_sl_energy_strain, dim3((unsigned)B), wave, 0, h->stream, (const double *)share, (const double *)wshare, c.d_moff, E, gsf);
+    } else {
+        if (ex)
+            hipLaunchKernelGGL(k_sl_atom_x, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
+                               (const double *)rpart, (const double *)xpart, ke, r.gq, phi, ffix, share);
+        else
+            hipLaunchKernelGGL(k_sl_atom, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
+                               (const double *)rpart, ke, r.gq, phi, ffix, share);
+        hipLaunchKernelGGL(k_cl_energy, dim3((unsigned)B), wave, 0, h->stream, (const double *)share, c.d_moff, E);
+    }
     HIPCHK(hipGetLastError());
-    if (gl_grad_backward(h, gl, r, B, false)) return 1;
-    // ---- one download: q | gxyz | flag | (the strain rows, unused) | (the step to the next buffer) | phi | ffix | flag | E
+    if (gl_grad_backward(h, gl, r, B, strain)) return 1;
+    // ---- one download: q | gxyz | flag | the charges' strain rows (plain: unused) | (the step to the next buffer) | phi | ffix | flag | E
+    // | strain: the fixed-charge strain
     const char *from = reinterpret_cast<const char *>(r.q_fin);
     const size_t nbytes = (size_t)(co + co_bytes - from), at_co = (size_t)(co - from);
     if (gl->pin_out.ensure(nbytes)) return 1;
@@ -219,16 +232,19 @@ static int coulomb_slab_run(epnn_handle *h, const char *name, int B, int N, cons
         if (out.fq) out.fq[k] = fq;
     }
     if (out.ffix) memcpy(out.ffix, bffix, (size_t)A * 12);
+    if (!strain) return 0;
+    const float *bgs = bq + 4 * (size_t)A + 1, *bgsf = reinterpret_cast<const float *>(back + at_co + o_gsf);
+    for (size_t k = 0; k < 9 * (size_t)B; ++k) out.gs[k] = bgsf[k] + bgs[k];
+    if (out.gs_fix) memcpy(out.gs_fix, bgsf, (size_t)B * 36);
+    if (out.gs_q) memcpy(out.gs_q, bgs, (size_t)B * 36);
     return 0;
 }
 
-extern "C" int epnn_coulomb_xyz_slab(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                                     const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
-                                     const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
-                                     float *ffix_out, float *fq_out) {
-    const char *name = "epnn_coulomb_xyz_slab";
-    const CoulombOut out{q_out, phi_out, e_out, f_out, ffix_out, fq_out, nullptr, nullptr, nullptr};
-    if (!cell || !ewald || !out.phi || !out.e) EPNN_FAIL("%s: null argument", name);
+// the two slab entries: the checks, the cells' rows and slots, the list; out.gs: the strain entry's required output, or NULL
+static int coulomb_slab_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
+                              const float *Q, const float *cell, const double *ewald, double ke, double alpha, int64_t npairs,
+                              const int32_t *ex_i, const int32_t *ex_j, const float *ex_scale, bool strain, const CoulombOut &out) {
+    if (!cell || !ewald || !out.phi || !out.e || (strain && !out.gs)) EPNN_FAIL("%s: null argument", name);
     if (!epnn_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
     if (!epnn_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
     GeoArg arg;
@@ -248,5 +264,21 @@ extern "C" int epnn_coulomb_xyz_slab(epnn_handle *h, int B, int N, const int32_t
     const ExclArgs xa{npairs, ex_i, ex_j, ex_scale};
     ExclCsr ex;
     if (excl_build(name, B, offsets, npairs, ex_i, ex_j, ex_scale, ex)) return 1;
-    return coulomb_slab_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, ew, sl, slots, npairs > 0 ? &ex : nullptr, xa, out);
+    return coulomb_slab_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, ew, sl, slots, npairs > 0 ? &ex : nullptr, xa, strain, out);
+}
+
+extern "C" int epnn_coulomb_xyz_slab(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                     const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
+                                     const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
+                                     float *ffix_out, float *fq_out) {
+    return coulomb_slab_enter(h, "epnn_coulomb_xyz_slab", B, N, offsets, xyz, x, Q, cell, ewald, ke, alpha, npairs, ex_i, ex_j, ex_scale, false,
+                              CoulombOut{q_out, phi_out, e_out, f_out, ffix_out, fq_out, nullptr, nullptr, nullptr});
+}
+
+extern "C" int epnn_coulomb_xyz_slab_strain(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                            const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
+                                            const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
+                                            float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out) {
+    return coulomb_slab_enter(h, "epnn_coulomb_xyz_slab_strain", B, N, offsets, xyz, x, Q, cell, ewald, ke, alpha, npairs, ex_i, ex_j, ex_scale,
+                              true, CoulombOut{q_out, phi_out, e_out, f_out, ffix_out, fq_out, gstrain_out, gstrain_fix_out, gstrain_q_out});
 }

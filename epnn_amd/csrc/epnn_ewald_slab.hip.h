@@ -24,12 +24,27 @@
 // (sincosf, erfcxf, expf, the products); the five running sums of a lane are float64: phi, the in-plane force's three components and
 // the force along nhat, which takes its vector in float64 in k_sl_atom.  No float atomics; every output word is written by exactly
 // one wavefront, in an order that depends on the cell alone.
+//
+// The strain derivative (epnn_coulomb_xyz_slab_strain; the formulas are in include/epnn.h): the reciprocal and k = 0 sums have no
+// structure factor, so their strain rides in the all-pairs sweep.  sl_sweep_body<STRAIN> is the one body: k_sl_sweep is its `false`
+// instance, the statements of the plain call, and k_sl_sweep_strain its `true` instance with six more float64 sums per lane, in the
+// basis of the slot integers (Cartesian would take ten: 1 + 3 + 6; four more float64 adds per term and eight more registers, for an
+// expansion that the atoms' kernel does once per atom; 113 VGPRs against the plain instance's 93, nothing spilled):
+//     [5]      sum_j q_j z_ij { sum_k (w k) cos Fd - (2 pi / A) erf(beta z_ij) }                       the z-weighted force along nhat
+//     [6], [7] sum_j q_j z_ij sum_k w sin Fs (m0, m1)                                                  the z-weighted in-plane force
+//     [8..10]  sum_j q_j sum_k w cos [Fs / k + |z| (Fb - Fa) + G] / k (m0^2, m0 m1, m1^2)              the k_a k_b tensor
+// with G = 2 / (beta sqrt(pi)) exp(-beta^2 z^2) (exp(-u^2) is in w), the three terms of the bracket of one sign.  Per (pair, slot) these
+// are float32 products of values already there; z_ij is rounded once from float64.  k_sl_atom_strain expands them through g_a, g_b
+// and nhat in float64, k = 2 pi (m0 g_a + m1 g_b), and adds the virial row of k_ew_sweep and of the listed pairs; k_sl_energy_strain
+// adds a cell's atoms.
 #pragma once
 #include "epnn_ewald.hip.h"
 
 #define SL_TILE 64                // partners, and k slots, staged in LDS at a time
 #define SL_SLOT_CAP (1 << 16)     // most slots (2 M0' + 1)(M1' + 1) of one cell's k box (M0', M1': the M of its two periodic rows)
 #define SL_PART 5                 // sums per (piece, atom) of k_sl_sweep: phi, the in-plane force x y z, the force along nhat (its sign turned)
+#define SL_PART_STRAIN 11         // of k_sl_sweep_strain: those five, then the six sums of the strain derivative (above)
+#define SL_SHARE_W 6              // an atom's strain shares xx yy zz yz xz xy
 
 // What the device needs of one slab cell (the host's sl_cell_row, from the checked row of the `ewald` argument)
 struct SlCell {
@@ -49,7 +64,7 @@ struct SlSlot {
     double k, u;                  // |k| and k / 2 beta
     float w, wk;                  // the doubled weight 2 pi / (A k) exp(-u^2), and k times it
     float kx, ky, kz;             // the vector k
-    float pad;
+    float ik;                     // 1 / |k| (the strain sweep's)
 };
 static_assert(sizeof(SlSlot) == 56, "SlSlot is staged as 14 words");
 
@@ -65,9 +80,12 @@ __device__ __forceinline__ void sl_coords(const SlCell &e, const float *p, doubl
 // task as in k_cl_sweep = (first atom, atoms | piece << 8, first partner, end of the partners).  A packed task holds several cells: they
 // are taken one after another, each with its own slots, and a lane adds only while its own cell is the one in turn.  A lane meets
 // (partner tile, slot tile, partner, slot) in that order; the tiles start at the piece's (or the cell's) first partner and at slot 0.
-// rpart [pieces][A][SL_PART], without q_i and ke.
-__global__ __launch_bounds__(64) void k_sl_sweep(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
-                                                 const SlCell *sl, const SlSlot *slots, int A, double *rpart) {
+// rpart [pieces][A][SL_PART], without q_i and ke.  STRAIN: [pieces][A][SL_PART_STRAIN], the five sums by the same statements and the
+// six of the strain derivative behind them (the top of this file).
+template <bool STRAIN>
+__device__ __forceinline__ void sl_sweep_body(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
+                                              const SlCell *sl, const SlSlot *slots, int A, double *rpart) {
+    constexpr int NS = STRAIN ? SL_PART_STRAIN : SL_PART;
     __shared__ double ts0[SL_TILE], ts1[SL_TILE], tz[SL_TILE];
     __shared__ float tq[SL_TILE];
     __shared__ SlSlot tslot[SL_TILE];
@@ -76,9 +94,9 @@ __global__ __launch_bounds__(64) void k_sl_sweep(const int4 *tasks, const int *m
     const bool valid = lane < na;
     const int i = tk.x + (valid ? lane : 0);
     const int b = mol_of[i];
-    double sum[SL_PART];
+    double sum[NS];
 #pragma unroll
-    for (int c = 0; c < SL_PART; ++c) sum[c] = 0.0;
+    for (int c = 0; c < NS; ++c) sum[c] = 0.0;
     const int c_first = tk.w > tk.z ? mol_of[tk.z] : 0, c_last = tk.w > tk.z ? mol_of[tk.w - 1] : -1;
     for (int c = c_first; c <= c_last; ++c) {                    // (wave-uniform)
         const SlCell e = sl[c];
@@ -87,6 +105,7 @@ __global__ __launch_bounds__(64) void k_sl_sweep(const int4 *tasks, const int *m
         double si0, si1, zi;
         sl_coords(e, xyz + 3 * (size_t)i, si0, si1, zi);         // (a lane of another cell: finite numbers that are not used)
         const float invb = (float)(1.0 / e.beta), c0 = (float)e.c0, cn = (float)e.cn;
+        const float cg = STRAIN ? (float)(1.1283791670955126 / e.beta) : 0.f;         // 2 / (beta sqrt(pi)): the Gaussian term of dFs/dk
         for (int t0 = p0; t0 < p1; t0 += SL_TILE) {
             const int cnt = min(SL_TILE, p1 - t0);
             __syncthreads();
@@ -102,6 +121,7 @@ __global__ __launch_bounds__(64) void k_sl_sweep(const int4 *tasks, const int *m
                     const float qj = tq[jj], eg = (float)exp(-bzd * bzd), er = erff((float)bzd);
                     sum[0] -= (double)((c0 * qj) * (eg * invb + 1.7724538509055160f * ((float)az * er)));
                     sum[4] -= (double)((cn * qj) * (dz < 0.0 ? -er : er));
+                    if (STRAIN) sum[5] -= (double)(((cn * qj) * er) * (float)az);         // z erf(beta z) = |z| erf(beta |z|)
                 }
             for (int s0 = 0; s0 < e.ns; s0 += SL_TILE) {
                 const int scnt = min(SL_TILE, e.ns - s0);
@@ -111,6 +131,7 @@ __global__ __launch_bounds__(64) void k_sl_sweep(const int4 *tasks, const int *m
                 for (int jj = 0; mine && jj < cnt; ++jj) {
                     const double dz = zi - tz[jj], f0 = si0 - ts0[jj], f1 = si1 - ts1[jj], az = fabs(dz), bzd = e.beta * az;
                     const float qj = tq[jj], eg = (float)exp(-bzd * bzd), sg = dz < 0.0 ? -1.f : 1.f;
+                    const float zf = STRAIN ? (float)dz : 0.f, azf = STRAIN ? (float)az : 0.f, ge = STRAIN ? cg * eg : 0.f;
                     for (int kk = 0; kk < scnt; ++kk) {
                         const SlSlot &r = tslot[kk];
                         double t = r.m0 * f0 + r.m1 * f1;
@@ -132,25 +153,50 @@ __global__ __launch_bounds__(64) void k_sl_sweep(const int4 *tasks, const int *m
                         sum[2] += (double)(a * r.ky);
                         sum[3] += (double)(a * r.kz);
                         sum[4] += (double)(((r.wk * qj) * cs) * Fd);
+                        if (STRAIN) {
+                            const float m0 = (float)r.m0, m1 = (float)r.m1;         // (integers: exact)
+                            const float pz = a * zf;
+                            sum[5] += (double)((((r.wk * qj) * cs) * Fd) * zf);
+                            sum[6] += (double)(pz * m0);
+                            sum[7] += (double)(pz * m1);
+                            // Fs / k^2 - (dFs/dk) / k = [Fs / k + |z| (Fb - Fa) + G] / k, three terms of one sign (Fa <= Fb)
+                            const float tt = ((wq * cs) * r.ik) * ((Fs * r.ik + azf * (Fb - Fa)) + ge);
+                            const float tm = tt * m0;
+                            sum[8] += (double)(tm * m0);
+                            sum[9] += (double)(tm * m1);
+                            sum[10] += (double)((tt * m1) * m1);
+                        }
                     }
                 }
             }
         }
     }
     if (valid) {
-        double *o = rpart + ((size_t)piece * A + i) * SL_PART;
+        double *o = rpart + ((size_t)piece * A + i) * NS;
 #pragma unroll
-        for (int c = 0; c < SL_PART; ++c) o[c] = sum[c];
+        for (int c = 0; c < NS; ++c) o[c] = sum[c];
     }
+}
+__global__ __launch_bounds__(64) void k_sl_sweep(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
+                                                 const SlCell *sl, const SlSlot *slots, int A, double *rpart) {
+    sl_sweep_body<false>(tasks, moff, mol_of, xyz, q, sl, slots, A, rpart);
+}
+__global__ __launch_bounds__(64) void k_sl_sweep_strain(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz,
+                                                        const float *q, const SlCell *sl, const SlSlot *slots, int A, double *rpart) {
+    sl_sweep_body<true>(tasks, moff, mol_of, xyz, q, sl, slots, A, rpart);
 }
 
 // Every atom adds, in this order: its real-space pieces in piece order (the first four sums of each EW_PART row of k_ew_sweep), its
 // reciprocal pieces in piece order, X: the listed pairs' row (k_cl_excl<., true>, its first four sums), the self term.  phi [A] is
 // written twice (the backward's seed and the output), then ffix [A][3] and the atom's share of the energy, 1/2 q_i phi_i, in float64.
-template <bool X>
+// STRAIN (the rows of k_sl_sweep_strain): the same additions in the same order, and the atom's strain shares wshare [A][SL_SHARE_W]
+// (xx yy zz yz xz xy) in float64: -1/2 ke q_i times its virial row (the six sums behind the four, the listed pairs' added behind the
+// sweep's, as k_ew_atom does) and 1/2 ke q_i times the reciprocal and k = 0 sums, expanded through g_a, g_b and nhat.
+template <bool X, bool STRAIN>
 __device__ __forceinline__ void sl_atom_body(int A, const int *moff, const int *mol_of, const float *q, const SlCell *sl, const double *part,
                                              const double *rpart, const double *xpart, double ke, float *seed, float *phi, float *ffix,
-                                             double *share) {
+                                             double *share, double *wshare) {
+    constexpr int NS = STRAIN ? SL_PART_STRAIN : SL_PART;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A) return;
     const int b = mol_of[i], np = cl_pieces(moff[b + 1] - moff[b]);
@@ -158,7 +204,7 @@ __device__ __forceinline__ void sl_atom_body(int A, const int *moff, const int *
     for (int k = 0; k < np; ++k)
         for (int c = 0; c < 4; ++c) s[c] += part[((size_t)k * A + i) * EW_PART + c];
     for (int k = 0; k < np; ++k)
-        for (int c = 0; c < SL_PART; ++c) r[c] += rpart[((size_t)k * A + i) * SL_PART + c];
+        for (int c = 0; c < SL_PART; ++c) r[c] += rpart[((size_t)k * A + i) * NS + c];
     for (int c = 0; c < 3; ++c) s[1 + c] += r[1 + c] - sl[b].nh[c] * r[4];
     s[0] += r[0];
     if (X)
@@ -167,13 +213,67 @@ __device__ __forceinline__ void sl_atom_body(int A, const int *moff, const int *
     seed[i] = phi[i] = (float)p;
     for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
     share[i] = 0.5 * qi * p;
+    if (STRAIN) {
+        double v[SL_SHARE_W] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, t[SL_PART_STRAIN - SL_PART] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < np; ++k)
+            for (int c = 0; c < SL_SHARE_W; ++c) v[c] += part[((size_t)k * A + i) * EW_PART + 4 + c];
+        if (X)
+            for (int c = 0; c < SL_SHARE_W; ++c) v[c] += xpart[(size_t)i * EW_PART + 4 + c];
+        for (int k = 0; k < np; ++k)
+            for (int c = 0; c < SL_PART_STRAIN - SL_PART; ++c) t[c] += rpart[((size_t)k * A + i) * NS + SL_PART + c];
+        const SlCell &e = sl[b];
+        const double two_pi = 6.283185307179586, P[3] = {two_pi * (t[1] * e.ga[0] + t[2] * e.gb[0]), two_pi * (t[1] * e.ga[1] + t[2] * e.gb[1]),
+                                                         two_pi * (t[1] * e.ga[2] + t[2] * e.gb[2])};
+        const int ia[SL_SHARE_W] = {0, 1, 2, 1, 0, 0}, ib[SL_SHARE_W] = {0, 1, 2, 2, 2, 1};
+        for (int c = 0; c < SL_SHARE_W; ++c) {
+            const int x = ia[c], y = ib[c];
+            const double nn = e.nh[x] * e.nh[y];
+            const double kk = two_pi * two_pi * (t[3] * e.ga[x] * e.ga[y] + t[4] * (e.ga[x] * e.gb[y] + e.gb[x] * e.ga[y]) + t[5] * e.gb[x] * e.gb[y]);
+            const double rec = kk - r[0] * ((x == y ? 1.0 : 0.0) - nn) + nn * t[0] - (e.nh[x] * P[y] + P[x] * e.nh[y]);
+            wshare[SL_SHARE_W * (size_t)i + c] = 0.5 * ke * qi * (rec - v[c]);
+        }
+    }
 }
 __global__ __launch_bounds__(256) void k_sl_atom(int A, const int *moff, const int *mol_of, const float *q, const SlCell *sl, const double *part,
                                                  const double *rpart, double ke, float *seed, float *phi, float *ffix, double *share) {
-    sl_atom_body<false>(A, moff, mol_of, q, sl, part, rpart, nullptr, ke, seed, phi, ffix, share);
+    sl_atom_body<false, false>(A, moff, mol_of, q, sl, part, rpart, nullptr, ke, seed, phi, ffix, share, nullptr);
 }
 __global__ __launch_bounds__(256) void k_sl_atom_x(int A, const int *moff, const int *mol_of, const float *q, const SlCell *sl, const double *part,
                                                    const double *rpart, const double *xpart, double ke, float *seed, float *phi, float *ffix,
                                                    double *share) {
-    sl_atom_body<true>(A, moff, mol_of, q, sl, part, rpart, xpart, ke, seed, phi, ffix, share);
+    sl_atom_body<true, false>(A, moff, mol_of, q, sl, part, rpart, xpart, ke, seed, phi, ffix, share, nullptr);
+}
+// the atoms' kernel of the strain call; xpart: the listed pairs' rows, or NULL without a list
+__global__ __launch_bounds__(256) void k_sl_atom_strain(int A, const int *moff, const int *mol_of, const float *q, const SlCell *sl,
+                                                        const double *part, const double *rpart, const double *xpart, double ke, float *seed,
+                                                        float *phi, float *ffix, double *share, double *wshare) {
+    if (xpart) sl_atom_body<true, true>(A, moff, mol_of, q, sl, part, rpart, xpart, ke, seed, phi, ffix, share, wshare);
+    else sl_atom_body<false, true>(A, moff, mol_of, q, sl, part, rpart, nullptr, ke, seed, phi, ffix, share, wshare);
+}
+
+// One wavefront per cell: E_b by k_cl_energy's additions on the same shares (its bits), and the fixed-charge strain derivative
+// [3][3]: the atoms' six strain shares, lane by lane in atom order, then across the lanes (the butterfly of k_ew_energy and
+// k_g_strain_mol), mirrored into nine slots.
+__global__ __launch_bounds__(64) void k_sl_energy_strain(const double *share, const double *wshare, const int *moff, double *e_out, float *gs_out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double v = 0.0, W[SL_SHARE_W] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int a = moff[b] + lane; a < moff[b + 1]; a += 64) v += share[a];
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    for (int a = moff[b] + lane; a < moff[b + 1]; a += 64)
+#pragma unroll
+        for (int c = 0; c < SL_SHARE_W; ++c) W[c] += wshare[SL_SHARE_W * (size_t)a + c];
+#pragma unroll
+    for (int c = 0; c < SL_SHARE_W; ++c) {
+        double w = W[c];
+        for (int m = 32; m >= 1; m >>= 1) w += __shfl_xor(w, m);
+        W[c] = w;
+    }
+    if (lane == 0) {
+        e_out[b] = v;
+        float *o = gs_out + 9 * (size_t)b;
+        o[0] = (float)W[0]; o[4] = (float)W[1]; o[8] = (float)W[2];
+        o[5] = o[7] = (float)W[3];
+        o[2] = o[6] = (float)W[4];
+        o[1] = o[3] = (float)W[5];
+    }
 }

@@ -36,6 +36,14 @@ def _cell_rows(cell, B):
     return np.ascontiguousarray(cell)
 
 
+def _slab_box(where, box, cell):
+    """A slab's box has exactly one zero, the open axis."""
+    if box is not None and cell is None:
+        rows = np.asarray(box, dtype=np.float32)
+        if rows.shape[-1:] != (3,) or ((rows.reshape(-1, 3) == 0).sum(1) != 1).any():
+            raise ValueError(f"{where}: box must have exactly one zero, the open axis (none: coulomb_xyz_cell)")
+
+
 def _one_periodic_argument(box, cell):
     if box is not None and cell is not None:
         raise ValueError("box and cell are two descriptions of the same thing: give one of them")
@@ -575,19 +583,29 @@ class Engine:
         neutralising background, which does not exist in two dimensions (include/epnn.h has the sum).  ewald (6,) or (B, 6) float64:
         the parameters the call runs at; None: ewald_slab_params(cell, alpha, tol) per cell.  parts=True appends ffix and fq
         (F = ffix + fq); fq is -gxyz of charges_vjp_xyz(g=phi, cell=) on "grad_path" 2, bit for bit.  exclusions = (pairs, scale) as
-        in coulomb_xyz_excl: the nearest image of every listed pair counts with weight scale; None: no list.  One periodic axis
-        (wires) and the strain derivative of the slab sum are not built."""
-        if box is not None and cell is None:
-            rows = np.asarray(box, dtype=np.float32)
-            if rows.shape[-1:] != (3,) or ((rows.reshape(-1, 3) == 0).sum(1) != 1).any():
-                raise ValueError("coulomb_xyz_slab: box must have exactly one zero, the open axis (none: coulomb_xyz_cell)")
+        in coulomb_xyz_excl: the nearest image of every listed pair counts with weight scale; None: no list.  The strain
+        derivative: coulomb_xyz_slab_strain.  One periodic axis (wires) is not built."""
+        _slab_box("coulomb_xyz_slab", box, cell)
         return self._coulomb("coulomb_xyz_slab", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, False),
                              exclusions=exclusions, slab=True)
 
+    def coulomb_xyz_slab_strain(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                                parts=False, exclusions=None):
+        """coulomb_xyz_slab with the strain derivative of the slab sum (epnn_coulomb_xyz_slab_strain): (q, phi, E, F, gstrain), gstrain
+        (B, 3, 3) the total dE/d eps under a homogeneous strain of coordinates and the two periodic rows (the convention of
+        charges_vjp_xyz(strain=True); beta, rc, kc, the k slots and the in-range pairs held fixed).  parts=True appends ffix, fq,
+        gstrain_fix and gstrain_q (gstrain = gstrain_fix + gstrain_q); gstrain_q is gs of charges_vjp_xyz(g=phi, cell=, strain=True)
+        on "grad_path" 2, bit for bit.  q, phi, E, F, ffix and fq have the bits of coulomb_xyz_slab on the same arguments, which all
+        mean what they mean there.  INTEGRATION.md, "Slabs", has the in-plane stress and the surface tension in terms of gstrain."""
+        _slab_box("coulomb_xyz_slab_strain", box, cell)
+        return self._coulomb("coulomb_xyz_slab_strain", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, True),
+                             exclusions=exclusions, slab=True)
+
     def _coulomb(self, where, offsets, xyz, x, Q, N, ke, alpha, parts, periodic=None, exclusions=None, slab=False):
-        """The five coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
+        """The six coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
         molecules, exclusions = (pairs, scale) or None for the plain C entry (an _excl method without a list is its plain method).
-        slab: the one slab entry, which always takes a list (None: an empty one), its own rule and no strain rows."""
+        slab: the two slab entries, which always take a list (None: an empty one) and their own rule; the plain one has no strain
+        rows, the other one is chosen by its name."""
         if exclusions is None:
             where = where.replace("_excl", "")
             if slab:
@@ -623,7 +641,7 @@ class Engine:
         F = np.empty((A, 3), dtype=np.float32)
         ffix, fq = (np.empty((A, 3), dtype=np.float32) if parts else None for _ in range(2))
         outs = [fptr(q), fptr(phi), dptr(E), fptr(F), opt(ffix), opt(fq)]
-        if periodic is not None and not slab:
+        if periodic is not None and (strain or not slab):
             gs = np.empty((B, 3, 3), dtype=np.float32)
             gs_fix, gs_q = (np.empty((B, 3, 3), dtype=np.float32) if parts else None for _ in range(2))
             outs = outs[:4] + [fptr(gs)] + outs[4:] + [opt(gs_fix), opt(gs_q)]

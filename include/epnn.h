@@ -494,7 +494,8 @@ int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const
  * Device scratch on top of the gradient path's: A (20 + 80 cpieces + 56) + 44 B + 32 slots + the task tables and 72 B of
  * parameters; slots = the batch's k slots, about 3600 for a cube at tol = 1e-6 whatever its size.  Nothing of size n nk or n^2.
  * Still missing: one periodic axis (wires); the strain derivative of the slab sum; PME (bonded exclusions: epnn_coulomb_xyz_cell_excl
- * below; two periodic axes: epnn_coulomb_xyz_slab below). */
+ * below; two periodic axes: epnn_coulomb_xyz_slab below).  The slab sum's strain derivative has since been built as an entry of its
+ * own, epnn_coulomb_xyz_slab_strain, behind epnn_coulomb_xyz_slab. */
 int epnn_ewald_params(const float *cell, double alpha, double tol, double *out);
 int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                           const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
@@ -582,7 +583,7 @@ int epnn_coulomb_xyz_cell_excl(epnn_handle *h, int B, int N, const int32_t *offs
  * then be NULL): the slab call needs one entry, not two.  A list whose factors are all 1 gives the bits of the call without a list;
  * the outputs depend neither on the order of the list nor on which atom of a pair is named first.
  * Outputs (host): q_out[A], phi_out[A], e_out[B] float64 (per cell), f_out[A][3]; ffix_out and fq_out may each be NULL and the
- * other outputs have the same bits either way.  No strain derivative (out of scope, as is one periodic axis).
+ * other outputs have the same bits either way.  The strain derivative: epnn_coulomb_xyz_slab_strain below (one periodic axis is not built).
  * Contract: that of epnn_coulomb_xyz_cell, word for word where it applies: the pair-list path whatever "grad_path" says, no
  * training state touched, waits for a "train_async" step, the same refusals by name (coincident atoms or images included, a
  * periodic width below twice the cutoff, a molecule that does not fit N), the handle left usable; h_dim below 48 zero-padded; no
@@ -608,6 +609,42 @@ int epnn_coulomb_xyz_slab(epnn_handle *h, int B, int N, const int32_t *offsets, 
                           const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
                           const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
                           float *ffix_out, float *fq_out);
+/* ---- the strain derivative of the slab sum: epnn_coulomb_xyz_slab with the strain outputs of epnn_coulomb_xyz_cell_excl (in-plane
+ * pressure coupling, fixed surface tension; INTEGRATION.md, "Slabs").  gstrain [B][3][3] = dE/d eps under r -> (1 + eps) r and
+ * a_k -> (1 + eps) a_k for the two periodic rows, eps symmetric: the strain of epnn_charges_vjp_xyz_cell.  beta, rc, kc, the listed
+ * slots (m0, m1) and the set of in-range pairs are held fixed, as in the periodic call.  To first order A -> A (1 + tr eps - n eps n),
+ * k -> k - (k eps k) / k, z_ij -> z_ij (1 + n eps n), and the phase k . d_ij changes by 2 z_ij (n eps k): a symmetric out-of-plane
+ * shear tilts the plane and the in-plane dual vectors stay in it.  In the notation above, c = pi / (A k) over the whole plane,
+ * Fs = F+ + F-, Fd = F+ - F-, theta = k . d_ij:   dFs/dz = k Fd;   dFs/dk = z Fd - (2 / (beta sqrt(pi))) exp(-u^2 - beta^2 z^2);
+ *     gstrain_fix_ab = -(E_rec + E_k0) (delta_ab - n_a n_b)
+ *                      + 1/2 sum_ij q_i q_j sum_k c cos(theta) [Fs / k^2 - (dFs/dk) / k] k_a k_b
+ *                      + n_a n_b 1/2 sum_ij q_i q_j z_ij { sum_k c k cos(theta) Fd - (2 pi / A) erf(beta z_ij) }
+ *                      - 1/2 sum_ij q_i q_j z_ij sum_k c sin(theta) Fs (n_a k_b + k_a n_b)                       (j == i included)
+ *                      + 1/2 sum_{i != j} q_i q_j kappa_s'(D) d_a d_b / D  +  sum_listed (s - 1) q_i q_j kappa_alpha'(D) d_a d_b / D
+ * all times ke; E_rec and E_k0 the reciprocal and k = 0 parts of E.  The self term has no strain and there is no background term.
+ * gstrain_q_ab = sum_k phi_k dq_k/d eps_ab, the backward's strain rows, and gstrain = gstrain_fix + gstrain_q.
+ * Arguments: those of epnn_coulomb_xyz_slab, with the outputs of epnn_coulomb_xyz_cell_excl.  gstrain_out [B][3][3] is required;
+ * ffix_out, fq_out, gstrain_fix_out and gstrain_q_out may each be NULL.  Contract, checks and refusals: epnn_coulomb_xyz_slab's, word
+ * for word.  epnn_coulomb_xyz_slab itself keeps its kernels, bits and scratch.
+ * Bits: q, phi, e, f, ffix and fq are those of epnn_coulomb_xyz_slab on the same inputs; gstrain_q_out is bit for bit gstrain_out of
+ * epnn_charges_vjp_xyz_cell on "grad_path" 2 called with g = phi_out; gstrain == gstrain_fix + gstrain_q in float32, and each is
+ * bitwise symmetric (six sums mirrored into nine slots).
+ * Arithmetic: the reciprocal and k = 0 sums have no structure factor, so their strain rides in the all-pairs sweep: six more float64
+ * sums per lane beside the five, in the basis of the slot integers (the z-weighted force along nhat; the z-weighted in-plane force
+ * times m0, m1; the bracket above times m0^2, m0 m1, m1^2), float32 products of values the sweep already has and no new
+ * transcendental; the atoms' kernel expands them through g_a, g_b and nhat in float64 and adds the virial rows of the real-space sweep
+ * and of the listed pairs; one wavefront per cell adds the atoms' shares.  No float atomics, every sum in a fixed order.
+ * Accuracy: every component of gstrain_fix is within 2e-6 of its absolute real-space and listed pairs' terms, plus 43 * 2^-24 of its
+ * absolute reciprocal terms, plus 16 * 2^-24 of its absolute k = 0 terms, plus 2 * 2^-24 of its own size (tests/
+ * test_gpu_coulomb_slab_strain.py counts the roundings and tests/slab_strain_ref.py defines the absolute terms: those of the formula
+ * above with |Fd| counted as Fs and k_a, k_a k_b counted in the slot integers' basis).
+ * Device scratch (epnn_last_stats out[2]): epnn_coulomb_xyz_slab's on the same batch and list, plus the wider rows of the sweep
+ * ([cpieces][A][11] instead of [5]), the atoms' strain shares [A][6] and the [B][9] fixed-charge rows behind E:
+ *     bytes = epnn_coulomb_xyz_slab's + 48 A cpieces + 48 A + 36 B */
+int epnn_coulomb_xyz_slab_strain(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                 const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
+                                 const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
+                                 float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out);
 /* ---- training on periodic and large systems. epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
  * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
  * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's

@@ -32,7 +32,14 @@ atoms in a cell whose third vector is nhat times three slab thicknesses and at l
 do before.  The workloads: 1024 QM9-sized 6.5 A square slabs 5 A thick, a 2048-atom and a 10 000-atom slab on a jittered lattice at
 the tool's cell density (0.1 per A^3, four layers).  Printed besides: the listed half-plane slots, the scratch beside the formula of
 include/epnn.h, and the checks q (bits) and fq against -gxyz of the gradient call seeded with phi (bits).  With --trace: three calls
-of coulomb_xyz_slab per system (the k_sl_* rows are the new kernels; k_ew_sweep is the real-space part)."""
+of coulomb_xyz_slab per system (the k_sl_* rows are the new kernels; k_ew_sweep is the real-space part).
+    python tools/bench_coulomb.py --slab --strain [--systems ...] [--rounds 5] [--alpha 0.0] [--tol 1e-6] [--against FILE] [--trace]
+is the strain call coulomb_xyz_slab_strain beside the plain slab call of the same build, alternating, on the same three workloads
+(profiles/r20_coulomb_slab_strain.txt).  Printed per system: the two medians and their ratio, the scratch of the strain call beside
+the formula of include/epnn.h, and the checks: q, phi, E, F, ffix, fq of the two calls (bits), gstrain_q against gs of the gradient
+call seeded with phi (bits), gstrain == gstrain_fix + gstrain_q and its symmetry (bits).  --against FILE: the JSON lines that
+`--slab` printed on another build (the parent commit) in the same session; adds the ratio of this build's plain call to that one's.
+With --trace: three calls of coulomb_xyz_slab_strain per system (k_sl_sweep_strain, k_sl_atom_strain, k_sl_energy_strain)."""
 import json
 import os
 import sys
@@ -218,6 +225,58 @@ def main_slab(eng, T, systems, rounds, alpha, tol, cutoff=3.0):
         print(json.dumps(line), flush=True)
 
 
+def main_slab_strain(eng, T, systems, rounds, alpha, tol, against):
+    other = {}
+    if against:
+        for text in open(against):
+            if text.startswith("{"):
+                rec = json.loads(text)
+                other[rec["workload"]] = rec
+    for system in systems:
+        name, offsets, xyz, x, Q, N, cells, thick = load_slab(system)
+        A = int(offsets[-1])
+        rows = np.stack([eng.ewald_slab_params(c, alpha, tol) for c in cells])
+        slots = slab_slots(cells, rows)
+        if "--trace" in sys.argv:
+            for _ in range(3):
+                eng.coulomb_xyz_slab_strain(offsets, xyz, x, Q, N, cell=cells, alpha=alpha, ewald=rows)
+            print(json.dumps({"workload": name, "atoms": A, "calls": 3, "alpha": alpha, "tol": tol, "k_slots": slots}), flush=True)
+            continue
+        calls = {"coulomb_slab": lambda: eng.coulomb_xyz_slab(offsets, xyz, x, Q, N, cell=cells, alpha=alpha, ewald=rows, parts=True),
+                 "coulomb_slab_strain": lambda: eng.coulomb_xyz_slab_strain(offsets, xyz, x, Q, N, cell=cells, alpha=alpha, ewald=rows, parts=True)}
+        for fn in calls.values():
+            fn()
+        times = {k: [] for k in calls}
+        outs = {}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t, outs[k] = window(fn)
+                times[k].append(t * 1e3)
+        q, phi, E, F, gs, ffix, fq, gs_fix, gs_q = outs["coulomb_slab_strain"]
+        st = eng.last_stats() if calls["coulomb_slab_strain"]() else None
+        seeded = eng.charges_vjp_xyz(offsets, xyz, x, Q, phi, N, cell=cells, strain=True)
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        ns = [int(n) for n in np.diff(offsets)]
+        cp = max(map(cl_pieces, ns))
+        line = {"workload": name, "atoms": A, "cells": len(cells), "near_pairs": int(st[0]), "rounds": rounds, "alpha": alpha, "tol": tol,
+                "k_slots": slots}
+        for k, t in times.items():
+            line[k + "_ms_median"] = round(med[k], 3)
+            line[k + "_ms_range"] = [round(min(t), 3), round(max(t), 3)]
+        line["strain_over_plain"] = round(med["coulomb_slab_strain"] / med["coulomb_slab"], 3)
+        if name in other:
+            line["parent_plain_ms_median"] = other[name]["coulomb_slab_ms_median"]
+            line["plain_over_parent"] = round(med["coulomb_slab"] / other[name]["coulomb_slab_ms_median"], 3)
+        line.update({"strain_scratch_bytes": int(st[2]),
+                     "strain_scratch_formula_bytes": scratch_formula(ns, int(st[0]), 9, T) + 88 * A * cp + 304 * len(ns) + 56 * slots
+                     + 48 * A * cp + 48 * A + 36 * len(ns),
+                     "six_outputs_bits_equal_plain_call": bool(all(np.array_equal(a, b) for a, b in zip((q, phi, E, F, ffix, fq), outs["coulomb_slab"]))),
+                     "gstrain_q_bits_equal_gs_of_phi": bool(np.array_equal(gs_q, seeded[2])),
+                     "gstrain_is_the_float32_sum_and_symmetric": bool(np.array_equal(gs, gs_fix + gs_q) and np.array_equal(gs, gs.transpose(0, 2, 1))),
+                     "max_abs_gstrain_fix": float(np.abs(gs_fix).max()), "max_abs_gstrain_q": float(np.abs(gs_q).max())})
+        print(json.dumps(line), flush=True)
+
+
 def exclusion_list(offsets, xyz, cells, near):
     """Every pair of a molecule nearer than `near` (minimum image in a cubic cell), factors cycling in sorted order; shuffled."""
     from scipy.spatial import cKDTree
@@ -346,6 +405,10 @@ def main():
     eng = Engine(nx=9, T=T)
     eng.set_weights(w)
     eng.set_option("grad_path", 2)
+    if slab_mode and "--strain" in sys.argv:
+        main_slab_strain(eng, T, systems, rounds, alpha, float(arg("--tol", "1e-6")), arg("--against", None))
+        eng.close()
+        return
     if slab_mode:
         main_slab(eng, T, systems, rounds, alpha, float(arg("--tol", "1e-6")))
         eng.close()
