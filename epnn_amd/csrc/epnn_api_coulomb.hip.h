@@ -1,6 +1,6 @@
 // epnn_coulomb_xyz and epnn_coulomb_xyz_excl: charges, electrostatic potential, Coulomb energy and total forces of a flat coordinate
 // batch in one call (kernels: epnn_coulomb.hip.h).  Here: the sweep's task table, the exclusion list's validator and CSR, and the two
-// open entries; the driver they share with the periodic entries, coulomb_run, is defined in epnn_api_coulomb_cell.hip.h.
+// open entries; the driver they share with the periodic and the slab entries, coulomb_run, is defined in epnn_api_coulomb_run.hip.h.
 // Part of the one translation unit epnn_api.hip.
 #pragma once
 #include "epnn_api_grad.hip.h"
@@ -114,15 +114,29 @@ static void excl_launch(epnn_handle *h, const GlCall &c, const char *d_csr, cons
                        d_cells, (float)alpha, xpart, hit);
 }
 
-// what an _excl entry adds to its plain entry's arguments, and the outputs of the four entries (the strain rows: the periodic ones only)
+// what an _excl entry adds to its plain entry's arguments, and the outputs of the six entries (the strain rows: the entries with strain)
 struct ExclArgs { int64_t npairs; const int32_t *i, *j; const float *scale; };
 struct CoulombOut { float *q, *phi; double *e; float *f, *ffix, *fq, *gs, *gs_fix, *gs_q; };
 
-// The one driver behind the four entries, defined in epnn_api_coulomb_cell.hip.h, where the periodic part is known; the open entries
-// hand it none, and then it stages no cell parameters, launches no Ewald kernel and allocates no strain rows.
-struct CoulombPeriodic;
+// What an entry adds to the open call: the kind of its sum, whether the strain rows are made, the cells' checked parameters (ew: the
+// real-space sweep's; sl and slots: the slab's reciprocal sweep's, types of epnn_ewald_slab.hip.h) and the caller's list for excl_name_far.
+struct EwCell;
+struct SlCell;
+struct SlSlot;
+enum CoulombKind { CL_OPEN, CL_CELL, CL_SLAB };
+struct CoulombSum {
+    CoulombKind kind;
+    bool strain;
+    std::vector<EwCell> *ew;
+    const std::vector<SlCell> *sl;
+    const std::vector<SlSlot> *slots;
+    const ExclArgs *xa;
+};
+
+// The one driver behind the six entries, defined in epnn_api_coulomb_run.hip.h, where the three kernel files are known; the open entries
+// hand it no sum, and then it stages no cell parameters, launches no Ewald kernel and allocates no strain rows.
 static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                       const HostGeo &geo, double ke, double alpha, CoulombPeriodic *per, const ExclCsr *ex, const CoulombOut &out);
+                       const HostGeo &geo, double ke, double alpha, const CoulombSum *sum, const ExclCsr *ex, const CoulombOut &out);
 
 static int coulomb_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                          double ke, double alpha, const ExclArgs *xa, const CoulombOut &out) {

@@ -1,8 +1,8 @@
 // epnn_coulomb_xyz_slab: epnn_coulomb_xyz in slab cells (two periodic axes, one open one) by the exact two-dimensional Ewald sum
-// (kernels: epnn_ewald_slab.hip.h); epnn_coulomb_xyz_slab_strain, the same call with the sum's strain derivative, on the same driver;
-// and epnn_ewald_slab_params, the host-only rule that chooses the sum's parameters.  The driver is a
-// sibling of coulomb_run: it shares gl_grad_forward, the open sweep's task table, k_ew_sweep, the exclusion list's kernel, the backward
-// and the one download; the plain and periodic entries keep their driver.  Part of the one translation unit epnn_api.hip.
+// (kernels: epnn_ewald_slab.hip.h); epnn_coulomb_xyz_slab_strain, the same call with the sum's strain derivative; and
+// epnn_ewald_slab_params, the host-only rule that chooses the sum's parameters.  Here: the slab cell's geometry, the rule and the row
+// check over its two periodic rows (ew_rule_rows, ew_row_check), the slot list and the two entries; the driver is coulomb_run
+// (epnn_api_coulomb_run.hip.h).  Part of the one translation unit epnn_api.hip.
 #pragma once
 #include "epnn_api_coulomb_cell.hip.h"
 #include "epnn_ewald_slab.hip.h"
@@ -64,23 +64,15 @@ static int sl_box_slots(const char *what, int b, double Ma, double Mb) {
 static int sl_rule(const char *what, int b, const float *cell, double alpha, double tol, double *out) {
     SlGeom G;
     if (sl_cell_geom(what, b, cell, G)) return 1;
-    const double s = sqrt(-log(tol));
-    double rc = 0.5 * G.wmin, beta = s / rc;
-    if (alpha > 0.0 && alpha <= beta) { beta = alpha; rc = 0.0; }
-    const double kc = 2.0 * beta * s;
-    out[0] = beta; out[1] = rc; out[2] = kc;
+    const int rows[2] = {G.pa, G.pb};
     out[3 + G.open] = 0.0;
-    out[3 + G.pa] = ceil(kc * G.len[0] / 6.283185307179586);
-    out[3 + G.pb] = ceil(kc * G.len[1] / 6.283185307179586);
+    ew_rule_rows(G.wmin, 2, rows, G.len, alpha, tol, out);
     return sl_box_slots(what, b, out[3 + G.pa], out[3 + G.pb]);
 }
 
 extern "C" int epnn_ewald_slab_params(const float *cell, double alpha, double tol, double *out) {
     const char *name = "epnn_ewald_slab_params";
-    if (!cell || !out) EPNN_FAIL("%s: null argument", name);
-    if (!epnn_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
-    if (!epnn_finite(tol) || !(tol > 0.0 && tol < 1.0)) EPNN_FAIL("%s: tol must be finite and inside (0, 1)", name);
-    return sl_rule(name, 0, cell, alpha, tol, out);
+    return ew_params_args(name, cell, out, alpha, tol) || sl_rule(name, 0, cell, alpha, tol, out);
 }
 
 // One checked row of the entry's `ewald` argument -> what the kernels take: the sweep's (rc, beta) in an EwCell, the cell's SlCell, and
@@ -88,31 +80,12 @@ extern "C" int epnn_ewald_slab_params(const float *cell, double alpha, double to
 static int sl_cell_row(const char *what, int b, const float *cell, const double *row, double alpha, EwCell &e, SlCell &c, std::vector<SlSlot> &slots) {
     SlGeom G;
     if (sl_cell_geom(what, b, cell, G)) return 1;
-    for (int k = 0; k < 6; ++k)
-        if (!epnn_finite(row[k])) EPNN_FAIL("%s: ewald[%d][%d] is not finite", what, b, k);
-    const double beta = row[0], rc = row[1], kc = row[2], *M = row + 3;
-    if (!(beta > 0.0)) EPNN_FAIL("%s: ewald[%d]: beta = %g must be positive", what, b, beta);
-    if (!(kc >= 0.0)) EPNN_FAIL("%s: ewald[%d]: kc = %g must not be negative", what, b, kc);
-    if (!(rc >= 0.0 && rc <= 0.5 * G.wmin))
-        EPNN_FAIL("%s: ewald[%d]: rc = %g must lie in [0, w_min / 2]: half the smaller perpendicular width of cell %d is %g, and beyond "
-                  "it a pair has more than one image in range", what, b, rc, b, 0.5 * G.wmin);
-    if (rc == 0.0 && !(alpha > 0.0 && beta == alpha))
-        EPNN_FAIL("%s: ewald[%d]: rc = 0 (no real-space part) takes beta == alpha > 0; beta = %g, alpha = %g", what, b, beta, alpha);
-    if (M[G.open] != 0.0) EPNN_FAIL("%s: ewald[%d]: M%d = %g, but axis %d of cell %d is open: its M must be 0", what, b, G.open, M[G.open], G.open, b);
     const int rows[2] = {G.pa, G.pb};
-    for (int t = 0; t < 2; ++t) {
-        const int k = rows[t];
-        const double need = ceil(kc * G.len[t] / 6.283185307179586 - 1e-9);
-        if (!(M[k] >= 0.0 && M[k] <= 1e6 && M[k] == floor(M[k]) && M[k] >= need))
-            EPNN_FAIL("%s: ewald[%d]: M%d = %g is not consistent with kc = %g: an integer of at least ceil(kc |a_%d| / 2 pi) = %g", what, b, k,
-                      M[k], kc, k, need);
-    }
+    memset(&e, 0, sizeof(e));
+    if (ew_row_check(what, b, row, alpha, G.wmin, "smaller", 2, rows, G.len, G.open, e)) return 1;
+    const double beta = row[0], kc = row[2], *M = row + 3;
     if (sl_box_slots(what, b, M[G.pa], M[G.pb])) return 1;
     const double pi = 3.141592653589793;
-    memset(&e, 0, sizeof(e));
-    e.rc = (float)rc;
-    if ((double)e.rc > rc) e.rc = nextafterf(e.rc, 0.f);
-    e.beta = (float)beta;
     memset(&c, 0, sizeof(c));
     for (int x = 0; x < 3; ++x) { c.ga[x] = G.ga[x]; c.gb[x] = G.gb[x]; c.nh[x] = G.nh[x]; }
     c.beta = beta;
@@ -131,112 +104,6 @@ static int sl_cell_row(const char *what, int b, const float *cell, const double 
             slots.push_back(SlSlot{(double)m0, (double)m1, k, u, (float)w, (float)(w * k), (float)kv[0], (float)kv[1], (float)kv[2], (float)(1.0 / k)});
         }
     c.ns = (int)slots.size() - c.soff;
-    return 0;
-}
-
-// The slab call: the pair-list gradient call with its seed made on the device, as coulomb_run.  Set-up and checkpointed forward; on that
-// forward's charges the real-space sweep (k_ew_sweep), the reciprocal sweep (k_sl_sweep), the listed pairs' correction (ex) and the
-// energy, phi = dE/dq into the seed; the shared backward; one download.  strain (epnn_coulomb_xyz_slab_strain): the reciprocal sweep is
-// k_sl_sweep_strain with its wider rows, the atoms write their strain shares, one wavefront per cell adds them, the backward runs with
-// its strain flag and the download carries both strain rows; without it the plain entry's kernels, bits and scratch.
-static int coulomb_slab_run(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
-                            const float *Q, const HostGeo &geo, double ke, double alpha, const std::vector<EwCell> &ew,
-                            const std::vector<SlCell> &sl, const std::vector<SlSlot> &slots, const ExclCsr *ex, const ExclArgs &xa,
-                            bool strain, const CoulombOut &out) {
-    GradLarge *gl = grad_large_state(h);
-    if (grad_large_weights(h, gl)) return 1;
-    const int T = h->cfg.T, A = offsets[B];
-    std::vector<int4> ctasks;
-    const size_t cpieces = (size_t)cl_build_tasks(B, offsets, ctasks);
-    bool sweep = false;
-    for (int b = 0; b < B; ++b) sweep = sweep || ew[b].rc > 0.f;
-    // one staged span: the sweeps' task table, the cells' parameters of either sweep and the slots, each at a multiple of 16 bytes
-    const size_t o_ew = ctasks.size() * sizeof(int4), o_sl = o_ew + (((size_t)B * sizeof(EwCell) + 15) & ~size_t(15)),
-                 o_slot = o_sl + (size_t)B * sizeof(SlCell), blob_bytes = o_slot + slots.size() * sizeof(SlSlot);
-    std::vector<char> blob(blob_bytes, 0);
-    memcpy(blob.data(), ctasks.data(), o_ew);
-    memcpy(blob.data() + o_ew, ew.data(), (size_t)B * sizeof(EwCell));
-    memcpy(blob.data() + o_sl, sl.data(), (size_t)B * sizeof(SlCell));
-    if (!slots.empty()) memcpy(blob.data() + o_slot, slots.data(), slots.size() * sizeof(SlSlot));
-    // [A] phi | [A][3] ffix | flag, then [B] E in float64: directly behind the backward's output block, one download for both; the two
-    // sweeps' partial rows [pieces][A][EW_PART] and [pieces][A][SL_PART] and the atoms' energy shares [A] in float64.  strain: [B][9]
-    // the fixed-charge strain behind E, rows of SL_PART_STRAIN, and the atoms' strain shares [A][SL_SHARE_W] behind the energy's
-    const size_t o_E = (((size_t)A * 4 + 1) * 4 + 7) & ~size_t(7), o_gsf = o_E + (size_t)B * 8, co_bytes = o_gsf + (strain ? (size_t)B * 36 : 0);
-    const size_t o_rpart = cpieces * (size_t)A * EW_PART * 8, o_share = o_rpart + cpieces * (size_t)A * (strain ? SL_PART_STRAIN : SL_PART) * 8,
-                 o_wshare = o_share + (size_t)A * 8, sc_bytes = o_wshare + (strain ? (size_t)A * SL_SHARE_W * 8 : 0);
-    const GlSpan spans[2] = {GlSpan{blob.data(), blob_bytes, false}, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false}};
-    const size_t more[3] = {co_bytes, sc_bytes, ex ? excl_xpart_bytes(A, true) : 0};
-    GlGrad r;
-    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
-    const GlCall &c = r.c;
-    char *co = c.dw + r.o_more[0], *sc = c.dw + r.o_more[1];
-    float *phi = reinterpret_cast<float *>(co), *ffix = phi + A, *gsf = reinterpret_cast<float *>(co + o_gsf);
-    int *hit = reinterpret_cast<int *>(phi + 4 * (size_t)A);
-    double *E = reinterpret_cast<double *>(co + o_E), *part = reinterpret_cast<double *>(sc), *rpart = reinterpret_cast<double *>(sc + o_rpart),
-           *share = reinterpret_cast<double *>(sc + o_share), *wshare = reinterpret_cast<double *>(sc + o_wshare);
-    double *xpart = ex ? reinterpret_cast<double *>(c.dw + r.o_more[2]) : nullptr;
-    const float *q_dev = r.qck + (size_t)T * A;
-    const char *d_blob = reinterpret_cast<const char *>(c.d_extra[0]), *d_csr = ex ? reinterpret_cast<const char *>(c.d_extra[1]) : nullptr;
-    const int4 *d_ctasks = reinterpret_cast<const int4 *>(d_blob);
-    const EwCell *d_ew = reinterpret_cast<const EwCell *>(d_blob + o_ew);
-    const SlCell *d_sl = reinterpret_cast<const SlCell *>(d_blob + o_sl);
-    const SlSlot *d_slots = reinterpret_cast<const SlSlot *>(d_blob + o_slot);
-    const EpnnCell *d_cells = c.geo.cells();
-    const dim3 gsweep((unsigned)ctasks.size()), wave(64);
-    // ---- the sum on the forward's own charges: phi is the backward's seed
-    HIPCHK(hipMemsetAsync(hit, 0, 4, h->stream));
-    if (!sweep)                                                  // beta == alpha in every cell: the real-space term vanishes identically
-        HIPCHK(hipMemsetAsync(part, 0, o_rpart, h->stream));
-    else
-        hipLaunchKernelGGL((alpha > 0.0 ? k_ew_sweep<true> : k_ew_sweep<false>), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz,
-                           q_dev, d_cells, d_ew, A, (float)alpha, part, hit);
-    hipLaunchKernelGGL((strain ? k_sl_sweep_strain : k_sl_sweep), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev, d_sl,
-                       d_slots, A, rpart);
-    if (ex) excl_launch(h, c, d_csr, *ex, q_dev, d_cells, alpha, xpart, hit);
-    if (strain) {
-        hipLaunchKernelGGL(k_sl_atom_strain, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
-                           (const double *)rpart, (const double *)xpart, ke, r.gq, phi, ffix, share, wshare);
-        hipLaunchKernelGGL(k_sl_energy_strain, dim3((unsigned)B), wave, 0, h->stream, (const double *)share, (const double *)wshare, c.d_moff, E, gsf);
-    } else {
-        if (ex)
-            hipLaunchKernelGGL(k_sl_atom_x, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
-                               (const double *)rpart, (const double *)xpart, ke, r.gq, phi, ffix, share);
-        else
-            hipLaunchKernelGGL(k_sl_atom, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
-                               (const double *)rpart, ke, r.gq, phi, ffix, share);
-        hipLaunchKernelGGL(k_cl_energy, dim3((unsigned)B), wave, 0, h->stream, (const double *)share, c.d_moff, E);
-    }
-    HIPCHK(hipGetLastError());
-    if (gl_grad_backward(h, gl, r, B, strain)) return 1;
-    // ---- one download: q | gxyz | flag | the charges' strain rows (plain: unused) | (the step to the next buffer) | phi | ffix | flag | E
-    // | strain: the fixed-charge strain
-    const char *from = reinterpret_cast<const char *>(r.q_fin);
-    const size_t nbytes = (size_t)(co + co_bytes - from), at_co = (size_t)(co - from);
-    if (gl->pin_out.ensure(nbytes)) return 1;
-    char *back = gl->pin_out.as<char>();
-    HIPCHK(hipMemcpyAsync(back, from, nbytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const float *bq = reinterpret_cast<const float *>(back), *bgx = bq + A, *bphi = reinterpret_cast<const float *>(back + at_co), *bffix = bphi + A;
-    const int flag = reinterpret_cast<const int *>(bq)[4 * (size_t)A], chit = reinterpret_cast<const int *>(bphi)[4 * (size_t)A];
-    if (flag & 2) EPNN_FAIL("%s: the pair list is not symmetric", name);
-    if (flag == 0 && chit == CL_FLAG_FAR && ex) return excl_name_far(name, offsets, xyz, geo, xa);
-    if (flag != 0 || chit != 0)
-        EPNN_FAIL("%s: two atoms of a cell or their periodic images coincide (distance 0: neither the Coulomb terms nor the edge features "
-                  "have a derivative there)", name);
-    memcpy(out.q, bq, (size_t)A * 4);
-    memcpy(out.phi, bphi, (size_t)A * 4);
-    memcpy(out.e, back + at_co + o_E, (size_t)B * 8);
-    for (size_t k = 0; k < 3 * (size_t)A; ++k) {
-        const float fq = -bgx[k];
-        out.f[k] = bffix[k] + fq;
-        if (out.fq) out.fq[k] = fq;
-    }
-    if (out.ffix) memcpy(out.ffix, bffix, (size_t)A * 12);
-    if (!strain) return 0;
-    const float *bgs = bq + 4 * (size_t)A + 1, *bgsf = reinterpret_cast<const float *>(back + at_co + o_gsf);
-    for (size_t k = 0; k < 9 * (size_t)B; ++k) out.gs[k] = bgsf[k] + bgs[k];
-    if (out.gs_fix) memcpy(out.gs_fix, bgsf, (size_t)B * 36);
-    if (out.gs_q) memcpy(out.gs_q, bgs, (size_t)B * 36);
     return 0;
 }
 
@@ -264,7 +131,8 @@ static int coulomb_slab_enter(epnn_handle *h, const char *name, int B, int N, co
     const ExclArgs xa{npairs, ex_i, ex_j, ex_scale};
     ExclCsr ex;
     if (excl_build(name, B, offsets, npairs, ex_i, ex_j, ex_scale, ex)) return 1;
-    return coulomb_slab_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, ew, sl, slots, npairs > 0 ? &ex : nullptr, xa, strain, out);
+    const CoulombSum sum{CL_SLAB, strain, &ew, &sl, &slots, &xa};
+    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, &sum, npairs > 0 ? &ex : nullptr, out);
 }
 
 extern "C" int epnn_coulomb_xyz_slab(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,

@@ -1,7 +1,7 @@
 // What the pair-list entries share on the host: the state GradLarge, their weights, one call's set-up (GlCall: staged inputs, the
 // front-end's pair list, the work buffer) and the checkpointed forward of the two reverse-mode entries.  Entries:
 // charges_vjp_large_impl (epnn_api_grad.hip.h, "grad_path"), train_step_large_impl (epnn_api_train_large.hip.h, "train_path"),
-// charges_jvp_multi_impl (epnn_api_jvp.hip.h), coulomb_run (epnn_api_coulomb_cell.hip.h, through the gradient call's two pieces).  Host code only; kernels: epnn_frontend.hip.h, epnn_grad_large.hip.h.
+// charges_jvp_multi_impl (epnn_api_jvp.hip.h), coulomb_run (epnn_api_coulomb_run.hip.h, through the gradient call's two pieces).  Host code only; kernels: epnn_frontend.hip.h, epnn_grad_large.hip.h.
 // Part of the one translation unit epnn_api.hip.
 #pragma once
 #include "epnn_grad_large.hip.h"

@@ -525,11 +525,15 @@ class Engine:
         """The Ewald parameters coulomb_xyz_cell runs at for one cell (3, 3) (epnn_ewald_params, host only): float64 (6,) = beta,
         rc, kc, M0, M1, M2 with s = sqrt(-ln tol), rc = w_min / 2, beta = s / rc capped at alpha (then rc = 0: no real-space
         part), kc = 2 beta s, M_k = ceil(kc |a_k| / 2 pi).  Refuses open axes, tol outside (0, 1) and k boxes above 2^18 slots."""
+        return self._ewald_rule("ewald_params", cell, alpha, tol)
+
+    def _ewald_rule(self, entry, cell, alpha, tol):
+        """ewald_params and ewald_slab_params: one cell (3, 3) through the host-only C entry epnn_<entry>"""
         cell = np.ascontiguousarray(cell, dtype=np.float32)
         if cell.shape != (3, 3):
-            raise ValueError(f"ewald_params: cell must have shape (3, 3), got {cell.shape}")
+            raise ValueError(f"{entry}: cell must have shape (3, 3), got {cell.shape}")
         out = np.empty((6,), dtype=np.float64)
-        check(self.lib.epnn_ewald_params(fptr(cell), float(alpha), float(tol), out.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
+        check(getattr(self.lib, "epnn_" + entry)(fptr(cell), float(alpha), float(tol), out.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
         return out
 
     def coulomb_xyz_cell(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None, parts=False,
@@ -567,12 +571,7 @@ class Engine:
         """The parameters coulomb_xyz_slab runs at for one slab cell (3, 3) with one row of zeros (epnn_ewald_slab_params, host only):
         float64 (6,) = beta, rc, kc, M0, M1, M2 by the rule of ewald_params over the two periodic rows; M of the open row is 0.
         Refuses three periodic rows (ewald_params), fewer than two, dependent rows, tol outside (0, 1) and k boxes above 2^16 slots."""
-        cell = np.ascontiguousarray(cell, dtype=np.float32)
-        if cell.shape != (3, 3):
-            raise ValueError(f"ewald_slab_params: cell must have shape (3, 3), got {cell.shape}")
-        out = np.empty((6,), dtype=np.float64)
-        check(self.lib.epnn_ewald_slab_params(fptr(cell), float(alpha), float(tol), out.ctypes.data_as(C.POINTER(C.c_double))), self.lib)
-        return out
+        return self._ewald_rule("ewald_slab_params", cell, alpha, tol)
 
     def coulomb_xyz_slab(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None, parts=False,
                          exclusions=None):

@@ -111,8 +111,10 @@ def test_the_source_files_are_part_of_the_translation_unit():
     api = open(os.path.join(csrc, "epnn_api.hip")).read()
     assert '#include "epnn_api_coulomb_slab.hip.h"' in api
     assert api.index('#include "epnn_api_coulomb_cell.hip.h"') < api.index('#include "epnn_api_coulomb_slab.hip.h"')
-    drv = open(os.path.join(csrc, "epnn_api_coulomb_slab.hip.h")).read()
-    assert '#include "epnn_ewald_slab.hip.h"' in drv and 'extern "C" int ' + NAME in drv and 'extern "C" int ' + HELPER in drv
+    assert api.index('#include "epnn_api_coulomb_slab.hip.h"') < api.index('#include "epnn_api_coulomb_run.hip.h"')
+    ent = open(os.path.join(csrc, "epnn_api_coulomb_slab.hip.h")).read()
+    assert '#include "epnn_ewald_slab.hip.h"' in ent and 'extern "C" int ' + NAME in ent and 'extern "C" int ' + HELPER in ent
+    drv = open(os.path.join(csrc, "epnn_api_coulomb_run.hip.h")).read()
     assert "k_ew_sweep<true>" in drv and "gl_grad_forward(" in drv and "gl_grad_backward(" in drv
     kernels = open(os.path.join(csrc, "epnn_ewald_slab.hip.h")).read()
     for k in ("k_sl_sweep", "k_sl_atom", "k_sl_atom_x"):
@@ -121,3 +123,10 @@ def test_the_source_files_are_part_of_the_translation_unit():
     # the open and the periodic call's kernels are in their own files and know nothing of the slab's
     for other in ("epnn_coulomb.hip.h", "epnn_ewald.hip.h"):
         assert "k_sl_" not in open(os.path.join(csrc, other)).read()
+
+
+def test_the_six_entries_share_one_forward_and_one_download():
+    csrc = os.path.join(ROOT, "epnn_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if re.fullmatch(r"epnn_api_coulomb.*\.hip\.h", f))
+    assert text.count('extern "C" int epnn_coulomb_xyz') == 6
+    assert text.count("gl_grad_forward(") == 1 and text.count("hipMemcpyDeviceToHost") == 1

@@ -61,8 +61,15 @@ def test_the_kernels_are_in_the_slab_file():
         assert re.search(r"__global__ __launch_bounds__\(\d+\) void " + k + r"\(", kernels), k
     assert "__launch_bounds__(64) void k_sl_sweep_strain" in kernels and "template <bool STRAIN>" in kernels
     assert "sl_sweep_body<false>" in kernels and "sl_sweep_body<true>" in kernels and "atomicAdd" not in kernels
-    drv = open(os.path.join(csrc, "epnn_api_coulomb_slab.hip.h")).read()
-    assert 'extern "C" int ' + NAME + "(" in drv and 'extern "C" int ' + PLAIN + "(" in drv
-    assert drv.count("static int coulomb_slab_run(") == 1 and "gl_grad_backward(h, gl, r, B, strain)" in drv
+    # the slab has no driver of its own: its two entries reach coulomb_run, which launches the strain kernels and runs the one backward
+    for f in os.listdir(csrc):
+        assert "coulomb_slab_run" not in open(os.path.join(csrc, f)).read(), f
+    ent = open(os.path.join(csrc, "epnn_api_coulomb_slab.hip.h")).read()
+    assert 'extern "C" int ' + NAME + "(" in ent and 'extern "C" int ' + PLAIN + "(" in ent
+    assert "return coulomb_run(" in ent and ent.count("coulomb_slab_enter(h, ") == 2
+    drv = open(os.path.join(csrc, "epnn_api_coulomb_run.hip.h")).read()
+    assert drv.count("gl_grad_backward(") == 1 and "gl_grad_backward(h, gl, r, B, strain)" in drv
+    for k in ("k_sl_sweep_strain", "k_sl_atom_strain", "k_sl_energy_strain"):
+        assert k in drv, k
     for other in ("epnn_coulomb.hip.h", "epnn_ewald.hip.h"):
         assert "k_sl_" not in open(os.path.join(csrc, other)).read()
