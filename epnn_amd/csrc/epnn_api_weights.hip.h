@@ -407,7 +407,7 @@ static int pack_weights(epnn_handle *h) {
             return off;
         };
         // [nrb][steps / 4][64][4]: lane (q,m) of (rb, step s) = fn(s, q, 16rb + m)  (input selector, output feature); a lane's
-        // four consecutive steps are 16 contiguous bytes (one dwordx4 load, W16_LDX in epnn_wave.hip.h)
+        // four consecutive steps are 16 contiguous bytes (one dwordx4 load, W16_LDX in epnn_common.h)
         auto frag = [&](int nrb, int steps, auto &&fn) {
             const int off = alloc((size_t)nrb * steps * 64);
             for (int rb = 0; rb < nrb; ++rb)
@@ -417,7 +417,7 @@ static int pack_weights(epnn_handle *h) {
             return off;
         };
         auto accf = [](int s, int q) { return 16 * (s >> 2) + 4 * q + (s & 3); };       // "acc" K order
-        // a K = 32 kernel as three bf16 pieces per weight (epnn_wave.hip.h, w16_split3: truncation, exact), [2][3][64 lanes][4 dwords]:
+        // a K = 32 kernel as three bf16 pieces per weight (epnn_common.h, w16_split3: truncation, exact), [2][3][64 lanes][4 dwords]:
         // lane (q, m) of row block rb: K slots s = 0..7 = input feature accf(s, q), output feature 16 rb + m; dword j = slots 2j | 2j+1 << 16
         // frag_bf3s: the K slot (lane group q, slot s) -> value mapping is the caller's (fn(q, s, out)); frag_bf3: acc order
         auto frag_bf3s = [&](auto &&fn) {
@@ -449,7 +449,7 @@ static int pack_weights(epnn_handle *h) {
         // a K = 16 kernel as three bf16 pieces w1, w2, w3 per weight, [2][2][64 lanes][4 dwords]: lane (q, m) of row block rb: K slots
         // s = 0..3 = fn(q, s, 16 rb + m), a piece is two dwords (dword j = slots 2j | 2j+1 << 16).  A lane's row block is the 32-byte
         // string w1 w2 w3 w1, stored as its two 16-byte halves w1 w2 | w3 w1: the two K = 32 operands of w16_mm_bfk16
-        // (epnn_wave.hip.h: two K = 16 products per v_mfma_f32_16x16x32_bf16)
+        // (epnn_common.h, w16_mm_bfk16: two K = 16 products per v_mfma_f32_16x16x32_bf16)
         auto frag_bf3k16 = [&](auto &&fn) {
             const int off = alloc((size_t)2 * 2 * 64 * 4);
             for (int rb = 0; rb < 2; ++rb)
@@ -637,7 +637,7 @@ static int pack_weights(epnn_handle *h) {
             E.wjf = fj.f32; E.wjfhb = fj.hb; E.wjfxb = fj.xb;
         }
         // ---- The same index with the pair MLPs' operands SCALED by s = 2^-EPNN_RELU_SHIFT: the packs of k_wave_forward's CLAMP form
-        //      (epnn_wave.hip.h, w16_clamp01).  Times s: everything that produces P, R and G of a pair MLP, and b2 -- so that its
+        //      (epnn_common.h, w16_clamp01).  Times s: everything that produces P, R and G of a pair MLP, and b2 -- so that its
         //      pre-activations, first-layer outputs, second-layer outputs and their sum are s times the unscaled kernel's, exactly:
         //      a power of two changes no mantissa, in float32 or in a bf16 piece.  Times 1 / s: the one linear map that takes the
         //      pair MLP's summed output (u1s: W3 Wu1_M of the GNN steps; w3 of the EPN steps), which brings the unscaled bits back.

@@ -485,7 +485,7 @@ __global__ __launch_bounds__(256) void k_lg_epn_static(LargeArgs L) {
 // tile).  Two partners per trip: the rows of partner j + 1 are fetched while partner j is in the matrix pipe, into the
 // other register set (no copies); the four accumulator chains of a partner (two column blocks x two row blocks) are issued
 // interleaved.
-// the sweep's kernel W2: three bf16 pieces per weight (f32-grade products on the bf16 matrix pipe, epnn_wave.hip.h: w16_split3), or
+// the sweep's kernel W2: three bf16 pieces per weight (f32-grade products on the bf16 matrix pipe, epnn_common.h: w16_split3), or
 // with -DEPNN_SWEEP_F32 (development builds, for comparison) the f32 fragments of v_mfma_f32_16x16x4_f32
 #ifdef EPNN_SWEEP_F32
 typedef float LgW2[2][8];
@@ -556,7 +556,7 @@ __device__ __forceinline__ void lg_sweep_rows(const float *Ns, const float *Ys, 
 }
 #else
 // The bf16 form (round 5).  Per partner and 32 atoms: 16 v_max (first layer), the three-piece split of the 16 activations per lane with
-// its remainders on the matrix pipe (w16_ident / w16_pack_hi, epnn_wave.hip.h: x - piece as D = C - I B, 2 MFMAs per 8 values and
+// its remainders on the matrix pipe (w16_ident / w16_pack_hi, epnn_common.h: x - piece as D = C - I B, 2 MFMAs per 8 values and
 // level instead of 8 v_and + 8 v_sub, the same pieces bit for bit; 24 v_perm + 8 MFMAs), 24 MFMAs of the Dense itself, and the
 // ReLU + sum of the partner BEFORE this one (16 v_max + 16 v_add) woven into those 24 MFMAs' gaps: a v_mfma_f32_16x16x32_bf16 holds
 // the SIMD's vector issue for 8 of its 16 cycles, so one or two independent vector instructions per gap cost nothing

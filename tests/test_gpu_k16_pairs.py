@@ -1,5 +1,5 @@
 """The K = 16 products of the fused kernels -- the xq block of every projection, the G tiles, the G term of both EPN block forms --
-issued as three v_mfma_f32_16x16x32_bf16 instead of six v_mfma_f32_16x16x16_bf16 (w16_mm_bfk16, epnn_wave.hip.h; the arithmetic
+issued as three v_mfma_f32_16x16x32_bf16 instead of six v_mfma_f32_16x16x16_bf16 (w16_mm_bfk16, epnn_common.h; the arithmetic
 and the layout: tests/test_k16_pairs_ref.py).
 
 Inputs under which a wrong pairing cannot hide: features are random float32 numbers with bits in every bf16 piece and the total
@@ -21,6 +21,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import micro_tool
 from conftest import ROOT, random_weights
 from test_gpu_epn_records import _cluster, _line, _pairs, _table_pairs
 
@@ -159,13 +160,12 @@ def test_charges_vs_float64_oracle(kind, nx, T):
 
 @pytest.mark.gpu
 def test_micro_paired_form_vs_f32_mfma():
-    """tools/micro/bf16x6 k16pairs issues the three instructions of w16_mm_bfk16 on its operand strings (w1 w2 | w3 w1; a = z3|z1,
-    b = a's upper half and z2).  On random operands whose three pieces are all non-zero the paired form's error against float64 is
+    """tools/micro/bf16x6 k16pairs runs w16_split3k16 and w16_mm_bfk16 themselves (epnn_common.h, under the library's flags) on
+    their operand strings (w1 w2 | w3 w1; a = z3|z1, b = a's upper half and z2).  On random operands whose three pieces are all non-zero the paired form's error against float64 is
     not above the f32 MFMA's on the same data (the bar the six-instruction form was held to, profiles/r05_micro_bf16x6.txt), and the
     operand's piece words are those of the v_and / v_sub split.  The end-to-end bound of 1e-5 does not see a third piece (truncating
     x to two pieces moves these charges by 1.5e-6 at most): this case does."""
-    exe = os.path.join(ROOT, "tools", "micro", "bf16x6")
-    out = subprocess.run([exe, "k16pairs"], check=True, capture_output=True, text=True, timeout=120).stdout
+    out = subprocess.run([micro_tool.bf16x6(), "k16pairs"], check=True, capture_output=True, text=True, timeout=120).stdout
     print(out)
     m = re.search(r"paired \(three K = 32 MFMAs\) ([0-9.e+-]+), six K = 16 MFMAs ([0-9.e+-]+), f32 MFMA ([0-9.e+-]+)", out)
     assert m, out

@@ -1208,18 +1208,15 @@ def test_more_atom_types_than_the_table_holds_falls_back_to_the_sweep(gpu_engine
 
 
 def test_bf16_split_forms_on_the_device():
-    """The arithmetic the Dense layers rest on, checked on the device itself (tools/micro/bf16x6, built by __graft_entry__.build):
-    the three-piece bf16 split with its remainders taken on the matrix pipe (x - piece as D = C - I B, both the K = 32 and the
+    """The arithmetic the Dense layers rest on, checked on the device itself (tools/micro/bf16x6, built by __graft_entry__.build
+    from the w16_* primitives of epnn_common.h under the library's flags): the three-piece bf16 split with its remainders taken on the matrix pipe (x - piece as D = C - I B, both the K = 32 and the
     K = 16 instruction) gives bit for bit the pieces of the v_and / v_sub form on 4 M float32 values of every kind, and the
     six-product sum of such pieces is at least as close to float64 as the f32 MFMA's own result.  (The kernels no longer issue
     either of the two: they take their remainders on the 4x4x4 instruction, which tests/test_gpu_rem4x4.py holds to the same bits.)"""
     import re
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "tools", "micro", "bf16x6")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.dirname(exe), "bf16x6"], check=True, capture_output=True, timeout=300)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300).stdout
+    import micro_tool
+    out = subprocess.run([micro_tool.bf16x6()], capture_output=True, text=True, timeout=300).stdout
     for k in (32, 16):
         m = re.search(r"MFMA remainders \(K = %d\): (\d+) of (\d+) piece words differ" % k, out)
         assert m, out[-2000:]

@@ -1,4 +1,4 @@
-"""The splits' remainders on v_mfma_f32_4x4x4_16b_bf16 (w16_ident / w16_rem, epnn_wave.hip.h; the operand placement without a GPU:
+"""The splits' remainders on v_mfma_f32_4x4x4_16b_bf16 (w16_ident / w16_rem, epnn_common.h; the operand placement without a GPU:
 tests/test_rem4x4_ref.py).
 
 Two parts.  The micro tool's sub-command (tools/micro/bf16x6 rem4x4): the piece words of a split with these remainders are those of the
@@ -21,6 +21,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import micro_tool
 from conftest import ROOT
 from test_gpu_f32_grade import CHARGES, K, TOL, _batch, _cluster, rms, three_pieces
 
@@ -124,8 +125,7 @@ def test_charges_within_float32_noise(name):
 
 @pytest.mark.gpu
 def test_micro_tool_exactness_and_layout():
-    exe = os.path.join(ROOT, "tools", "micro", "bf16x6")
-    out = subprocess.run([exe, "rem4x4"], check=True, capture_output=True, text=True, timeout=120).stdout
+    out = subprocess.run([micro_tool.bf16x6(), "rem4x4"], check=True, capture_output=True, text=True, timeout=120).stdout
     print(out)
     m = re.search(r"rem4x4 exactness: (\d+) of (\d+) piece words differ", out)
     assert m and int(m.group(1)) == 0 and int(m.group(2)) >= 6_000_000, out

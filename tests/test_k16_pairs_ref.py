@@ -1,4 +1,4 @@
-"""The K = 16 products of the fused kernels as three K = 32 MFMAs (w16_mm_bfk16, epnn_wave.hip.h), emulated in NumPy: no GPU.
+"""The K = 16 products of the fused kernels as three K = 32 MFMAs (w16_mm_bfk16, epnn_common.h), emulated in NumPy: no GPU.
 
 Both operands are split by truncation into three bf16 pieces, x = x1 + x2 + x3 exactly.  Two K = 16 operands side by side in four
 dwords are one K = 32 operand (lane group q: K slots 8q .. 8q + 3 from the first, 8q + 4 .. 8q + 7 from the second), so

@@ -1,4 +1,4 @@
-"""(no GPU) NumPy model of the splits' remainder instruction as the kernels use it (w16_ident / w16_rem, epnn_wave.hip.h):
+"""(no GPU) NumPy model of the splits' remainder instruction as the kernels use it (w16_ident / w16_rem, epnn_common.h):
 v_mfma_f32_4x4x4_16b_bf16 is sixteen independent 4x4x4 products D = C + A B.  Lane 4 b + i holds row i of block b's A and column i of
 its B, each as two dwords of bf16 pairs (K slots 0 | 1 and 2 | 3, even slot in the low half), and column i of its C / D as four
 registers (rows 0..3).  With A = -I per block (the dwords of w16_ident), a lane's four values as its accumulator and their packed upper

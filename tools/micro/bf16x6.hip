@@ -1,10 +1,16 @@
 // f32-grade products on the bf16 matrix pipe: C[16x16] = W[16x32] * Z[32x16] with both operands split EXACTLY into three bf16 pieces
 // (truncation: x = x1 + x2 + x3, 8 + 8 + 8 mantissa bits) and the six largest of the nine partial products summed in f32
-// (v_mfma_f32_16x16x32_bf16, 16 cycles each on gfx950 against 8 x 32 cycles of v_mfma_f32_16x16x4_f32 for the same K = 32).
+// (the 16x16x32 bf16 MFMA, w16_mfma_bf: 16 cycles each on gfx950 against 8 x 32 cycles of v_mfma_f32_16x16x4_f32 for the same K = 32).
 // Checks the operand layout (lane 16q + m: row / column m, K slots 8q .. 8q + 7 as four dwords of bf16 pairs) and the accuracy
 // against float64 and against the f32 MFMA, then times both forms with the split's VALU work included.
-//   hipcc --offload-arch=gfx950 -O3 -o bf16x6 bf16x6.hip && ./bf16x6            (./bf16x6 k16pairs: only the K = 16 pairing;
-//   ./bf16x6 rem4x4: the remainders on v_mfma_f32_4x4x4_16b_bf16 -- exactness, operand layout and cost beside the K = 16 form)
+// The split, the products and the ReLU forms are the library's own: the w16_* primitives of epnn_amd/csrc/epnn_common.h, compiled
+// here under the library's flags.  Only the forms the kernels no longer issue are defined in this file, as comparison arms.
+//   python3 ../../__graft_entry__.py --micro  (or make bf16x6: the same), then  ./bf16x6      (./bf16x6 k16pairs: only the K = 16
+//   pairing; ./bf16x6 rem4x4: the remainders on the 4x4x4 bf16 MFMA -- exactness, operand layout and cost beside the K = 16
+//   form; ./bf16x6 clamp: the sweep tile's two ReLU forms)
+// The library's flags switch packed f32 instructions off, so the timing arm "+ 8 v_pk_add_f32" is left out of that build; by hand:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffinite-math-only -fno-signed-zeros -mllvm -amdgpu-mfma-vgpr-form -Wno-unused-value \
+//         -DBF16X6_PK_ADD -I ../../epnn_amd/csrc -o bf16x6 bf16x6.hip
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -12,31 +18,15 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void split3(const float (&v)[8], u32x4 &p1, u32x4 &p2, u32x4 &p3) {
-    float r1[8], r2[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        r1[s] = v[s] - __uint_as_float(__float_as_uint(v[s]) & 0xffff0000u);
-        r2[s] = r1[s] - __uint_as_float(__float_as_uint(r1[s]) & 0xffff0000u);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        p1[j] = __builtin_amdgcn_perm(__float_as_uint(v[2 * j + 1]), __float_as_uint(v[2 * j]), 0x07060302u);
-        p2[j] = __builtin_amdgcn_perm(__float_as_uint(r1[2 * j + 1]), __float_as_uint(r1[2 * j]), 0x07060302u);
-        p3[j] = __builtin_amdgcn_perm(__float_as_uint(r2[2 * j + 1]), __float_as_uint(r2[2 * j]), 0x07060302u);
-    }
-}
+#include "epnn_common.h"
+
 // The same decomposition with round-to-nearest pieces: v_cvt_pk_bf16_f32 rounds and packs two values in one instruction and
 // v_dot2c_f32_bf16 takes a remainder straight from the packed pair (x - 1 * piece_lo - 0 * piece_hi: exact, the result is representable),
 // so no piece is ever expanded to float32 again: 7 instructions per two values instead of 11.
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2_ __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned cvt_pk(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_{lo, hi}, bf16x2));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
 }
 __device__ __forceinline__ float rem_lo(unsigned pk, float x) { return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk), __builtin_bit_cast(bf16x2, 0x8000bf80u), x, false); }
 __device__ __forceinline__ float rem_hi(unsigned pk, float x) { return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk), __builtin_bit_cast(bf16x2, 0xbf800000u), x, false); }
@@ -57,71 +47,40 @@ __device__ __forceinline__ void split3r(const float (&v)[8], u32x4 &p1, u32x4 &p
 // its values v[s]) and the values themselves as the accumulator (rows 4 q + r of row block rb = v[4 rb + r]), D = C + A B with
 // A[i][k] = -1 for k = 8 (i / 4) + 4 rb + i % 4 is x - x1 in place: 2 MFMAs per level and 8 values instead of 8 v_and + 8 v_sub.
 // (-1) * piece is exact, the other 31 products are zeros, the result is representable: exact if the pipe adds C unrounded.
-__device__ __forceinline__ f32x4 mm(u32x4 a, u32x4 b, f32x4 c);
 __device__ __forceinline__ void ident_operand(u32x4 (&A)[2]) {
     const int lane = threadIdx.x & 63, qa = lane >> 4, ma = lane & 15;
     for (int rb = 0; rb < 2; ++rb)
         for (int d = 0; d < 4; ++d)
             A[rb][d] = (qa == (ma >> 2) && d == 2 * rb + ((ma & 3) >> 1)) ? (0xbf80u << (16 * (ma & 1))) : 0u;
 }
-__device__ __forceinline__ u32x4 pack_hi(const f32x4 &lo, const f32x4 &hi) {
-    u32x4 p;
-    p[0] = __builtin_amdgcn_perm(__float_as_uint(lo[1]), __float_as_uint(lo[0]), 0x07060302u);
-    p[1] = __builtin_amdgcn_perm(__float_as_uint(lo[3]), __float_as_uint(lo[2]), 0x07060302u);
-    p[2] = __builtin_amdgcn_perm(__float_as_uint(hi[1]), __float_as_uint(hi[0]), 0x07060302u);
-    p[3] = __builtin_amdgcn_perm(__float_as_uint(hi[3]), __float_as_uint(hi[2]), 0x07060302u);
-    return p;
-}
 __device__ __forceinline__ void split3m(const float (&v)[8], const u32x4 (&A)[2], u32x4 &p1, u32x4 &p2, u32x4 &p3) {
     f32x4 x0 = {v[0], v[1], v[2], v[3]}, x1 = {v[4], v[5], v[6], v[7]};
-    p1 = pack_hi(x0, x1);
-    x0 = mm(A[0], p1, x0); x1 = mm(A[1], p1, x1);
-    p2 = pack_hi(x0, x1);
-    x0 = mm(A[0], p2, x0); x1 = mm(A[1], p2, x1);
-    p3 = pack_hi(x0, x1);
+    p1 = w16_pack_hi(x0, x1);
+    x0 = w16_mfma_bf(A[0], p1, x0); x1 = w16_mfma_bf(A[1], p1, x1);
+    p2 = w16_pack_hi(x0, x1);
+    x0 = w16_mfma_bf(A[0], p2, x0); x1 = w16_mfma_bf(A[1], p2, x1);
+    p3 = w16_pack_hi(x0, x1);
 }
 // Fourth form: the same remainders with v_mfma_f32_16x16x16_bf16 (K = 16: lane 16 q + m holds K slots 4 q .. 4 q + 3; a row block's
 // four values are two dwords of the packed piece, the -I operand is the same for both row blocks)
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32x2 pack_hi2(const f32x4 &v);
-__device__ __forceinline__ f32x4 mm16(u32x2 a, u32x2 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
+__device__ __forceinline__ f32x4 mm16(w16_u32x2 a, w16_u32x2 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(w16_s16x4, a), __builtin_bit_cast(w16_s16x4, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ void split3k(const float (&v)[8], u32x4 &p1, u32x4 &p2, u32x4 &p3) {
     const int lane = threadIdx.x & 63, qa = lane >> 4, ma = lane & 15;
-    u32x2 I;
+    w16_u32x2 I;
     for (int d = 0; d < 2; ++d) I[d] = (qa == (ma >> 2) && d == ((ma & 3) >> 1)) ? (0xbf80u << (16 * (ma & 1))) : 0u;
     f32x4 x0 = {v[0], v[1], v[2], v[3]}, x1 = {v[4], v[5], v[6], v[7]};
-    p1 = pack_hi(x0, x1);
-    x0 = mm16(I, u32x2{p1[0], p1[1]}, x0); x1 = mm16(I, u32x2{p1[2], p1[3]}, x1);
-    p2 = pack_hi(x0, x1);
-    x0 = mm16(I, u32x2{p2[0], p2[1]}, x0); x1 = mm16(I, u32x2{p2[2], p2[3]}, x1);
-    p3 = pack_hi(x0, x1);
+    p1 = w16_pack_hi(x0, x1);
+    x0 = mm16(I, w16_u32x2{p1[0], p1[1]}, x0); x1 = mm16(I, w16_u32x2{p1[2], p1[3]}, x1);
+    p2 = w16_pack_hi(x0, x1);
+    x0 = mm16(I, w16_u32x2{p2[0], p2[1]}, x0); x1 = mm16(I, w16_u32x2{p2[2], p2[3]}, x1);
+    p3 = w16_pack_hi(x0, x1);
 }
-// Fifth form (what the kernels issue, w16_ident / w16_rem in epnn_wave.hip.h): the same remainders with v_mfma_f32_4x4x4_16b_bf16,
-// sixteen independent 4x4x4 blocks.  Lane 4 b + i holds row i of block b's A, column i of its B (four K slots, two dwords) and column
-// i of its C / D (rows 0..3): with A = -I per block (-1 in K slot i) D[r] = C[r] - B[r] inside the lane, whatever the lane's values mean.
-__device__ __forceinline__ u32x2 ident4() {
-    const int i = threadIdx.x & 3;
-    u32x2 I;
-    for (int d = 0; d < 2; ++d) I[d] = (d == (i >> 1)) ? (0xbf80u << (16 * (i & 1))) : 0u;
-    return I;
-}
-__device__ __forceinline__ f32x4 mm4(u32x2 a, u32x2 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void split3q(const float (&v)[8], u32x4 &p1, u32x4 &p2, u32x4 &p3) {
-    const u32x2 I = ident4();
-    f32x4 x0 = {v[0], v[1], v[2], v[3]}, x1 = {v[4], v[5], v[6], v[7]};
-    p1 = pack_hi(x0, x1);
-    x0 = mm4(I, u32x2{p1[0], p1[1]}, x0); x1 = mm4(I, u32x2{p1[2], p1[3]}, x1);
-    p2 = pack_hi(x0, x1);
-    x0 = mm4(I, u32x2{p2[0], p2[1]}, x0); x1 = mm4(I, u32x2{p2[2], p2[3]}, x1);
-    p3 = pack_hi(x0, x1);
-}
+// SPLIT 0: the truncated pieces by v_and_b32 / v_sub_f32 (w16_split3_valu), 1: nearest / dot2c, 2: remainders on the K = 32 MFMA,
+// 3: on the K = 16 MFMA, 4: what the kernels issue (w16_split3: the remainders on the 4x4x4 bf16 MFMA, w16_ident / w16_rem)
 template <int SPLIT> __device__ __forceinline__ void split_any(const float (&v)[8], const u32x4 (&A)[2], u32x4 &p1, u32x4 &p2, u32x4 &p3) {
-    if (SPLIT == 4) split3q(v, p1, p2, p3); else if (SPLIT == 3) split3k(v, p1, p2, p3); else if (SPLIT == 2) split3m(v, A, p1, p2, p3); else if (SPLIT) split3r(v, p1, p2, p3); else split3(v, p1, p2, p3);
+    if (SPLIT == 4) w16_split3(v, p1, p2, p3); else if (SPLIT == 3) split3k(v, p1, p2, p3); else if (SPLIT == 2) split3m(v, A, p1, p2, p3); else if (SPLIT) split3r(v, p1, p2, p3); else w16_split3_valu(v, p1, p2, p3);
 }
 // exactness of a split: every lane splits 8 values, the host adds the pieces in float64
 template <int SPLIT> __global__ void k_exact(const float *x, unsigned *pieces) {
@@ -133,30 +92,26 @@ template <int SPLIT> __global__ void k_exact(const float *x, unsigned *pieces) {
     split_any<SPLIT>(v, A, p1, p2, p3);
     for (int j = 0; j < 4; ++j) { pieces[(t * 3 + 0) * 4 + j] = p1[j]; pieces[(t * 3 + 1) * 4 + j] = p2[j]; pieces[(t * 3 + 2) * 4 + j] = p3[j]; }
 }
-__device__ __forceinline__ f32x4 mm(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // W [16][32] row-major, Z [32][16] (k, n); out C [16][16]
 template <int SPLIT> __global__ void k_check(const float *W, const float *Z, float *C6, float *C32) {
     const int lane = threadIdx.x, q = lane >> 4, m = lane & 15;
     float w[8], z[8];
     for (int s = 0; s < 8; ++s) { w[s] = W[m * 32 + 8 * q + s]; z[s] = Z[(8 * q + s) * 16 + m]; }
-    u32x4 w1, w2, w3, z1, z2, z3;
-    split3(w, w1, w2, w3);                 // the weights' pieces come from the host: truncation in both forms
+    u32x4 wb[2][3], z1, z2, z3;            // (w16_mm_bf takes two row blocks: this product has one, the second is a copy nobody reads)
+    w16_split3_valu(w, wb[0][0], wb[0][1], wb[0][2]);      // the weights' pieces come from the host: truncation in both forms
+    for (int pc = 0; pc < 3; ++pc) wb[1][pc] = wb[0][pc];
     u32x4 A[2];
     ident_operand(A);
     split_any<SPLIT>(z, A, z1, z2, z3);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = mm(w1, z3, acc); acc = mm(w2, z2, acc); acc = mm(w3, z1, acc);
-    acc = mm(w1, z2, acc); acc = mm(w2, z1, acc); acc = mm(w1, z1, acc);
-    for (int r = 0; r < 4; ++r) C6[(4 * q + r) * 16 + m] = acc[r];
+    f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    w16_mm_bf(wb, z1, z2, z3, acc);
+    for (int r = 0; r < 4; ++r) C6[(4 * q + r) * 16 + m] = acc[0][r];
     f32x4 a32 = {0.f, 0.f, 0.f, 0.f};
     for (int k4 = 0; k4 < 8; ++k4)      // f32 MFMA: K = 4 per instruction, lane q supplies k = 4 k4 + q
         a32 = __builtin_amdgcn_mfma_f32_16x16x4f32(W[m * 32 + 4 * k4 + q], Z[(4 * k4 + q) * 16 + m], a32, 0, 0, 0);
     for (int r = 0; r < 4; ++r) C32[(4 * q + r) * 16 + m] = a32[r];
 }
 // timing: `tiles` dependent-free tiles per wave; MODE 0 = f32 MFMA (16 per tile: 2 row blocks x 8), 1 = bf16x6 incl. the split of z
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // RELU 1 / 2: the tile with the pair sweep's own element-wise work around the MFMAs -- z1 = relu((P + R) + G), S += relu(acc) -- and the
 // first ReLU as v_max_f32 (1) or as the output clamp of the add in front of it (2: min(max(a + b, 0), 1), one v_add_f32 ... clamp; the
 // operands here keep every sum below 1, so both forms give the same bits)
@@ -167,19 +122,26 @@ __device__ __forceinline__ void time_body(const float *src, float *dst, int tile
     u32x4 wb[2][3], A[2];
     ident_operand(A);
     for (int s = 0; s < 8; ++s) { z[s] = src[lane * 8 + s]; w32[0][s] = src[512 + lane * 8 + s]; w32[1][s] = src[1024 + lane * 8 + s]; }
-    for (int rb = 0; rb < 2; ++rb) split3(w32[rb], wb[rb][0], wb[rb][1], wb[rb][2]);
+    for (int rb = 0; rb < 2; ++rb) w16_split3_valu(w32[rb], wb[rb][0], wb[rb][1], wb[rb][2]);
     f32x4 S[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     for (int t = 0; t < tiles; ++t) {
         float zz[8];
+        if (RELU == 0) {
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            if (RELU == 0) zz[s] = fmaxf(z[s] + S[s >> 2][s & 3] * 1e-9f, 0.f);     // (a dependence on the last tile, like S += relu(acc))
-            else {
-                const float pre = (z[s] + S[s >> 2][s & 3] * 1e-9f) + 0.25f * w32[1][s];
-                zz[s] = RELU == 2 ? fminf(fmaxf(pre, 0.f), 1.f) : fmaxf(pre, 0.f);
+            for (int s = 0; s < 8; ++s) zz[s] = fmaxf(z[s] + S[s >> 2][s & 3] * 1e-9f, 0.f);     // (a dependence on the last tile, like S += relu(acc))
+        } else {
+#pragma unroll
+            for (int hb = 0; hb < 2; ++hb) {
+                f32x4 pre;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pre[r] = (z[4 * hb + r] + S[hb][r] * 1e-9f) + 0.25f * w32[1][4 * hb + r];
+                pre = RELU == 2 ? w16_clamp01(pre) : w16_relu(pre);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zz[4 * hb + r] = pre[r];
             }
         }
         if (EXTRA == 1) {
+#ifdef BF16X6_PK_ADD               // (inline assembly that the library's flags, packed f32 instructions off, do not assemble)
 #pragma unroll
             for (int s = 0; s < 8; s += 2) {
                 f32x2 a = {zz[s], zz[s + 1]}, b = {z[s], z[s + 1]}, c;
@@ -187,6 +149,7 @@ __device__ __forceinline__ void time_body(const float *src, float *dst, int tile
                 asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(a) : "v"(c), "v"(b));
                 zz[s] = a[0]; zz[s + 1] = a[1];
             }
+#endif
         } else if (EXTRA == 2) {
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
@@ -206,7 +169,7 @@ __device__ __forceinline__ void time_body(const float *src, float *dst, int tile
             for (int s = 0; s < 8; ++s) {
                 float c;
                 asm volatile("v_and_b32 %0, %1, %2" : "=v"(c) : "v"(zz[s]), "v"(z[s]));
-                asm volatile("v_perm_b32 %0, %1, %2, %3" : "=v"(zz[s]) : "v"(c), "v"(zz[s]), "v"(0x07060302u));
+                asm volatile("v_perm_b32 %0, %1, %2, %3" : "=v"(zz[s]) : "v"(c), "v"(zz[s]), "v"(0x05040100u));      // (any selector: the arm times the instruction)
             }
         }
         f32x4 d[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
@@ -218,16 +181,10 @@ __device__ __forceinline__ void time_body(const float *src, float *dst, int tile
         } else {
             u32x4 z1, z2, z3;
             split_any<SPLIT>(zz, A, z1, z2, z3);
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-                d[rb] = mm(wb[rb][0], z3, d[rb]); d[rb] = mm(wb[rb][1], z2, d[rb]); d[rb] = mm(wb[rb][2], z1, d[rb]);
-                d[rb] = mm(wb[rb][0], z2, d[rb]); d[rb] = mm(wb[rb][1], z1, d[rb]); d[rb] = mm(wb[rb][0], z1, d[rb]);
-            }
+            w16_mm_bf(wb, z1, z2, z3, d);
         }
         if (RELU == 0) { S[0] += d[0]; S[1] += d[1]; }
-        else
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { S[0][r] += fmaxf(d[0][r], 0.f); S[1][r] += fmaxf(d[1][r], 0.f); }
+        else { S[0] += w16_relu(d[0]); S[1] += w16_relu(d[1]); }
     }
     const size_t o = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
     for (int r = 0; r < 4; ++r) dst[o + r] = S[0][r], dst[o + 4 + r] = S[1][r];
@@ -249,7 +206,8 @@ __global__ __launch_bounds__(512) void k_time_wg(const float *src, float *dst, i
 __global__ void k_probe4(const float *x, float *y) {
     const int lane = threadIdx.x;
     f32x4 v = {x[lane * 4], x[lane * 4 + 1], x[lane * 4 + 2], x[lane * 4 + 3]};
-    v = mm4(ident4(), pack_hi2(v), v);
+    const w16_u32x2 p = w16_pack_hi2(v);
+    v = w16_rem(w16_ident(), p[0], p[1], v);
     for (int r = 0; r < 4; ++r) y[lane * 4 + r] = v[r];
 }
 // Back-to-back MFMAs of one kind, n x 32 per wavefront: INDEP 1 = eight accumulators in turn (no instruction waits for the one before
@@ -266,9 +224,9 @@ __global__ __launch_bounds__(512) void k_rate(const float *src, float *dst, int 
 #pragma unroll
         for (int k = 0; k < 32; ++k) {
             f32x4 &c = acc[INDEP ? k & 7 : 0];
-            if (KIND == 0) c = mm4(u32x2{a[0], a[1]}, u32x2{b[0], b[1]}, c);
-            else if (KIND == 1) c = mm16(u32x2{a[0], a[1]}, u32x2{b[0], b[1]}, c);
-            else c = mm(a, b, c);
+            if (KIND == 0) c = w16_rem(w16_u32x2{a[0], a[1]}, b[0], b[1], c);
+            else if (KIND == 1) c = mm16(w16_u32x2{a[0], a[1]}, w16_u32x2{b[0], b[1]}, c);
+            else c = w16_mfma_bf(a, b, c);
         }
     }
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -279,60 +237,33 @@ __global__ __launch_bounds__(512) void k_rate(const float *src, float *dst, int 
     const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (lane == 0) { cyc[2 * w] = t1 - t0; cyc[2 * w + 1] = r1 - r0; }
 }
-// The K = 16 products of the fused kernels (w16_mm_bfk16, epnn_wave.hip.h): C[16x16] = W[16x16] * Z[16x16], six partial products.
-// Six-instruction form (what the kernels issued before): six v_mfma_f32_16x16x16_bf16.  Paired form, instruction for instruction
-// and register for register what w16_mm_bfk16 issues: two K = 16 operands side by side in four consecutive registers are one
-// K = 32 operand, so three v_mfma_f32_16x16x32_bf16 take the same six products two at a time --
+// The K = 16 products of the fused kernels (w16_mm_bfk16, epnn_common.h): C[16x16] = W[16x16] * Z[16x16], six partial products.
+// Six-instruction form (what the kernels issued before): six v_mfma_f32_16x16x16_bf16.  Paired form: w16_split3k16 and
+// w16_mm_bfk16 themselves -- two K = 16 operands side by side in four consecutive registers are one K = 32 operand, so three
+// 16x16x32 bf16 MFMAs take the same six products two at a time --
 //     (w1|w2) . (z3|z1),   (w3|w1) . (z1|z2),   (w1|w2) . (z1|z2)
 // with the kernel's row block as the two tuples w1 w2 | w3 w1 (the host's pack) and the activation as a = z3|z1 plus z2, b = z1|z2
 // being a's upper half and z2 (W16K16).  Every block takes its own 16x16 pair of operands; `zs` receives the six operand dwords
 // a, z2 (MFMA-remainder split), `zp` the pieces of the v_and / v_sub form in the same order.
-__device__ __forceinline__ void split3k16_valu(const float (&v)[4], u32x2 &p1, u32x2 &p2, u32x2 &p3) {
-    float r1[4], r2[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        r1[s] = v[s] - __uint_as_float(__float_as_uint(v[s]) & 0xffff0000u);
-        r2[s] = r1[s] - __uint_as_float(__float_as_uint(r1[s]) & 0xffff0000u);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        p1[j] = __builtin_amdgcn_perm(__float_as_uint(v[2 * j + 1]), __float_as_uint(v[2 * j]), 0x07060302u);
-        p2[j] = __builtin_amdgcn_perm(__float_as_uint(r1[2 * j + 1]), __float_as_uint(r1[2 * j]), 0x07060302u);
-        p3[j] = __builtin_amdgcn_perm(__float_as_uint(r2[2 * j + 1]), __float_as_uint(r2[2 * j]), 0x07060302u);
-    }
-}
-__device__ __forceinline__ u32x2 pack_hi2(const f32x4 &v) {
-    return u32x2{__builtin_amdgcn_perm(__float_as_uint(v[1]), __float_as_uint(v[0]), 0x07060302u),
-                 __builtin_amdgcn_perm(__float_as_uint(v[3]), __float_as_uint(v[2]), 0x07060302u)};
-}
 __global__ void k_check16(const float *Wa, const float *Za, float *C6, float *C3, float *C32, unsigned *zs, unsigned *zp) {
     const int lane = threadIdx.x, q = lane >> 4, m = lane & 15, t = blockIdx.x;
     const float *W = Wa + t * 256, *Z = Za + t * 256;
-    float w[4], z[4];
-    for (int s = 0; s < 4; ++s) { w[s] = W[m * 16 + 4 * q + s]; z[s] = Z[(4 * q + s) * 16 + m]; }
-    u32x2 w1, w2, w3, y1, y2, y3;
-    split3k16_valu(w, w1, w2, w3);         // the weights' pieces come from the host: truncation
-    split3k16_valu(z, y1, y2, y3);
-    // the activation's split as the kernels do it: one remainder MFMA per level, the pieces in the order z3 z1 z2
-    const int qa = lane >> 4, ma = lane & 15;
-    u32x2 I;
-    for (int d = 0; d < 2; ++d) I[d] = (qa == (ma >> 2) && d == ((ma & 3) >> 1)) ? (0xbf80u << (16 * (ma & 1))) : 0u;
-    f32x4 x = {z[0], z[1], z[2], z[3]};
-    const u32x2 z1 = pack_hi2(x);
-    x = mm16(I, z1, x);
-    const u32x2 z2 = pack_hi2(x);
-    x = mm16(I, z2, x);
-    const u32x2 z3 = pack_hi2(x);
-    const u32x4 za = {z3[0], z3[1], z1[0], z1[1]};                        // W16K16::a
-    const u32x4 zb = {za[2], za[3], z2[0], z2[1]};                        // put together where it is used
-    const u32x4 w12 = {w1[0], w1[1], w2[0], w2[1]}, w31 = {w3[0], w3[1], w1[0], w1[1]};      // the pack's two halves
+    f32x4 w, x;
+    for (int s = 0; s < 4; ++s) { w[s] = W[m * 16 + 4 * q + s]; x[s] = Z[(4 * q + s) * 16 + m]; }
+    w16_u32x2 w1, w2, w3, y1, y2, y3;
+    w16_split3k16_valu(w, w1, w2, w3);     // the weights' pieces come from the host: truncation
+    w16_split3k16_valu(x, y1, y2, y3);
+    const W16K16 z = w16_split3k16(x);     // the activation's split as the kernels do it: a = z3|z1, and z2
+    const w16_u32x2 z3 = {z.a[0], z.a[1]}, z1 = {z.a[2], z.a[3]}, z2 = z.z2;
     f32x4 a6 = {0.f, 0.f, 0.f, 0.f};
     a6 = mm16(w1, z3, a6); a6 = mm16(w2, z2, a6); a6 = mm16(w3, z1, a6);
     a6 = mm16(w1, z2, a6); a6 = mm16(w2, z1, a6); a6 = mm16(w1, z1, a6);
-    f32x4 a3 = {0.f, 0.f, 0.f, 0.f};
-    a3 = mm(w12, za, a3);
-    a3 = mm(w31, zb, a3);
-    a3 = mm(w12, zb, a3);
+    // (w16_mm_bfk16 takes two row blocks: this product has one, the second is a copy nobody reads)
+    const u32x4 w12 = {w1[0], w1[1], w2[0], w2[1]}, w31 = {w3[0], w3[1], w1[0], w1[1]};      // the pack's two halves
+    const u32x4 wk[2][2] = {{w12, w31}, {w12, w31}};
+    f32x4 d3[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    w16_mm_bfk16(wk, z, d3);
+    const f32x4 a3 = d3[0];
     f32x4 a32 = {0.f, 0.f, 0.f, 0.f};
     for (int k4 = 0; k4 < 4; ++k4)
         a32 = __builtin_amdgcn_mfma_f32_16x16x4f32(W[m * 16 + 4 * k4 + q], Z[(4 * k4 + q) * 16 + m], a32, 0, 0, 0);
@@ -342,7 +273,7 @@ __global__ void k_check16(const float *Wa, const float *Za, float *C6, float *C3
         C32[t * 256 + (4 * q + r) * 16 + m] = a32[r];
     }
     const unsigned yy[6] = {y3[0], y3[1], y1[0], y1[1], y2[0], y2[1]};
-    const unsigned zz[6] = {za[0], za[1], za[2], za[3], z2[0], z2[1]};
+    const unsigned zz[6] = {z.a[0], z.a[1], z.a[2], z.a[3], z.z2[0], z.z2[1]};
     for (int j = 0; j < 6; ++j) { zs[(t * 64 + lane) * 6 + j] = zz[j]; zp[(t * 64 + lane) * 6 + j] = yy[j]; }
 }
 static bool three_pieces(float v) {        // all three truncated bf16 pieces of v are non-zero
@@ -446,7 +377,7 @@ static long not_reproduced(const std::vector<unsigned> &pc, const std::vector<fl
     return bad;
 }
 static double median(std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; }
-// ./bf16x6 rem4x4: the split's remainders on v_mfma_f32_4x4x4_16b_bf16 (tests/test_gpu_rem4x4.py reads the first two parts)
+// ./bf16x6 rem4x4: the split's remainders on the 4x4x4 bf16 MFMA (tests/test_gpu_rem4x4.py reads the first two parts)
 static int check_rem4x4() {
     int fails = 0;
     {   // 1. exactness, on the default run's 2^22 values
@@ -512,7 +443,7 @@ static int check_rem4x4() {
             ticks = median(t); ghz = median(g);
             return true;
         };
-        const char *kinds[3] = {"v_mfma_f32_4x4x4_16b_bf16", "v_mfma_f32_16x16x16_bf16 ", "v_mfma_f32_16x16x32_bf16 "};
+        const char *kinds[3] = {"v_mfma 4x4x4 (16b bf16)  ", "v_mfma_f32_16x16x16_bf16 ", "v_mfma 16x16x32 (bf16)   "};
         const int n = 4000;
         for (int kind = 0; kind < 3; ++kind) {
             double t[2], g[2];
@@ -530,7 +461,7 @@ static int check_rem4x4() {
             printf("rem4x4 cost: %s back to back, one wavefront per SIMD: %.2f cycles per instruction on eight accumulators in turn, %.2f on one accumulator (clock %.3f GHz)\n",
                    kinds[kind], t[1], t[0], g[1]);
         }
-        const char *splits[3] = {"v_and / v_sub            ", "v_mfma_f32_16x16x16_bf16 ", "v_mfma_f32_4x4x4_16b_bf16"};
+        const char *splits[3] = {"v_and / v_sub            ", "v_mfma_f32_16x16x16_bf16 ", "v_mfma 4x4x4 (16b bf16)  "};
         const int tiles = 4000;
         for (int sp = 0; sp < 3; ++sp) {
             double t[2], g[2];
@@ -642,6 +573,9 @@ int main(int argc, char **argv) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     const char *names[10] = {"f32 MFMA     ", "bf16x6 + split", "  + 8 v_pk_add_f32 (16 adds)", "  + 16 v_add_f32", "  + 16 v_max_f32", "  + 8 v_and_b32 + 8 v_perm_b32", "bf16x6 + split by v_cvt_pk_bf16_f32 / v_dot2c_f32_bf16", "bf16x6 + split with the remainders by MFMA (16 per tile)", "bf16x6 + split with the remainders by v_mfma_f32_16x16x16_bf16", ""};
     for (int mode = 0; mode < 9; ++mode) {
+#ifndef BF16X6_PK_ADD
+        if (mode == 2) { printf("%s: not built (packed f32 instructions are off in the library's flags: see the head of this file)\n", names[mode]); continue; }
+#endif
         for (int rep = 0; rep < 2; ++rep) {
             hipEventRecord(e0);
             if (mode == 0) hipLaunchKernelGGL(k_time<0>, dim3(blocks), dim3(64), 0, 0, src, dst, tiles);
