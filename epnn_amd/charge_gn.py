@@ -438,6 +438,21 @@ class EPNNModel(_Stack):
         return self._eng().charges_jvp_xyz_multi(offsets, xyz, x, Q, self.natom if N is None else N, v=v, strain=strain, dQ=dQ,
                                                  box=box, cell=cell)
 
+    def charges_vjp_xyz_multi(self, offsets, xyz, x, Q, g, N=None, box=None, cell=None, strain=False):
+        """charges_vjp_xyz for K cotangents g (K, A) in one pass: (q (A,), gxyz (K, A, 3)), with strain=True also gstrain
+        (K, B, 3, 3); row k has the bits of the single call with g[k] on the pair-list path.  K is 1..16.  The forward and the
+        primal half of the backward are paid once.  N defaults to the model's natom; box and cell as in predict_xyz."""
+        return self._eng().charges_vjp_xyz_multi(offsets, xyz, x, Q, g, self.natom if N is None else N, box=box, cell=cell, strain=strain)
+
+    def dipole_xyz(self, offsets, xyz, x, Q, N=None, origin=None):
+        """Dipoles and atomic polar tensors of open molecules in one call: (q (A,), mu (B, 3) float64, apt (A, 3, 3) float32) with
+        mu_b = sum_k q_k (r_k - o_b) and apt[i][a][b] = d mu_a / d r_ib = q_i delta_ab + sum_k (r_ka - o_a) dq_k/dr_ib, from three
+        cotangents g_a[k] = float32(r_ka - o_a) (Engine.dipole_xyz).  origin (3,) or (B, 3); by default each molecule's unweighted
+        centroid, taken in float64 and held fixed.  In exact arithmetic sum_i apt[i] = Q_b I, and the APT does not depend on the
+        origin, because the model conserves charge under translation.  Open molecules only: a cell's dipole is not a function of
+        the positions.  N defaults to the model's natom."""
+        return self._eng().dipole_xyz(offsets, xyz, x, Q, self.natom if N is None else N, origin=origin)
+
     def charge_strain_response(self, offsets, xyz, x, Q, N=None, box=None, cell=None):
         """(q (A,), dq_deps (A, 3, 3)): the response of every charge to a homogeneous strain of coordinates and cell, from one
         K = 6 forward-mode call on the symmetric unit strains (e_a e_b^T + e_b e_a^T) / 2, a <= b, filled in symmetrically:

@@ -30,10 +30,11 @@ struct GlGrad {
 };
 
 // spans: the entry's own staged inputs (r.c.d_extra); more[k] bytes: buffers of the entry alone (r.o_more[k]; the first one follows
-// `out` directly); in_cap: epnn_last_stats counts the staged inputs with their buffer's capacity, not with this call's bytes.
+// `out` directly), more_pairs[k]: further bytes of buffer k per listed pair (P1 of them: the count is not known before the call);
+// in_cap: epnn_last_stats counts the staged inputs with their buffer's capacity, not with this call's bytes.
 static int gl_grad_forward(epnn_handle *h, GradLarge *gl, const char *where, int B, int N, const int32_t *offsets, const float *xyz,
                            const float *x, const float *Q, const HostGeo &geo, const GlSpan *spans, int n_spans, const size_t *more, int n_more,
-                           bool in_cap, GlGrad &r) {
+                           bool in_cap, GlGrad &r, const size_t *more_pairs = nullptr) {
     const int T = h->cfg.T, A = offsets[B];
     GlCall &c = r.c;
     if (gl_call_count(h, gl, where, B, N, offsets, xyz, x, Q, geo, spans, n_spans, c)) return 1;
@@ -44,7 +45,7 @@ static int gl_grad_forward(epnn_handle *h, GradLarge *gl, const char *where, int
                  o_slotP = c.place(SL * GL_H * 4), o_slotR = c.place(SL * GL_H * 4), o_slotq = c.place(SL * 4), o_gE = c.place(P1 * GL_E * 4),
                  o_gh = c.place(rowE), o_ghp = c.place(rowE), o_slotx = c.place(SL * 72), o_share = c.place((size_t)A * 48),
                  o_out = c.place(((size_t)A * 5 + 1 + (size_t)B * 9) * 4);
-    for (int k = 0; k < n_more; ++k) r.o_more[k] = c.place(more[k]);
+    for (int k = 0; k < n_more; ++k) r.o_more[k] = c.place(more[k] + (more_pairs ? more_pairs[k] * P1 : 0));
     if (gl_call_fill(h, gl, c, in_cap ? gl->in.cap : c.in_total)) return 1;
     r.o_slotx = o_slotx; r.o_share = o_share;
     r.hck = c.fp(o_h); r.Sck = c.fp(o_S); r.qck = c.fp(o_q); r.dP = c.fp(o_P); r.dR = c.fp(o_R); r.Yb = c.fp(o_Yb); r.Yc = c.fp(o_Yc);

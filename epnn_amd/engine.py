@@ -510,6 +510,59 @@ class Engine:
                                                        opt(v), opt(strain), opt(dQ), fptr(q), fptr(tq)), self.lib)
         return q, tq
 
+    def charges_vjp_xyz_multi(self, offsets, xyz, x, Q, g, N, box=None, cell=None, strain=False):
+        """Reverse mode for K cotangents in one pass (epnn_charges_vjp_multi_xyz_cell): g (K, A) -> (q (A,), gxyz (K, A, 3)), with
+        strain=True also gstrain (K, B, 3, 3); row k has the bits charges_vjp_xyz gives for g[k] on "grad_path" 2, whatever K and
+        the other rows are.  K is 1..16.  The call always runs from the pair list; the set-up, the pair list, the checkpointed
+        forward and every primal statement of the backward run once.  box (3,) or (B, 3) is taken as its diagonal cell; cell
+        (3, 3) or (B, 3, 3); neither: open molecules (with strain=True an all-zero cell, as in charges_vjp_xyz)."""
+        _one_periodic_argument(box, cell)
+        offsets, xyz, x, Q, _, B, A = self._flat_batch("charges_vjp_xyz_multi: array shapes do not match offsets", offsets, xyz, x, Q)
+        g = _f32(g)
+        if g.ndim != 2 or g.shape[1] != A:
+            raise ValueError(f"charges_vjp_xyz_multi: g must have shape (K, {A}), got {g.shape}")
+        K = g.shape[0]
+        _, rows = _geometry(box, np.zeros((3, 3), np.float32) if strain and cell is None and box is None else cell, B, cells_only=True)
+        q = np.empty((A,), dtype=np.float32)
+        gxyz = np.empty((max(K, 1), A, 3), dtype=np.float32)
+        gs = np.empty((max(K, 1), B, 3, 3), dtype=np.float32) if strain else None
+        opt = lambda a: None if a is None else fptr(a)
+        check(self.lib.epnn_charges_vjp_multi_xyz_cell(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), opt(rows), int(K),
+                                                       fptr(g), fptr(q), fptr(gxyz), opt(gs)), self.lib)
+        return (q, gxyz, gs) if strain else (q, gxyz)
+
+    def dipole_xyz(self, offsets, xyz, x, Q, N, origin=None):
+        """Dipoles and atomic polar tensors of open molecules from one K = 3 call of charges_vjp_xyz_multi:
+        (q (A,), mu (B, 3) float64, apt (A, 3, 3) float32).  With o_b the origin of molecule b -- origin (3,) or (B, 3); by default
+        the molecule's unweighted centroid, taken in float64 and treated as a fixed point --
+            mu_b        = sum_k q_k (r_k - o_b)                         in float64,
+            seeds       g_a[k] = float32(r_ka - o_a),   a = x, y, z,
+            apt[i][a][b] = d mu_a / d r_ib = q_i delta_ab + gxyz[a][i][b]    (one float32 add on the diagonal).
+        In exact arithmetic sum_i apt[i] = Q_b I over a molecule's atoms (moving the whole molecule moves the dipole by Q_b times
+        the displacement), and the APT does not depend on o: the model conserves charge under translation, sum_k dq_k/dr_ib = 0, so
+        a shift of o adds nothing.  box / cell are not arguments: a cell's dipole is not a function of the positions."""
+        offsets, xyz, x, Q, _, B, A = self._flat_batch("dipole_xyz: array shapes do not match offsets", offsets, xyz, x, Q)
+        r = xyz.astype(np.float64)
+        counts = np.diff(offsets)
+        mol = np.repeat(np.arange(B), counts)
+        if origin is None:
+            o = np.stack([r[offsets[b]:offsets[b + 1]].mean(axis=0) for b in range(B)])
+        else:
+            o = np.asarray(origin, dtype=np.float64)
+            if o.shape == (3,):
+                o = np.tile(o, (B, 1))
+            if o.shape != (B, 3):
+                raise ValueError(f"dipole_xyz: origin must have shape (3,) or ({B}, 3), got {o.shape}")
+        rel = r - o[mol]
+        g = np.ascontiguousarray(rel.T.astype(np.float32))
+        q, gxyz = self.charges_vjp_xyz_multi(offsets, xyz, x, Q, g, N)
+        mu = np.stack([(q[offsets[b]:offsets[b + 1]].astype(np.float64)[:, None] * rel[offsets[b]:offsets[b + 1]]).sum(axis=0)
+                       for b in range(B)])
+        apt = np.ascontiguousarray(gxyz.transpose(1, 0, 2))
+        for a in range(3):
+            apt[:, a, a] += q
+        return q, mu, apt
+
     def coulomb_xyz(self, offsets, xyz, x, Q, N, ke=KE_EV_ANGSTROM, alpha=0.0, parts=False):
         """Electrostatics of the predicted charges in one call (epnn_coulomb_xyz): flat batch -> (q (A,), phi (A,), E (B,) float64,
         F (A, 3)) with phi_i = ke sum_{j != i} q_j kappa(D_ij) = dE/dq_i, E = 1/2 sum_i q_i phi_i per molecule and F = -dE/dxyz in

@@ -405,6 +405,38 @@ int epnn_charges_jvp_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offse
 int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                     const float *cell, int K, const float *vxyz, const float *vstrain, const float *vQ, float *q_out,
                                     float *tq_out);
+/* ---- reverse mode, K cotangents in one pass: epnn_charges_vjp_xyz_cell with K seeds beside one primal.  K is in 1..16 (any other
+ * value is refused by name; the handle stays usable).  g[K][A]: the cotangents.  q_out[A] is computed once; gxyz_out[K][A][3] and
+ * gstrain_out[K][B][3][3] (or NULL): row k is, word for word, gxyz_out / gstrain_out of epnn_charges_vjp_xyz_cell on "grad_path" 2
+ * called with g[k].  cell [B][3][3] has the meaning and the checks of epnn_charges_vjp_xyz_cell; NULL: open molecules.  Three seeds
+ * g = x, y, z (coordinates relative to a fixed origin) give the charge-flux part of the atomic polar tensor,
+ *     d mu_a / d r_ib = q_i delta_ab + sum_k r_ka dq_k/dr_ib,        mu = sum_k q_k r_k,
+ * in one call (engine.py dipole_xyz); K potentials give K force sets.
+ * Contract: that of the pair-list path of epnn_charges_vjp_xyz: the entry always runs from the pair list, whatever "grad_path"
+ * says; works on a handle that never trained, uses the current weights, leaves weights, gradients, Adam state and step count
+ * untouched, waits first for a "train_async" step in flight and finishes a forward begun with epnn_forward_xyz_begin, as the single
+ * entry does; refuses by name update layers other than [32, 32], a partitioned handle, a fused-only handle, bad offsets, a molecule
+ * that does not fit N, a null required pointer, coincident atoms or images (the handle stays usable); h_dim below 48 runs
+ * zero-padded; no float atomics and every sum in a fixed order; a molecule's rows do not depend on the rest of the batch at the
+ * same N.
+ * Bits: q_out has the bits of epnn_charges_vjp_xyz_cell on "grad_path" 2, and row k the bits that entry gives for g[k] alone,
+ * whatever K, the row's position and the other rows are; gstrain_out = NULL changes no other bit.  No cotangent statement reads
+ * another cotangent, and each is the fmaf chain or MFMA sequence of the single entry's backward kernel: accumulators from zero, the
+ * same pieces and slot order.
+ * Cost: the front-end, the pair list, the checkpointed forward, the primal projections and every pair's and atom's primal
+ * pre-activations and masks run once; the two all-pairs backward sweeps carry the cotangents in chunks of 4, 2 or 1 (K = 7 is
+ * 4 + 2 + 1) and each chunk's launch repeats the 16 primal MFMAs per partner: sum over chunks of 2 (16 + 16 kc) MFMAs per partner and
+ * tile against 64 K for K single calls (profiles/r24_vjp_multi.txt).  Device scratch: the single entry's rows (its backward rows
+ * stay unused) plus K copies of the cotangent rows gq, gh, ghp, dS, the sweeps' pieces, the slots, gE, the coordinate slots, the
+ * strain shares and the outputs; with `pieces` as at epnn_charges_vjp_xyz,
+ *     bytes = A (1324 + 4 nx + 324 T + 257 pieces + K (580 + 256 pieces)) + (1116 + 848 K) listed pairs + 36 K B + 13 KB
+ *                                                                                         (+- 256 per buffer of rounding)
+ * with the staged inputs counted by this call's bytes.  Shared with the other pair-list calls: the handle keeps the scratch of its
+ * largest call.  After a call epnn_last_stats gives out[0] = listed pairs, out[1] = 0, out[2] = bytes of device scratch the call used.
+ * Out of scope: a dense-path twin; dF/dQ, the adjoint of the JVP's vQ; box rows (a box is its diagonal cell, whose bits are the box
+ * entry's). */
+int epnn_charges_vjp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                    const float *cell, int K, const float *g, float *q_out, float *gxyz_out, float *gstrain_out);
 /* ---- electrostatics of the predicted charges in one call: charges, potential, Coulomb energy and total forces.  Replaces the three
  * steps of INTEGRATION.md, "Forces from the charges" (a forward, the caller's own all-pairs sum for g = dE/dq, a gradient call with
  * a second forward inside) for the potential most used with a charge model.  Per molecule b of the flat batch, over its real atoms
