@@ -85,6 +85,11 @@ SIGNATURES = {
                                         C.POINTER(C.c_double), _fp, _fp, _fp]),
     "epnn_coulomb_xyz_cell_excl": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), C.c_double, C.c_double,
                                              C.c_int64, _ip, _ip, _fp, _fp, _fp, C.POINTER(C.c_double), _fp, _fp, _fp, _fp, _fp, _fp]),
+    "epnn_coulomb_xyz_site": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, C.c_int, C.c_int64,
+                                        _ip, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), _fp, _fp, _fp]),
+    "epnn_coulomb_xyz_cell_site": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                             _fp, _fp, _fp, C.c_int, C.c_int64, _ip, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), _fp, _fp, _fp,
+                                             _fp, _fp, _fp]),
     "epnn_ewald_slab_params": (C.c_int, [_fp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "epnn_coulomb_xyz_slab": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), C.c_double, C.c_double,
                                         C.c_int64, _ip, _ip, _fp, _fp, _fp, C.POINTER(C.c_double), _fp, _fp, _fp]),

@@ -424,6 +424,22 @@ class EPNNModel(_Stack):
         return self._eng().coulomb_xyz_excl(offsets, xyz, x, Q, self.natom if N is None else N, ke=ke, alpha=alpha, parts=parts,
                                             exclusions=exclusions)
 
+    def coulomb_xyz_site(self, offsets, xyz, x, Q, N=None, ke=KE_EV_ANGSTROM, alpha=0.0, sigma=None, chi=None, hardness=None,
+                         self_energy=True, exclusions=None, parts=False):
+        """The energy of a charge-model potential in one call: per-atom Gaussian widths sigma, electronegativities chi, hardnesses J
+        (arrays (A,); engine.per_element makes them from a table by element) and the Gaussians' self-energy: (q, phi, mu, E, F), mu =
+        dE/dq = chi + J q + phi; with parts=True also ffix and fq.  Engine.coulomb_xyz_site has the formulas.  N defaults to natom."""
+        return self._eng().coulomb_xyz_site(offsets, xyz, x, Q, self.natom if N is None else N, ke=ke, alpha=alpha, sigma=sigma, chi=chi,
+                                            hardness=hardness, self_energy=self_energy, exclusions=exclusions, parts=parts)
+
+    def coulomb_xyz_cell_site(self, offsets, xyz, x, Q, N=None, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                              sigma=None, chi=None, hardness=None, self_energy=True, exclusions=None, parts=False, strain=False):
+        """coulomb_xyz_site in fully periodic cells, by an Ewald sum: (q, phi, mu, E, F[, gstrain][, parts]).  A cell whose widest
+        Gaussian does not fit the Ewald split (sigma_max > 1 / (2 beta)) is refused by name."""
+        return self._eng().coulomb_xyz_cell_site(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke, alpha=alpha,
+                                                 tol=tol, ewald=ewald, sigma=sigma, chi=chi, hardness=hardness, self_energy=self_energy,
+                                                 exclusions=exclusions, parts=parts, strain=strain)
+
     def coulomb_xyz_cell_excl(self, offsets, xyz, x, Q, N=None, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
                               parts=False, strain=False, exclusions=None):
         """coulomb_xyz_cell with bonded exclusions and pair scaling: the nearest image of every listed pair counts with weight scale.

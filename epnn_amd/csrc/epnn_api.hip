@@ -504,4 +504,5 @@ extern "C" int epnn_set_option(epnn_handle *h, const char *name, int value) {
 #include "epnn_api_coulomb_cell.hip.h"
 #include "epnn_api_coulomb_slab.hip.h"
 #include "epnn_api_coulomb_run.hip.h"
+#include "epnn_api_site.hip.h"
 #include "epnn_api_vjp_multi.hip.h"

@@ -103,20 +103,73 @@ static int excl_build(const char *name, int B, const int32_t *offsets, int64_t n
     return 0;
 }
 // the correction's launch: one lane per atom (k_cl_excl), on the stream, behind the sweep; d_cells: the periodic entries' cells, or NULL
+// d_site: the site entries' per-atom rows when they carry widths (the pair term's third mode), or NULL
 static void excl_launch(epnn_handle *h, const GlCall &c, const char *d_csr, const ExclCsr &ex, const float *q_dev, const EpnnCell *d_cells,
-                        double alpha, double *xpart, int *hit) {
+                        const float4 *d_site, double alpha, double *xpart, int *hit) {
     const int A = ex.A;
     const int *row_off = reinterpret_cast<const int *>(d_csr), *partner = reinterpret_cast<const int *>(d_csr + ex.o_partner());
     const float *factor = reinterpret_cast<const float *>(d_csr + ex.o_factor());
-    auto *kern = d_cells ? (alpha > 0.0 ? k_cl_excl<true, true> : k_cl_excl<false, true>)
-                         : (alpha > 0.0 ? k_cl_excl<true, false> : k_cl_excl<false, false>);
+    auto *kern = d_cells ? (d_site ? k_cl_excl<CL_WIDTHS, true> : alpha > 0.0 ? k_cl_excl<CL_ERF, true> : k_cl_excl<CL_BARE, true>)
+                         : (d_site ? k_cl_excl<CL_WIDTHS, false> : alpha > 0.0 ? k_cl_excl<CL_ERF, false> : k_cl_excl<CL_BARE, false>);
     hipLaunchKernelGGL(kern, dim3((unsigned)((A + 63) / 64)), dim3(64), 0, h->stream, A, c.d_molof, c.d_xyz, q_dev, row_off, partner, factor,
-                       d_cells, (float)alpha, xpart, hit);
+                       d_cells, d_site, (float)alpha, xpart, hit);
 }
 
 // what an _excl entry adds to its plain entry's arguments, and the outputs of the six entries (the strain rows: the entries with strain)
 struct ExclArgs { int64_t npairs; const int32_t *i, *j; const float *scale; };
-struct CoulombOut { float *q, *phi; double *e; float *f, *ffix, *fq, *gs, *gs_fix, *gs_q; };
+struct CoulombOut { float *q, *phi; double *e; float *f, *ffix, *fq, *gs, *gs_fix, *gs_q, *mu; };      // mu: the site entries' dE/dq, may be NULL
+
+// ---- per-atom Gaussian widths, self-energy and on-site terms (epnn_coulomb_xyz_site, epnn_coulomb_xyz_cell_site): one float4 per atom,
+// (w = 2 sigma^2, chi, J, gamma_ii), made in float64 and rounded once, staged as one more span.  widths: sigma was given and the pair
+// terms take gamma_ij = 1 / sqrt(w_i + w_j); otherwise w = 0 and the call's alpha holds.  gamma_ii = 1 / (2 sigma_i), or alpha, with
+// the self term and 0 without it.  sigma_max: per molecule, for the cells' width check.
+struct CoulombSite {
+    std::vector<float4> rows;
+    std::vector<double> sigma_max;
+    bool widths = false;
+};
+// Refused by name, each with the atom: sigma together with alpha > 0; a width that is not finite and positive, or whose 2 sigma^2 is not
+// a positive finite float32; chi or J not finite; self_term other than 0 or 1, or 1 with neither sigma nor alpha > 0.
+static int site_build(const char *name, int B, const int32_t *offsets, double alpha, const float *sigma, const float *chi, const float *hard,
+                      int self_term, CoulombSite &out) {
+    const int A = offsets[B];
+    if (self_term != 0 && self_term != 1) EPNN_FAIL("%s: self_term = %d must be 0 or 1", name, self_term);
+    if (sigma && alpha > 0.0)
+        EPNN_FAIL("%s: both sigma and alpha = %g are given: per-atom widths take alpha == 0 (equal widths sigma are alpha = 1 / (2 sigma))", name,
+                  alpha);
+    if (self_term && !sigma && !(alpha > 0.0))
+        EPNN_FAIL("%s: self_term = 1 with neither sigma nor alpha > 0: the self-energy of a point charge is infinite", name);
+    out.widths = sigma != nullptr;
+    out.rows.assign((size_t)A, make_float4(0.f, 0.f, 0.f, 0.f));
+    out.sigma_max.assign((size_t)B, 0.0);
+    for (int b = 0; b < B; ++b)
+        for (int a = offsets[b]; a < offsets[b + 1]; ++a) {
+            float4 &r = out.rows[a];
+            double gii = alpha;
+            if (sigma) {
+                const double sg = (double)sigma[a];
+                const float w = (float)(2.0 * sg * sg);
+                if (!epnn_finite(sigma[a]) || !(sg > 0.0)) EPNN_FAIL("%s: sigma[%d] (molecule %d) must be finite and positive", name, a, b);
+                if (!epnn_finite(w) || !(w > 0.f))
+                    EPNN_FAIL("%s: sigma[%d] = %g (molecule %d): 2 sigma^2 is not a positive finite float32", name, a, sg, b);
+                r.x = w;
+                gii = 0.5 / sg;
+                out.sigma_max[b] = std::max(out.sigma_max[b], sg);
+            }
+            if (chi) {
+                if (!epnn_finite(chi[a])) EPNN_FAIL("%s: chi[%d] (molecule %d) is not finite", name, a, b);
+                r.y = chi[a];
+            }
+            if (hard) {
+                if (!epnn_finite(hard[a])) EPNN_FAIL("%s: hard[%d] (molecule %d) is not finite", name, a, b);
+                r.z = hard[a];
+            }
+            r.w = self_term ? (float)gii : 0.f;
+        }
+    return 0;
+}
+// what a site entry adds to its _excl entry's arguments
+struct SiteArgs { const float *sigma, *chi, *hard; int self_term; };
 
 // What an entry adds to the open call: the kind of its sum, whether the strain rows are made, the cells' checked parameters (ew: the
 // real-space sweep's; sl and slots: the slab's reciprocal sweep's, types of epnn_ewald_slab.hip.h) and the caller's list for excl_name_far.
@@ -136,10 +189,13 @@ struct CoulombSum {
 // The one driver behind the six entries, defined in epnn_api_coulomb_run.hip.h, where the three kernel files are known; the open entries
 // hand it no sum, and then it stages no cell parameters, launches no Ewald kernel and allocates no strain rows.
 static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                       const HostGeo &geo, double ke, double alpha, const CoulombSum *sum, const ExclCsr *ex, const CoulombOut &out);
+                       const HostGeo &geo, double ke, double alpha, const CoulombSum *sum, const ExclCsr *ex, const CoulombOut &out,
+                       const CoulombSite *site = nullptr);
 
+// sa: the site entry's arguments; with nothing in them the call is the _excl entry's (the existing kernels) and mu is phi
+static bool site_plain(const SiteArgs *sa) { return !sa || (!sa->sigma && !sa->chi && !sa->hard && sa->self_term == 0); }
 static int coulomb_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                         double ke, double alpha, const ExclArgs *xa, const CoulombOut &out) {
+                         double ke, double alpha, const ExclArgs *xa, const CoulombOut &out, const SiteArgs *sa = nullptr) {
     if (!out.phi || !out.e) EPNN_FAIL("%s: null argument", name);
     if (!epnn_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
     if (!epnn_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
@@ -147,7 +203,11 @@ static int coulomb_enter(epnn_handle *h, const char *name, int B, int N, const i
     if (charges_jvp_enter(h, name, B, N, offsets, xyz, x, Q, nullptr, 1, out.q, out.f, arg)) return 1;
     ExclCsr ex;
     if (xa && excl_build(name, B, offsets, xa->npairs, xa->i, xa->j, xa->scale, ex)) return 1;
-    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, nullptr, xa ? &ex : nullptr, out);
+    CoulombSite site;
+    if (sa && site_build(name, B, offsets, alpha, sa->sigma, sa->chi, sa->hard, sa->self_term, site)) return 1;
+    if (sa && xa && xa->npairs == 0) xa = nullptr;                       // (a site entry takes its list or none: one entry per geometry)
+    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, nullptr, xa ? &ex : nullptr, out,
+                       site_plain(sa) ? nullptr : &site);
 }
 
 extern "C" int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,

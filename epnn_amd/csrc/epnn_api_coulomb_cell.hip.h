@@ -166,9 +166,19 @@ static int excl_name_far(const char *name, const int32_t *offsets, const float *
     EPNN_FAIL("%s: an exclusion pair lies beyond half the smallest perpendicular width of its cell", name);
 }
 
+// The site entry's widths against a cell's split: the real-space term [erf(gamma_ij D) - erf(beta D)] / D is cut at rc, where only
+// erfc(beta rc) is known to be under tol, so every gamma_ij must be at least beta: gamma_min = 1 / (2 sigma_max) >= beta.
+static int site_width_check(const char *name, int b, double sigma_max, double beta) {
+    if (sigma_max > 0.0 && !(0.5 / sigma_max >= beta))
+        EPNN_FAIL("%s: cell %d: sigma_max = %g is above the largest width 1 / (2 beta) = %g its Ewald split allows (beta = %g): beyond it the "
+                  "erf(gamma D) tail at rc is not under tol; a larger tol, or an ewald row with a smaller beta, moves the limit",
+                  name, b, sigma_max, 0.5 / beta, beta);
+    return 0;
+}
+
 static int coulomb_cell_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                               const float *Q, const float *cell, const double *ewald, double ke, double alpha, const ExclArgs *xa,
-                              const CoulombOut &out) {
+                              const CoulombOut &out, const SiteArgs *sa = nullptr) {
     if (!cell || !ewald || !out.phi || !out.e || !out.gs) EPNN_FAIL("%s: null argument", name);
     if (!epnn_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
     if (!epnn_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
@@ -179,8 +189,13 @@ static int coulomb_cell_enter(epnn_handle *h, const char *name, int B, int N, co
         if (ew_cell_row(name, b, cell + 9 * (size_t)b, ewald + 6 * (size_t)b, alpha, ew[b])) return 1;
     ExclCsr ex;
     if (xa && excl_build(name, B, offsets, xa->npairs, xa->i, xa->j, xa->scale, ex)) return 1;
+    CoulombSite site;
+    if (sa && site_build(name, B, offsets, alpha, sa->sigma, sa->chi, sa->hard, sa->self_term, site)) return 1;
+    for (int b = 0; sa && b < B; ++b)
+        if (site_width_check(name, b, site.sigma_max[b], ewald[6 * (size_t)b])) return 1;
+    if (sa && xa && xa->npairs == 0) xa = nullptr;                       // (a site entry takes its list or none: one entry per geometry)
     const CoulombSum sum{CL_CELL, true, &ew, nullptr, nullptr, xa};
-    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, &sum, xa ? &ex : nullptr, out);
+    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, &sum, xa ? &ex : nullptr, out, site_plain(sa) ? nullptr : &site);
 }
 
 extern "C" int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,

@@ -15,16 +15,18 @@ static size_t seg_add(size_t &end, size_t bytes, size_t align = 1) {
 // not empty: nothing is rounded for it.
 //   blob, the one staged span: ctasks | cell: atasks | stasks | kinds with cells: EwCell [B] at 16 | slab: SlCell [B] at 16 | SlSlot []
 //   co, directly behind the backward's output block, one download for both: [A] phi | [A][3] ffix | flag | [B] E in float64 at 8 |
-//       strain: [B][9] the fixed-charge strain
+//       strain: [B][9] the fixed-charge strain | site: [A] mu
 //   sc, float64: part [pieces][A][4 or EW_PART] | slab: rpart [pieces][A][SL_PART or SL_PART_STRAIN] | share [A][1, cell: EW_SHARE] |
-//       slab with strain: wshare [A][SL_SHARE_W] | cell: S [slots] at 16 | rec [slots]
+//       slab with strain: wshare [A][SL_SHARE_W] | cell: S [slots] at 16 | rec [slots] | cell with site: wsum [B]
+//   site, one more staged span of the site entries: [A] float4 = (2 sigma^2, chi, J, gamma_ii)
 struct CoulombLayout {
     size_t atasks, stasks, ew, sl, slot, blob_bytes;
-    size_t E, gsf, co_bytes;
-    size_t part_bytes, rpart, share, wshare, S, rec, sc_bytes;
+    size_t E, gsf, mu, co_bytes;
+    size_t part_bytes, rpart, share, wshare, S, rec, wsum, sc_bytes;
+    size_t site_bytes;
 };
 static CoulombLayout coulomb_layout(CoulombKind kind, bool strain, size_t A, size_t B, size_t nctasks, size_t natasks, size_t nstasks,
-                                    size_t cpieces, size_t slots) {
+                                    size_t cpieces, size_t slots, bool site = false) {
     CoulombLayout L{};
     size_t end = 0;
     seg_add(end, nctasks * sizeof(int4));
@@ -42,6 +44,7 @@ static CoulombLayout coulomb_layout(CoulombKind kind, bool strain, size_t A, siz
     seg_add(end, (A * 4 + 1) * 4);
     L.E = seg_add(end, B * 8, 8);
     L.gsf = seg_add(end, strain ? B * 36 : 0);
+    if (site) L.mu = seg_add(end, A * 4);
     L.co_bytes = end;
     end = 0;
     seg_add(end, L.part_bytes = cpieces * A * (kind == CL_OPEN ? 4 : EW_PART) * 8);
@@ -51,17 +54,21 @@ static CoulombLayout coulomb_layout(CoulombKind kind, bool strain, size_t A, siz
     if (kind == CL_CELL) {
         L.S = seg_add(end, slots * 16, 16);
         L.rec = seg_add(end, slots * 16);
+        if (site) L.wsum = seg_add(end, B * 8);
     }
     L.sc_bytes = end;
+    L.site_bytes = site ? A * sizeof(float4) : 0;
     return L;
 }
 
 // The driver of the six entries: the pair-list gradient call with its seed made on the device.  Set-up and checkpointed forward; on
 // that forward's charges the real-space sweep, the listed pairs' correction (ex), the rest of the sum by its kind and the energy,
 // phi = dE/dq into the seed; the shared backward; one download.  sum->strain: the fixed-charge strain rows are made, the backward runs
-// with its strain flag and the download carries both strain rows (the cells' entries always, the slab's strain entry).
+// with its strain flag and the download carries both strain rows (the cells' entries always, the slab's strain entry).  site (open and
+// cells): the per-atom rows of the site entries; the atoms' kernels are the _site ones, the seed is mu, and with widths the sweeps too.
 static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
-                       const HostGeo &geo, double ke, double alpha, const CoulombSum *sum, const ExclCsr *ex, const CoulombOut &out) {
+                       const HostGeo &geo, double ke, double alpha, const CoulombSum *sum, const ExclCsr *ex, const CoulombOut &out,
+                       const CoulombSite *site) {
     GradLarge *gl = grad_large_state(h);
     if (grad_large_weights(h, gl)) return 1;
     const CoulombKind kind = sum ? sum->kind : CL_OPEN;
@@ -77,7 +84,8 @@ static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int
     }
     bool sweep = kind == CL_OPEN;
     for (int b = 0; sum && b < B; ++b) sweep = sweep || (*sum->ew)[b].rc > 0.f;
-    const CoulombLayout L = coulomb_layout(kind, strain, (size_t)A, (size_t)B, ctasks.size(), atasks.size(), stasks.size(), cpieces, slots);
+    const CoulombLayout L = coulomb_layout(kind, strain, (size_t)A, (size_t)B, ctasks.size(), atasks.size(), stasks.size(), cpieces, slots,
+                                           site != nullptr);
     std::vector<char> blob(L.blob_bytes, 0);
     memcpy(blob.data(), ctasks.data(), ctasks.size() * sizeof(int4));
     if (kind == CL_CELL) {
@@ -90,10 +98,12 @@ static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int
         if (slots) memcpy(blob.data() + L.slot, sum->slots->data(), slots * sizeof(SlSlot));
     }
     // (the entries with a list: the CSR is one more span beside the blob, the correction's rows [A][4 or EW_PART] one more buffer behind the others)
-    const GlSpan spans[2] = {GlSpan{blob.data(), L.blob_bytes, false}, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false}};
+    // (the site entries: the atoms' rows are a third span; without a list the second one is empty)
+    const GlSpan spans[3] = {GlSpan{blob.data(), L.blob_bytes, false}, GlSpan{ex ? ex->blob.data() : nullptr, ex ? ex->blob.size() : 0, false},
+                             GlSpan{site ? site->rows.data() : nullptr, L.site_bytes, false}};
     const size_t more[3] = {L.co_bytes, L.sc_bytes, ex ? excl_xpart_bytes(A, sum != nullptr) : 0};
     GlGrad r;
-    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
+    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, site ? 3 : ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
     const GlCall &c = r.c;
     char *co = c.dw + r.o_more[0], *sc = c.dw + r.o_more[1];
     float *phi = reinterpret_cast<float *>(co), *ffix = phi + A, *gsf = reinterpret_cast<float *>(co + L.gsf);
@@ -103,6 +113,9 @@ static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int
     double *xpart = ex ? reinterpret_cast<double *>(c.dw + r.o_more[2]) : nullptr;
     double2 *S = reinterpret_cast<double2 *>(sc + L.S);
     float4 *rec = reinterpret_cast<float4 *>(sc + L.rec);
+    float *mu = reinterpret_cast<float *>(co + L.mu);
+    double *wsum = reinterpret_cast<double *>(sc + L.wsum);
+    const float4 *d_site = site ? reinterpret_cast<const float4 *>(c.d_extra[2]) : nullptr, *d_wid = site && site->widths ? d_site : nullptr;
     const float *q_dev = r.qck + (size_t)T * A;
     const char *d_blob = reinterpret_cast<const char *>(c.d_extra[0]), *d_csr = ex ? reinterpret_cast<const char *>(c.d_extra[1]) : nullptr;
     const int4 *d_ctasks = reinterpret_cast<const int4 *>(d_blob), *d_atasks = reinterpret_cast<const int4 *>(d_blob + L.atasks);
@@ -116,16 +129,24 @@ static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int
     HIPCHK(hipMemsetAsync(hit, 0, 4, h->stream));
     if (!sweep)                                                  // beta == alpha in every cell: the real-space term vanishes identically
         HIPCHK(hipMemsetAsync(part, 0, L.part_bytes, h->stream));
+    else if (d_wid && sum)
+        hipLaunchKernelGGL(k_ew_sweep_site, gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev, d_wid, d_cells, d_ew, A, part,
+                           hit);
+    else if (d_wid)
+        hipLaunchKernelGGL(k_cl_sweep_site, gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev, d_wid, A, part, hit);
     else if (sum)
         hipLaunchKernelGGL((alpha > 0.0 ? k_ew_sweep<true> : k_ew_sweep<false>), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz,
                            q_dev, d_cells, d_ew, A, (float)alpha, part, hit);
     else
         hipLaunchKernelGGL((alpha > 0.0 ? k_cl_sweep<true> : k_cl_sweep<false>), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz,
                            q_dev, A, (float)alpha, part, hit);
-    if (ex) excl_launch(h, c, d_csr, *ex, q_dev, d_cells, alpha, xpart, hit);     // (nothing of it depends on rc: it runs on a zeroed `part` too)
+    if (ex) excl_launch(h, c, d_csr, *ex, q_dev, d_cells, d_wid, alpha, xpart, hit);     // (nothing of it depends on rc: it runs on a zeroed `part` too)
     switch (kind) {
     case CL_OPEN:
-        if (ex)
+        if (site)
+            hipLaunchKernelGGL((ex ? k_cl_atom_site<true> : k_cl_atom_site<false>), dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev,
+                               (const double *)part, (const double *)xpart, d_site, ke, r.gq, phi, mu, ffix, share);
+        else if (ex)
             hipLaunchKernelGGL(k_cl_atom_x, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, (const double *)part,
                                (const double *)xpart, ke, r.gq, phi, ffix, share);
         else
@@ -135,6 +156,15 @@ static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int
         break;
     case CL_CELL:
         hipLaunchKernelGGL(k_ew_sfac, dim3((unsigned)stasks.size()), wave, 0, h->stream, d_stasks, c.d_moff, c.d_xyz, q_dev, d_cells, d_ew, S, rec);
+        if (site) {
+            hipLaunchKernelGGL(k_ew_wsum, gmol, wave, 0, h->stream, c.d_moff, q_dev, d_site, wsum);
+            hipLaunchKernelGGL((ex ? k_ew_atom_site<true> : k_ew_atom_site<false>), gatom, wave, 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells,
+                               d_ew, (const double2 *)S, (const float4 *)rec, (const double *)part, (const double *)xpart, d_site,
+                               (const double *)wsum, ke, r.gq, phi, mu, ffix, share);
+            hipLaunchKernelGGL(k_ew_energy_site, gmol, wave, 0, h->stream, c.d_moff, d_cells, d_ew, (const double2 *)S, (const double *)share,
+                               (const double *)wsum, ke, E, gsf);
+            break;
+        }
         if (ex)
             hipLaunchKernelGGL(k_ew_atom_x, gatom, wave, 0, h->stream, d_atasks, A, c.d_xyz, q_dev, d_cells, d_ew, (const double2 *)S,
                                (const float4 *)rec, (const double *)part, (const double *)xpart, ke, r.gq, phi, ffix, share);
@@ -183,6 +213,7 @@ static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int
                   name);
     memcpy(out.q, bq, (size_t)A * 4);
     memcpy(out.phi, bphi, (size_t)A * 4);
+    if (out.mu) memcpy(out.mu, site ? back + at_co + L.mu : reinterpret_cast<const char *>(bphi), (size_t)A * 4);
     memcpy(out.e, back + at_co + L.E, (size_t)B * 8);
     for (size_t k = 0; k < 3 * (size_t)A; ++k) {
         const float fq = -bgx[k];

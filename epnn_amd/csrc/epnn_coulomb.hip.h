@@ -54,14 +54,25 @@ __device__ __forceinline__ float cl_g(float u, float erf_u) {
     return two_rpi * (u * w) * s;
 }
 
+// The pair-term modes of the sweeps and of k_cl_excl, a template parameter: bare 1 / D, erf(alpha D) / D with the call's one alpha, and
+// erf(gamma_ij D) / D with gamma_ij = 1 / sqrt(w_i + w_j) from the atoms' own w = 2 sigma^2 (the _site entries' per-atom widths).
+enum ClMode { CL_BARE = 0, CL_ERF = 1, CL_WIDTHS = 2 };
+// gamma_ij of the widths mode; every other mode takes the call's alpha as it is
+template <int MODE>
+__device__ __forceinline__ float cl_pair_alpha(float alpha, float wi, float wj) {
+    if constexpr (MODE == CL_WIDTHS) return rsqrtf(wi + wj);
+    else return alpha;
+}
+
 // The float32 pair term of the open sweep and of k_cl_excl, from the squared length r2 of the rounded displacement: kap = kappa(D),
 // g = g(alpha D) and r3 = 1 / D^3; kap and r3 are 0 at r2 == 0 and for a pair that does not count (use: k_cl_excl counts every one).
-template <bool ERF>
+// MODE CL_WIDTHS: alpha is the pair's gamma_ij (cl_pair_alpha), and the term is that of CL_ERF.
+template <int MODE>
 __device__ __forceinline__ void cl_pair_term(bool use, float r2, float alpha, float &kap, float &g, float &r3) {
     const float rinv = (use && r2 > 0.f) ? rsqrtf(r2) : 0.f;
     g = 1.f;
     kap = rinv;
-    if (ERF) {
+    if (MODE != CL_BARE) {
         const float u = alpha * (r2 * rinv), e = erff(u);
         kap = e * rinv;
         g = cl_g(u, e);
@@ -69,19 +80,23 @@ __device__ __forceinline__ void cl_pair_term(bool use, float r2, float alpha, fl
     r3 = rinv * rinv * rinv;
 }
 // (the periodic sweep's pair term, with the same outputs: epnn_ewald.hip.h, beside ew_h)
-template <bool ERF>
+template <int MODE>
 __device__ __forceinline__ void ew_pair_term(bool use, float r2, float alpha, float beta, float rc, float &kap, float &g, float &r3);
 
 // The sweep of both geometries.  task = (first atom, atoms | piece << 8, first partner, end of the partners); atoms and partners are flat
 // atom indices.  CELL: the displacement goes through the minimum image of the lane's own cell, the pair term is the split one inside
 // rc (EW: EwCell, of which the open file knows only that it has rc and beta) and six more sums follow the open sweep's four, the virial
-// row xx yy zz yz xz xy: part [pieces][A][NS].
-template <bool ERF, bool CELL, class EW>
+// row xx yy zz yz xz xy: part [pieces][A][NS].  MODE CL_WIDTHS: site [A] = (2 sigma^2, chi, J, gamma_ii) per atom, of which the sweep takes
+// the first word: the lane holds its own w_i, the partners' w_j are staged beside tq, and gamma_ij = rsqrtf(w_i + w_j) stands for alpha.
+template <int MODE, bool CELL, class EW>
 __device__ __forceinline__ void cl_sweep_body(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
-                                              const EpnnCell *cells, const EW *ew, int A, float alpha, double *part, int *bad) {
+                                              const float4 *site, const EpnnCell *cells, const EW *ew, int A, float alpha, double *part,
+                                              int *bad) {
     constexpr int NS = CELL ? 10 : 4;                            // (10: EW_PART, asserted in epnn_ewald.hip.h)
+    constexpr bool WID = MODE == CL_WIDTHS;
     __shared__ double tx[CL_TILE], ty[CL_TILE], tz[CL_TILE];
     __shared__ float tq[CL_TILE];
+    __shared__ float tw[WID ? CL_TILE : 1];
     const int4 tk = tasks[blockIdx.x];
     const int lane = threadIdx.x, na = tk.y & 255, piece = tk.y >> 8;
     const bool valid = lane < na;
@@ -95,6 +110,8 @@ __device__ __forceinline__ void cl_sweep_body(const int4 *tasks, const int *moff
         beta = ew[b].beta;
     }
     const double xi = (double)xyz[3 * (size_t)i], yi = (double)xyz[3 * (size_t)i + 1], zi = (double)xyz[3 * (size_t)i + 2];
+    float wi = 0.f;
+    if constexpr (WID) wi = site[i].x;
     double sum[NS];
 #pragma unroll
     for (int c = 0; c < NS; ++c) sum[c] = 0.0;
@@ -106,6 +123,7 @@ __device__ __forceinline__ void cl_sweep_body(const int4 *tasks, const int *moff
             const size_t j = (size_t)(t0 + lane);
             tx[lane] = (double)xyz[3 * j]; ty[lane] = (double)xyz[3 * j + 1]; tz[lane] = (double)xyz[3 * j + 2];
             tq[lane] = q[j];
+            if constexpr (WID) tw[lane] = site[j].x;
         }
         __syncthreads();
         for (int jj = 0; jj < cnt; ++jj) {
@@ -117,8 +135,9 @@ __device__ __forceinline__ void cl_sweep_body(const int4 *tasks, const int *moff
             const bool use = valid && j != i && j >= lo && j < hi;        // the self term goes by index
             hit |= use && r2 == 0.f;
             float kap, gg, r3;
-            if constexpr (CELL) ew_pair_term<ERF>(use, r2, alpha, beta, rc, kap, gg, r3);
-            else cl_pair_term<ERF>(use, r2, alpha, kap, gg, r3);
+            const float al = cl_pair_alpha<MODE>(alpha, wi, WID ? tw[jj] : 0.f);
+            if constexpr (CELL) ew_pair_term<MODE>(use, r2, al, beta, rc, kap, gg, r3);
+            else cl_pair_term<MODE>(use, r2, al, kap, gg, r3);
             const float s = qj * gg * r3;
             const float fx = s * dx, fy = s * dy, fz = s * dz;
             sum[0] += (double)(qj * kap);
@@ -145,14 +164,23 @@ __device__ __forceinline__ void cl_sweep_body(const int4 *tasks, const int *moff
 template <bool ERF>
 __global__ __launch_bounds__(64) void k_cl_sweep(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q, int A,
                                                  float alpha, double *part, int *bad) {
-    cl_sweep_body<ERF, false, void>(tasks, moff, mol_of, xyz, q, nullptr, nullptr, A, alpha, part, bad);
+    cl_sweep_body<ERF ? CL_ERF : CL_BARE, false, void>(tasks, moff, mol_of, xyz, q, nullptr, nullptr, nullptr, A, alpha, part, bad);
+}
+// the sweep of epnn_coulomb_xyz_site with per-atom widths
+__global__ __launch_bounds__(64) void k_cl_sweep_site(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
+                                                      const float4 *site, int A, double *part, int *bad) {
+    cl_sweep_body<CL_WIDTHS, false, void>(tasks, moff, mol_of, xyz, q, site, nullptr, nullptr, A, 0.f, part, bad);
 }
 
 // every atom adds its pieces in piece order: phi [A] (float32, written twice: the backward's seed and the output), ffix [A][3],
 // and its share of the energy, 1/2 q_i phi_i, in float64.  X: the listed pairs' row xpart [A][4] (k_cl_excl) is one more piece, added last.
-template <bool X>
+// SITE (epnn_coulomb_xyz_site): site [A] = (2 sigma^2, chi, J, gamma_ii; gamma_ii 0 without the self term).  phi gets the self term
+// ke 2 gamma_ii q_i / sqrt(pi); mu = chi + J q + phi goes into the seed and into mu [A], phi into phi [A] only; the share is
+// q (chi + 1/2 J q) + 1/2 q phi.
+template <bool X, bool SITE = false>
 __device__ __forceinline__ void cl_atom_body(int A, const int *moff, const int *mol_of, const float *q, const double *part, const double *xpart,
-                                             double ke, float *seed, float *phi, float *ffix, double *share) {
+                                             double ke, float *seed, float *phi, float *ffix, double *share, const float4 *site = nullptr,
+                                             float *mu = nullptr) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A) return;
     const int b = mol_of[i], np = cl_pieces(moff[b + 1] - moff[b]);
@@ -161,10 +189,20 @@ __device__ __forceinline__ void cl_atom_body(int A, const int *moff, const int *
         for (int c = 0; c < 4; ++c) s[c] += part[((size_t)k * A + i) * 4 + c];
     if (X)
         for (int c = 0; c < 4; ++c) s[c] += xpart[(size_t)i * 4 + c];
-    const double p = ke * s[0], qi = (double)q[i];
-    seed[i] = phi[i] = (float)p;
-    for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
-    share[i] = 0.5 * qi * p;
+    const double qi = (double)q[i];
+    if constexpr (SITE) {
+        const float4 st = site[i];
+        const double p = ke * (s[0] + 1.1283791670955126 * (double)st.w * qi), chi = (double)st.y, J = (double)st.z;
+        phi[i] = (float)p;
+        seed[i] = mu[i] = (float)(chi + J * qi + p);
+        for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
+        share[i] = qi * (chi + 0.5 * J * qi) + 0.5 * qi * p;
+    } else {
+        const double p = ke * s[0];
+        seed[i] = phi[i] = (float)p;
+        for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
+        share[i] = 0.5 * qi * p;
+    }
 }
 __global__ __launch_bounds__(256) void k_cl_atom(int A, const int *moff, const int *mol_of, const float *q, const double *part, double ke,
                                                  float *seed, float *phi, float *ffix, double *share) {
@@ -173,6 +211,13 @@ __global__ __launch_bounds__(256) void k_cl_atom(int A, const int *moff, const i
 __global__ __launch_bounds__(256) void k_cl_atom_x(int A, const int *moff, const int *mol_of, const float *q, const double *part,
                                                    const double *xpart, double ke, float *seed, float *phi, float *ffix, double *share) {
     cl_atom_body<true>(A, moff, mol_of, q, part, xpart, ke, seed, phi, ffix, share);
+}
+// the atoms' kernel of epnn_coulomb_xyz_site; xpart NULL: no list
+template <bool X>
+__global__ __launch_bounds__(256) void k_cl_atom_site(int A, const int *moff, const int *mol_of, const float *q, const double *part,
+                                                      const double *xpart, const float4 *site, double ke, float *seed, float *phi, float *mu,
+                                                      float *ffix, double *share) {
+    cl_atom_body<X, true>(A, moff, mol_of, q, part, xpart, ke, seed, phi, ffix, share, site, mu);
 }
 
 // E_b: a molecule's shares, lane by lane in atom order, then across the lanes (the order of k_g_strain_mol)
@@ -196,9 +241,11 @@ __global__ __launch_bounds__(64) void k_cl_energy(const double *share, const int
 // D^3, .. dy, .. dz), f the row's factor; CELL: xpart [A][10], the six virial sums f q_j g d_a d_b / D^3 (xx yy zz yz xz xy) behind
 // them, in the order of the periodic sweep's row.  Each word is written by exactly one lane; the only atomic is the OR into the flag word.
 // cells: the batch's EpnnCell records (CELL), from which every lane takes half the smallest width, 1 / (2 max_k |g_k|).
-template <bool ERF, bool CELL>
+// MODE: the pair term's (ClMode); CL_WIDTHS reads w_i and w_j from site [A] as the sweep does.
+template <int MODE, bool CELL>
 __global__ __launch_bounds__(64) void k_cl_excl(int A, const int *mol_of, const float *xyz, const float *q, const int *row_off, const int *partner,
-                                                const float *factor, const EpnnCell *cells, float alpha, double *xpart, int *bad) {
+                                                const float *factor, const EpnnCell *cells, const float4 *site, float alpha, double *xpart,
+                                                int *bad) {
     constexpr int NS = CELL ? 10 : CL_XPART;
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= A) return;
@@ -212,6 +259,8 @@ __global__ __launch_bounds__(64) void k_cl_excl(int A, const int *mol_of, const 
         half_w = (float)(0.5 / sqrt(g2));
     }
     const double xi = (double)xyz[3 * (size_t)i], yi = (double)xyz[3 * (size_t)i + 1], zi = (double)xyz[3 * (size_t)i + 2];
+    float wi = 0.f;
+    if constexpr (MODE == CL_WIDTHS) wi = site[i].x;
     double sum[NS];
 #pragma unroll
     for (int c = 0; c < NS; ++c) sum[c] = 0.0;
@@ -226,7 +275,9 @@ __global__ __launch_bounds__(64) void k_cl_excl(int A, const int *mol_of, const 
         if (r2 == 0.f) flag |= CL_FLAG_ZERO;
         if (CELL && r2 > half_w * half_w) flag |= CL_FLAG_FAR;
         float kap, gg, r3;
-        cl_pair_term<ERF>(true, r2, alpha, kap, gg, r3);
+        float wj = 0.f;
+        if constexpr (MODE == CL_WIDTHS) wj = site[j].x;
+        cl_pair_term<MODE>(true, r2, cl_pair_alpha<MODE>(alpha, wi, wj), kap, gg, r3);
         const float s = qj * (gg * r3);                                   // (the sweep multiplies from the left: (q_j g) / D^3)
         const float fx = fac * (s * dx), fy = fac * (s * dy), fz = fac * (s * dz);
         sum[0] += (double)(fac * (qj * kap));

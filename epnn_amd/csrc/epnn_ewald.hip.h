@@ -61,14 +61,14 @@ __device__ __forceinline__ float ew_h(float u) { return erfcf(u) + 1.12837916709
 
 // The split pair term of the periodic sweep, cl_pair_term's outputs: kap = kappa_s(D) = de / D, g = gs = g_alpha - g_beta = -D^2 kappa_s'
 // and r3 = 1 / D^3, kap and r3 0 at r2 == 0, beyond rc and without use.  The two differences cancel where alpha D and beta D are both large
-// (erf -> 1, g -> 1): there they are taken between the complements erfc and h = 1 - g.
-template <bool ERF>
+// (erf -> 1, g -> 1): there they are taken between the complements erfc and h = 1 - g.  MODE CL_WIDTHS: alpha is the pair's gamma_ij.
+template <int MODE>
 __device__ __forceinline__ void ew_pair_term(bool use, float r2, float alpha, float beta, float rc, float &kap, float &g, float &r3) {
     const float rinv0 = r2 > 0.f ? rsqrtf(r2) : 0.f, D = r2 * rinv0;
     const float rinv = (use && r2 > 0.f && D <= rc) ? rinv0 : 0.f;
     const float ub = beta * D;
     float de;
-    if (ERF) {
+    if (MODE != CL_BARE) {
         const float ua = alpha * D, um = fminf(ua, ub);
         de = um >= 0.5f ? erfcf(ub) - erfcf(ua) : erff(ua) - erff(ub);
         g = um >= 1.f ? ew_h(ub) - ew_h(ua) : cl_g(ua, erff(ua)) - cl_g(ub, erff(ub));
@@ -85,7 +85,22 @@ __device__ __forceinline__ void ew_pair_term(bool use, float r2, float alpha, fl
 template <bool ERF>
 __global__ __launch_bounds__(64) void k_ew_sweep(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
                                                  const EpnnCell *cells, const EwCell *ew, int A, float alpha, double *part, int *bad) {
-    cl_sweep_body<ERF, true>(tasks, moff, mol_of, xyz, q, cells, ew, A, alpha, part, bad);
+    cl_sweep_body<ERF ? CL_ERF : CL_BARE, true>(tasks, moff, mol_of, xyz, q, nullptr, cells, ew, A, alpha, part, bad);
+}
+// the real-space sweep of epnn_coulomb_xyz_cell_site with per-atom widths: gamma_ij for alpha (the host has checked gamma_min >= beta)
+__global__ __launch_bounds__(64) void k_ew_sweep_site(const int4 *tasks, const int *moff, const int *mol_of, const float *xyz, const float *q,
+                                                      const float4 *site, const EpnnCell *cells, const EwCell *ew, int A, double *part, int *bad) {
+    cl_sweep_body<CL_WIDTHS, true>(tasks, moff, mol_of, xyz, q, site, cells, ew, A, 0.f, part, bad);
+}
+
+// The per-cell sum of the site entry's background, one wavefront per cell in the order of k_cl_energy: wsum [B] = sum_j q_j w_j,
+// w = 2 sigma^2 (site[j].x; 0 without widths), float64.  (Q is S(k = 0), as in the plain entry.)
+__global__ __launch_bounds__(64) void k_ew_wsum(const int *moff, const float *q, const float4 *site, double *wsum) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double v = 0.0;
+    for (int a = moff[b] + lane; a < moff[b + 1]; a += 64) v += (double)q[a] * (double)site[a].x;
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    if (lane == 0) wsum[b] = v;
 }
 
 // task = (cell, first slot): S(k) of 64 slots of the cell's k box, a slot per lane, over the cell's atoms in index order.  The
@@ -147,10 +162,15 @@ __global__ __launch_bounds__(64) void k_ew_sfac(const int2 *tasks, const int *mo
 // in piece order, the self and background terms, and writes phi [A] (twice: the backward's seed and the output), ffix [A][3] and its
 // shares [A][EW_SHARE] in float64: 1/2 q_i (phi_i - its reciprocal part) and -1/2 ke q_i times its virial row.
 // X: the listed pairs' row xpart [A][EW_PART] (k_cl_excl) is one more piece, added behind the sweep's: its virial sums take the same 1/2.
-template <bool X>
+// SITE (epnn_coulomb_xyz_cell_site): site [A] = (w = 2 sigma^2, chi, J, gamma_ii; gamma_ii 0 without the self term), wsum [B]:
+// W = sum_j q_j w_j.  The background is taken per pair, phi_bg_i = -ke (pi / V) [Q / beta^2 - w_i Q - W] (e.bg is made with alpha = 0
+// then); phi gets the Gaussians' self term ke 2 gamma_ii q_i / sqrt(pi); mu = chi + J q + phi goes into the seed and into mu [A], phi
+// into phi [A] only; the first share gets q (chi + 1/2 J q) as well.
+template <bool X, bool SITE = false>
 __device__ __forceinline__ void ew_atom_body(const int4 *tasks, int A, const float *xyz, const float *q, const EpnnCell *cells, const EwCell *ew,
                                              const double2 *S, const float4 *rec, const double *part, const double *xpart, double ke, float *seed,
-                                             float *phi, float *ffix, double *share) {
+                                             float *phi, float *ffix, double *share, const float4 *site = nullptr, const double *wsum = nullptr,
+                                             float *mu = nullptr) {
     __shared__ double tm[3][EW_TILE];
     __shared__ float4 tr[EW_TILE];
     __shared__ float2 tS[EW_TILE];
@@ -212,13 +232,25 @@ __device__ __forceinline__ void ew_atom_body(const int4 *tasks, int A, const flo
 #pragma unroll
         for (int c = 0; c < EW_PART; ++c) s[c] += xpart[(size_t)i * EW_PART + c];
     const double qi = (double)q[i], Qs = S[(size_t)e.soff + (size_t)e.M1 * (2 * e.M0 + 1) + e.M0].x;
-    const double local = ke * ((s[0] - e.self * qi) - e.bg * Qs), p = local + ke * pr;
-    seed[i] = phi[i] = (float)p;
+    double local, onsite = 0.0;
+    if constexpr (SITE) {
+        const float4 st = site[i];
+        const double w = (double)st.x, chi = (double)st.y, J = (double)st.z;
+        local = ke * (((s[0] - e.self * qi) - e.bg * Qs) + 0.25 * e.c0 * (w * Qs + wsum[b]) + 1.1283791670955126 * (double)st.w * qi);
+        const double p = local + ke * pr;
+        phi[i] = (float)p;
+        seed[i] = mu[i] = (float)(chi + J * qi + p);
+        onsite = qi * (chi + 0.5 * J * qi);
+    } else {
+        local = ke * ((s[0] - e.self * qi) - e.bg * Qs);
+        const double p = local + ke * pr;
+        seed[i] = phi[i] = (float)p;
+    }
     ffix[3 * (size_t)i] = (float)(ke * qi * (s[1] + fx));
     ffix[3 * (size_t)i + 1] = (float)(ke * qi * (s[2] + fy));
     ffix[3 * (size_t)i + 2] = (float)(ke * qi * (s[3] + fz));
     double *o = share + EW_SHARE * (size_t)i;
-    o[0] = 0.5 * qi * local;
+    o[0] = SITE ? onsite + 0.5 * qi * local : 0.5 * qi * local;
 #pragma unroll
     for (int c = 0; c < 6; ++c) o[1 + c] = -0.5 * ke * qi * s[4 + c];
 }
@@ -232,13 +264,23 @@ __global__ __launch_bounds__(64) void k_ew_atom_x(const int4 *tasks, int A, cons
                                                   float *seed, float *phi, float *ffix, double *share) {
     ew_atom_body<true>(tasks, A, xyz, q, cells, ew, S, rec, part, xpart, ke, seed, phi, ffix, share);
 }
+// the atoms' kernel of epnn_coulomb_xyz_cell_site; X: with a list
+template <bool X>
+__global__ __launch_bounds__(64) void k_ew_atom_site(const int4 *tasks, int A, const float *xyz, const float *q, const EpnnCell *cells,
+                                                     const EwCell *ew, const double2 *S, const float4 *rec, const double *part, const double *xpart,
+                                                     const float4 *site, const double *wsum, double ke, float *seed, float *phi, float *mu,
+                                                     float *ffix, double *share) {
+    ew_atom_body<X, true>(tasks, A, xyz, q, cells, ew, S, rec, part, xpart, ke, seed, phi, ffix, share, site, wsum, mu);
+}
 
 // One wavefront per cell: E = sum of the atoms' shares + E_rec and the fixed-charge strain derivative [3][3] = the atoms' virial shares
 // + the reciprocal part - E_bg delta_ab, with E_rec = 1/2 sum_k c |S|^2 and the reciprocal strain 1/2 sum_k c |S|^2 [-delta_ab +
 // 2 k_a k_b (1 / k^2 + 1 / 4 beta^2)] over the whole sphere, here the half space with c doubled, in float64 throughout.  Lane l adds
 // slots l, l + 64, ... and then atoms l, l + 64, ... in ascending order; a fixed butterfly combines the lanes (k_g_strain_mol's order).
-__global__ __launch_bounds__(64) void k_ew_energy(const int *moff, const EpnnCell *cells, const EwCell *ew, const double2 *S, const double *share,
-                                                  double ke, double *e_out, float *gs_out) {
+// SITE: E_bg = -ke (pi / 2 V) [Q^2 / beta^2 - 2 Q W], W = wsum [b] (k_ew_wsum): the per-pair background of the site entry.
+template <bool SITE>
+__device__ __forceinline__ void ew_energy_body(const int *moff, const EpnnCell *cells, const EwCell *ew, const double2 *S, const double *share,
+                                               const double *wsum, double ke, double *e_out, float *gs_out) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const EwCell e = ew[b];
     double g[9];
@@ -266,7 +308,9 @@ __global__ __launch_bounds__(64) void k_ew_energy(const int *moff, const EpnnCel
         W[c] = v;
     }
     if (lane == 0) {
-        const double Qs = S[(size_t)e.soff + (size_t)e.M1 * (2 * e.M0 + 1) + e.M0].x, e_bg = -0.5 * ke * e.bg * Qs * Qs;
+        const double Qs = S[(size_t)e.soff + (size_t)e.M1 * (2 * e.M0 + 1) + e.M0].x;
+        double e_bg = -0.5 * ke * e.bg * Qs * Qs;
+        if constexpr (SITE) e_bg += 0.25 * ke * e.c0 * Qs * wsum[b];
         e_out[b] = W[0];
         float *o = gs_out + 9 * (size_t)b;
         o[0] = (float)(W[1] - e_bg); o[4] = (float)(W[2] - e_bg); o[8] = (float)(W[3] - e_bg);
@@ -274,4 +318,12 @@ __global__ __launch_bounds__(64) void k_ew_energy(const int *moff, const EpnnCel
         o[2] = o[6] = (float)W[5];
         o[1] = o[3] = (float)W[6];
     }
+}
+__global__ __launch_bounds__(64) void k_ew_energy(const int *moff, const EpnnCell *cells, const EwCell *ew, const double2 *S, const double *share,
+                                                  double ke, double *e_out, float *gs_out) {
+    ew_energy_body<false>(moff, cells, ew, S, share, nullptr, ke, e_out, gs_out);
+}
+__global__ __launch_bounds__(64) void k_ew_energy_site(const int *moff, const EpnnCell *cells, const EwCell *ew, const double2 *S,
+                                                       const double *share, const double *wsum, double ke, double *e_out, float *gs_out) {
+    ew_energy_body<true>(moff, cells, ew, S, share, wsum, ke, e_out, gs_out);
 }

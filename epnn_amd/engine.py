@@ -119,6 +119,27 @@ def _exclusion_lists(where, exclusions):
             np.ascontiguousarray(scale))
 
 
+def per_element(Z, table, default=None):
+    """A per-atom float32 array (A,) for coulomb_xyz_site's sigma, chi and hardness from a table by element: Z (A,) the atomic numbers
+    (x[:, 0] of the flat batch), table a dict {Z: value}.  An element the table lacks takes default; with default None it raises,
+    naming the element."""
+    Z = np.asarray(Z)
+    if Z.ndim != 1:
+        raise ValueError(f"per_element: Z must have shape (A,), got {Z.shape}")
+    zi = np.rint(Z).astype(np.int64)
+    if Z.size and np.abs(np.asarray(Z, dtype=np.float64) - zi).max() != 0.0:
+        raise ValueError("per_element: Z must hold whole atomic numbers")
+    out = np.empty(zi.shape, dtype=np.float32)
+    for z in np.unique(zi):
+        if int(z) in table:
+            out[zi == z] = table[int(z)]
+        elif default is not None:
+            out[zi == z] = default
+        else:
+            raise KeyError(f"per_element: the table has no value for element Z = {int(z)}")
+    return out
+
+
 def bonded_exclusions(bonds, n_atoms, scale12=0.0, scale13=0.0, scale14=0.5):
     """The exclusion list of a force field from a bond list: bonds (nb, 2) int, flat atom indices below n_atoms -> (pairs (P, 2) int32,
     scale (P,) float32) for coulomb_xyz_excl and coulomb_xyz_cell_excl.  Every pair at graph distance 1, 2 or 3 once, i < j, sorted;
@@ -620,6 +641,32 @@ class Engine:
         return self._coulomb("coulomb_xyz_cell_excl", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, strain),
                              exclusions=exclusions)
 
+    def coulomb_xyz_site(self, offsets, xyz, x, Q, N, ke=KE_EV_ANGSTROM, alpha=0.0, sigma=None, chi=None, hardness=None, self_energy=True,
+                         exclusions=None, parts=False):
+        """The energy of a charge-model potential in one call (epnn_coulomb_xyz_site): coulomb_xyz_excl with per-atom Gaussian widths,
+        the Gaussians' self-energy and on-site terms -> (q (A,), phi (A,), mu (A,), E (B,) float64, F (A, 3)),
+            E = sum_i (chi_i q_i + 1/2 J_i q_i^2) + [self_energy] ke sum_i gamma_ii q_i^2 / sqrt(pi)
+                + ke sum_{i<j} w_ij q_i q_j erf(gamma_ij D_ij) / D_ij,   gamma_ij = 1 / sqrt(2 (sigma_i^2 + sigma_j^2)),
+        mu = dE/dq = chi + J q + phi, the seed of the part of F through dq/dxyz.  sigma, chi, hardness: float arrays (A,), one value
+        per real atom (per_element makes them from a table by element), each may be None.  sigma=None: every pair uses alpha, as in
+        coulomb_xyz; with sigma alpha must be 0 (equal widths sigma are alpha = 1 / (2 sigma)), and gamma_ii = 1 / (2 sigma_i), or alpha.
+        chi and hardness are in the caller's energy units and are not multiplied by ke.  self_energy=True needs sigma or alpha > 0 (a
+        point charge's self-energy is infinite).  exclusions = (pairs, scale) as in coulomb_xyz_excl, or None.  parts=True appends ffix
+        and fq; fq is -gxyz of charges_vjp_xyz(g=mu) on "grad_path" 2, bit for bit.  With nothing given and self_energy=False the
+        outputs have the bits of coulomb_xyz_excl and mu is phi."""
+        return self._coulomb("coulomb_xyz_site", offsets, xyz, x, Q, N, ke, alpha, parts, exclusions=exclusions,
+                             site=(sigma, chi, hardness, self_energy))
+
+    def coulomb_xyz_cell_site(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                              sigma=None, chi=None, hardness=None, self_energy=True, exclusions=None, parts=False, strain=False):
+        """coulomb_xyz_site in fully periodic cells (epnn_coulomb_xyz_cell_site): the Ewald sum of coulomb_xyz_cell_excl with gamma_ij in
+        its real-space term, the background of a charged cell worked out per pair, the self-energy and the on-site terms -> (q, phi,
+        mu, E, F[, gstrain][, ffix, fq[, gstrain_fix, gstrain_q]]).  ewald=None: ewald_params(cell, alpha, tol) per cell (alpha is 0
+        with sigma).  A cell whose widest Gaussian does not fit the split, sigma_max > 1 / (2 beta), is refused by name: a larger
+        tol, or an ewald row with a smaller beta, moves the limit."""
+        return self._coulomb("coulomb_xyz_cell_site", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, strain),
+                             exclusions=exclusions, site=(sigma, chi, hardness, self_energy))
+
     def ewald_slab_params(self, cell, alpha=0.0, tol=1e-6):
         """The parameters coulomb_xyz_slab runs at for one slab cell (3, 3) with one row of zeros (epnn_ewald_slab_params, host only):
         float64 (6,) = beta, rc, kc, M0, M1, M2 by the rule of ewald_params over the two periodic rows; M of the open row is 0.
@@ -653,14 +700,15 @@ class Engine:
         return self._coulomb("coulomb_xyz_slab_strain", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, True),
                              exclusions=exclusions, slab=True)
 
-    def _coulomb(self, where, offsets, xyz, x, Q, N, ke, alpha, parts, periodic=None, exclusions=None, slab=False):
-        """The six coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
+    def _coulomb(self, where, offsets, xyz, x, Q, N, ke, alpha, parts, periodic=None, exclusions=None, slab=False, site=None):
+        """The eight coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
         molecules, exclusions = (pairs, scale) or None for the plain C entry (an _excl method without a list is its plain method).
         slab: the two slab entries, which always take a list (None: an empty one) and their own rule; the plain one has no strain
-        rows, the other one is chosen by its name."""
+        rows, the other one is chosen by its name.  site = (sigma, chi, hardness, self_energy): the two _site entries, which always
+        take a list too and return mu behind phi."""
         if exclusions is None:
             where = where.replace("_excl", "")
-            if slab:
+            if slab or site is not None:
                 exclusions = (np.zeros((0, 2), dtype=np.int32), 1.0)
         strain = False
         if periodic is not None:
@@ -672,6 +720,20 @@ class Engine:
         dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         opt = lambda a: None if a is None else fptr(a)
         args = [float(ke), float(alpha)]
+        if site is not None:
+            sigma, chi, hardness, self_energy = site
+            rows = []
+            for name, a in (("sigma", sigma), ("chi", chi), ("hardness", hardness)):
+                if a is not None:
+                    a = np.ascontiguousarray(a, dtype=np.float32)
+                    if a.shape != (A,):
+                        raise ValueError(f"{where}: {name} must have shape ({A},), one value per real atom, got {a.shape}")
+                rows.append(a)
+            if rows[0] is not None and float(alpha) > 0.0:
+                raise ValueError(f"{where}: both sigma and alpha = {alpha} are given: per-atom widths take alpha = 0")
+            if self_energy and rows[0] is None and not float(alpha) > 0.0:
+                raise ValueError(f"{where}: self_energy=True with neither sigma nor alpha > 0: the self-energy of a point charge is infinite")
+            args += [opt(rows[0]), opt(rows[1]), opt(rows[2]), 1 if self_energy else 0]
         if periodic is not None:
             _, cell = _geometry(box, cell, B, cells_only=True)
             if ewald is None:
@@ -697,8 +759,11 @@ class Engine:
             gs = np.empty((B, 3, 3), dtype=np.float32)
             gs_fix, gs_q = (np.empty((B, 3, 3), dtype=np.float32) if parts else None for _ in range(2))
             outs = outs[:4] + [fptr(gs)] + outs[4:] + [opt(gs_fix), opt(gs_q)]
+        if site is not None:
+            mu = np.empty((A,), dtype=np.float32)
+            outs = outs[:2] + [fptr(mu)] + outs[2:]
         check(getattr(self.lib, "epnn_" + where)(self.h, B, int(N), iptr(offsets), fptr(xyz), fptr(x), fptr(Q), *args, *outs), self.lib)
-        out = (q, phi, E, F) + ((gs,) if strain else ())
+        out = (q, phi) + ((mu,) if site is not None else ()) + (E, F) + ((gs,) if strain else ())
         if parts:
             out += (ffix, fq) + ((gs_fix, gs_q) if strain else ())
         return out

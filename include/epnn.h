@@ -451,7 +451,8 @@ int epnn_charges_vjp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t 
  * ke is the caller's unit constant (14.3996454784255 eV A / e^2, 332.0637 kcal A / mol e^2).  q is the model's output, so sum q = Q
  * holds by construction and no constraint term appears.  Open systems only: the entry takes no box or cell (fully periodic cells:
  * epnn_coulomb_xyz_cell below, an Ewald sum; slabs, two periodic axes: epnn_coulomb_xyz_slab below).  No self-energy term (for alpha > 0 the
- * Gaussians' self-energy -ke alpha / sqrt(pi) sum q_i^2 is left out; it depends on q alone).  Every pair of a molecule counts in full
+ * Gaussians' self-energy -ke alpha / sqrt(pi) sum q_i^2 is left out; it depends on q alone; the entry with it, with per-atom widths and
+ * with on-site terms: epnn_coulomb_xyz_site below).  Every pair of a molecule counts in full
  * here; bonded exclusions and the scaling of near neighbours: epnn_coulomb_xyz_excl below.
  * Outputs (host): q_out[A], phi_out[A], e_out[B] in float64 (a float32 energy of a 100 000-atom system loses the digits its forces
  * live in), f_out[A][3]; ffix_out[A][3] and fq_out[A][3] may each be NULL, and the other outputs have the same bits either way.
@@ -527,7 +528,8 @@ int epnn_coulomb_xyz(epnn_handle *h, int B, int N, const int32_t *offsets, const
  * parameters; slots = the batch's k slots, about 3600 for a cube at tol = 1e-6 whatever its size.  Nothing of size n nk or n^2.
  * Still missing: one periodic axis (wires); the strain derivative of the slab sum; PME (bonded exclusions: epnn_coulomb_xyz_cell_excl
  * below; two periodic axes: epnn_coulomb_xyz_slab below).  The slab sum's strain derivative has since been built as an entry of its
- * own, epnn_coulomb_xyz_slab_strain, behind epnn_coulomb_xyz_slab. */
+ * own, epnn_coulomb_xyz_slab_strain, behind epnn_coulomb_xyz_slab; per-atom Gaussian widths, the Gaussians' self-energy and on-site
+ * terms: epnn_coulomb_xyz_site and epnn_coulomb_xyz_cell_site below. */
 int epnn_ewald_params(const float *cell, double alpha, double tol, double *out);
 int epnn_coulomb_xyz_cell(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                           const float *cell, const double *ewald, double ke, double alpha, float *q_out, float *phi_out,
@@ -572,6 +574,74 @@ int epnn_coulomb_xyz_excl(epnn_handle *h, int B, int N, const int32_t *offsets, 
 int epnn_coulomb_xyz_cell_excl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
                                const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
+                               float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out);
+/* ---- per-atom Gaussian widths, self-energy and on-site terms: the energy of the potentials built on a charge model (4G-HDNNP, CENT,
+ * QEq-style models driven by predicted charges; INTEGRATION.md, "Charge-model energies: widths, hardness, electronegativity"),
+ *     E = sum_i (chi_i q_i + 1/2 J_i q_i^2) + ke sum_i q_i^2 / (2 sqrt(pi) sigma_i) + ke sum_{i<j} q_i q_j erf(gamma_ij D_ij) / D_ij,
+ *     gamma_ij = 1 / sqrt(2 (sigma_i^2 + sigma_j^2)),
+ * for open molecules and fully periodic cells.  A caller cannot add these terms afterwards: phi is the backward's seed on the device,
+ * and a term of dE/dq added outside leaves fq and the charges' part of the strain wrong.
+ * New inputs, all host arrays, float32, one value per real atom:
+ *     sigma[A]     may be NULL: every pair then uses the call's alpha, as in the entries above.  Otherwise every value is finite and
+ *                  positive, 2 sigma^2 rounded to float32 is a positive finite float, and alpha must be 0 (both given is refused by
+ *                  name).  Equal widths sigma are the existing alpha = 1 / (2 sigma).
+ *     chi[A], hard[A] (J)   may each be NULL (= 0); in the caller's energy units per charge and per charge squared, NOT multiplied by
+ *                  ke; they must be finite.
+ *     self_term    0 or 1.  With 1, E_self = ke sum_i gamma_ii q_i^2 / sqrt(pi) is added, gamma_ii = 1 / (2 sigma_i), or alpha when sigma
+ *                  is NULL.  self_term = 1 with neither sigma nor alpha > 0 is refused by name (a point charge's self-energy is infinite).
+ *     the list     (npairs, ex_i, ex_j, ex_scale) has the meaning, the checks and the refusals of epnn_coulomb_xyz_excl / _cell_excl;
+ *                  npairs == 0 with NULL pointers is allowed: one entry per geometry.  A listed pair gets (s - 1) times its bare
+ *                  erf(gamma_ij D) / D term; w_ij = s for listed pairs and 1 otherwise.
+ * Open:
+ *     phi_i  = ke [ sum_{j != i} w_ij q_j erf(gamma_ij D_ij) / D_ij  +  [self_term] 2 gamma_ii q_i / sqrt(pi) ]
+ *     mu_i   = chi_i + J_i q_i + phi_i                        = dE/dq_i, the seed of the backward
+ *     E_b    = sum_i [ chi_i q_i + 1/2 J_i q_i^2 + 1/2 q_i phi_i ]                                       (float64)
+ *     ffix_i = -ke q_i sum_{j != i} w_ij q_j kappa_ij'(D_ij) (r_i - r_j) / D_ij,   kappa_ij' = -g(gamma_ij D) / D^2
+ *     fq_i   = -sum_k mu_k dq_k/dr_i,     f = ffix + fq     (one float32 add)
+ * Fully periodic cells: the sum of epnn_coulomb_xyz_cell with gamma_ij in place of alpha in the real-space term
+ * [erf(gamma_ij D) - erf(beta D)] / D, D <= rc; the point-charge reciprocal and -2 beta / sqrt(pi) q_i terms stay as they are.  The
+ * background of a charged cell is worked out per pair, from int (1/D - erf(gamma D)/D) d^3D = pi / gamma^2:
+ *     phi_bg_i = -ke (pi / V) [ Q / beta^2 - 2 sigma_i^2 Q - 2 sum_j q_j sigma_j^2 ]                     (j == i included)
+ * which is the existing background for equal widths; the uniform constant 2 ke pi / V sum_j q_j sigma_j^2 is there for Q = 0 too.
+ * E_bg = 1/2 sum_i q_i phi_bg_i, with strain -E_bg delta_ab; the real-space virial and the listed pairs' virial are the existing sums
+ * with the new g; the self and on-site terms have no strain; gstrain_q = sum_k mu_k dq_k/d eps comes from the backward's strain rows.
+ * The cell entry runs at the ewald [B][6] numbers it is given, as epnn_coulomb_xyz_cell does; with sigma use
+ * epnn_ewald_params(cell, 0, tol).  It refuses by name a cell whose widest Gaussian does not fit the split: gamma_min = 1 / (2 sigma_max)
+ * >= beta is required, and the message names the cell, sigma_max and the largest width 1 / (2 beta) allowed (beyond it the
+ * erf(gamma D) tail at rc is no longer under what tol means; a larger tol or the caller's own row with a smaller beta moves the limit).
+ * With sigma NULL and alpha > 0 the existing rule (beta capped at alpha, rc = 0) applies unchanged.
+ * Outputs: those of the _excl entries plus mu_out[A]; mu_out, ffix_out, fq_out, gstrain_fix_out and gstrain_q_out may each be NULL
+ * and the other outputs have the same bits either way.
+ * Contract: that of the _excl entries, word for word: the pair-list path whatever "grad_path" says, no training state touched, waits
+ * for a "train_async" step, the same refusals with the handle left usable, no float atomics, every sum in a fixed order, a molecule's
+ * rows independent of the rest of the batch and of the list's order.  Refused by name besides: sigma with alpha > 0; a sigma that is
+ * zero, negative or not finite, or whose 2 sigma^2 is not a positive finite float32; chi or hard not finite; self_term other than 0 or
+ * 1, or 1 with neither sigma nor alpha > 0; a cell whose sigma_max exceeds 1 / (2 beta).
+ * Bits: q_out has the bits of epnn_charges_vjp_xyz[_cell] on "grad_path" 2; fq_out and gstrain_q_out are bit for bit -gxyz_out and
+ * gstrain_out of that entry called with g = mu_out; f == ffix + fq and gstrain == gstrain_fix + gstrain_q in float32.  With sigma, chi
+ * and hard all NULL and self_term = 0 the call runs the existing kernels: every output has the bits of epnn_coulomb_xyz_excl /
+ * _cell_excl on the same arguments, and mu_out == phi_out.
+ * Arithmetic: the sweeps and the listed pairs' kernel take a third pair-term mode, a template parameter beside "bare" and
+ * "erf(alpha)": the lane holds w_i = 2 sigma_i^2, the partners' w_j are staged beside their charges in LDS, gamma = rsqrtf(w_i + w_j)
+ * per pair, then the erff / g path of alpha > 0 with gamma for alpha (one add, one reciprocal square root and one multiply more in
+ * front of erff, about 4 * 2^-24 on the argument, and |u erf'(u)| <= erf(u): the bounds of the entries above hold).  One float4 per atom,
+ * (2 sigma^2, chi, J, gamma_ii), is made on the host in float64, rounded once and staged as one more span; the atoms' kernels add the
+ * self term to phi, write mu = chi + J q + phi into the seed and into mu_out, and q (chi + 1/2 J q) + 1/2 q phi into the energy share,
+ * in float64.  The on-site terms are exact float64 products of float32 values: they add 2 * 2^-24 of |chi_i| + |J_i q_i| to mu's error,
+ * its rounding to float32.  Cells: one wavefront per cell adds sum_j q_j 2 sigma_j^2 in the order of the energy sum.
+ * Device scratch (epnn_last_stats out[2]) on top of the _excl entry's on the same batch and list (for npairs == 0: the plain entry's),
+ * when any of sigma, chi, hard, self_term is given: the staged rows [A] float4, one buffer more (plus up to 256 of rounding), mu [A]
+ * at the end of the outputs' buffer and, in cells, the per-cell sums [B] float64 at the end of the sweep's buffer (a buffer that
+ * grows moves its rounding to 256 by less than 256 either way):
+ *     open      16 A + 4 A          periodic  16 A + 4 A + 8 B */
+int epnn_coulomb_xyz_site(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                          double ke, double alpha, const float *sigma, const float *chi, const float *hard, int self_term,
+                          int64_t npairs, const int32_t *ex_i, const int32_t *ex_j, const float *ex_scale,
+                          float *q_out, float *phi_out, float *mu_out, double *e_out, float *f_out, float *ffix_out, float *fq_out);
+int epnn_coulomb_xyz_cell_site(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                               const float *cell, const double *ewald, double ke, double alpha, const float *sigma, const float *chi,
+                               const float *hard, int self_term, int64_t npairs, const int32_t *ex_i, const int32_t *ex_j,
+                               const float *ex_scale, float *q_out, float *phi_out, float *mu_out, double *e_out, float *f_out,
                                float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out);
 /* ---- electrostatics of the predicted charges in slab cells: epnn_coulomb_xyz for two periodic axes and one open axis (surfaces,
  * membranes, electrodes, adsorbed layers), by the exact two-dimensional Ewald sum (Parry; Heyes, Barber and Clarke; de Leeuw and

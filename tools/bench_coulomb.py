@@ -39,7 +39,15 @@ is the strain call coulomb_xyz_slab_strain beside the plain slab call of the sam
 the formula of include/epnn.h, and the checks: q, phi, E, F, ffix, fq of the two calls (bits), gstrain_q against gs of the gradient
 call seeded with phi (bits), gstrain == gstrain_fix + gstrain_q and its symmetry (bits).  --against FILE: the JSON lines that
 `--slab` printed on another build (the parent commit) in the same session; adds the ratio of this build's plain call to that one's.
-With --trace: three calls of coulomb_xyz_slab_strain per system (k_sl_sweep_strain, k_sl_atom_strain, k_sl_energy_strain)."""
+With --trace: three calls of coulomb_xyz_slab_strain per system (k_sl_sweep_strain, k_sl_atom_strain, k_sl_energy_strain).
+    python tools/bench_coulomb.py --site [--cell] [--systems ...] [--rounds 5] [--alpha 0.0] [--near 2.2] [--tol 1e-6] [--trace]
+is the call with per-atom Gaussian widths, self-energy and on-site terms, coulomb_xyz_site or coulomb_xyz_cell_site, beside the _excl
+call of the same batch and list at --alpha, alternating on one handle (profiles/r25_coulomb_site.txt).  Widths, chi and J come from
+tables by element through engine.per_element; in cells the widths' table is scaled so that the widest Gaussian is 0.9 of the largest
+width 1 / (2 beta) the batch's cells allow.  Printed per system: the two medians and their ratio, the scratch the site data adds beside
+the formula of include/epnn.h, and the checks q (bits against the _excl call) and fq (and gstrain_q) against the gradient call
+seeded with mu (bits).  With --trace: three calls of the site entry per system (k_cl_sweep_site, k_ew_sweep_site, k_cl_atom_site,
+k_ew_atom_site, k_ew_wsum, k_ew_energy_site and the widths instances of k_cl_excl are the new kernels)."""
 import json
 import os
 import sys
@@ -351,6 +359,68 @@ def main_excl(eng, systems, rounds, alpha, tol, near, cell_mode):
         print(json.dumps(line), flush=True)
 
 
+# widths (A), electronegativities and hardnesses (eV, eV / e^2) by element for --site: round numbers of the size such models fit
+SITE_SIGMA = {1: 0.45, 6: 0.75, 7: 0.70, 8: 0.65, 9: 0.60, 15: 1.05, 16: 1.00, 17: 0.95, 35: 1.15}
+SITE_CHI = {1: -1.0, 6: 0.2, 7: 1.1, 8: 1.9, 9: 2.6, 15: -0.2, 16: 0.6, 17: 1.6, 35: 1.3}
+SITE_J = {1: 13.0, 6: 10.0, 7: 11.5, 8: 12.5, 9: 14.0, 15: 8.0, 16: 8.5, 17: 9.5, 35: 8.5}
+
+
+def main_site(eng, systems, rounds, alpha, tol, near, cell_mode):
+    from epnn_amd.engine import per_element
+    for system in systems:
+        if cell_mode:
+            name, offsets, xyz, x, Q, N, cells = load_cell(system)
+            rows = np.stack([eng.ewald_params(c, 0.0, tol) for c in cells])
+            rows_excl = np.stack([eng.ewald_params(c, alpha, tol) for c in cells])
+            kw, kw_excl = dict(cell=cells, ewald=rows, parts=True, strain=True), dict(cell=cells, ewald=rows_excl, parts=True, strain=True)
+            site_fn, excl_fn = eng.coulomb_xyz_cell_site, eng.coulomb_xyz_cell_excl
+        else:
+            name, offsets, xyz, x, Q, N = load(system)
+            cells, kw = None, dict(parts=True)
+            kw_excl = kw
+            site_fn, excl_fn = eng.coulomb_xyz_site, eng.coulomb_xyz_excl
+        A, B = int(offsets[-1]), len(offsets) - 1
+        sigma, chi, J = (per_element(x[:, 0], t) for t in (SITE_SIGMA, SITE_CHI, SITE_J))
+        if cell_mode:
+            sigma = (sigma * np.float32(0.9 * 0.5 / rows[:, 0].max() / max(SITE_SIGMA.values()))).astype(np.float32)
+        ex = exclusion_list(offsets, xyz, cells, near)
+        P = len(ex[0])
+        site_kw = dict(sigma=sigma, chi=chi, hardness=J, self_energy=True, exclusions=ex, **kw)
+        if "--trace" in sys.argv:
+            for _ in range(3):
+                site_fn(offsets, xyz, x, Q, N, **site_kw)
+            print(json.dumps({"workload": name, "atoms": A, "calls": 3, "listed_pairs": P}), flush=True)
+            continue
+        calls = {"excl": lambda: excl_fn(offsets, xyz, x, Q, N, alpha=alpha, exclusions=ex, **kw_excl),
+                 "site": lambda: site_fn(offsets, xyz, x, Q, N, **site_kw)}
+        for fn in calls.values():
+            fn()
+        times = {k: [] for k in calls}
+        outs, stats = {}, {}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t, outs[k] = window(fn)
+                stats[k] = eng.last_stats()
+                times[k].append(t * 1e3)
+        mu, fq = outs["site"][2], outs["site"][7 if cell_mode else 6]
+        seeded = eng.charges_vjp_xyz(offsets, xyz, x, Q, mu, N, **({"cell": cells, "strain": True} if cell_mode else {}))
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        line = {"workload": name, "atoms": A, "listed_pairs": P, "near": near, "rounds": rounds, "alpha_of_the_excl_call": alpha,
+                "sigma_range": [round(float(sigma.min()), 4), round(float(sigma.max()), 4)]}
+        for k, t in times.items():
+            line[k + "_ms_median"] = round(med[k], 3)
+            line[k + "_ms_range"] = [round(min(t), 3), round(max(t), 3)]
+        line.update({"site_over_excl": round(med["site"] / med["excl"], 4), "scratch_bytes_added": int(stats["site"][2]) - int(stats["excl"][2]),
+                     "scratch_formula_added": 20 * A + (8 * B if cell_mode else 0),
+                     "q_bits_equal_excl_call": bool(np.array_equal(outs["site"][0], outs["excl"][0])),
+                     "fq_bits_equal_minus_gxyz_of_mu": bool(np.array_equal(fq, -seeded[1])),
+                     "max_abs_phi": float(np.abs(outs["site"][1]).max()), "max_abs_mu": float(np.abs(mu).max()),
+                     "energy_sum_excl": float(outs["excl"][2].sum()), "energy_sum_site": float(outs["site"][3].sum())})
+        if cell_mode:
+            line["gstrain_q_bits_equal_gstrain_of_mu"] = bool(np.array_equal(outs["site"][9], seeded[2]))
+        print(json.dumps(line), flush=True)
+
+
 def main_cell(eng, T, systems, rounds, alpha, tol):
     for system in systems:
         name, offsets, xyz, x, Q, N, cells = load_cell(system)
@@ -411,6 +481,10 @@ def main():
         return
     if slab_mode:
         main_slab(eng, T, systems, rounds, alpha, float(arg("--tol", "1e-6")))
+        eng.close()
+        return
+    if "--site" in sys.argv:
+        main_site(eng, systems, rounds, alpha, float(arg("--tol", "1e-6")), float(arg("--near", "2.2")), cell_mode)
         eng.close()
         return
     if "--excl" in sys.argv:

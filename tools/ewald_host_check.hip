@@ -2,7 +2,8 @@
 // (epnn_ewald_params, epnn_ewald_slab_params), the check of an `ewald` row (ew_row_check through ew_cell_row and sl_cell_row), the
 // slab's slot list, the task builders (cl_build_tasks, ew_build_tasks) and the driver's byte layout (coulomb_layout) -- run on the CPU
 // over the shapes of tests/test_gpu_coulomb_cell.py and tests/test_gpu_coulomb_slab.py, with every task checked against the arrays it
-// indexes and every layout against the formulas of include/epnn.h.  No HIP call is made: build it for the host
+// indexes and every layout against the formulas of include/epnn.h; and the site entries' argument checks and per-atom rows (site_build,
+// site_width_check) on arrays of exactly the stated lengths.  No HIP call is made: build it for the host
 // with the sanitizers and run it, from the repository root:
 //     hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -ffinite-math-only -Xarch_host -fsanitize=address,undefined \
 //           -Xarch_host -fno-sanitize-recover=undefined -o /tmp/ewald_host_check tools/ewald_host_check.hip -L/opt/rocm/lib -lrccl \
@@ -122,6 +123,80 @@ static void check_layouts() {
     }
 }
 
+// The site entries' host part: site_build reads exactly A values of each array it is given (the arrays here are heap blocks of exactly
+// that length: a read past them is the sanitizer's to report) and writes A rows, each the float64 formula rounded once; every
+// refusal of include/epnn.h; the cells' width check at and around its limit; the layout's added segments.
+static void check_site() {
+    const std::vector<int> ns = {70, 1, 33, 120};
+    const int B = (int)ns.size();
+    std::vector<int32_t> offsets(B + 1, 0);
+    for (int b = 0; b < B; ++b) offsets[b + 1] = offsets[b] + ns[b];
+    const int A = offsets[B];
+    std::vector<float> sigma(A), chi(A), hard(A);
+    for (int a = 0; a < A; ++a) {
+        sigma[a] = 0.3f + 0.9f * (float)((a * 37) % 101) / 100.f;
+        chi[a] = (float)((a * 17) % 23) / 7.f - 1.5f;
+        hard[a] = 2.f + (float)((a * 5) % 13);
+    }
+    for (int self_term : {0, 1})
+        for (int mask = 0; mask < 8; ++mask) {
+            const float *sg = mask & 1 ? sigma.data() : nullptr, *ch = mask & 2 ? chi.data() : nullptr, *hd = mask & 4 ? hard.data() : nullptr;
+            for (double alpha : {0.0, 0.7}) {
+                CoulombSite site;
+                const int rc = site_build("check", B, offsets.data(), alpha, sg, ch, hd, self_term, site);
+                const bool refused = (sg && alpha > 0.0) || (self_term && !sg && !(alpha > 0.0));
+                EXPECT(rc == (refused ? 1 : 0));
+                if (rc) continue;
+                EXPECT((int)site.rows.size() == A && (int)site.sigma_max.size() == B && site.widths == (sg != nullptr));
+                for (int b = 0; b < B; ++b) {
+                    double top = 0.0;
+                    for (int a = offsets[b]; a < offsets[b + 1]; ++a) {
+                        const float4 r = site.rows[a];
+                        const double s = (double)sigma[a];
+                        EXPECT(r.x == (sg ? (float)(2.0 * s * s) : 0.f) && r.y == (ch ? chi[a] : 0.f) && r.z == (hd ? hard[a] : 0.f));
+                        EXPECT(r.w == (self_term ? (float)(sg ? 0.5 / s : alpha) : 0.f));
+                        EXPECT(epnn_finite(r.x) && epnn_finite(r.w) && (!sg || r.x > 0.f));
+                        top = std::max(top, s);
+                    }
+                    EXPECT(site.sigma_max[b] == (sg ? top : 0.0));
+                }
+            }
+        }
+    CoulombSite sink;
+    auto with = [&](std::vector<float> &v, int k, float bad, const float *sg, const float *ch, const float *hd) {
+        const float keep = v[k];
+        v[k] = bad;
+        const int rc = site_build("check", B, offsets.data(), 0.0, sg, ch, hd, 0, sink);
+        v[k] = keep;
+        return rc;
+    };
+    // (infinities and a NaN come as their bits: this program is built with -ffinite-math-only, where they may not be named as floats)
+    auto bits = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+    const float inf = bits(0x7f800000u), minf = bits(0xff800000u), nan = bits(0x7fc00000u);
+    for (float bad : {0.f, -0.5f, inf, minf, nan, 1e-30f, 1e25f}) EXPECT(with(sigma, A - 1, bad, sigma.data(), nullptr, nullptr) == 1);
+    EXPECT(with(sigma, 0, 1e-19f, sigma.data(), nullptr, nullptr) == 0 && with(sigma, 0, 1e18f, sigma.data(), nullptr, nullptr) == 0);
+    for (float bad : {inf, minf, nan}) {
+        EXPECT(with(chi, 7, bad, sigma.data(), chi.data(), hard.data()) == 1 && with(hard, A - 1, bad, nullptr, chi.data(), hard.data()) == 1);
+        EXPECT(with(chi, 7, bad, sigma.data(), nullptr, hard.data()) == 0);                // (an array that is not given is not read)
+    }
+    EXPECT(site_build("check", B, offsets.data(), 0.0, sigma.data(), nullptr, nullptr, 2, sink) == 1);
+    EXPECT(site_build("check", B, offsets.data(), 0.0, sigma.data(), nullptr, nullptr, -1, sink) == 1);
+    // the width check: gamma_min = 1 / (2 sigma_max) >= beta
+    EXPECT(site_width_check("check", 0, 0.5, 1.0) == 0 && site_width_check("check", 0, 0.5000001, 1.0) == 1 && site_width_check("check", 0, 0.0, 1.0) == 0);
+    EXPECT(site_width_check("check", 2, 1.2, 0.3) == 0 && site_width_check("check", 2, 1.2, 0.42) == 1);
+    // the layout: mu behind the strain rows, the per-cell sums behind rec, the rows' span; nothing else moves
+    const size_t nct = 21, nat = 9, nst = 37, cp = 3, slots = 5819;
+    for (CoulombKind kind : {CL_OPEN, CL_CELL}) {
+        const bool strain = kind == CL_CELL;
+        const CoulombLayout P = coulomb_layout(kind, strain, (size_t)A, (size_t)B, nct, nat, nst, cp, slots),
+                            S = coulomb_layout(kind, strain, (size_t)A, (size_t)B, nct, nat, nst, cp, slots, true);
+        EXPECT(P.site_bytes == 0 && P.mu == 0 && P.wsum == 0 && S.site_bytes == (size_t)A * 16);
+        EXPECT(S.blob_bytes == P.blob_bytes && S.E == P.E && S.gsf == P.gsf && S.mu == P.co_bytes && S.co_bytes == P.co_bytes + (size_t)A * 4);
+        EXPECT(S.part_bytes == P.part_bytes && S.share == P.share && S.S == P.S && S.rec == P.rec);
+        EXPECT(kind == CL_OPEN ? S.sc_bytes == P.sc_bytes : (S.wsum == P.sc_bytes && S.sc_bytes == P.sc_bytes + (size_t)B * 8 && S.wsum % 8 == 0));
+    }
+}
+
 int main() {
     const float cube8[9] = {8, 0, 0, 0, 8, 0, 0, 0, 8}, sheared[9] = {7, 0, 0, 1.5f, 6.5f, 0, -1, 2, 8}, slab[9] = {6, 0, 0, 0, 6, 0, 0, 0, 20},
                 cube14[9] = {14, 0, 0, 0, 14, 0, 0, 0, 14}, open_z[9] = {8, 0, 0, 0, 8, 0, 0, 0, 0}, needle[9] = {6, 0, 0, 0, 6, 0, 0, 0, 20000};
@@ -155,6 +230,7 @@ int main() {
             check_slab_batch({70, 1, 33, 120, 300}, {sq65, sl_sheared, tilted, openy, sq14}, alpha, tol);
         }
     check_layouts();
+    check_site();
     // the shared row check through the slab path
     SlGeom G;
     SlCell c;
