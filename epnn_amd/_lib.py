@@ -95,6 +95,11 @@ SIGNATURES = {
                                         C.c_int64, _ip, _ip, _fp, _fp, _fp, C.POINTER(C.c_double), _fp, _fp, _fp]),
     "epnn_coulomb_xyz_slab_strain": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), C.c_double, C.c_double,
                                                C.c_int64, _ip, _ip, _fp, _fp, _fp, C.POINTER(C.c_double), _fp, _fp, _fp, _fp, _fp, _fp]),
+    "epnn_coulomb_xyz_slab_site": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                             _fp, _fp, _fp, C.c_int, C.c_int64, _ip, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), _fp, _fp, _fp]),
+    "epnn_coulomb_xyz_slab_strain_site": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                                    _fp, _fp, _fp, C.c_int, C.c_int64, _ip, _ip, _fp, _fp, _fp, _fp, C.POINTER(C.c_double), _fp, _fp,
+                                                    _fp, _fp, _fp, _fp]),
     "epnn_charges_jvp_multi_xyz_cell": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "epnn_charges_vjp_multi_xyz_cell": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp]),
     "epnn_comm_unique_id": (C.c_int, [C.c_char_p]),

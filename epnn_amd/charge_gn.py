@@ -440,6 +440,15 @@ class EPNNModel(_Stack):
                                                  tol=tol, ewald=ewald, sigma=sigma, chi=chi, hardness=hardness, self_energy=self_energy,
                                                  exclusions=exclusions, parts=parts, strain=strain)
 
+    def coulomb_xyz_slab_site(self, offsets, xyz, x, Q, N=None, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                              sigma=None, chi=None, hardness=None, self_energy=True, exclusions=None, parts=False, strain=False):
+        """coulomb_xyz_site in slab cells, by the exact two-dimensional Ewald sum: (q, phi, mu, E, F[, gstrain][, parts]); strain=True
+        adds the strain derivative.  No background term, for charged slabs too.  A cell whose widest Gaussian does not fit the split
+        (sigma_max > 1 / (2 beta)) is refused by name.  N defaults to natom."""
+        return self._eng().coulomb_xyz_slab_site(offsets, xyz, x, Q, self.natom if N is None else N, cell=cell, box=box, ke=ke, alpha=alpha,
+                                                 tol=tol, ewald=ewald, sigma=sigma, chi=chi, hardness=hardness, self_energy=self_energy,
+                                                 exclusions=exclusions, parts=parts, strain=strain)
+
     def coulomb_xyz_cell_excl(self, offsets, xyz, x, Q, N=None, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
                               parts=False, strain=False, exclusions=None):
         """coulomb_xyz_cell with bonded exclusions and pair scaling: the nearest image of every listed pair counts with weight scale.

@@ -64,8 +64,9 @@ static CoulombLayout coulomb_layout(CoulombKind kind, bool strain, size_t A, siz
 // The driver of the six entries: the pair-list gradient call with its seed made on the device.  Set-up and checkpointed forward; on
 // that forward's charges the real-space sweep, the listed pairs' correction (ex), the rest of the sum by its kind and the energy,
 // phi = dE/dq into the seed; the shared backward; one download.  sum->strain: the fixed-charge strain rows are made, the backward runs
-// with its strain flag and the download carries both strain rows (the cells' entries always, the slab's strain entry).  site (open and
-// cells): the per-atom rows of the site entries; the atoms' kernels are the _site ones, the seed is mu, and with widths the sweeps too.
+// with its strain flag and the download carries both strain rows (the cells' entries always, the slab's strain entries).  site (every
+// kind): the per-atom rows of the site entries; the atoms' kernels are the _site ones, the seed is mu, and with widths the real-space
+// sweeps too (slabs: k_ew_sweep_site, as in cells; the reciprocal and k = 0 sweep is the point charges', unchanged).
 static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                        const HostGeo &geo, double ke, double alpha, const CoulombSum *sum, const ExclCsr *ex, const CoulombOut &out,
                        const CoulombSite *site) {
@@ -176,6 +177,20 @@ static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int
     case CL_SLAB:
         hipLaunchKernelGGL((strain ? k_sl_sweep_strain : k_sl_sweep), gsweep, wave, 0, h->stream, d_ctasks, c.d_moff, c.d_molof, c.d_xyz, q_dev, d_sl,
                            d_slots, A, rpart);
+        if (site) {                                              // (the sweeps above are the point charges': the site terms are the atoms' alone)
+            if (strain) {
+                hipLaunchKernelGGL(k_sl_atom_strain_site, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl,
+                                   (const double *)part, (const double *)rpart, (const double *)xpart, d_site, ke, r.gq, phi, mu, ffix, share,
+                                   wshare);
+                hipLaunchKernelGGL(k_sl_energy_strain, gmol, wave, 0, h->stream, (const double *)share, (const double *)wshare, c.d_moff, E, gsf);
+                break;
+            }
+            hipLaunchKernelGGL((ex ? k_sl_atom_site<true> : k_sl_atom_site<false>), dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof,
+                               q_dev, d_sl, (const double *)part, (const double *)rpart, (const double *)xpart, d_site, ke, r.gq, phi, mu, ffix,
+                               share);
+            hipLaunchKernelGGL(k_cl_energy, gmol, wave, 0, h->stream, (const double *)share, c.d_moff, E);
+            break;
+        }
         if (strain) {
             hipLaunchKernelGGL(k_sl_atom_strain, dim3(c.gA), dim3(256), 0, h->stream, A, c.d_moff, c.d_molof, q_dev, d_sl, (const double *)part,
                                (const double *)rpart, (const double *)xpart, ke, r.gq, phi, ffix, share, wshare);

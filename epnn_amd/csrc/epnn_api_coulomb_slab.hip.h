@@ -107,10 +107,13 @@ static int sl_cell_row(const char *what, int b, const float *cell, const double 
     return 0;
 }
 
-// the two slab entries: the checks, the cells' rows and slots, the list; out.gs: the strain entry's required output, or NULL
+// the slab entries: the checks, the cells' rows and slots, the list; out.gs: the strain entries' required output, or NULL.  sa: the
+// _site entries' arguments (epnn_api_site.hip.h): the per-atom rows and the slab case of the width check, sigma_max against the row's beta;
+// with nothing in them the call is the plain entry's (the existing kernels) and mu is phi
 static int coulomb_slab_enter(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x,
                               const float *Q, const float *cell, const double *ewald, double ke, double alpha, int64_t npairs,
-                              const int32_t *ex_i, const int32_t *ex_j, const float *ex_scale, bool strain, const CoulombOut &out) {
+                              const int32_t *ex_i, const int32_t *ex_j, const float *ex_scale, bool strain, const CoulombOut &out,
+                              const SiteArgs *sa = nullptr) {
     if (!cell || !ewald || !out.phi || !out.e || (strain && !out.gs)) EPNN_FAIL("%s: null argument", name);
     if (!epnn_finite(ke)) EPNN_FAIL("%s: ke must be finite", name);
     if (!epnn_finite(alpha) || alpha < 0.0) EPNN_FAIL("%s: alpha must be finite and not negative (0: bare Coulomb)", name);
@@ -131,8 +134,13 @@ static int coulomb_slab_enter(epnn_handle *h, const char *name, int B, int N, co
     const ExclArgs xa{npairs, ex_i, ex_j, ex_scale};
     ExclCsr ex;
     if (excl_build(name, B, offsets, npairs, ex_i, ex_j, ex_scale, ex)) return 1;
+    CoulombSite site;
+    if (sa && site_build(name, B, offsets, alpha, sa->sigma, sa->chi, sa->hard, sa->self_term, site)) return 1;
+    for (int b = 0; sa && b < B; ++b)
+        if (site_width_check(name, b, site.sigma_max[b], ewald[6 * (size_t)b])) return 1;
     const CoulombSum sum{CL_SLAB, strain, &ew, &sl, &slots, &xa};
-    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, &sum, npairs > 0 ? &ex : nullptr, out);
+    return coulomb_run(h, name, B, N, offsets, xyz, x, Q, arg.geo, ke, alpha, &sum, npairs > 0 ? &ex : nullptr, out,
+                       site_plain(sa) ? nullptr : &site);
 }
 
 extern "C" int epnn_coulomb_xyz_slab(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,

@@ -192,10 +192,13 @@ __global__ __launch_bounds__(64) void k_sl_sweep_strain(const int4 *tasks, const
 // STRAIN (the rows of k_sl_sweep_strain): the same additions in the same order, and the atom's strain shares wshare [A][SL_SHARE_W]
 // (xx yy zz yz xz xy) in float64: -1/2 ke q_i times its virial row (the six sums behind the four, the listed pairs' added behind the
 // sweep's, as k_ew_atom does) and 1/2 ke q_i times the reciprocal and k = 0 sums, expanded through g_a, g_b and nhat.
-template <bool X, bool STRAIN>
+// SITE (epnn_coulomb_xyz_slab_site, _slab_strain_site): site [A] = (2 sigma^2, chi, J, gamma_ii; gamma_ii 0 without the self term).  phi
+// gets the Gaussians' self term ke 2 gamma_ii q_i / sqrt(pi) behind the split's; mu = chi + J q + phi goes into the seed and into
+// mu [A], phi into phi [A] only; the share is q (chi + 1/2 J q) + 1/2 q phi.  Neither term has a strain: wshare is made as without SITE.
+template <bool X, bool STRAIN, bool SITE = false>
 __device__ __forceinline__ void sl_atom_body(int A, const int *moff, const int *mol_of, const float *q, const SlCell *sl, const double *part,
                                              const double *rpart, const double *xpart, double ke, float *seed, float *phi, float *ffix,
-                                             double *share, double *wshare) {
+                                             double *share, double *wshare, const float4 *site = nullptr, float *mu = nullptr) {
     constexpr int NS = STRAIN ? SL_PART_STRAIN : SL_PART;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A) return;
@@ -209,10 +212,20 @@ __device__ __forceinline__ void sl_atom_body(int A, const int *moff, const int *
     s[0] += r[0];
     if (X)
         for (int c = 0; c < 4; ++c) s[c] += xpart[(size_t)i * EW_PART + c];
-    const double qi = (double)q[i], p = ke * (s[0] - sl[b].self * qi);
-    seed[i] = phi[i] = (float)p;
-    for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
-    share[i] = 0.5 * qi * p;
+    const double qi = (double)q[i];
+    if constexpr (SITE) {
+        const float4 st = site[i];
+        const double p = ke * ((s[0] - sl[b].self * qi) + 1.1283791670955126 * (double)st.w * qi), chi = (double)st.y, J = (double)st.z;
+        phi[i] = (float)p;
+        seed[i] = mu[i] = (float)(chi + J * qi + p);
+        for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
+        share[i] = qi * (chi + 0.5 * J * qi) + 0.5 * qi * p;
+    } else {                                                     // (the statements of the plain entries, in their order)
+        const double p = ke * (s[0] - sl[b].self * qi);
+        seed[i] = phi[i] = (float)p;
+        for (int c = 0; c < 3; ++c) ffix[3 * (size_t)i + c] = (float)(ke * qi * s[1 + c]);
+        share[i] = 0.5 * qi * p;
+    }
     if (STRAIN) {
         double v[SL_SHARE_W] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, t[SL_PART_STRAIN - SL_PART] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int k = 0; k < np; ++k)
@@ -249,6 +262,20 @@ __global__ __launch_bounds__(256) void k_sl_atom_strain(int A, const int *moff, 
                                                         float *phi, float *ffix, double *share, double *wshare) {
     if (xpart) sl_atom_body<true, true>(A, moff, mol_of, q, sl, part, rpart, xpart, ke, seed, phi, ffix, share, wshare);
     else sl_atom_body<false, true>(A, moff, mol_of, q, sl, part, rpart, nullptr, ke, seed, phi, ffix, share, wshare);
+}
+// the atoms' kernels of epnn_coulomb_xyz_slab_site (X: with a list) and of epnn_coulomb_xyz_slab_strain_site (xpart NULL: no list)
+template <bool X>
+__global__ __launch_bounds__(256) void k_sl_atom_site(int A, const int *moff, const int *mol_of, const float *q, const SlCell *sl,
+                                                      const double *part, const double *rpart, const double *xpart, const float4 *site, double ke,
+                                                      float *seed, float *phi, float *mu, float *ffix, double *share) {
+    sl_atom_body<X, false, true>(A, moff, mol_of, q, sl, part, rpart, xpart, ke, seed, phi, ffix, share, nullptr, site, mu);
+}
+__global__ __launch_bounds__(256) void k_sl_atom_strain_site(int A, const int *moff, const int *mol_of, const float *q, const SlCell *sl,
+                                                             const double *part, const double *rpart, const double *xpart, const float4 *site,
+                                                             double ke, float *seed, float *phi, float *mu, float *ffix, double *share,
+                                                             double *wshare) {
+    if (xpart) sl_atom_body<true, true, true>(A, moff, mol_of, q, sl, part, rpart, xpart, ke, seed, phi, ffix, share, wshare, site, mu);
+    else sl_atom_body<false, true, true>(A, moff, mol_of, q, sl, part, rpart, nullptr, ke, seed, phi, ffix, share, wshare, site, mu);
 }
 
 // One wavefront per cell: E_b by k_cl_energy's additions on the same shares (its bits), and the fixed-charge strain derivative

@@ -700,8 +700,23 @@ class Engine:
         return self._coulomb("coulomb_xyz_slab_strain", offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, True),
                              exclusions=exclusions, slab=True)
 
+    def coulomb_xyz_slab_site(self, offsets, xyz, x, Q, N, cell=None, box=None, ke=KE_EV_ANGSTROM, alpha=0.0, tol=1e-6, ewald=None,
+                              sigma=None, chi=None, hardness=None, self_energy=True, exclusions=None, parts=False, strain=False):
+        """coulomb_xyz_site in slab cells (epnn_coulomb_xyz_slab_site, with strain=True epnn_coulomb_xyz_slab_strain_site): the exact
+        two-dimensional Ewald sum of coulomb_xyz_slab with gamma_ij in its real-space term and in the listed pairs' term, the
+        Gaussians' self-energy and the on-site terms -> (q, phi, mu, E, F[, gstrain][, ffix, fq[, gstrain_fix, gstrain_q]]).  No
+        background term and no per-pair k = 0 correction, for charged slabs too: the Gaussians' sum differs from the point charges'
+        by a short-ranged real-space sum alone.  ewald=None: ewald_slab_params(cell, alpha, tol) per cell (alpha is 0 with sigma).  A
+        cell whose widest Gaussian does not fit the split, sigma_max > 1 / (2 beta), is refused by name.  fq and gstrain_q are -gxyz
+        and gstrain of charges_vjp_xyz(g=mu, cell=, strain=True) on "grad_path" 2, bit for bit.  With nothing given and
+        self_energy=False the outputs have the bits of coulomb_xyz_slab / coulomb_xyz_slab_strain and mu is phi."""
+        where = "coulomb_xyz_slab_strain_site" if strain else "coulomb_xyz_slab_site"
+        _slab_box(where, box, cell)
+        return self._coulomb(where, offsets, xyz, x, Q, N, ke, alpha, parts, periodic=(cell, box, tol, ewald, bool(strain)),
+                             exclusions=exclusions, slab=True, site=(sigma, chi, hardness, self_energy))
+
     def _coulomb(self, where, offsets, xyz, x, Q, N, ke, alpha, parts, periodic=None, exclusions=None, slab=False, site=None):
-        """The eight coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
+        """The coulomb_xyz* methods: where names the method in an error, periodic = (cell, box, tol, ewald, strain) or None for open
         molecules, exclusions = (pairs, scale) or None for the plain C entry (an _excl method without a list is its plain method).
         slab: the two slab entries, which always take a list (None: an empty one) and their own rule; the plain one has no strain
         rows, the other one is chosen by its name.  site = (sigma, chi, hardness, self_energy): the two _site entries, which always

@@ -579,7 +579,7 @@ int epnn_coulomb_xyz_cell_excl(epnn_handle *h, int B, int N, const int32_t *offs
  * QEq-style models driven by predicted charges; INTEGRATION.md, "Charge-model energies: widths, hardness, electronegativity"),
  *     E = sum_i (chi_i q_i + 1/2 J_i q_i^2) + ke sum_i q_i^2 / (2 sqrt(pi) sigma_i) + ke sum_{i<j} q_i q_j erf(gamma_ij D_ij) / D_ij,
  *     gamma_ij = 1 / sqrt(2 (sigma_i^2 + sigma_j^2)),
- * for open molecules and fully periodic cells.  A caller cannot add these terms afterwards: phi is the backward's seed on the device,
+ * for open molecules and fully periodic cells (slabs: epnn_coulomb_xyz_slab_site below).  A caller cannot add these terms afterwards: phi is the backward's seed on the device,
  * and a term of dE/dq added outside leaves fq and the charges' part of the strain wrong.
  * New inputs, all host arrays, float32, one value per real atom:
  *     sigma[A]     may be NULL: every pair then uses the call's alpha, as in the entries above.  Otherwise every value is finite and
@@ -747,6 +747,60 @@ int epnn_coulomb_xyz_slab_strain(epnn_handle *h, int B, int N, const int32_t *of
                                  const float *cell, const double *ewald, double ke, double alpha, int64_t npairs, const int32_t *ex_i,
                                  const int32_t *ex_j, const float *ex_scale, float *q_out, float *phi_out, double *e_out, float *f_out,
                                  float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out);
+/* ---- per-atom Gaussian widths, self-energy and on-site terms in slab cells: the energy of epnn_coulomb_xyz_site / _cell_site (its
+ * block above has E, gamma_ij, the new inputs sigma, chi, hard, self_term and what they mean) for two periodic axes and one open one.
+ * epnn_coulomb_xyz_slab_site takes epnn_coulomb_xyz_slab's arguments with sigma, chi, hard, self_term behind alpha and mu_out behind
+ * phi_out, epnn_coulomb_xyz_slab_strain_site the same on epnn_coulomb_xyz_slab_strain: the order of epnn_coulomb_xyz_cell_site.  The
+ * sum of epnn_coulomb_xyz_slab (its notation) changes as follows:
+ *     real         kappa_s(D) = [erf(gamma_ij D) - erf(beta D)] / D over the minimum image, D <= rc; with sigma NULL gamma_ij is alpha
+ *     reciprocal, k = 0 and the split's self term -(2 beta / sqrt(pi)) q_i: the point charges' sums, unchanged
+ *     self         [self_term]  phi_i += 2 gamma_ii q_i / sqrt(pi),   gamma_ii = 1 / (2 sigma_i), or alpha when sigma is NULL
+ *     listed       (s - 1) times the bare erf(gamma_ij D) / D term of the one nearest image, whatever beta
+ *     mu_i   = chi_i + J_i q_i + phi_i                        = dE/dq_i, the seed of the backward
+ *     E      = sum_i [ chi_i q_i + 1/2 J_i q_i^2 + 1/2 q_i phi_i ]   per cell (float64)
+ *     fq_i   = -sum_k mu_k dq_k/dr_i,     f = ffix + fq
+ * all of phi times ke; chi and J are not multiplied by ke.  There is no background term and no per-pair k = 0 correction, for charged
+ * slabs too, and this is the one point where the slab differs from epnn_coulomb_xyz_cell_site: the Gaussians' sum equals the point
+ * charges' sum minus sum over images erfc(gamma_ij D) / D, that difference is short-ranged and is summed in real space (the real term
+ * above, inside the width check), and the constant dropped for a charged sheet depends on neither beta nor gamma.  (tests/
+ * test_slab_site_ref.py pins it: E equals the Gaussians' own two-dimensional sum, the reciprocal and k = 0 formulas with beta = gamma_ij
+ * per pair, for Q = 0 and Q != 0.)
+ * Strain: gstrain_fix of epnn_coulomb_xyz_slab_strain with the new kappa_s' in the real-space virial and kappa_gamma' in the listed
+ * pairs' virial; the self and on-site terms have no strain and nothing is added for a background.  gstrain_q = sum_k mu_k dq_k/d eps
+ * comes from the backward's strain rows, and gstrain = gstrain_fix + gstrain_q.
+ * Width check: a cell whose gamma_min = 1 / (2 sigma_max) is below its row's beta is refused by name, in the words of
+ * epnn_coulomb_xyz_cell_site: the cell, sigma_max and the largest width 1 / (2 beta) allowed.  With widths the caller takes
+ * epnn_ewald_slab_params(cell, 0, tol); sigma NULL with alpha > 0 keeps the existing rule (beta capped at alpha, rc = 0).
+ * Refusals: those of the _site entries above, word for word (sigma with alpha > 0; a sigma that is zero, negative or not finite, or
+ * whose 2 sigma^2 is not a positive finite float32; chi or hard not finite; self_term other than 0 or 1, or 1 with neither sigma nor
+ * alpha > 0; the width check), and everything epnn_coulomb_xyz_slab refuses (cubes, wires, the row checks, the list's checks, a listed
+ * pair beyond half the smaller width); the handle stays usable.  Contract otherwise: epnn_coulomb_xyz_slab's, word for word.
+ * Outputs: those of the slab entries plus mu_out[A]; mu_out, ffix_out, fq_out, gstrain_fix_out and gstrain_q_out may each be NULL and
+ * the other outputs have the same bits either way (gstrain_out is required by the strain entry).
+ * Bits: q_out has the bits of epnn_charges_vjp_xyz_cell on "grad_path" 2; fq_out and gstrain_q_out are bit for bit -gxyz_out and
+ * gstrain_out of that entry called with g = mu_out; f == ffix + fq and gstrain == gstrain_fix + gstrain_q in float32; gstrain_fix and
+ * gstrain are bitwise symmetric; q, phi, mu, e, f, ffix and fq of the strain entry are those of the plain one.  With sigma, chi and
+ * hard all NULL and self_term = 0 the call runs the existing slab kernels: every output has the bits of epnn_coulomb_xyz_slab /
+ * _slab_strain on the same arguments, and mu_out == phi_out.
+ * Arithmetic: the real-space sweep with widths is epnn_coulomb_xyz_cell_site's (k_ew_sweep_site, with its virial sums), the listed
+ * pairs' kernel its widths mode through the minimum image; the reciprocal and k = 0 sweeps are the slab entries' as they are.  The
+ * atoms' kernels get a site form: they add the Gaussian self term to phi behind the split's, write mu into the seed and into mu_out,
+ * and q (chi + 1/2 J q) + 1/2 q phi into the energy share, in float64, as the open and periodic site kernels do.  The bounds of the
+ * slab entries hold with 2 * 2^-24 more of the self and on-site terms (the rounding of phi and mu to float32).
+ * Device scratch (epnn_last_stats out[2]) when any of sigma, chi, hard, self_term is given: the slab entry's on the same batch and
+ * list (epnn_coulomb_xyz_slab's, or _slab_strain's) plus the staged rows [A] float4, one buffer more (plus up to 256 of rounding), and
+ * mu [A] at the end of the outputs' buffer; slabs have no per-cell sum:
+ *     bytes = the slab entry's + 16 A + 4 A */
+int epnn_coulomb_xyz_slab_site(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                               const float *cell, const double *ewald, double ke, double alpha, const float *sigma, const float *chi,
+                               const float *hard, int self_term, int64_t npairs, const int32_t *ex_i, const int32_t *ex_j,
+                               const float *ex_scale, float *q_out, float *phi_out, float *mu_out, double *e_out, float *f_out,
+                               float *ffix_out, float *fq_out);
+int epnn_coulomb_xyz_slab_strain_site(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
+                                      const float *cell, const double *ewald, double ke, double alpha, const float *sigma, const float *chi,
+                                      const float *hard, int self_term, int64_t npairs, const int32_t *ex_i, const int32_t *ex_j,
+                                      const float *ex_scale, float *q_out, float *phi_out, float *mu_out, double *e_out, float *f_out,
+                                      float *gstrain_out, float *ffix_out, float *fq_out, float *gstrain_fix_out, float *gstrain_q_out);
 /* ---- training on periodic and large systems. epnn_train_step_xyz with a cell: cell [B][3][3] (host) has exactly the meaning and
  * the checks of epnn_forward_xyz_cell (zero rows are open axes, a perpendicular width below 2 * cutoff is refused, a diagonal cell
  * is an orthorhombic box), NULL means open molecules.  Loss = sum (y - p)^2 over the real atoms; the gradient goes into the handle's

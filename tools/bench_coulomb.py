@@ -47,7 +47,14 @@ tables by element through engine.per_element; in cells the widths' table is scal
 width 1 / (2 beta) the batch's cells allow.  Printed per system: the two medians and their ratio, the scratch the site data adds beside
 the formula of include/epnn.h, and the checks q (bits against the _excl call) and fq (and gstrain_q) against the gradient call
 seeded with mu (bits).  With --trace: three calls of the site entry per system (k_cl_sweep_site, k_ew_sweep_site, k_cl_atom_site,
-k_ew_atom_site, k_ew_wsum, k_ew_energy_site and the widths instances of k_cl_excl are the new kernels)."""
+k_ew_atom_site, k_ew_wsum, k_ew_energy_site and the widths instances of k_cl_excl are the new kernels).
+    python tools/bench_coulomb.py --slab --site [--strain] [--systems qm9slab,slab2048,slab10000] [--rounds 5] [--near 2.2] [--tol 1e-6] [--trace]
+is the slab call with per-atom widths, self-energy and on-site terms, coulomb_xyz_slab_site, beside coulomb_xyz_slab with the same list,
+alternating on one handle (profiles/r26_coulomb_slab_site.txt); with --strain the two strain entries.  Widths, chi and J by element as
+for --site, the widths scaled down only where the widest would exceed 0.9 of the largest width 1 / (2 beta) the batch's cells allow (the
+6.5 A slabs).  Printed per system: the two medians and their ratio, the scratch the site data adds beside 20 A, and the checks q (bits
+against the slab call) and fq (with --strain gstrain_q too) against the gradient call seeded with mu (bits).  With --trace: three calls
+of the site entry per system (k_sl_atom_site or k_sl_atom_strain_site are the new kernels; k_ew_sweep_site is the real-space part)."""
 import json
 import os
 import sys
@@ -421,6 +428,82 @@ def main_site(eng, systems, rounds, alpha, tol, near, cell_mode):
         print(json.dumps(line), flush=True)
 
 
+def exclusion_list_slab(offsets, xyz, cells, near):
+    """exclusion_list for rectangular slab cells open along z: every pair of a cell nearer than `near` through the in-plane minimum image"""
+    from scipy.spatial import cKDTree
+    out = []
+    for b in range(len(offsets) - 1):
+        a0, a1 = int(offsets[b]), int(offsets[b + 1])
+        if a1 - a0 < 2:
+            continue
+        c = cells[b]
+        assert np.array_equal(c, np.diag([c[0, 0], c[1, 1], 0])), "the list maker takes rectangular slab cells open along z"
+        L = np.float64([c[0, 0], c[1, 1], 1e6])
+        r = xyz[a0:a1].astype(np.float64)
+        r[:, 2] -= r[:, 2].min()
+        r[:, :2] -= L[:2] * np.floor(r[:, :2] / L[:2])
+        p = cKDTree(r, boxsize=L).query_pairs(near, output_type="ndarray")
+        if len(p):
+            out.append(np.sort(p, 1) + a0)
+    pairs = np.concatenate(out) if out else np.zeros((0, 2), np.int64)
+    pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]
+    scale = np.float32([0.0, 0.5, 0.8333])[np.arange(len(pairs)) % 3]
+    rng = np.random.default_rng(11)
+    o = rng.permutation(len(pairs))
+    pairs, scale = pairs[o], scale[o]
+    swap = rng.permutation(len(pairs))[:len(pairs) // 2]
+    pairs[swap] = pairs[swap][:, ::-1]
+    return np.ascontiguousarray(pairs.astype(np.int32)), scale
+
+
+def main_slab_site(eng, systems, rounds, tol, near, strain):
+    """--slab --site [--strain]: coulomb_xyz_slab_site beside coulomb_xyz_slab (or, with --strain, the two strain entries) with the same
+    list, alternating on one handle.  Widths by element, scaled down where the widest Gaussian would exceed 0.9 of 1 / (2 beta_max)."""
+    from epnn_amd.engine import per_element
+    for system in systems:
+        name, offsets, xyz, x, Q, N, cells, thick = load_slab(system)
+        A = int(offsets[-1])
+        rows = np.stack([eng.ewald_slab_params(c, 0.0, tol) for c in cells])
+        sigma, chi, J = (per_element(x[:, 0], t) for t in (SITE_SIGMA, SITE_CHI, SITE_J))
+        sigma = (sigma * np.float32(min(1.0, 0.9 * 0.5 / rows[:, 0].max() / max(SITE_SIGMA.values())))).astype(np.float32)
+        ex = exclusion_list_slab(offsets, xyz, cells, near)
+        P = len(ex[0])
+        kw = dict(cell=cells, ewald=rows, parts=True, exclusions=ex)
+        plain_fn = eng.coulomb_xyz_slab_strain if strain else eng.coulomb_xyz_slab
+        site_kw = dict(sigma=sigma, chi=chi, hardness=J, self_energy=True, strain=strain, **kw)
+        if "--trace" in sys.argv:
+            for _ in range(3):
+                eng.coulomb_xyz_slab_site(offsets, xyz, x, Q, N, **site_kw)
+            print(json.dumps({"workload": name, "atoms": A, "calls": 3, "listed_pairs": P, "strain": strain}), flush=True)
+            continue
+        calls = {"slab": lambda: plain_fn(offsets, xyz, x, Q, N, **kw), "site": lambda: eng.coulomb_xyz_slab_site(offsets, xyz, x, Q, N, **site_kw)}
+        for fn in calls.values():
+            fn()
+        times = {k: [] for k in calls}
+        outs, stats = {}, {}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t, outs[k] = window(fn)
+                stats[k] = eng.last_stats()
+                times[k].append(t * 1e3)
+        mu, fq = outs["site"][2], outs["site"][7 if strain else 6]
+        seeded = eng.charges_vjp_xyz(offsets, xyz, x, Q, mu, N, cell=cells, strain=True)
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        line = {"workload": name, "atoms": A, "cells": len(cells), "strain": strain, "listed_pairs": P, "near": near, "rounds": rounds, "tol": tol,
+                "k_slots": slab_slots(cells, rows), "sigma_range": [round(float(sigma.min()), 4), round(float(sigma.max()), 4)]}
+        for k, t in times.items():
+            line[k + "_ms_median"] = round(med[k], 3)
+            line[k + "_ms_range"] = [round(min(t), 3), round(max(t), 3)]
+        line.update({"site_over_slab": round(med["site"] / med["slab"], 4), "scratch_bytes_added": int(stats["site"][2]) - int(stats["slab"][2]),
+                     "scratch_formula_added": 20 * A, "q_bits_equal_slab_call": bool(np.array_equal(outs["site"][0], outs["slab"][0])),
+                     "fq_bits_equal_minus_gxyz_of_mu": bool(np.array_equal(fq, -seeded[1])),
+                     "max_abs_phi": float(np.abs(outs["site"][1]).max()), "max_abs_mu": float(np.abs(mu).max()),
+                     "energy_sum_slab": float(outs["slab"][2].sum()), "energy_sum_site": float(outs["site"][3].sum())})
+        if strain:
+            line["gstrain_q_bits_equal_gstrain_of_mu"] = bool(np.array_equal(outs["site"][9], seeded[2]))
+        print(json.dumps(line), flush=True)
+
+
 def main_cell(eng, T, systems, rounds, alpha, tol):
     for system in systems:
         name, offsets, xyz, x, Q, N, cells = load_cell(system)
@@ -475,6 +558,10 @@ def main():
     eng = Engine(nx=9, T=T)
     eng.set_weights(w)
     eng.set_option("grad_path", 2)
+    if slab_mode and "--site" in sys.argv:
+        main_slab_site(eng, systems, rounds, float(arg("--tol", "1e-6")), float(arg("--near", "2.2")), "--strain" in sys.argv)
+        eng.close()
+        return
     if slab_mode and "--strain" in sys.argv:
         main_slab_strain(eng, T, systems, rounds, alpha, float(arg("--tol", "1e-6")), arg("--against", None))
         eng.close()

@@ -3,7 +3,8 @@
 // slab's slot list, the task builders (cl_build_tasks, ew_build_tasks) and the driver's byte layout (coulomb_layout) -- run on the CPU
 // over the shapes of tests/test_gpu_coulomb_cell.py and tests/test_gpu_coulomb_slab.py, with every task checked against the arrays it
 // indexes and every layout against the formulas of include/epnn.h; and the site entries' argument checks and per-atom rows (site_build,
-// site_width_check) on arrays of exactly the stated lengths.  No HIP call is made: build it for the host
+// site_width_check) on arrays of exactly the stated lengths, the slab case of the width check and the slab kind of the layout
+// (epnn_coulomb_xyz_slab_site) included.  No HIP call is made: build it for the host
 // with the sanitizers and run it, from the repository root:
 //     hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -ffinite-math-only -Xarch_host -fsanitize=address,undefined \
 //           -Xarch_host -fno-sanitize-recover=undefined -o /tmp/ewald_host_check tools/ewald_host_check.hip -L/opt/rocm/lib -lrccl \
@@ -186,14 +187,35 @@ static void check_site() {
     EXPECT(site_width_check("check", 2, 1.2, 0.3) == 0 && site_width_check("check", 2, 1.2, 0.42) == 1);
     // the layout: mu behind the strain rows, the per-cell sums behind rec, the rows' span; nothing else moves
     const size_t nct = 21, nat = 9, nst = 37, cp = 3, slots = 5819;
-    for (CoulombKind kind : {CL_OPEN, CL_CELL}) {
-        const bool strain = kind == CL_CELL;
-        const CoulombLayout P = coulomb_layout(kind, strain, (size_t)A, (size_t)B, nct, nat, nst, cp, slots),
-                            S = coulomb_layout(kind, strain, (size_t)A, (size_t)B, nct, nat, nst, cp, slots, true);
-        EXPECT(P.site_bytes == 0 && P.mu == 0 && P.wsum == 0 && S.site_bytes == (size_t)A * 16);
-        EXPECT(S.blob_bytes == P.blob_bytes && S.E == P.E && S.gsf == P.gsf && S.mu == P.co_bytes && S.co_bytes == P.co_bytes + (size_t)A * 4);
-        EXPECT(S.part_bytes == P.part_bytes && S.share == P.share && S.S == P.S && S.rec == P.rec);
-        EXPECT(kind == CL_OPEN ? S.sc_bytes == P.sc_bytes : (S.wsum == P.sc_bytes && S.sc_bytes == P.sc_bytes + (size_t)B * 8 && S.wsum % 8 == 0));
+    for (CoulombKind kind : {CL_OPEN, CL_CELL, CL_SLAB})
+        for (bool strain : {false, true}) {
+            if (strain != (kind == CL_CELL) && kind != CL_SLAB) continue;            // (open: never, cells: always, slabs: both entries)
+            const CoulombLayout P = coulomb_layout(kind, strain, (size_t)A, (size_t)B, nct, nat, nst, cp, slots),
+                                S = coulomb_layout(kind, strain, (size_t)A, (size_t)B, nct, nat, nst, cp, slots, true);
+            EXPECT(P.site_bytes == 0 && P.mu == 0 && P.wsum == 0 && S.site_bytes == (size_t)A * 16);
+            EXPECT(S.blob_bytes == P.blob_bytes && S.E == P.E && S.gsf == P.gsf && S.mu == P.co_bytes && S.co_bytes == P.co_bytes + (size_t)A * 4);
+            EXPECT(S.part_bytes == P.part_bytes && S.share == P.share && S.S == P.S && S.rec == P.rec);
+            EXPECT(S.rpart == P.rpart && S.wshare == P.wshare && S.ew == P.ew && S.sl == P.sl && S.slot == P.slot);
+            // slabs have no per-cell sum: the sweeps' buffer does not grow
+            EXPECT(kind != CL_CELL ? (S.sc_bytes == P.sc_bytes && S.wsum == 0)
+                                   : (S.wsum == P.sc_bytes && S.sc_bytes == P.sc_bytes + (size_t)B * 8 && S.wsum % 8 == 0));
+        }
+}
+
+// The slab case of the width check (epnn_coulomb_xyz_slab_site): at the beta of the slab rule, tol = 1e-6 and alpha = 0, a cell's widest
+// Gaussian passes at 1 / (2 beta) and is refused just above it, in the words of the periodic entry: the cell, sigma_max and the limit.
+static void check_slab_width(const std::vector<const float *> &cells) {
+    const char *name = "epnn_coulomb_xyz_slab_site";
+    for (int b = 0; b < (int)cells.size(); ++b) {
+        double row[6];
+        EXPECT(epnn_ewald_slab_params(cells[b], 0.0, 1e-6, row) == 0 && row[1] > 0.0);
+        const double limit = 0.5 / row[0];
+        EXPECT(site_width_check(name, b, limit, row[0]) == 0 && site_width_check(name, b, 0.4 * limit, row[0]) == 0);
+        EXPECT(site_width_check(name, b, 0.0, row[0]) == 0);                           // (no widths given: sigma_max is 0)
+        EXPECT(site_width_check(name, b, limit * (1.0 + 1e-9), row[0]) == 1);
+        char want[256];
+        snprintf(want, sizeof(want), "%s: cell %d: sigma_max = %g is above the largest width 1 / (2 beta) = %g ", name, b, limit * (1.0 + 1e-9), limit);
+        EXPECT(strncmp(epnn_last_error(), want, strlen(want)) == 0);
     }
 }
 
@@ -231,6 +253,7 @@ int main() {
         }
     check_layouts();
     check_site();
+    check_slab_width({sq65, sl_sheared, tilted, openy, sq14});
     // the shared row check through the slab path
     SlGeom G;
     SlCell c;
