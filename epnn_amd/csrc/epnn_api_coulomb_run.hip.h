@@ -104,7 +104,7 @@ static int coulomb_run(epnn_handle *h, const char *name, int B, int N, const int
                              GlSpan{site ? site->rows.data() : nullptr, L.site_bytes, false}};
     const size_t more[3] = {L.co_bytes, L.sc_bytes, ex ? excl_xpart_bytes(A, sum != nullptr) : 0};
     GlGrad r;
-    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, spans, site ? 3 : ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
+    if (gl_grad_forward(h, gl, name, B, N, offsets, xyz, x, Q, geo, 1, spans, site ? 3 : ex ? 2 : 1, more, ex ? 3 : 2, false, r)) return 1;
     const GlCall &c = r.c;
     char *co = c.dw + r.o_more[0], *sc = c.dw + r.o_more[1];
     float *phi = reinterpret_cast<float *>(co), *ffix = phi + A, *gsf = reinterpret_cast<float *>(co + L.gsf);

@@ -18,55 +18,89 @@ static void xyz_grad_release(epnn_handle *h) {
 }
 
 // ------------------------------------------------------------------------------------------------ pair-list path ("grad_path")
-// State, weights, the call's set-up and the checkpointed forward: epnn_api_pairlist.hip.h.  Here: this entry's scratch and its backward.
+// State, weights, the call's set-up and the checkpointed forward: epnn_api_pairlist.hip.h.  Here: the reverse-mode entries' scratch and
+// their one backward, for K cotangents (kernels: epnn_vjp_multi.hip.h; the single-cotangent entries are K = 1).
 // One call of a reverse-mode entry, in the two pieces its entries share: gl_grad_forward (set-up, scratch, checkpointed forward) and
-// gl_grad_backward (the backward from a seed already on the device, in r.gq).  Between the two an entry writes its seed.
+// gl_grad_backward (the backward from K seeds already on the device, in r.gq).  Between the two an entry writes its seeds.
 struct GlGrad {
     GlCall c;
     size_t o_slotx, o_share, o_more[3];                          // o_more: the entry's own buffers, placed behind the shared ones
     float *hck, *Sck, *qck, *dP, *dR, *Yb, *Yc, *dS, *partP, *partR, *slotP, *slotR, *slotq, *gE, *gh, *ghp;
-    float *out, *gq, *q_fin, *gx, *gs;                           // out: [A] gq | [A] q | [A][3] gxyz | bad | [B][9] gstrain
+    float *out, *gq, *q_fin, *gx, *gs;                           // out: [K][A] gq | [A] q | [K][A][3] gxyz | bad | [K][B][9] gstrain
     int *bad;
 };
 
+// K: the cotangents; the backward's rows (dS, partP, partR, slotP, slotR, gE, gh, ghp, slotx, share, out) are K copies of one
+// cotangent's, cotangent t at t times that size (the forward uses the first copy of partP and slotP as its scratch).
 // spans: the entry's own staged inputs (r.c.d_extra); more[k] bytes: buffers of the entry alone (r.o_more[k]; the first one follows
-// `out` directly), more_pairs[k]: further bytes of buffer k per listed pair (P1 of them: the count is not known before the call);
-// in_cap: epnn_last_stats counts the staged inputs with their buffer's capacity, not with this call's bytes.
+// `out` directly); in_cap: epnn_last_stats counts the staged inputs with their buffer's capacity, not with this call's bytes.
 static int gl_grad_forward(epnn_handle *h, GradLarge *gl, const char *where, int B, int N, const int32_t *offsets, const float *xyz,
-                           const float *x, const float *Q, const HostGeo &geo, const GlSpan *spans, int n_spans, const size_t *more, int n_more,
-                           bool in_cap, GlGrad &r, const size_t *more_pairs = nullptr) {
+                           const float *x, const float *Q, const HostGeo &geo, int K, const GlSpan *spans, int n_spans, const size_t *more,
+                           int n_more, bool in_cap, GlGrad &r) {
     const int T = h->cfg.T, A = offsets[B];
     GlCall &c = r.c;
     if (gl_call_count(h, gl, where, B, N, offsets, xyz, x, Q, geo, spans, n_spans, c)) return 1;
-    const size_t P1 = c.P1, SL = 2 * P1, rowH = (size_t)A * GL_H * 4, rowE = (size_t)A * GL_E * 4, maxp = (size_t)c.maxp;
+    const size_t Kz = (size_t)K, P1 = c.P1, SL = 2 * P1, rowH = (size_t)A * GL_H * 4, rowE = (size_t)A * GL_E * 4, maxp = (size_t)c.maxp;
     const size_t o_h = c.place((size_t)(T + 1) * rowE), o_S = c.place((size_t)T * rowH),
                  o_q = c.place((size_t)(T + 1) * A * 4), o_P = c.place(rowH), o_R = c.place(rowH), o_Yb = c.place(rowH), o_Yc = c.place(rowH),
-                 o_dS = c.place(rowH), o_partP = c.place(maxp * rowH), o_partR = c.place(maxp * rowH),
-                 o_slotP = c.place(SL * GL_H * 4), o_slotR = c.place(SL * GL_H * 4), o_slotq = c.place(SL * 4), o_gE = c.place(P1 * GL_E * 4),
-                 o_gh = c.place(rowE), o_ghp = c.place(rowE), o_slotx = c.place(SL * 72), o_share = c.place((size_t)A * 48),
-                 o_out = c.place(((size_t)A * 5 + 1 + (size_t)B * 9) * 4);
-    for (int k = 0; k < n_more; ++k) r.o_more[k] = c.place(more[k] + (more_pairs ? more_pairs[k] * P1 : 0));
+                 o_dS = c.place(Kz * rowH), o_partP = c.place(Kz * maxp * rowH), o_partR = c.place(Kz * maxp * rowH),
+                 o_slotP = c.place(Kz * SL * GL_H * 4), o_slotR = c.place(Kz * SL * GL_H * 4), o_slotq = c.place(SL * 4),
+                 o_gE = c.place(Kz * P1 * GL_E * 4), o_gh = c.place(Kz * rowE), o_ghp = c.place(Kz * rowE), o_slotx = c.place(Kz * SL * 72),
+                 o_share = c.place(Kz * A * 48), o_out = c.place(((size_t)A + Kz * ((size_t)A * 4 + (size_t)B * 9) + 1) * 4);
+    for (int k = 0; k < n_more; ++k) r.o_more[k] = c.place(more[k]);
     if (gl_call_fill(h, gl, c, in_cap ? gl->in.cap : c.in_total)) return 1;
     r.o_slotx = o_slotx; r.o_share = o_share;
     r.hck = c.fp(o_h); r.Sck = c.fp(o_S); r.qck = c.fp(o_q); r.dP = c.fp(o_P); r.dR = c.fp(o_R); r.Yb = c.fp(o_Yb); r.Yc = c.fp(o_Yc);
     r.dS = c.fp(o_dS); r.partP = c.fp(o_partP); r.partR = c.fp(o_partR); r.slotP = c.fp(o_slotP); r.slotR = c.fp(o_slotR);
     r.slotq = c.fp(o_slotq); r.gE = c.fp(o_gE); r.gh = c.fp(o_gh); r.ghp = c.fp(o_ghp); r.out = c.fp(o_out);
     r.gq = r.out;
-    r.q_fin = r.out + A; r.gx = r.out + 2 * (size_t)A;
-    r.bad = reinterpret_cast<int *>(r.out + 5 * (size_t)A);
-    r.gs = r.out + 5 * (size_t)A + 1;
+    r.q_fin = r.out + Kz * A; r.gx = r.q_fin + A;
+    r.bad = reinterpret_cast<int *>(r.gx + Kz * A * 3);
+    r.gs = r.gx + Kz * A * 3 + 1;
     return gl_forward_ckpt(h, c, gl->msg, gl->pas, gl->upd, r.hck, r.Sck, r.qck, r.dP, r.dR, r.Yb, r.Yc, r.partP, r.slotP, r.slotq);
 }
 
-static void launch_gl_pair_xyz(epnn_handle *h, const GlCall &c, const float *gE, double *slotx, int *bad);      // (below)
+// A backward sweep over K cotangents in chunks, the widest instantiated k_gl_sweep<MODE, KC> that fits what is left (jvm_chunk: K = 7
+// runs 4 + 2 + 1, K = 1 the one-row kernel).  dS, out: the first cotangent's, the next at dstride / ostride floats.
+template <int MODE>
+static void gvm_sweep_launch(epnn_handle *h, const GlCall &c, int K, const float *W2, const float *Xres, const float *Xstr, const float *Y,
+                             const float *dS, size_t dstride, float *out, size_t ostride) {
+    for (int k0 = 0; k0 < K;) {
+        const int kc = jvm_chunk(K - k0);
+        const float *cd = dS + k0 * dstride;
+        float *co = out + k0 * ostride;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(c.nt), dim3(64), 0, h->stream, c.d_tasks, c.d_moff, c.G.A, W2, Xres, Xstr, Y, cd, dstride, co, ostride,
+                               (int)c.nt, 1, (float *)nullptr);
+        };
+        if (kc == 4) launch(k_gl_sweep<MODE, 4>);
+        else if (kc == 2) launch(k_gl_sweep<MODE, 2>);
+        else launch(k_gl_sweep<MODE, 1>);
+        k0 += kc;
+    }
+}
 
-// The backward from the seed in r.gq (overwritten), down to gxyz (r.gx), the strain derivative (r.gs; want_strain) and the final
-// charges beside them (r.q_fin): everything up to the entry's download.
-static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, bool want_strain) {
+// The listed pairs' edge gradients gE [K][P1][48] -> their coordinate slots, in the call's geometry (box rows: K = 1 only, the multi
+// entry takes cells)
+template <int KM>
+static void launch_gvm_pair_xyz(epnn_handle *h, const GlCall &c, int K, const float *gE, double *slotx, int *bad) {
+    geo_dispatch(c.geo.kind, [&](auto kind) {
+        if constexpr (decltype(kind)::value != GEO_BOX || KM == 1)
+            hipLaunchKernelGGL((k_gvm_pair_xyz<decltype(kind)::value, KM>), dim3((unsigned)((c.np + 255) / 256)), dim3(256), 0, h->stream, c.L, c.np,
+                               K, c.P1, 2 * c.P1, c.d_molof, c.d_xyz, c.geo.words(), gE, (double)h->cfg.cutoff, (double)h->cfg.eta,
+                               h->d_mu.as<double>(), slotx, bad);
+    });
+}
+
+// The backward from the K seeds in r.gq (overwritten), down to gxyz (r.gx), the strain derivative (r.gs; want_strain) and the final
+// charges beside them (r.q_fin): everything up to the entry's download.  The per-pair and per-atom kernels are chosen by the bucket
+// of K (jvm_bucket).
+static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, int K, bool want_strain) {
     const GlCall &c = r.c;
+    if (c.geo.kind == GEO_BOX && K > 1) EPNN_FAIL("gl_grad_backward: internal error (box rows with K = %d: the coordinate kernel takes them at K = 1 only)", K);
     const int T = h->cfg.T, A = c.G.A, np = c.np;
-    const size_t P1 = c.P1;
-    const unsigned nt = c.nt, gP = (unsigned)np, gA = c.gA;
+    const size_t Kz = (size_t)K, P1 = c.P1, SL = 2 * P1;
+    const unsigned gP = (unsigned)np, gA = c.gA;
     const GlGeom &G = c.G;
     const GlPairs &L = c.L;
     const int *inc = c.inc;
@@ -74,64 +108,70 @@ static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, boo
     float *hck = r.hck, *Sck = r.Sck, *qck = r.qck, *dP = r.dP, *dR = r.dR, *Yb = r.Yb, *Yc = r.Yc, *dS = r.dS, *partP = r.partP,
           *partR = r.partR, *slotP = r.slotP, *slotR = r.slotR, *gE = r.gE, *gh = r.gh, *ghp = r.ghp, *gq = r.gq, *gx = r.gx, *gs = r.gs;
     int *bad = r.bad;
-    const size_t nH = (size_t)A * GL_H, nE = (size_t)A * GL_E;
+    const size_t nH = (size_t)A * GL_H, nE = (size_t)A * GL_E, pstride = (size_t)c.maxp * nH;
     const dim3 w64(64);
     const float *feats = hck + T * nE;
     // ---- backward: EPN stack
-    HIPCHK(hipMemsetAsync(gh, 0, nE * 4, h->stream));
-    HIPCHK(hipMemsetAsync(gE, 0, P1 * GL_E * 4, h->stream));
+    HIPCHK(hipMemsetAsync(gh, 0, Kz * nE * 4, h->stream));
+    HIPCHK(hipMemsetAsync(gE, 0, Kz * P1 * GL_E * 4, h->stream));
     HIPCHK(hipMemsetAsync(bad, 0, 4, h->stream));
     for (int t = T - 1; t >= 0; --t) {
         hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, gl->pas[t], G, d_x, feats, (const float *)(qck + (size_t)t * A), d_Q, dP, dR,
                            (float *)nullptr, (float *)nullptr);
         if (np > 0)
-            hipLaunchKernelGGL(k_gl_epn_pair<1>, dim3(gP), w64, 0, h->stream, gl->pas[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)gq, (float *)nullptr, slotP, slotR, gE, GlTape{});
-        hipLaunchKernelGGL(k_gl_epn_atom_bwd, dim3(A), w64, 0, h->stream, gl->pas[t], G, inc, (const float *)slotP, (const float *)slotR, gh, gq, GlTape{});
+            jvm_bucket(K, [&](auto km) {
+                hipLaunchKernelGGL((k_gvm_epn_pair<decltype(km)::value>), dim3(gP), w64, 0, h->stream, gl->pas[t], L, K, A, P1, SL, (const float *)dP,
+                                   (const float *)dR, (const float *)gq, slotP, slotR, gE, GlTape{});
+            });
+        jvm_bucket(K, [&](auto km) {
+            hipLaunchKernelGGL((k_gvm_epn_atom_bwd<decltype(km)::value>), dim3(A), w64, 0, h->stream, gl->pas[t], G, K, SL, inc, (const float *)slotP,
+                               (const float *)slotR, gh, gq, GlTape{});
+        });
     }
     HIPCHK(hipGetLastError());
     // ---- backward: GNN steps
     for (int t = T - 1; t >= 0; --t) {
         const float *ht = t ? hck + t * nE : nullptr;
-        hipLaunchKernelGGL(k_gl_upd_bwd, dim3(A), w64, 0, h->stream, gl->msg[t], gl->upd, G, ht, (const float *)(Sck + t * nH), (const float *)gh,
-                           ghp, dS, GlTape{});
+        jvm_bucket(K, [&](auto km) {
+            hipLaunchKernelGGL((k_gvm_upd_bwd<decltype(km)::value>), dim3(A), w64, 0, h->stream, gl->msg[t], gl->upd, G, K, ht,
+                               (const float *)(Sck + t * nH), (const float *)gh, ghp, dS, GlTape{});
+        });
         hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, gl->msg[t], G, d_x, ht, (const float *)nullptr, d_Q, dP, dR, Yb, Yc);
         if (t == 0) {                                            // a_i of step 0 is constant: only dG of the listed pairs
             if (np > 0)
-                hipLaunchKernelGGL(k_gl_gnn_pair<1>, dim3(gP), w64, 0, h->stream, gl->msg[t], L, (const float *)dP, (const float *)dR,
-                                   (const float *)dS, (float *)nullptr, (float *)nullptr, gE, GlTape{});
+                jvm_bucket(K, [&](auto km) {
+                    hipLaunchKernelGGL((k_gvm_gnn_pair<decltype(km)::value>), dim3(gP), w64, 0, h->stream, gl->msg[t], L, K, A, P1, SL,
+                                       (const float *)dP, (const float *)dR, (const float *)dS, (float *)nullptr, (float *)nullptr, gE, GlTape{});
+                });
             break;
         }
-        hipLaunchKernelGGL(k_gl_sweep<1>, dim3(nt), w64, 0, h->stream, c.d_tasks, c.d_moff, A, gl->msg[t].W2, (const float *)dP, (const float *)dR,
-                           (const float *)Yb, (const float *)dS, partP, (int)nt, 1, (float *)nullptr);
-        hipLaunchKernelGGL(k_gl_sweep<2>, dim3(nt), w64, 0, h->stream, c.d_tasks, c.d_moff, A, gl->msg[t].W2, (const float *)dR, (const float *)dP,
-                           (const float *)Yc, (const float *)dS, partR, (int)nt, 1, (float *)nullptr);
+        gvm_sweep_launch<1>(h, c, K, gl->msg[t].W2, dP, dR, Yb, dS, nH, partP, pstride);
+        gvm_sweep_launch<2>(h, c, K, gl->msg[t].W2, dR, dP, Yc, dS, nH, partR, pstride);
         if (np > 0)
-            hipLaunchKernelGGL(k_gl_gnn_pair<1>, dim3(gP), w64, 0, h->stream, gl->msg[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)dS, slotP, slotR, gE, GlTape{});
-        hipLaunchKernelGGL(k_gl_gnn_atom_bwd, dim3(A), w64, 0, h->stream, gl->msg[t], G, inc, (const float *)partP, (const float *)partR,
-                           (const float *)slotP, (const float *)slotR, (const float *)dP, (const float *)dS, ghp, GlTape{});
+            jvm_bucket(K, [&](auto km) {
+                hipLaunchKernelGGL((k_gvm_gnn_pair<decltype(km)::value>), dim3(gP), w64, 0, h->stream, gl->msg[t], L, K, A, P1, SL, (const float *)dP,
+                                   (const float *)dR, (const float *)dS, slotP, slotR, gE, GlTape{});
+            });
+        jvm_bucket(K, [&](auto km) {
+            hipLaunchKernelGGL((k_gvm_gnn_atom_bwd<decltype(km)::value>), dim3(A), w64, 0, h->stream, gl->msg[t], G, K, pstride, SL, inc,
+                               (const float *)partP, (const float *)partR, (const float *)slotP, (const float *)slotR, (const float *)dP,
+                               (const float *)dS, ghp, GlTape{});
+        });
         std::swap(gh, ghp);
     }
     HIPCHK(hipGetLastError());
     // ---- edges -> coordinates
     double *slotx = reinterpret_cast<double *>(c.dw + r.o_slotx), *share = want_strain ? reinterpret_cast<double *>(c.dw + r.o_share) : nullptr;
-    if (np > 0) launch_gl_pair_xyz(h, c, gE, slotx, bad);
-    hipLaunchKernelGGL(k_gl_atom_xyz, dim3(gA), dim3(256), 0, h->stream, A, inc, (const double *)slotx, gx, share);
-    if (share) hipLaunchKernelGGL(k_g_strain_mol, dim3((unsigned)B), dim3(64), 0, h->stream, (const double *)share, c.d_moff, gs);
+    if (np > 0) jvm_bucket(K, [&](auto km) { launch_gvm_pair_xyz<decltype(km)::value>(h, c, K, gE, slotx, bad); });
+    hipLaunchKernelGGL(k_gvm_atom_xyz, dim3(gA, (unsigned)K), dim3(256), 0, h->stream, A, SL, inc, (const double *)slotx, gx, share);
+    if (share) hipLaunchKernelGGL(k_gvm_strain_mol, dim3((unsigned)B, (unsigned)K), dim3(64), 0, h->stream, A, (const double *)share, c.d_moff, gs);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(r.q_fin, qck + (size_t)T * A, (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 
-// The listed pairs' edge gradients gE -> their coordinate slots, in the call's geometry.  (Behind its caller: kernels are emitted in the
-// order the host code first names them, and a build's device listing is compared with its parent's.)
-static void launch_gl_pair_xyz(epnn_handle *h, const GlCall &c, const float *gE, double *slotx, int *bad) {
-    geo_dispatch(c.geo.kind, [&](auto kind) {
-        hipLaunchKernelGGL(k_gl_pair_xyz<decltype(kind)::value>, dim3((unsigned)((c.np + 255) / 256)), dim3(256), 0, h->stream, c.L, c.np,
-                           c.d_molof, c.d_xyz, c.geo.words(), gE, (double)h->cfg.cutoff, (double)h->cfg.eta, h->d_mu.as<double>(), slotx, bad);
-    });
-}
+// one cotangent: the single VJP and the Coulomb entries
+static int gl_grad_backward(epnn_handle *h, GradLarge *gl, GlGrad &r, int B, bool want_strain) { return gl_grad_backward(h, gl, r, B, 1, want_strain); }
 
 static int charges_vjp_large_impl(epnn_handle *h, const char *name, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
                                   const float *g, float *q_out, float *gxyz_out, const HostGeo &geo, float *gstrain_out) {
@@ -141,7 +181,7 @@ static int charges_vjp_large_impl(epnn_handle *h, const char *name, int B, int N
     const std::string where = std::string(name) + " (pair-list path)";
     const GlSpan span_g{g, (size_t)A * 4, false};
     GlGrad r;
-    if (gl_grad_forward(h, gl, where.c_str(), B, N, offsets, xyz, x, Q, geo, &span_g, 1, nullptr, 0, true, r)) return 1;
+    if (gl_grad_forward(h, gl, where.c_str(), B, N, offsets, xyz, x, Q, geo, 1, &span_g, 1, nullptr, 0, true, r)) return 1;
     HIPCHK(hipMemcpyAsync(r.gq, r.c.d_extra[0], (size_t)A * 4, hipMemcpyDeviceToDevice, h->stream));    // the seed: the staged g
     if (gl_grad_backward(h, gl, r, B, gstrain_out != nullptr)) return 1;
     const float *q_fin = r.q_fin;

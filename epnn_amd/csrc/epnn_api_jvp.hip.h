@@ -4,25 +4,12 @@
 #pragma once
 #include "epnn_jvp.hip.h"
 
-// The sweep carries the tangents in chunks: the widest instantiated k_jvm_sweep<KC> that fits what is left, so K = 7 runs 4 + 2 + 1.
-static int jvm_chunk(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
-
+// (jvm_chunk, jvm_bucket: epnn_api_pairlist.hip.h, shared with the reverse-mode backward)
 template <int KC>
 static void jvm_sweep_launch(epnn_handle *h, const GlCall &c, const float *W2, const float *P, const float *tP, const float *R, const float *Yb,
                              const float *tR, size_t tstride, float *outS, float *outT, size_t ostride) {
     hipLaunchKernelGGL(k_jvm_sweep<KC>, dim3(c.nt), dim3(64), 0, h->stream, c.d_tasks, c.d_moff, c.G.A, W2, P, tP, R, Yb, tR, tstride, outS, outT,
                        ostride, (int)c.nt);
-}
-
-// The per-pair and per-atom kernels are instantiated for buckets of K, KM = 1, 2, 4, 8, 16: launch(km) is called with the bucket
-// as an integral constant, the way jvm_sweep_launch<KC> is chosen by the chunk width.
-template <class Launch>
-static void jvm_bucket(int K, Launch &&launch) {
-    if (K <= 1) launch(std::integral_constant<int, 1>{});
-    else if (K <= 2) launch(std::integral_constant<int, 2>{});
-    else if (K <= 4) launch(std::integral_constant<int, 4>{});
-    else if (K <= 8) launch(std::integral_constant<int, 8>{});
-    else launch(std::integral_constant<int, 16>{});
 }
 
 // The listed pairs' edge tangents te in the call's geometry: open molecules or cells (charges_jvp_multi_impl refuses box rows: no box instance)

@@ -1,10 +1,12 @@
 // What the pair-list entries share on the host: the state GradLarge, their weights, one call's set-up (GlCall: staged inputs, the
 // front-end's pair list, the work buffer) and the checkpointed forward of the two reverse-mode entries.  Entries:
 // charges_vjp_large_impl (epnn_api_grad.hip.h, "grad_path"), train_step_large_impl (epnn_api_train_large.hip.h, "train_path"),
-// charges_jvp_multi_impl (epnn_api_jvp.hip.h), coulomb_run (epnn_api_coulomb_run.hip.h, through the gradient call's two pieces).  Host code only; kernels: epnn_frontend.hip.h, epnn_grad_large.hip.h.
+// charges_jvp_multi_impl (epnn_api_jvp.hip.h), coulomb_run (epnn_api_coulomb_run.hip.h, through the gradient call's two pieces).  Host code only; kernels: epnn_frontend.hip.h, epnn_grad_large.hip.h
+// (forward, sweep), epnn_vjp_multi.hip.h (backward).
 // Part of the one translation unit epnn_api.hip.
 #pragma once
 #include "epnn_grad_large.hip.h"
+#include "epnn_vjp_multi.hip.h"
 
 // ------------------------------------------------------------------------------------------------ pair-list path ("grad_path")
 // The same result from the pair list (kernels and arithmetic: epnn_grad_large.hip.h): per-atom rows, the near pairs of the
@@ -32,6 +34,21 @@ static bool grad_large_possible(const epnn_handle *h) { return !h->upd_generic &
 // automatic routing: the dense path while its [B][N][N] tensors stay small (no caller of this repository's tests, bench or tools
 // is above it, so every call that ran before takes the path it took)
 static bool grad_large_auto(int B, int N) { return (size_t)B * (size_t)N * (size_t)N > ((size_t)1 << 22); }
+
+// ------------------------------------------------------------------------------------------------ K tangents or cotangents
+// A sweep carries them in chunks: the widest instantiated kernel that fits what is left, so K = 7 runs 4 + 2 + 1.
+static int jvm_chunk(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
+
+// The per-pair and per-atom kernels are instantiated for buckets of K, KM = 1, 2, 4, 8, 16: launch(km) is called with the bucket
+// as an integral constant.
+template <class Launch>
+static void jvm_bucket(int K, Launch &&launch) {
+    if (K <= 1) launch(std::integral_constant<int, 1>{});
+    else if (K <= 2) launch(std::integral_constant<int, 2>{});
+    else if (K <= 4) launch(std::integral_constant<int, 4>{});
+    else if (K <= 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 16>{});
+}
 
 // ------------------------------------------------------------------------------------------------ weights
 // Dense: HostDense (the handle's host copies) or TDense (the training state's flat vector); F = nx + 48 + 1 input features per atom
@@ -226,10 +243,9 @@ static int gl_forward_ckpt(epnn_handle *h, const GlCall &c, const GlPair *msg, c
         const float *ht = t ? hck + t * nE : nullptr;
         hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, msg[t], G, c.d_x, ht, (const float *)nullptr, c.d_Q, dP, dR, Yb, Yc);
         hipLaunchKernelGGL(k_gl_sweep<0>, dim3(nt), w64, 0, h->stream, c.d_tasks, c.d_moff, A, msg[t].W2, (const float *)dP, (const float *)dR,
-                           (const float *)Yb, (const float *)nullptr, partP, (int)nt, 1, (float *)nullptr);
+                           (const float *)Yb, (const float *)nullptr, (size_t)0, partP, (size_t)0, (int)nt, 1, (float *)nullptr);
         if (np > 0)
-            hipLaunchKernelGGL(k_gl_gnn_pair<0>, dim3(gP), w64, 0, h->stream, msg[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)nullptr, slotP, (float *)nullptr, (float *)nullptr, GlTape{});
+            hipLaunchKernelGGL(k_gl_gnn_pair, dim3(gP), w64, 0, h->stream, msg[t], L, (const float *)dP, (const float *)dR, slotP);
         hipLaunchKernelGGL(k_gl_gnn_tail, dim3(A), w64, 0, h->stream, msg[t], upd, G, c.inc, (const float *)partP, (const float *)slotP,
                            (const float *)dP, ht, Sck + t * nH, hck + (t + 1) * nE);
     }
@@ -240,8 +256,7 @@ static int gl_forward_ckpt(epnn_handle *h, const GlCall &c, const GlPair *msg, c
         hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, pas[t], G, c.d_x, feats, (const float *)(qck + (size_t)t * A), c.d_Q, dP, dR,
                            (float *)nullptr, (float *)nullptr);
         if (np > 0)
-            hipLaunchKernelGGL(k_gl_epn_pair<0>, dim3(gP), w64, 0, h->stream, pas[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)nullptr, slotq, (float *)nullptr, (float *)nullptr, (float *)nullptr, GlTape{});
+            hipLaunchKernelGGL(k_gl_epn_pair, dim3(gP), w64, 0, h->stream, pas[t], L, (const float *)dP, (const float *)dR, slotq);
         hipLaunchKernelGGL(k_gl_epn_atom, dim3(gA), dim3(256), 0, h->stream, A, c.inc, (const float *)slotq, (const float *)(qck + (size_t)t * A),
                            qck + (size_t)(t + 1) * A);
     }

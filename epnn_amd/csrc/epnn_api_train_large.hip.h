@@ -5,7 +5,7 @@
 
 // The pair-list step: the checkpointed forward and the activation backward of charges_vjp_large_impl with the seed gq = 2 (q - y),
 // without its coordinate tail, with step 0 run in full (a_i of step 0 does not depend on the coordinates, but on the weights it does)
-// and every kernel keeping the rows of its weight gradients (GlTape).  It reads the training state's device masters where they are
+// and every kernel keeping the rows of its weight gradients (the TAPE instances of the one backward, epnn_vjp_multi.hip.h, at K = 1).  It reads the training state's device masters where they are
 // (the flat vector has the layout GlPair / GlUpd point into), adds into the state's gradient vector, and returns when all of it is
 // done.  Inputs, pair list and scratch are those of the gradient path (GradLarge).
 static int train_step_large_impl(epnn_handle *h, int B, int N, const int32_t *offsets, const float *xyz, const float *x, const float *Q,
@@ -101,9 +101,10 @@ static int train_step_large_impl(epnn_handle *h, int B, int N, const int32_t *of
         hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, pas[t], G, d_x, feats, qt, d_Q, dP, dR, (float *)nullptr, (float *)nullptr);
         hipLaunchKernelGGL(k_tl_arow, dim3(gA64), dim3(256), 0, h->stream, G, d_x, feats, qt, d_Q, arow);
         if (np > 0)
-            hipLaunchKernelGGL(k_gl_epn_pair<1>, dim3(gP), w64, 0, h->stream, pas[t], L, (const float *)dP, (const float *)dR,
-                               (const float *)gq, (float *)nullptr, slotP, slotR, (float *)nullptr, K);
-        hipLaunchKernelGGL(k_gl_epn_atom_bwd, dim3(A), w64, 0, h->stream, pas[t], G, inc, (const float *)slotP, (const float *)slotR, gh, gq, K);
+            hipLaunchKernelGGL((k_gvm_epn_pair<1, true>), dim3(gP), w64, 0, h->stream, pas[t], L, 1, A, P1, SL, (const float *)dP, (const float *)dR,
+                               (const float *)gq, slotP, slotR, (float *)nullptr, K);
+        hipLaunchKernelGGL((k_gvm_epn_atom_bwd<1, true>), dim3(A), w64, 0, h->stream, pas[t], G, 1, SL, inc, (const float *)slotP,
+                           (const float *)slotR, gh, gq, K);
         const TDense *D = ts->pas[t];
         job(arow, 64, F, K.dv, 64, GL_H, A, D[0].offW, D[0].offB);                                   // Wi, b1
         job(arow, 64, F, K.dv + GL_H, 64, GL_H, A, D[0].offW + F * GL_H, -1);                        // Wj
@@ -116,14 +117,14 @@ static int train_step_large_impl(epnn_handle *h, int B, int N, const int32_t *of
     // ---- backward: GNN steps
     for (int t = T - 1; t >= 0; --t) {
         const float *ht = t ? hck + t * nE : nullptr;
-        hipLaunchKernelGGL(k_gl_upd_bwd, dim3(A), w64, 0, h->stream, msg[t], upd, G, ht, (const float *)(Sck + t * nH), (const float *)gh,
-                           ghp, dS, K);
+        hipLaunchKernelGGL((k_gvm_upd_bwd<1, true>), dim3(A), w64, 0, h->stream, msg[t], upd, G, 1, ht, (const float *)(Sck + t * nH),
+                           (const float *)gh, ghp, dS, K);
         hipLaunchKernelGGL(k_gl_proj, dim3(A), w64, 0, h->stream, msg[t], G, d_x, ht, (const float *)nullptr, d_Q, dP, dR, Yb, Yc);
         hipLaunchKernelGGL(k_tl_arow, dim3(gA64), dim3(256), 0, h->stream, G, d_x, ht, (const float *)nullptr, d_Q, arow);
-        hipLaunchKernelGGL((k_gl_sweep<1, 1>), dim3(nw), w64, 0, h->stream, c.d_tasks, c.d_moff, A, msg[t].W2, (const float *)dP, (const float *)dR,
-                           (const float *)Yb, (const float *)dS, partP, (int)nt, run, wpart);
+        hipLaunchKernelGGL((k_gl_sweep<1, 1, 1>), dim3(nw), w64, 0, h->stream, c.d_tasks, c.d_moff, A, msg[t].W2, (const float *)dP, (const float *)dR,
+                           (const float *)Yb, (const float *)dS, (size_t)0, partP, (size_t)0, (int)nt, run, wpart);
         hipLaunchKernelGGL(k_gl_sweep<2>, dim3(nt), w64, 0, h->stream, c.d_tasks, c.d_moff, A, msg[t].W2, (const float *)dR, (const float *)dP,
-                           (const float *)Yc, (const float *)dS, partR, (int)nt, 1, (float *)nullptr);
+                           (const float *)Yc, (const float *)dS, (size_t)0, partR, (size_t)0, (int)nt, 1, (float *)nullptr);
         const TDense *D = ts->msg[t];
         {                                                          // W2, b2 of all pairs: the sweep's partials
             TlRed Rs{};
@@ -133,10 +134,10 @@ static int train_step_large_impl(epnn_handle *h, int B, int N, const int32_t *of
             hipLaunchKernelGGL(k_tl_reduce, dim3(GL_H * GL_H / 64, 2), dim3(1024), 0, h->stream, Rs, (const float *)wpart, grad);
         }
         if (np > 0)
-            hipLaunchKernelGGL(k_gl_gnn_pair<1>, dim3(gP), w64, 0, h->stream, msg[t], L, (const float *)dP, (const float *)dR,
+            hipLaunchKernelGGL((k_gvm_gnn_pair<1, true>), dim3(gP), w64, 0, h->stream, msg[t], L, 1, A, P1, SL, (const float *)dP, (const float *)dR,
                                (const float *)dS, slotP, slotR, (float *)nullptr, K);
-        hipLaunchKernelGGL(k_gl_gnn_atom_bwd, dim3(A), w64, 0, h->stream, msg[t], G, inc, (const float *)partP, (const float *)partR,
-                           (const float *)slotP, (const float *)slotR, (const float *)dP, (const float *)dS, ghp, K);
+        hipLaunchKernelGGL((k_gvm_gnn_atom_bwd<1, true>), dim3(A), w64, 0, h->stream, msg[t], G, 1, (size_t)0, SL, inc, (const float *)partP,
+                           (const float *)partR, (const float *)slotP, (const float *)slotR, (const float *)dP, (const float *)dS, ghp, K);
         job(K.u0, GL_E + GL_H, GL_E + GL_H, K.ud1, GL_H, GL_H, A, ts->upd[0].offW, ts->upd[0].offB);  // update MLP
         job(K.u1, GL_H, GL_H, K.ud2, GL_H, GL_H, A, ts->upd[1].offW, ts->upd[1].offB);
         job(K.u2, GL_H, GL_H, gh, GL_E, GL_E, A, ts->upd[2].offW, ts->upd[2].offB);

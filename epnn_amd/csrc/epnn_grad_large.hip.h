@@ -1,5 +1,5 @@
-// Charge gradients with respect to the coordinates from the pair list (option "grad_path" = 2): the kernels.
-// Part of the one translation unit epnn_api.hip.
+// Charge gradients with respect to the coordinates from the pair list (option "grad_path" = 2): the structures, the checkpointed
+// forward and the all-pairs sweep.  The backward's other kernels: epnn_vjp_multi.hip.h.  Part of the one translation unit epnn_api.hip.
 //
 // The dense path (epnn_grad_xyz.hip.h) pads every molecule to [B][N][N] rows.  This path runs the factorised form of DESIGN.md
 // section 2 backwards on per-atom rows [A][32] / [A][48], the list of pairs under the cutoff (pi, pj, pe [P][48], near weights)
@@ -15,14 +15,16 @@
 //   GNN step 0                   a_i = [x_i | 0 | Q/n] does not depend on the coordinates: only the listed pairs' dG
 //   edges -> coordinates         gE [P][48] -> gD (float64) -> +-gD d / D into the pair's two slots, summed per atom in float64
 //
-// A training step (option "train_path", epnn_train_large.hip.h) runs the same kernels with step 0 in full and a GlTape: they then also
-// store the rows its weight gradients are outer products of, and the row pass adds up dW2 / db2 of all pairs (k_gl_sweep<1, 1>).
+// The backward runs for K seeds beside the one primal (k_gvm_*<KM>, k_gl_sweep<MODE, KC>); the single-cotangent calls are K = 1.
+// A training step (option "train_path", epnn_train_large.hip.h) runs the same kernels at K = 1 with step 0 in full and a GlTape
+// (their TAPE instances): they then also store the rows its weight gradients are outer products of, and the row pass adds up
+// dW2 / db2 of all pairs (k_gl_sweep<1, 1, 1>).
 //
 // Plain float32 throughout (the Dense layers of the two sweeps on v_mfma_f32_16x16x4_f32).  Every sum has a fixed order, there
 // are no float atomics: results are bit-reproducible and a molecule's rows do not depend on the rest of the batch (the number of
 // pieces its partner range is cut into depends on its own size alone).
 //
-// Why the checkpointed forward is this file's own (k_gl_proj, k_gl_sweep<0>, k_gl_gnn_pair<0>, k_gl_gnn_tail, k_gl_epn_*) and not the
+// Why the checkpointed forward is this file's own (k_gl_proj, k_gl_sweep<0>, k_gl_gnn_pair, k_gl_gnn_tail, k_gl_epn_*) and not the
 // tiled forward of epnn_large.hip.h: the backward needs S_t and h_t of every step as rows in memory (the tiled forward folds W3 and
 // Wu3 into the next step's matrices and never forms h between steps, and its first step runs by atom types), and it takes its ReLU
 // decisions from recomputed f32 pre-activations, which must be the ones the forward took -- the tiled sweep's bf16 three-piece
@@ -45,8 +47,8 @@ struct GlGeom {                   // the batch
     const int *moff, *mol_of;     // [B + 1], [A]
     int A, N, nx;
 };
-// What a training step (epnn_train_large.hip.h) keeps of the backward kernels' intermediates for its weight gradients; all null
-// (GlTape{}) in a gradient call, which stores nothing.  Rows of 32 unless noted.
+// What a training step (epnn_train_large.hip.h) keeps of the backward kernels' intermediates for its weight gradients: the TAPE
+// instances of the k_gvm_* kernels write it; the others take a GlTape{} and do not read it.  Rows of 32 unless noted.
 //   z1, d2   a Dense-2 input and its output gradient: EPN pair p, order o at row 2 p + o; GNN pair p, order o at rows 4 p + 2 o
 //            (with G) and 4 p + 2 o + 1 (without G, d2 negated: the correction rows' sign); GNN atom a at row pad0 + a: relu(P_a)
 //            and (N - n) d2 of its padded partners
@@ -108,19 +110,24 @@ __global__ __launch_bounds__(64) void k_gl_proj(GlPair M, GlGeom G, const float 
 //   MODE 2 (backward, column pass: resident R_j; streamed P_i, Yc_i, dS_i):  dR_j += the same with the streamed dS_i
 // The sums stay in the lane that owns them; out [piece][A][32] gets one row per (piece, resident atom), written by exactly one
 // wavefront (an empty piece writes zeros), and the per-atom kernels add the pieces in order.
-// WG 1 (a training step's row pass, MODE 1): the wavefront also adds up the weight gradient of the second Dense over every pair
+// KC (MODE 1, 2): the cotangents of one launch.  The primal (z1, z2pre) stands once per partner; each cotangent u has its own dS (the
+// first at dS, the next at dstride floats), its own 16 backward MFMAs from zero and its own out (at ostride floats), and reads
+// nothing of another: a row has the same bits at every KC.  KC >= 2 runs one task per wavefront (`run` is not read).
+// WG 1 (a training step's row pass, MODE 1, KC 1): the wavefront also adds up the weight gradient of the second Dense over every pair
 // it sees, dW2[k][m] += sum_c z1_c[k] d2_c[m] and db2[m] += sum_c d2_c[m] with z1 = relu(P + R) itself.  That product reduces over
 // the tile's columns, which the accumulator layout keeps in the lane index: the two 16 x 32 tiles go through LDS (rows of GL_TS
 // floats) and come back as MFMA operands with the column on the K index, 16 more v_mfma_f32_16x16x4_f32 per partner; the 32 x 32 + 32
 // sums stay in registers across the partners of all `run` tasks of the wavefront (tasks blockIdx.x * run ...) and leave as one row
 // of wpart [wavefronts][1056], which k_tl_reduce_sweep adds up in order.  A gradient call has run = 1 and one task per wavefront.
 #define GL_TS 36
-template <int MODE, int WG = 0>
+template <int MODE, int KC = 1, int WG = 0>
 __global__ __launch_bounds__(64) void k_gl_sweep(const int4 *tasks, const int *moff, int A, const float *W2, const float *Xres,
-                                                 const float *Xstr, const float *Y, const float *dS, float *out, int ntask, int run,
-                                                 float *wpart) {
+                                                 const float *Xstr, const float *Y, const float *dS, size_t dstride, float *out,
+                                                 size_t ostride, int ntask, int run, float *wpart) {
+    static_assert(KC == 1 || (MODE != 0 && WG == 0), "the forward pass and the weight-gradient pass carry one row");
     __shared__ float tz[WG ? 16 * GL_TS : 1], td[WG ? 16 * GL_TS : 1];
     const int lane = threadIdx.x, c = lane & 15, qd = lane >> 4;
+    if (KC > 1 && (int)blockIdx.x >= ntask) return;                 // (a chunk of cotangents: one task per wavefront)
     float wf[2][8], wb[2][8];
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
@@ -132,8 +139,8 @@ __global__ __launch_bounds__(64) void k_gl_sweep(const int4 *tasks, const int *m
         }
     f32x4 aw[2][2] = {{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}};
     float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int t_end = min(ntask, ((int)blockIdx.x + 1) * run);
-    for (int task = (int)blockIdx.x * run; task < t_end; ++task) {
+    const int t_end = KC == 1 ? min(ntask, ((int)blockIdx.x + 1) * run) : (int)blockIdx.x + 1;
+    for (int task = KC == 1 ? (int)blockIdx.x * run : (int)blockIdx.x; task < t_end; ++task) {
         const int4 tk = tasks[task];                                // (first resident atom, molecule, piece, pieces)
         const int a0 = moff[tk.y], a1 = moff[tk.y + 1];
         const int len = (a1 - a0 + tk.w - 1) / tk.w;
@@ -141,13 +148,16 @@ __global__ __launch_bounds__(64) void k_gl_sweep(const int4 *tasks, const int *m
         const int col = tk.x + c;
         const bool valid = col < a1;
         const int colc = valid ? col : a1 - 1;
-        float xr[8], ds[8], acc[8];
+        float xr[8], ds[MODE == 1 ? KC : 1][8], acc[KC][8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int f = 16 * (e >> 2) + 4 * qd + (e & 3);
             xr[e] = Xres[(size_t)colc * GL_H + f];
-            ds[e] = (MODE == 1 && valid) ? dS[(size_t)colc * GL_H + f] : 0.f;
-            acc[e] = 0.f;
+#pragma unroll
+            for (int u = 0; u < KC; ++u) {
+                if (MODE == 1) ds[u][e] = valid ? dS[u * dstride + (size_t)colc * GL_H + f] : 0.f;
+                acc[u][e] = 0.f;
+            }
         }
         for (int j = j0; j < j1; ++j) {
             const float *xs = Xstr + (size_t)j * GL_H + 4 * qd, *ys = Y + (size_t)j * GL_H + 4 * qd;
@@ -165,17 +175,20 @@ __global__ __launch_bounds__(64) void k_gl_sweep(const int4 *tasks, const int *m
             }
             if (MODE == 0) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { acc[e] += fmaxf(o0[e], 0.f); acc[4 + e] += fmaxf(o1[e], 0.f); }
-            } else {
+                for (int e = 0; e < 4; ++e) { acc[0][e] += fmaxf(o0[e], 0.f); acc[0][4 + e] += fmaxf(o1[e], 0.f); }
+                continue;
+            }
+#pragma unroll
+            for (int u = 0; u < KC; ++u) {
                 float d2[8];
                 if (MODE == 2) {
-                    const float *dp = dS + (size_t)j * GL_H + 4 * qd;
+                    const float *dp = dS + u * dstride + (size_t)j * GL_H + 4 * qd;
                     const f32x4 d0 = *reinterpret_cast<const f32x4 *>(dp), d1 = *reinterpret_cast<const f32x4 *>(dp + 16);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? d0[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? d1[e] : 0.f; }
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? ds[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? ds[4 + e] : 0.f; }
+                    for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? ds[u][e] : 0.f; d2[4 + e] = o1[e] > 0.f ? ds[u][4 + e] : 0.f; }
                 }
                 if (WG) {
                     // (an invalid column has dS = 0, so d2 = 0: its z1 row, the last real atom's, adds nothing)
@@ -205,15 +218,18 @@ __global__ __launch_bounds__(64) void k_gl_sweep(const int4 *tasks, const int *m
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    acc[e] += xr[e] > nn[e] ? g0[e] : 0.f;
-                    acc[4 + e] += xr[4 + e] > nn[4 + e] ? g1[e] : 0.f;
+                    acc[u][e] += xr[e] > nn[e] ? g0[e] : 0.f;
+                    acc[u][4 + e] += xr[4 + e] > nn[4 + e] ? g1[e] : 0.f;
                 }
             }
         }
         if (valid) {
-            float *o = out + ((size_t)tk.z * A + col) * GL_H + 4 * qd;
-            *reinterpret_cast<f32x4 *>(o) = f32x4{acc[0], acc[1], acc[2], acc[3]};
-            *reinterpret_cast<f32x4 *>(o + 16) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+#pragma unroll
+            for (int u = 0; u < KC; ++u) {
+                float *o = out + u * ostride + ((size_t)tk.z * A + col) * GL_H + 4 * qd;
+                *reinterpret_cast<f32x4 *>(o) = f32x4{acc[u][0], acc[u][1], acc[u][2], acc[u][3]};
+                *reinterpret_cast<f32x4 *>(o + 16) = f32x4{acc[u][4], acc[u][5], acc[u][6], acc[u][7]};
+            }
         }
     }
     if (WG) {
@@ -244,13 +260,10 @@ struct GlPairs {
     const float *pe, *pw;
 };
 
-// GNN step: the pair's correction rows.  BWD 0: relu(W2^T relu(P + R + G) + b2) minus the same without G, into the first atom's
-// slot (corr [slots][32]).  BWD 1: dz1 with G minus dz1 without it into slotP of the first and slotR of the second atom (null for
-// step 0, which needs no dP / dR), and gE_ij += We (dz1_ij + dz1_ji) with G.
-template <int BWD>
-__global__ __launch_bounds__(64) void k_gl_gnn_pair(GlPair M, GlPairs L, const float *P, const float *R, const float *dS, float *slotP,
-                                                    float *slotR, float *gE, GlTape K) {
-    __shared__ float ev[GL_E], z[2][2][GL_H], d2[2][2][GL_H], dg[2][GL_H];
+// GNN step, forward: the pair's correction rows, relu(W2^T relu(P + R + G) + b2) minus the same without G, into the first atom's
+// slot (corr [slots][32]).  Its backward: k_gvm_gnn_pair (epnn_vjp_multi.hip.h).
+__global__ __launch_bounds__(64) void k_gl_gnn_pair(GlPair M, GlPairs L, const float *P, const float *R, float *corr) {
+    __shared__ float ev[GL_E], z[2][2][GL_H];
     const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     const int i = L.pi[p], j = L.pj[p];
     const int a = half ? j : i, b = half ? i : j;                 // this half's row is [a_a | a_b | e]
@@ -265,46 +278,14 @@ __global__ __launch_bounds__(64) void k_gl_gnn_pair(GlPair M, GlPairs L, const f
     z[half][1][f] = fmaxf(base, 0.f);
     __syncthreads();
     const float z2g = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half][0]), z2n = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half][1]);
-    const int sa = half ? L.dest_j[p] : L.dest_i[p], sb = half ? L.dest_i[p] : L.dest_j[p];
-    if (!BWD) {
-        slotP[(size_t)sa * GL_H + f] = fmaxf(z2g, 0.f) - fmaxf(z2n, 0.f);
-        return;
-    }
-    const float dsv = dS[(size_t)a * GL_H + f];
-    d2[half][0][f] = z2g > 0.f ? dsv : 0.f;
-    d2[half][1][f] = z2n > 0.f ? dsv : 0.f;
-    if (K.z1) {
-        const size_t r = (4 * (size_t)p + 2 * half) * GL_H + f;
-        K.z1[r] = z[half][0][f]; K.z1[r + GL_H] = z[half][1][f];
-        K.d2[r] = d2[half][0][f]; K.d2[r + GL_H] = -d2[half][1][f];
-    }
-    __syncthreads();
-    const float dg1 = z1g > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half][0], GL_H) : 0.f;
-    const float dn1 = base > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half][1], GL_H) : 0.f;
-    if (slotP) {
-        slotP[(size_t)sa * GL_H + f] = dg1 - dn1;
-        slotR[(size_t)sb * GL_H + f] = dg1 - dn1;
-    }
-    dg[half][f] = dg1;
-    __syncthreads();
-    if (K.dz) {                                                   // (a training step: the We block's rows, no gE)
-        if (lane < GL_H) K.dz[(size_t)p * GL_H + lane] = dg[0][lane] + dg[1][lane];
-        return;
-    }
-    if (lane < GL_E) {
-        float acc = 0.f;
-        for (int k = 0; k < GL_H; ++k) acc = fmaf(M.We[lane * GL_H + k], dg[0][k] + dg[1][k], acc);
-        gE[(size_t)p * GL_E + lane] += acc;
-    }
+    const int sa = half ? L.dest_j[p] : L.dest_i[p];
+    corr[(size_t)sa * GL_H + f] = fmaxf(z2g, 0.f) - fmaxf(z2n, 0.f);
 }
 
-// EPN step.  BWD 0: delta = (f(a_i, a_j, e) - f(a_j, a_i, e)) / 2, slotq[dest_i] = w delta, slotq[dest_j] = -w delta.
-// BWD 1: the row [a_i | a_j | e] is seeded with s = w (gq_i - gq_j) / 2, the row [a_j | a_i | e] with -s; a row's dz1 goes to slotP
-// of its first atom and slotR of its second, and gE_ij += We (dz1_ij + dz1_ji).
-template <int BWD>
-__global__ __launch_bounds__(64) void k_gl_epn_pair(GlPair M, GlPairs L, const float *P, const float *R, const float *gq, float *slotq,
-                                                    float *slotP, float *slotR, float *gE, GlTape K) {
-    __shared__ float ev[GL_E], z[2][GL_H], d2[2][GL_H], dg[2][GL_H], red[2][GL_H];
+// EPN step, forward: delta = (f(a_i, a_j, e) - f(a_j, a_i, e)) / 2, slotq[dest_i] = w delta, slotq[dest_j] = -w delta.  Its
+// backward: k_gvm_epn_pair (epnn_vjp_multi.hip.h).
+__global__ __launch_bounds__(64) void k_gl_epn_pair(GlPair M, GlPairs L, const float *P, const float *R, float *slotq) {
+    __shared__ float ev[GL_E], z[2][GL_H], red[2][GL_H];
     const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
     const int i = L.pi[p], j = L.pj[p];
     const int a = half ? j : i, b = half ? i : j;
@@ -318,40 +299,14 @@ __global__ __launch_bounds__(64) void k_gl_epn_pair(GlPair M, GlPairs L, const f
     __syncthreads();
     const float z2 = M.b2[f] + gl_dotT(M.W2, GL_H, f, z[half]);
     const float w = L.pw[p];
-    const int sa = half ? L.dest_j[p] : L.dest_i[p], sb = half ? L.dest_i[p] : L.dest_j[p];
-    if (!BWD) {
-        red[half][f] = fmaxf(z2, 0.f) * M.W3[f];
-        __syncthreads();
-        if (f == 0) {
-            float fi = 0.f, fj = 0.f;                               // (b3 cancels in the difference)
-            for (int k = 0; k < GL_H; ++k) { fi += red[0][k]; fj += red[1][k]; }
-            const float delta = 0.5f * (fi - fj);
-            slotq[sa] = half ? -(w * delta) : w * delta;
-        }
-        return;
-    }
-    const float seed = 0.5f * w * (gq[i] - gq[j]);
-    d2[half][f] = z2 > 0.f ? (half ? -seed : seed) * M.W3[f] : 0.f;
-    if (K.z1) {
-        const size_t r = (2 * (size_t)p + half) * GL_H + f;
-        K.z1[r] = z[half][f];
-        K.d2[r] = d2[half][f];
-        K.r3[r] = fmaxf(z2, 0.f) * (half ? -seed : seed);
-    }
+    const int sa = half ? L.dest_j[p] : L.dest_i[p];
+    red[half][f] = fmaxf(z2, 0.f) * M.W3[f];
     __syncthreads();
-    const float dz1 = z1 > 0.f ? gl_dotN(M.W2, GL_H, f, d2[half], GL_H) : 0.f;
-    slotP[(size_t)sa * GL_H + f] = dz1;
-    slotR[(size_t)sb * GL_H + f] = dz1;
-    dg[half][f] = dz1;
-    __syncthreads();
-    if (K.dz) {
-        if (lane < GL_H) K.dz[(size_t)p * GL_H + lane] = dg[0][lane] + dg[1][lane];
-        return;
-    }
-    if (lane < GL_E) {
-        float acc = 0.f;
-        for (int k = 0; k < GL_H; ++k) acc = fmaf(M.We[lane * GL_H + k], dg[0][k] + dg[1][k], acc);
-        gE[(size_t)p * GL_E + lane] += acc;
+    if (f == 0) {
+        float fi = 0.f, fj = 0.f;                               // (b3 cancels in the difference)
+        for (int k = 0; k < GL_H; ++k) { fi += red[0][k]; fj += red[1][k]; }
+        const float delta = 0.5f * (fi - fj);
+        slotq[sa] = half ? -(w * delta) : w * delta;
     }
 }
 
@@ -397,80 +352,6 @@ __global__ __launch_bounds__(64) void k_gl_gnn_tail(GlPair M, GlUpd U, GlGeom G,
     if (lane < GL_E) h_out[(size_t)a * GL_E + lane] = U.c3[lane] + gl_dotT(U.U3, GL_E, lane, u2);
 }
 
-// Backward of the update MLP, one wavefront per atom: recomputes u1pre, u2pre from the checkpoints (h, S), carries gh [48] back:
-// gh_prev [A][48] = the h columns of the first layer's input gradient, dS [A][32] = W3 (its M columns).
-__global__ __launch_bounds__(64) void k_gl_upd_bwd(GlPair M, GlUpd U, GlGeom G, const float *h, const float *S, const float *gh,
-                                                   float *gh_prev, float *dS, GlTape K) {
-    __shared__ float u0[GL_E + GL_H], sv[GL_H], u1[GL_H], gv[GL_E], d2[GL_H], d1[GL_H], gm[GL_H];
-    const int a = blockIdx.x, lane = threadIdx.x;
-    if (lane < GL_E) { u0[lane] = h ? h[(size_t)a * GL_E + lane] : 0.f; gv[lane] = gh[(size_t)a * GL_E + lane]; }
-    if (lane < GL_H) sv[lane] = S[(size_t)a * GL_H + lane];
-    __syncthreads();
-    if (lane < GL_H) u0[GL_E + lane] = (float)G.N * M.b3[lane] + gl_dotT(M.W3, GL_H, lane, sv);
-    __syncthreads();
-    float t = 0.f;
-    if (lane < GL_H) {
-        t = U.c1[lane];
-        for (int k = 0; k < GL_E + GL_H; ++k) t = fmaf(u0[k], U.U1[k * GL_H + lane], t);
-        u1[lane] = fmaxf(t, 0.f);
-    }
-    __syncthreads();
-    if (lane < GL_H) {
-        const float u2pre = U.c2[lane] + gl_dotT(U.U2, GL_H, lane, u1);
-        d2[lane] = u2pre > 0.f ? gl_dotN(U.U3, GL_E, lane, gv, GL_E) : 0.f;
-        if (K.u2) K.u2[(size_t)a * GL_H + lane] = fmaxf(u2pre, 0.f);
-    }
-    __syncthreads();
-    if (lane < GL_H) d1[lane] = t > 0.f ? gl_dotN(U.U2, GL_H, lane, d2, GL_H) : 0.f;
-    __syncthreads();
-    if (lane < GL_E) gh_prev[(size_t)a * GL_E + lane] = gl_dotN(U.U1, GL_H, lane, d1, GL_H);
-    if (lane < GL_H) gm[lane] = gl_dotN(U.U1, GL_H, GL_E + lane, d1, GL_H);
-    __syncthreads();
-    if (K.u0) {
-        K.u0[(size_t)a * (GL_E + GL_H) + lane] = u0[lane];
-        if (lane < GL_E + GL_H - 64) K.u0[(size_t)a * (GL_E + GL_H) + 64 + lane] = u0[64 + lane];
-        if (lane < GL_H) {
-            const size_t r = (size_t)a * GL_H + lane;
-            K.u1[r] = u1[lane]; K.ud2[r] = d2[lane]; K.ud1[r] = d1[lane]; K.gm[r] = gm[lane];
-        }
-    }
-    if (lane < GL_H) dS[(size_t)a * GL_H + lane] = gl_dotN(M.W3, GL_H, lane, gm, GL_H);
-}
-
-// End of a backward GNN step t >= 1, one wavefront per atom (lanes 0..31: dP, lanes 32..63: dR): pieces in order, dP's padded
-// partners in closed form, the atom's slots in order; then gh = gh_prev + the h columns of Wi dP + Wj dR (in place).
-__global__ __launch_bounds__(64) void k_gl_gnn_atom_bwd(GlPair M, GlGeom G, const int *inc_off, const float *partP, const float *partR,
-                                                        const float *slotP, const float *slotR, const float *P, const float *dS,
-                                                        float *gh, GlTape K) {
-    __shared__ float v[GL_H], d2[GL_H], dv[2][GL_H];
-    const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
-    const int b = G.mol_of[a], n = G.moff[b + 1] - G.moff[b];
-    const float pa = P[(size_t)a * GL_H + f];
-    if (!half) v[f] = fmaxf(pa, 0.f);
-    __syncthreads();
-    if (!half) d2[f] = M.b2[f] + gl_dotT(M.W2, GL_H, f, v) > 0.f ? dS[(size_t)a * GL_H + f] : 0.f;
-    __syncthreads();
-    const float *part = half ? partR : partP, *slot = half ? slotR : slotP;
-    float s = 0.f;
-    const int np = gl_pieces(n);
-    for (int k = 0; k < np; ++k) s += part[((size_t)k * G.A + a) * GL_H + f];
-    if (!half) s += (float)(G.N - n) * (pa > 0.f ? gl_dotN(M.W2, GL_H, f, d2, GL_H) : 0.f);
-    for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slot[(size_t)k * GL_H + f];
-    dv[half][f] = s;
-    if (K.dv) {
-        K.dv[(size_t)a * 64 + lane] = s;
-        if (!half) {
-            K.z1[(K.pad0 + a) * GL_H + f] = v[f];
-            K.d2[(K.pad0 + a) * GL_H + f] = (float)(G.N - n) * d2[f];
-        }
-    }
-    __syncthreads();
-    if (lane < GL_E) {
-        const int row = G.nx + lane;
-        gh[(size_t)a * GL_E + lane] += gl_dotN(M.Wi, GL_H, row, dv[0], GL_H) + gl_dotN(M.Wj, GL_H, row, dv[1], GL_H);
-    }
-}
-
 // EPN forward: every atom adds its transfer slots in order.
 __global__ __launch_bounds__(256) void k_gl_epn_atom(int A, const int *inc_off, const float *slotq, const float *q, float *q_out) {
     const int a = blockIdx.x * 256 + threadIdx.x;
@@ -485,74 +366,4 @@ __global__ __launch_bounds__(256) void k_gl_q0(GlGeom G, const float *Q, float *
     if (a >= G.A) return;
     const int b = G.mol_of[a];
     q[a] = Q[b] / (float)(G.moff[b + 1] - G.moff[b]);
-}
-
-// EPN backward, one wavefront per atom: dP / dR from the slots in order, then gfeat += the h columns and gq += the q column of
-// Wi dP + Wj dR.
-__global__ __launch_bounds__(64) void k_gl_epn_atom_bwd(GlPair M, GlGeom G, const int *inc_off, const float *slotP, const float *slotR,
-                                                        float *gfeat, float *gq, GlTape K) {
-    __shared__ float dv[2][GL_H];
-    const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
-    const float *slot = half ? slotR : slotP;
-    float s = 0.f;
-    for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slot[(size_t)k * GL_H + f];
-    dv[half][f] = s;
-    if (K.dv) K.dv[(size_t)a * 64 + lane] = s;
-    __syncthreads();
-    if (lane <= GL_E) {
-        const int row = G.nx + lane;                               // lane 48: the charge's column
-        const float add = gl_dotN(M.Wi, GL_H, row, dv[0], GL_H) + gl_dotN(M.Wj, GL_H, row, dv[1], GL_H);
-        if (lane < GL_E) gfeat[(size_t)a * GL_E + lane] += add;
-        else gq[a] += add;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------- edges -> coordinates
-// One thread per listed pair: the displacement d = image of r_j - r_i and D in float64 as the front-end measures them (PairGeo<GEO>,
-// pair_dist: GEO 0 open, 1 box rows [B][3], 2 EpnnCell records [B]), gD = sum_k gE_k de_k/dD, w = gD / D; the first atom's slot gets -w d, the
-// second's +w d (d D / d r_i = (r_i - r_j) / D), and with strain each gets half of w d_a d_c (xx, yy, zz, yz, xz, xy).
-// slotx [slots][9] float64.  bad: bit 0 = two atoms or images coincide, bit 1 = a pair without both slots (atomicOr: the word does
-// not depend on which thread comes last).
-template <int GEO>
-__global__ __launch_bounds__(256) void k_gl_pair_xyz(GlPairs L, int npairs, const int *mol_of, const float *xyz, const float *geo,
-                                                     const float *gE, double cutoff, double eta, const double *mu, double *slotx, int *bad) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= npairs) return;
-    const int i = L.pi[p], j = L.pj[p], b = mol_of[i];
-    double dx = (double)xyz[3 * j] - (double)xyz[3 * i], dy = (double)xyz[3 * j + 1] - (double)xyz[3 * i + 1],
-           dz = (double)xyz[3 * j + 2] - (double)xyz[3 * i + 2];
-    PairGeo<GEO> pg;
-    pg.load_lane(geo, b);
-    pg.image(dx, dy, dz);
-    const double D = pair_dist(dx, dy, dz);
-    double w = 0.0;
-    if (!(D > 0.0)) atomicOr(bad, 1);
-    else if (D < cutoff) {
-        const double C = edge_cut(D, cutoff), dC = edge_dcut(D, cutoff);
-        double gD = 0.0;
-        for (int k = 0; k < GL_E; ++k) {
-            const double u = D - mu[k];
-            gD += (double)gE[(size_t)p * GL_E + k] * edge_slope(C, dC, u, eta) * edge_gauss(u, eta);
-        }
-        w = gD / D;
-    }
-    if (L.dest_i[p] < 0 || L.dest_j[p] < 0) { atomicOr(bad, 2); return; }
-    double *si = slotx + 9 * (size_t)L.dest_i[p], *sj = slotx + 9 * (size_t)L.dest_j[p];
-    si[0] = -w * dx; si[1] = -w * dy; si[2] = -w * dz;
-    sj[0] = w * dx; sj[1] = w * dy; sj[2] = w * dz;
-    const double hw = 0.5 * w;
-    const double s6[6] = {hw * dx * dx, hw * dy * dy, hw * dz * dz, hw * dy * dz, hw * dx * dz, hw * dx * dy};
-    for (int k = 0; k < 6; ++k) { si[3 + k] = s6[k]; sj[3 + k] = s6[k]; }
-}
-// every atom adds its slots in order, in float64: gxyz [A][3] float32, and its strain share [A][6] float64 (k_g_strain_mol adds
-// a molecule's atoms up) when asked for
-__global__ __launch_bounds__(256) void k_gl_atom_xyz(int A, const int *inc_off, const double *slotx, float *gxyz, double *share) {
-    const int a = blockIdx.x * 256 + threadIdx.x;
-    if (a >= A) return;
-    double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int k = inc_off[a]; k < inc_off[a + 1]; ++k)
-        for (int c = 0; c < 9; ++c) s[c] += slotx[9 * (size_t)k + c];
-    for (int c = 0; c < 3; ++c) gxyz[3 * (size_t)a + c] = (float)s[c];
-    if (share)
-        for (int c = 0; c < 6; ++c) share[6 * (size_t)a + c] = s[3 + c];
 }

@@ -53,7 +53,7 @@ __device__ __forceinline__ void jvm_dotT(const float *W, int stride, int col, co
 }
 
 // ---------------------------------------------------------------------------------------------------------- edge tangents
-// One thread per listed pair, the displacement d' and D in float64 from PairGeo<GEO> and pair_dist, as k_gl_pair_xyz takes them; d', D
+// One thread per listed pair, the displacement d' and D in float64 from PairGeo<GEO> and pair_dist, as k_gvm_pair_xyz takes them; d', D
 // and de/dD once, tD and te per tangent (tD in LDS, a thread's column; in a register at KM = 1).  v [K][A][3] or null,
 // E [K][B][3][3] or null, te [K][P1][48] float32 (te_stride = P1 * 48).  bad: bit 0 = two atoms or images coincide, bit 1 = a pair
 // without both incidence slots.
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(64) void k_jvm_sweep(const int4 *tasks, const int *
 // Lanes as in k_gl_gnn_pair: one wavefront per listed pair {i < j}, lanes 0..31 the order (i, j), lanes 32..63 the order (j, i),
 // a lane one hidden unit.  G = We^T e and tG = We^T te are the same for both orders.
 //
-// GNN step: the correction rows of S (k_gl_gnn_pair<0>'s) and of tS into the first atom's slot: with G the first layer's tangent
+// GNN step: the correction rows of S (k_gl_gnn_pair's) and of tS into the first atom's slot: with G the first layer's tangent
 // is tP_a + tR_b + tG, without it tP_a + tR_b.  G, the two first-layer rows and their ReLU decisions once; tG, tz1, tz2 per
 // tangent.  te [K][P1][48], tP, tR [K][A][32], slotT [K][SL][32].
 template <int KM>
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(64) void k_jvm_gnn_pair(GlPair M, GlPairs L, int K,
         if (t < K) slotT[((size_t)t * SL + sa) * GL_H + f] = (z2g > 0.f ? t2g[t] : 0.f) - (z2n > 0.f ? t2n[t] : 0.f);
 }
 
-// EPN step: delta = (f(a_i, a_j, e) - f(a_j, a_i, e)) / 2 as k_gl_epn_pair<0> forms it, once, and per tangent
+// EPN step: delta = (f(a_i, a_j, e) - f(a_j, a_i, e)) / 2 as k_gl_epn_pair forms it, once, and per tangent
 // tf = W3 . ([z2pre > 0] W2^T ([z1pre > 0] (tP_a + tR_b + tG))), tdelta = (tf_ij - tf_ji) / 2; w delta, w tdelta into the first
 // atom's slots and their negatives into the second's.  slott [K][SL].
 template <int KM>

@@ -9,7 +9,7 @@
 //                      partners' share of W2 / b2 (relu(P) x (N - n) d2)
 //   per listed pair    the We block (e x (dz1_ij + dz1_ji)), the near-pair corrections' share of W2 / b2 (with G minus without),
 //                      and W2, b2, W3 of a pass MLP for both orders of the pair (b3 of a pass MLP cancels between the two orders)
-//   all pairs          W2 / b2 of a message MLP: inside the row pass of the sweep (k_gl_sweep<1, 1>), on the matrix pipe
+//   all pairs          W2 / b2 of a message MLP: inside the row pass of the sweep (k_gl_sweep<1, 1, 1>), on the matrix pipe
 //
 // Every product is a job of k_tl_outer: rows [r] of X (K wide) and Y (O wide) -> sum_r X_r (x) Y_r and sum_r Y_r.  A job's rows are
 // cut into TL_G runs, one workgroup each, a thread owns up to TL_EPT entries of the result and adds its run's rows in order; the TL_G

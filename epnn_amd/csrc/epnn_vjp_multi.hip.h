@@ -1,26 +1,27 @@
-// Reverse-mode derivative of the charges along K cotangents in one pass (epnn_charges_vjp_multi_xyz_cell): the kernels.  Part of the
-// one translation unit epnn_api.hip.
+// The backward of the pair-list path, for K cotangents in one pass: the kernels.  Part of the one translation unit epnn_api.hip.
 //
-// The pair-list gradient path (epnn_grad_large.hip.h) runs its checkpointed forward and then one backward from one seed g [A].  Its
-// backward is linear in the seed, and every ReLU decision in it comes from the primal alone.  This file is that backward for
-// K <= GVM_MAXK seeds beside the one primal: the forward (gl_forward_ckpt) and the primal projections (k_gl_proj) are the gradient
-// path's own launches, run once; the kernels below recompute a pair's or an atom's primal pre-activations and masks once and then
-// loop over the cotangents.
+// The pair-list gradient path (epnn_grad_large.hip.h: the structures, the checkpointed forward and the all-pairs sweep k_gl_sweep) runs
+// its forward and then a backward that is linear in the seed g, with every ReLU decision taken from the primal alone.  This file is
+// that backward for K <= GVM_MAXK seeds beside the one primal: the kernels below recompute a pair's or an atom's primal
+// pre-activations and masks once and then loop over the cotangents.  It is the only one: epnn_charges_vjp_xyz*, every Coulomb entry
+// and the training step run it at K = 1 (gl_grad_backward, train_step_large_impl), epnn_charges_vjp_multi_xyz_cell at its K.
 //
-//   k_gvm_epn_pair, k_gvm_epn_atom_bwd            the EPN stack (k_gl_epn_pair<1>, k_gl_epn_atom_bwd)
-//   k_gvm_upd_bwd                                 the update MLP (k_gl_upd_bwd)
-//   k_gvm_sweep<MODE, KC>                         the two all-pairs backward sweeps (k_gl_sweep<1>, <2>), KC cotangents per launch
-//   k_gvm_gnn_pair, k_gvm_gnn_atom_bwd            the listed pairs' correction rows and the end of a GNN step (k_gl_gnn_pair<1>,
-//                                                 k_gl_gnn_atom_bwd); step 0 keeps the shortcut: only gE of the listed pairs
-//   k_gvm_pair_xyz<GEO>, k_gvm_atom_xyz, k_gvm_strain_mol     edges -> coordinates and strain (k_gl_pair_xyz, k_gl_atom_xyz,
-//                                                 k_g_strain_mol); open molecules and cells, no box instance
+//   k_gvm_epn_pair, k_gvm_epn_atom_bwd            the EPN stack, t = T-1 .. 0
+//   k_gvm_upd_bwd                                 the update MLP
+//   k_gl_sweep<1, KC>, <2, KC>                    the two all-pairs backward sweeps (epnn_grad_large.hip.h), KC cotangents per launch
+//   k_gvm_gnn_pair, k_gvm_gnn_atom_bwd            the listed pairs' correction rows and the end of a GNN step; step 0 keeps the
+//                                                 shortcut: only gE of the listed pairs
+//   k_gvm_pair_xyz<GEO>, k_gvm_atom_xyz, k_gvm_strain_mol     edges -> coordinates and strain (the dense path's k_g_strain_mol per
+//                                                 cotangent); box rows at K = 1 only: the multi entry takes cells
 //
 // Every cotangent buffer is K copies of one cotangent's, cotangent t at t times that size (gq [K][A], gh, ghp [K][A][48], dS
 // [K][A][32], partP, partR [K][piece][A][32], slotP, slotR [K][slots][32], gE [K][P][48], slotx [K][slots][9] float64, share
-// [K][A][6] float64, gxyz [K][A][3], gstrain [K][B][9]).  Each cotangent statement is the fmaf chain or MFMA sequence of the k_gl_*
-// kernel it stands for: accumulators from zero, k ascending, pieces and slots added in the same order; none reads another
-// cotangent.  Row t therefore has the bits epnn_charges_vjp_xyz_cell gives on "grad_path" 2 for g[t] alone, whatever K, the row's
-// position and the other rows are.
+// [K][A][6] float64, gxyz [K][A][3], gstrain [K][B][9]).  Each cotangent statement is one fmaf chain or MFMA sequence: accumulators
+// from zero, k ascending, pieces and slots added in the same order; none reads another cotangent.  Row t therefore has the same bits
+// whatever K, the row's position and the other rows are: those of a K = 1 call for g[t] alone.
+//
+// TAPE (KM == 1 only; a training step, epnn_train_large.hip.h): the kernel also stores the rows the weight gradients are outer
+// products of into the GlTape; the pair kernels then store dz and write no gE.  Other instances do not read the tape argument.
 //
 // Plain float32 (float64 from gE on), every sum in a fixed order, no float atomics.
 #pragma once
@@ -44,106 +45,20 @@ __device__ __forceinline__ void gvm_dotN(const float *W, int stride, int row, co
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------- the all-pairs sweeps
-// k_gl_sweep<1> (row pass: resident P_i and dS_i per cotangent, streamed R_j, Yb_j) and k_gl_sweep<2> (column pass: resident R_j,
-// streamed P_i, Yc_i and dS_i per cotangent) with its tasks, lanes and layout.  Per partner the primal stands once,
-//     z1 = max(X_res, -X_str),   z2pre = W2^T z1 + Y      (16 MFMAs),
-// and per cotangent u of the launch's KC
-//     d2_u = z2pre > 0 ? dS_u : 0,   g_u = W2 d2_u          (16 MFMAs, accumulators from zero),   acc_u += X_res > -X_str ? g_u : 0.
-// dS: the chunk's first cotangent, the next at dstride floats; out [piece][A][32] likewise at ostride: one row per (piece, resident
-// atom), written by exactly one wavefront (an empty piece writes zeros).
-template <int MODE, int KC>
-__global__ __launch_bounds__(64) void k_gvm_sweep(const int4 *tasks, const int *moff, int A, const float *W2, const float *Xres,
-                                                  const float *Xstr, const float *Y, const float *dS, size_t dstride, float *out,
-                                                  size_t ostride, int ntask) {
-    const int lane = threadIdx.x, c = lane & 15, qd = lane >> 4;
-    const int task = blockIdx.x;
-    if (task >= ntask) return;
-    float wf[2][8], wb[2][8];
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int kf = 16 * (s >> 2) + 4 * qd + (s & 3), m = 16 * rb + c;
-            wf[rb][s] = W2[kf * GL_H + m];                      // out[m] = sum_k W2[k][m] z1[k]
-            wb[rb][s] = W2[m * GL_H + kf];                      // out[m] = sum_k W2[m][k] d2[k]
-        }
-    const int4 tk = tasks[task];                                    // (first resident atom, molecule, piece, pieces)
-    const int a0 = moff[tk.y], a1 = moff[tk.y + 1];
-    const int len = (a1 - a0 + tk.w - 1) / tk.w;
-    const int j0 = min(a0 + tk.z * len, a1), j1 = min(j0 + len, a1);
-    const int col = tk.x + c;
-    const bool valid = col < a1;
-    const int colc = valid ? col : a1 - 1;
-    float xr[8], ds[MODE == 1 ? KC : 1][8], acc[KC][8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int f = 16 * (e >> 2) + 4 * qd + (e & 3);
-        xr[e] = Xres[(size_t)colc * GL_H + f];
-#pragma unroll
-        for (int u = 0; u < KC; ++u) {
-            if (MODE == 1) ds[u][e] = valid ? dS[u * dstride + (size_t)colc * GL_H + f] : 0.f;
-            acc[u][e] = 0.f;
-        }
-    }
-    for (int j = j0; j < j1; ++j) {
-        const float *xs = Xstr + (size_t)j * GL_H + 4 * qd, *ys = Y + (size_t)j * GL_H + 4 * qd;
-        const f32x4 n0 = *reinterpret_cast<const f32x4 *>(xs), n1 = *reinterpret_cast<const f32x4 *>(xs + 16);
-        f32x4 o0 = *reinterpret_cast<const f32x4 *>(ys), o1 = *reinterpret_cast<const f32x4 *>(ys + 16);
-        float nn[8], z1[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { nn[e] = -n0[e]; nn[4 + e] = -n1[e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) z1[e] = fmaxf(xr[e], nn[e]);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[0][s], z1[s], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[1][s], z1[s], o1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < KC; ++u) {
-            float d2[8];
-            if (MODE == 2) {
-                const float *dp = dS + u * dstride + (size_t)j * GL_H + 4 * qd;
-                const f32x4 d0 = *reinterpret_cast<const f32x4 *>(dp), d1 = *reinterpret_cast<const f32x4 *>(dp + 16);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? d0[e] : 0.f; d2[4 + e] = o1[e] > 0.f ? d1[e] : 0.f; }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { d2[e] = o0[e] > 0.f ? ds[u][e] : 0.f; d2[4 + e] = o1[e] > 0.f ? ds[u][4 + e] : 0.f; }
-            }
-            f32x4 g0 = {0.f, 0.f, 0.f, 0.f}, g1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                g0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[0][s], d2[s], g0, 0, 0, 0);
-                g1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[1][s], d2[s], g1, 0, 0, 0);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[u][e] += xr[e] > nn[e] ? g0[e] : 0.f;
-                acc[u][4 + e] += xr[4 + e] > nn[4 + e] ? g1[e] : 0.f;
-            }
-        }
-    }
-    if (valid) {
-#pragma unroll
-        for (int u = 0; u < KC; ++u) {
-            float *o = out + u * ostride + ((size_t)tk.z * A + col) * GL_H + 4 * qd;
-            *reinterpret_cast<f32x4 *>(o) = f32x4{acc[u][0], acc[u][1], acc[u][2], acc[u][3]};
-            *reinterpret_cast<f32x4 *>(o + 16) = f32x4{acc[u][4], acc[u][5], acc[u][6], acc[u][7]};
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------- per listed pair
-// One wavefront per listed pair, lanes and halves as in k_gl_gnn_pair / k_gl_epn_pair.  SL: slots of one cotangent (2 P1); A, P1:
-// atoms and pair rows of one cotangent.
+// One wavefront per listed pair, lanes and halves as in the forward's k_gl_gnn_pair / k_gl_epn_pair.  SL: slots of one cotangent
+// (2 P1); A, P1: atoms and pair rows of one cotangent.
 //
-// GNN step (k_gl_gnn_pair<1>): G, z1 with and without G and the two z2 pre-activations once; per cotangent dz1 with G minus dz1
+// (Eight wavefronts per SIMD are asked for at KM == 1: the gradient call's instances then take 63 / 64 VGPRs instead of 65 / 66.  The
+// taped GNN instance would spill under that bound and keeps 65; the buckets above 1 compile as without the hint.)
+//
+// GNN step: G, z1 with and without G and the two z2 pre-activations once; per cotangent dz1 with G minus dz1
 // without it into slotP of the first and slotR of the second atom (null for step 0) and gE_ij += We (dz1_ij + dz1_ji) with G.
-template <int KM>
-__global__ __launch_bounds__(64) void k_gvm_gnn_pair(GlPair M, GlPairs L, int K, int A, size_t P1, size_t SL, const float *P, const float *R,
-                                                     const float *dS, float *slotP, float *slotR, float *gE) {
+template <int KM, bool TAPE = false>
+__global__ __launch_bounds__(64, KM == 1 && !TAPE ? 8 : 1) void k_gvm_gnn_pair(GlPair M, GlPairs L, int K, int A, size_t P1, size_t SL,
+                                                                               const float *P, const float *R, const float *dS, float *slotP,
+                                                                               float *slotR, float *gE, GlTape tp) {
+    static_assert(!TAPE || KM == 1, "a training step has one cotangent");
     __shared__ float ev[GL_E], z[2][2][GL_H], d2[2][2][KM][GL_H], dg[2][KM][GL_H];
     if (KM == 1) K = 1;
     const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
@@ -166,6 +81,11 @@ __global__ __launch_bounds__(64) void k_gvm_gnn_pair(GlPair M, GlPairs L, int K,
         d2[half][0][t][f] = z2g > 0.f ? dsv : 0.f;
         d2[half][1][t][f] = z2n > 0.f ? dsv : 0.f;
     }
+    if (TAPE) {
+        const size_t r = (4 * (size_t)p + 2 * half) * GL_H + f;
+        tp.z1[r] = z[half][0][f]; tp.z1[r + GL_H] = z[half][1][f];
+        tp.d2[r] = d2[half][0][0][f]; tp.d2[r + GL_H] = -d2[half][1][0][f];
+    }
     __syncthreads();
     float ag[KM], an[KM];
     gvm_dotN<KM, GL_H>(M.W2, GL_H, f, &d2[half][0][0][0], GL_H, K, ag);
@@ -182,6 +102,10 @@ __global__ __launch_bounds__(64) void k_gvm_gnn_pair(GlPair M, GlPairs L, int K,
             dg[half][t][f] = dg1;
         }
     __syncthreads();
+    if (TAPE) {                                                   // (a training step: the We block's rows, no gE)
+        if (lane < GL_H) tp.dz[(size_t)p * GL_H + lane] = dg[0][0][lane] + dg[1][0][lane];
+        return;
+    }
     if (lane < GL_E) {
         float acc[KM];
 #pragma unroll
@@ -198,11 +122,13 @@ __global__ __launch_bounds__(64) void k_gvm_gnn_pair(GlPair M, GlPairs L, int K,
     }
 }
 
-// EPN step (k_gl_epn_pair<1>): G, z1 and z2 once; per cotangent the row [a_i | a_j | e] is seeded with s = w (gq_i - gq_j) / 2, the
+// EPN step: G, z1 and z2 once; per cotangent the row [a_i | a_j | e] is seeded with s = w (gq_i - gq_j) / 2, the
 // row [a_j | a_i | e] with -s; a row's dz1 goes to slotP of its first atom and slotR of its second, and gE_ij += We (dz1_ij + dz1_ji).
-template <int KM>
-__global__ __launch_bounds__(64) void k_gvm_epn_pair(GlPair M, GlPairs L, int K, int A, size_t P1, size_t SL, const float *P, const float *R,
-                                                     const float *gq, float *slotP, float *slotR, float *gE) {
+template <int KM, bool TAPE = false>
+__global__ __launch_bounds__(64, KM == 1 && !TAPE ? 8 : 1) void k_gvm_epn_pair(GlPair M, GlPairs L, int K, int A, size_t P1, size_t SL,
+                                                                               const float *P, const float *R, const float *gq, float *slotP,
+                                                                               float *slotR, float *gE, GlTape tp) {
+    static_assert(!TAPE || KM == 1, "a training step has one cotangent");
     __shared__ float ev[GL_E], z[2][GL_H], d2[2][KM][GL_H], dg[2][KM][GL_H];
     if (KM == 1) K = 1;
     const int p = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
@@ -222,6 +148,12 @@ __global__ __launch_bounds__(64) void k_gvm_epn_pair(GlPair M, GlPairs L, int K,
     for (int t = 0; t < K; ++t) {
         const float seed = 0.5f * w * (gq[(size_t)t * A + i] - gq[(size_t)t * A + j]);
         d2[half][t][f] = z2 > 0.f ? (half ? -seed : seed) * M.W3[f] : 0.f;
+        if (TAPE) {
+            const size_t r = (2 * (size_t)p + half) * GL_H + f;
+            tp.z1[r] = z[half][f];
+            tp.d2[r] = d2[half][t][f];
+            tp.r3[r] = fmaxf(z2, 0.f) * (half ? -seed : seed);
+        }
     }
     __syncthreads();
     float ad[KM];
@@ -235,6 +167,10 @@ __global__ __launch_bounds__(64) void k_gvm_epn_pair(GlPair M, GlPairs L, int K,
             dg[half][t][f] = dz1;
         }
     __syncthreads();
+    if (TAPE) {
+        if (lane < GL_H) tp.dz[(size_t)p * GL_H + lane] = dg[0][0][lane] + dg[1][0][lane];
+        return;
+    }
     if (lane < GL_E) {
         float acc[KM];
 #pragma unroll
@@ -252,12 +188,13 @@ __global__ __launch_bounds__(64) void k_gvm_epn_pair(GlPair M, GlPairs L, int K,
 }
 
 // ---------------------------------------------------------------------------------------------------------- per atom
-// Backward of the update MLP (k_gl_upd_bwd), one wavefront per atom: u0, u1pre and u2pre from the checkpoints (h, S) once; per
+// Backward of the update MLP, one wavefront per atom: u0, u1pre and u2pre from the checkpoints (h, S) once; per
 // cotangent gh [48] is carried back: gh_prev [K][A][48] = the h columns of the first layer's input gradient, dS [K][A][32] = W3 (its
 // M columns).
-template <int KM>
+template <int KM, bool TAPE = false>
 __global__ __launch_bounds__(64) void k_gvm_upd_bwd(GlPair M, GlUpd U, GlGeom G, int K, const float *h, const float *S, const float *gh,
-                                                    float *gh_prev, float *dS) {
+                                                    float *gh_prev, float *dS, GlTape tp) {
+    static_assert(!TAPE || KM == 1, "a training step has one cotangent");
     __shared__ float u0[GL_E + GL_H], sv[GL_H], u1[GL_H], gv[KM][GL_E], d2[KM][GL_H], d1[KM][GL_H], gm[KM][GL_H];
     if (KM == 1) K = 1;
     const int a = blockIdx.x, lane = threadIdx.x;
@@ -283,6 +220,7 @@ __global__ __launch_bounds__(64) void k_gvm_upd_bwd(GlPair M, GlUpd U, GlGeom G,
 #pragma unroll
         for (int t = 0; t < KM; ++t)
             if (t < K) d2[t][lane] = u2pre > 0.f ? acc[t] : 0.f;
+        if (TAPE) tp.u2[(size_t)a * GL_H + lane] = fmaxf(u2pre, 0.f);
     }
     __syncthreads();
     if (lane < GL_H) {
@@ -305,6 +243,14 @@ __global__ __launch_bounds__(64) void k_gvm_upd_bwd(GlPair M, GlUpd U, GlGeom G,
             if (t < K) gm[t][lane] = acc[t];
     }
     __syncthreads();
+    if (TAPE) {
+        tp.u0[(size_t)a * (GL_E + GL_H) + lane] = u0[lane];
+        if (lane < GL_E + GL_H - 64) tp.u0[(size_t)a * (GL_E + GL_H) + 64 + lane] = u0[64 + lane];
+        if (lane < GL_H) {
+            const size_t r = (size_t)a * GL_H + lane;
+            tp.u1[r] = u1[lane]; tp.ud2[r] = d2[0][lane]; tp.ud1[r] = d1[0][lane]; tp.gm[r] = gm[0][lane];
+        }
+    }
     if (lane < GL_H) {
         gvm_dotN<KM, GL_H>(M.W3, GL_H, lane, &gm[0][0], GL_H, K, acc);
 #pragma unroll
@@ -313,13 +259,14 @@ __global__ __launch_bounds__(64) void k_gvm_upd_bwd(GlPair M, GlUpd U, GlGeom G,
     }
 }
 
-// End of a backward GNN step t >= 1 (k_gl_gnn_atom_bwd), one wavefront per atom (lanes 0..31: dP, lanes 32..63: dR): the padded
+// End of a backward GNN step t >= 1, one wavefront per atom (lanes 0..31: dP, lanes 32..63: dR): the padded
 // partners' mask once; per cotangent the pieces in order, dP's padded partners in closed form, the atom's slots in order, then
 // gh = gh_prev + the h columns of Wi dP + Wj dR (in place).  pstride: floats of one cotangent's pieces.
-template <int KM>
+template <int KM, bool TAPE = false>
 __global__ __launch_bounds__(64) void k_gvm_gnn_atom_bwd(GlPair M, GlGeom G, int K, size_t pstride, size_t SL, const int *inc_off,
                                                          const float *partP, const float *partR, const float *slotP, const float *slotR,
-                                                         const float *P, const float *dS, float *gh) {
+                                                         const float *P, const float *dS, float *gh, GlTape tp) {
+    static_assert(!TAPE || KM == 1, "a training step has one cotangent");
     __shared__ float v[GL_H], d2[KM][GL_H], dv[2][KM][GL_H];
     if (KM == 1) K = 1;
     const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
@@ -341,11 +288,17 @@ __global__ __launch_bounds__(64) void k_gvm_gnn_atom_bwd(GlPair M, GlGeom G, int
         if (t < K) {
             float s = 0.f;
             for (int k = 0; k < np; ++k) s += part[t * pstride + ((size_t)k * G.A + a) * GL_H + f];
-            // (one fused multiply-add, as k_gl_gnn_atom_bwd's `s += (N - n) * ...` is compiled: spelt out, so that it does not hang
-            // on what the compiler contracts in a loop over cotangents)
+            // (one fused multiply-add, spelt out: the same bits whatever the compiler contracts in a loop over cotangents)
             if (!half) s = fmaf((float)(G.N - n), pa > 0.f ? pad[t] : 0.f, s);
             for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slot[((size_t)t * SL + k) * GL_H + f];
             dv[half][t][f] = s;
+            if (TAPE) {
+                tp.dv[(size_t)a * 64 + lane] = s;
+                if (!half) {
+                    tp.z1[(tp.pad0 + a) * GL_H + f] = v[f];
+                    tp.d2[(tp.pad0 + a) * GL_H + f] = (float)(G.N - n) * d2[0][f];
+                }
+            }
         }
     __syncthreads();
     if (lane < GL_E) {
@@ -359,11 +312,12 @@ __global__ __launch_bounds__(64) void k_gvm_gnn_atom_bwd(GlPair M, GlGeom G, int
     }
 }
 
-// EPN backward (k_gl_epn_atom_bwd), one wavefront per atom: per cotangent dP / dR from the slots in order, then gfeat += the h columns
+// EPN backward, one wavefront per atom: per cotangent dP / dR from the slots in order, then gfeat += the h columns
 // and gq += the q column of Wi dP + Wj dR; the weights pass once.
-template <int KM>
+template <int KM, bool TAPE = false>
 __global__ __launch_bounds__(64) void k_gvm_epn_atom_bwd(GlPair M, GlGeom G, int K, size_t SL, const int *inc_off, const float *slotP,
-                                                         const float *slotR, float *gfeat, float *gq) {
+                                                         const float *slotR, float *gfeat, float *gq, GlTape tp) {
+    static_assert(!TAPE || KM == 1, "a training step has one cotangent");
     __shared__ float dv[2][KM][GL_H];
     if (KM == 1) K = 1;
     const int a = blockIdx.x, lane = threadIdx.x, half = lane >> 5, f = lane & 31;
@@ -372,6 +326,7 @@ __global__ __launch_bounds__(64) void k_gvm_epn_atom_bwd(GlPair M, GlGeom G, int
         float s = 0.f;
         for (int k = inc_off[a]; k < inc_off[a + 1]; ++k) s += slot[((size_t)t * SL + k) * GL_H + f];
         dv[half][t][f] = s;
+        if (TAPE) tp.dv[(size_t)a * 64 + lane] = s;
     }
     __syncthreads();
     if (lane <= GL_E) {
@@ -390,8 +345,11 @@ __global__ __launch_bounds__(64) void k_gvm_epn_atom_bwd(GlPair M, GlGeom G, int
 }
 
 // ---------------------------------------------------------------------------------------------------------- edges -> coordinates
-// k_gl_pair_xyz, one thread per listed pair: the image d, D and the 48 channel slopes de_k/dD once in float64; per cotangent
-// gD = sum_k gE_k de_k/dD, w = gD / D and the pair's two slots of slotx [K][slots][9].  GEO 0 open, 2 cells.  bad as there.
+// One thread per listed pair: the displacement d = image of r_j - r_i and D in float64 as the front-end measures them (PairGeo<GEO>,
+// pair_dist: GEO 0 open, 1 box rows [B][3], 2 EpnnCell records [B]) and the 48 channel slopes de_k/dD once; per cotangent
+// gD = sum_k gE_k de_k/dD, w = gD / D; the first atom's slot gets -w d, the second's +w d (d D / d r_i = (r_i - r_j) / D), and each
+// gets half of w d_a d_c (xx, yy, zz, yz, xz, xy) for the strain.  slotx [K][slots][9] float64.  bad: bit 0 = two atoms or images
+// coincide, bit 1 = a pair without both slots (atomicOr: the word does not depend on which thread comes last).
 template <int GEO, int KM>
 __global__ __launch_bounds__(256) void k_gvm_pair_xyz(GlPairs L, int npairs, int K, size_t P1, size_t SL, const int *mol_of, const float *xyz,
                                                       const float *geo, const float *gE, double cutoff, double eta, const double *mu,
@@ -435,8 +393,8 @@ __global__ __launch_bounds__(256) void k_gvm_pair_xyz(GlPairs L, int npairs, int
             for (int k = 0; k < 6; ++k) { si[3 + k] = s6[k]; sj[3 + k] = s6[k]; }
         }
 }
-// k_gl_atom_xyz per (atom, cotangent = blockIdx.y): there is no primal to share, the statement is that kernel's.  gxyz [K][A][3],
-// share [K][A][6] float64 or null.
+// Per (atom, cotangent = blockIdx.y): the atom adds its slots in order, in float64: gxyz [K][A][3] float32, and its strain share
+// [K][A][6] float64 (k_gvm_strain_mol adds a molecule's atoms up) or null.
 __global__ __launch_bounds__(256) void k_gvm_atom_xyz(int A, size_t SL, const int *inc_off, const double *slotx, float *gxyz, double *share) {
     const int a = blockIdx.x * 256 + threadIdx.x;
     const size_t t = blockIdx.y;

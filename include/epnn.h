@@ -421,17 +421,17 @@ int epnn_charges_jvp_multi_xyz_cell(epnn_handle *h, int B, int N, const int32_t 
  * same N.
  * Bits: q_out has the bits of epnn_charges_vjp_xyz_cell on "grad_path" 2, and row k the bits that entry gives for g[k] alone,
  * whatever K, the row's position and the other rows are; gstrain_out = NULL changes no other bit.  No cotangent statement reads
- * another cotangent, and each is the fmaf chain or MFMA sequence of the single entry's backward kernel: accumulators from zero, the
- * same pieces and slot order.
+ * another cotangent, and the single entry runs these kernels at K = 1: one fmaf chain or MFMA sequence per cotangent, accumulators
+ * from zero, the same pieces and slot order.
  * Cost: the front-end, the pair list, the checkpointed forward, the primal projections and every pair's and atom's primal
  * pre-activations and masks run once; the two all-pairs backward sweeps carry the cotangents in chunks of 4, 2 or 1 (K = 7 is
  * 4 + 2 + 1) and each chunk's launch repeats the 16 primal MFMAs per partner: sum over chunks of 2 (16 + 16 kc) MFMAs per partner and
- * tile against 64 K for K single calls (profiles/r24_vjp_multi.txt).  Device scratch: the single entry's rows (its backward rows
- * stay unused) plus K copies of the cotangent rows gq, gh, ghp, dS, the sweeps' pieces, the slots, gE, the coordinate slots, the
- * strain shares and the outputs; with `pieces` as at epnn_charges_vjp_xyz,
- *     bytes = A (1324 + 4 nx + 324 T + 257 pieces + K (580 + 256 pieces)) + (1116 + 848 K) listed pairs + 36 K B + 13 KB
+ * tile against 64 K for K single calls (profiles/r24_vjp_multi.txt).  Device scratch: the single entry's inputs, pair list,
+ * checkpoints and primal rows once and K copies of the cotangent rows gq, gh, ghp, dS, the sweeps' pieces, the slots, gE, the
+ * coordinate slots, the strain shares and the outputs; with `pieces` as at epnn_charges_vjp_xyz,
+ *     bytes = A (744 + 4 nx + 324 T + pieces + K (580 + 256 pieces)) + (268 + 848 K) listed pairs + 36 K B + 13 KB
  *                                                                                         (+- 256 per buffer of rounding)
- * with the staged inputs counted by this call's bytes.  Shared with the other pair-list calls: the handle keeps the scratch of its
+ * which at K = 1 is epnn_charges_vjp_xyz's formula, with the staged inputs counted by this call's bytes.  Shared with the other pair-list calls: the handle keeps the scratch of its
  * largest call.  After a call epnn_last_stats gives out[0] = listed pairs, out[1] = 0, out[2] = bytes of device scratch the call used.
  * Out of scope: a dense-path twin; dF/dQ, the adjoint of the JVP's vQ; box rows (a box is its diagonal cell, whose bits are the box
  * entry's). */

@@ -424,3 +424,58 @@ def test_three_entries_share_one_handle(gpu_engine_factory):
         want = call(fresh)
         assert pairs == int(fresh.last_stats()[0]) and pairs > 0, k
         assert len(got) == len(want) and all(np.array_equal(a, b) for a, b in zip(got, want)), k
+
+
+def test_reverse_entries_share_one_backward(gpu_engine_factory):
+    """The train step, the single VJP, the Coulomb call and the K = 3 VJP run one set of backward kernels on one scratch buffer, with
+    tape pointers (the train step) or without, one cotangent or three.  On one handle: train step, VJP, Coulomb, VJP at K = 3, then the
+    first three again; each call gives the bits of the same call on a fresh handle.  Molecules of 1, 2 (atoms 50 A apart: no listed
+    pair), 17 and 40 atoms in one batch."""
+    from test_gpu_train_cell import ZERO
+    w = random_weights(9, 2, seed=5, scale=0.6)
+    far = _lattice_molecule(2, 9, seed=2)
+    far[0][1] = far[0][0] + np.float32([50.0, 0.0, 0.0])
+    offsets, xyz, x, Q = _batch([_lattice_molecule(1, 9, seed=1), far, _lattice_molecule(17, 9, seed=17), _lattice_molecule(40, 9, seed=40)])
+    A, N = int(offsets[-1]), 40
+    rng = np.random.default_rng(27)
+    g, y = rng.normal(size=(3, A)).astype(np.float32), rng.normal(scale=0.3, size=A).astype(np.float32)
+
+    def step(eng):
+        q, loss = eng.train_step_xyz(offsets, xyz, x, Q, y, N, apply=False, cell=ZERO)
+        return q, np.float32(loss), eng.get_gradients()
+
+    first = [step,
+             lambda e: e.charges_vjp_xyz(offsets, xyz, x, Q, g[0], N),
+             lambda e: e.coulomb_xyz(offsets, xyz, x, Q, N, parts=True)]
+    calls = first + [lambda e: e.charges_vjp_xyz_multi(offsets, xyz, x, Q, g, N, strain=True)] + first
+
+    def engine():
+        eng = _engine(gpu_engine_factory, w, 9)
+        eng.set_option("train_path", 2)
+        eng.train_init()
+        return eng
+
+    shared = engine()
+    wants = {}
+    for k, call in enumerate(calls):
+        got, stats = call(shared), shared.last_stats()
+        if call not in wants:
+            fresh = engine()
+            wants[call] = (call(fresh), fresh.last_stats())
+        want, want_stats = wants[call]
+        assert int(stats[0]) > 0 and int(stats[0]) == int(want_stats[0]), k
+        assert len(got) == len(want) and all(np.array_equal(a, b) for a, b in zip(got, want)), k
+        assert all(np.isfinite(np.asarray(a, dtype=np.float64)).all() for a in got), k
+
+
+def test_box_rows_on_the_pair_list_path(gpu_engine_factory):
+    """The single VJP with box= on the pair-list path (the box instance of the coordinate kernel, K = 1 only) on a 20-atom box against
+    the periodic float64 VJP, at the tolerance of test_gpu_periodic.test_charge_gradients_in_cells: q within 2e-4, gxyz within
+    2e-4 max |ref| + the ReLU-kink bracket."""
+    w = random_weights(9, 2, seed=6, scale=0.5)
+    eng = _engine(gpu_engine_factory, w, 9)
+    rng = np.random.default_rng(320)
+    L = np.float32([6.0, 6.5, 7.0])
+    mol = (periodic_ref.random_cell(rng, 20, L),) + _features(rng, 20, 9)
+    ref = lambda xyz, x, Q, g, **kw: vjp64_pbc(xyz, x, Q, g, L, w, **kw)
+    _check(eng, [mol], 24, [ref], both_paths=False, box=L)

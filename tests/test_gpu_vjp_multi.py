@@ -316,13 +316,13 @@ def test_the_model_method(gpu_engine_factory):
 
 
 # ---------------------------------------------------------------------------------------------------- 8: scratch
-BUFFERS = 52      # 14 staged inputs and counts, 10 of the pair list, 19 rows of the single entry, 9 of the K-fold block: 256 bytes each
+BUFFERS = 43      # 14 staged inputs and counts, 10 of the pair list, 19 rows (11 of them K-fold): 256 bytes each
 
 
 def _formula(ns, nx, T, pairs, K, B):
-    """include/epnn.h: bytes = A (1324 + 4 nx + 324 T + 257 pieces + K (580 + 256 pieces)) + (1116 + 848 K) listed pairs + 36 K B + 13 KB"""
+    """include/epnn.h: bytes = A (744 + 4 nx + 324 T + pieces + K (580 + 256 pieces)) + (268 + 848 K) listed pairs + 36 K B + 13 KB"""
     pieces = max(min(16, max(1, -(-2048 // -(-n // 16)))) for n in ns)
-    return sum(ns) * (1324 + 4 * nx + 324 * T + 257 * pieces + K * (580 + 256 * pieces)) + (1116 + 848 * K) * pairs + 36 * K * B + 13 * 1024
+    return sum(ns) * (744 + 4 * nx + 324 * T + pieces + K * (580 + 256 * pieces)) + (268 + 848 * K) * pairs + 36 * K * B + 13 * 1024
 
 
 def test_scratch_follows_the_formula(gpu_engine_factory):

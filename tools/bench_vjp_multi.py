@@ -33,7 +33,7 @@ def pieces(n):
 
 
 def scratch_formula(A, B, P, nx, T, n, K):
-    return A * (1324 + 4 * nx + 324 * T + 257 * pieces(n) + K * (580 + 256 * pieces(n))) + (1116 + 848 * K) * max(P, 1) + 36 * K * B + 13 * 1024
+    return A * (744 + 4 * nx + 324 * T + pieces(n) + K * (580 + 256 * pieces(n))) + (268 + 848 * K) * max(P, 1) + 36 * K * B + 13 * 1024
 
 
 def window(fn, seconds=0.3):

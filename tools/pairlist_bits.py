@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The bits of the pair-list entries (charges_vjp_xyz at "grad_path" 2, train_step_xyz at "train_path" 2 with apply=False,
+"""The bits of the pair-list entries (charges_vjp_xyz at "grad_path" 2, with strain where there is a cell and there also without;
+charges_vjp_xyz_multi at K = 1, 3 and 7, which runs sweep chunks 4 + 2 + 1; train_step_xyz at "train_path" 2 with apply=False;
 charges_jvp_xyz, charges_jvp_xyz_multi at K = 1 and at K = 3, which runs sweep chunks 2 + 1) on the smallest systems that reach each
 branch of their shared set-up (csrc/epnn_api_pairlist.hip.h):
     python tools/pairlist_bits.py record FILE      # on the build to compare against
@@ -57,6 +58,11 @@ def run():
 
         strain = "cell" in geo
         keep("vjp", ("q", "gxyz", "gstrain"), eng.charges_vjp_xyz(offsets, xyz, x, Q, g, N, strain=strain, **geo))
+        if strain:
+            keep("vjp_nostrain", ("q", "gxyz"), eng.charges_vjp_xyz(offsets, xyz, x, Q, g, N, **geo))
+        gk = np.concatenate([g[None], np.random.default_rng(4000 + k).normal(size=(6, A)).astype(np.float32)])
+        for K in (1, 3, 7):
+            keep(f"vjp_multi_K{K}", ("q", "gxyz", "gstrain"), eng.charges_vjp_xyz_multi(offsets, xyz, x, Q, gk[:K], N, strain=strain, **geo))
         q, loss = eng.train_step_xyz(offsets, xyz, x, Q, y, N, apply=False, **(geo or {"cell": ZERO}))
         grad = eng.get_gradients()
         sums = np.array([grad[sl].astype(np.float64).sum() for sl in _tensor_slices(w)])
